@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- utterances/s of the TC-ResNet keyword-spotting hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one eval-mode pass of the hot path over one batch of synthetic 1 s @ 16 kHz waveforms
@@ -92,6 +92,25 @@ def timed(fn, steps: int, warmup: int, dist_on: bool):
     return dt
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays, rank: int, world: int):
+    """--dump-outputs: each array as float32 <out_dir>/<name>.npy (<name>_rank<r>.npy with several ranks).  Over 64 MB in all (a --batch
+    far above the default), every rank keeps the same fixed, seeded sample of rows, in ascending order."""
+    import numpy as np
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a[0].nbytes for a in arrays.values())
+    keep = max(1, DUMP_LIMIT_BYTES // (world * row_bytes))
+    if n > keep:
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy" if world == 1 else f"{k}_rank{rank}.npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -103,6 +122,8 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the train / 3010 legs (profiling runs); same as --legs none")
     ap.add_argument("--legs", default="all", help="secondary legs to run next to the headline: 'all', 'none' or a comma list of " + ", ".join(LEGS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the (logits, probs) of the last timed headline step to "
+                    "DIR/logits.npy and DIR/probs.npy (float32; with N > 1 ranks: logits_rank<r>.npy ...), to compare two builds output for output")
     args = ap.parse_args()
     if args.no_extras or args.legs == "none":
         legs = set()
@@ -225,16 +246,19 @@ def main():
     nev = args.steps + args.warmup
     ev = {i: [new_event() for _ in range(3)] for i in range(args.warmup, nev) if (i - args.warmup) % EV_EVERY == 2 or (args.steps <= 2 and i == args.warmup)}       # timed steps 2, 10, 18, ...
     counter = [0]
+    last_out = [outbuf]         # the (logits, probs) buffers of the latest step (pipelined: one pair per stream)
 
     def fwd_step():
         i = counter[0]
         counter[0] += 1
         if pipelined:
-            pipe.submit(wav, events=ev.get(i))
+            last_out[0] = pipe.submit(wav, events=ev.get(i))
         else:
             seq_step(ev.get(i))
 
     dt = timed(fwd_step, args.steps, args.warmup, dist_on)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logits": last_out[0][0], "probs": last_out[0][1]}, rank, world)
     value = world * B * args.steps / dt
     timed_ev = [ev[i] for i in range(args.warmup, args.warmup + args.steps) if i in ev]
     fe_in = sum(e[0].elapsed_time(e[1]) for e in timed_ev) / len(timed_ev)          # inside the timed region (co-running when pipelined)
