@@ -394,6 +394,48 @@ int tcr_augment_fwd(const int16_t* pcm, const int64_t* clip_off, const int32_t* 
                     int desired_samples, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Streaming detection: S concurrent audio streams, k new frames per stream and step.          */
+/* ------------------------------------------------------------------------------------------ */
+/* Each stream conceptually carries audio = zeros(n_samples) ++ every sample pushed since its last reset.  A step appends k * hop
+ * samples to every stream; afterwards, for every stream:
+ *   - its window (the first S * n_coef * (T + 2*TCR_HALO) floats of `state`, planar [S][n_coef][Tp], halo zero) is bitwise
+ *     tcr_frontend_fwd (default knobs) of audio[-n_samples:] -- only the k new frames are computed (the window's columns k..T-1
+ *     move to 0..T-k-1; the new ones come from frontend_pk3's arithmetic), nothing accumulates;
+ *   - logits / probs [S][num_classes] are bitwise tcr_net_forward_frozen of the S windows at batch S with `frozen_ss`;
+ *   - the detector (per stream: a ring of the last W = average_steps probability vectors, count = min(steps since reset, W),
+ *     prev_label = -1, prev_step, a step counter n):
+ *       smoothed = (sum of the ring's vectors, oldest to newest, float32) * (1.0f / count);
+ *       count < min_count: top = -1, score = 0, is_new = 0;
+ *       else top = argmax(smoothed) (lowest index on ties), score = smoothed[top],
+ *            is_new = score > threshold && top != prev_label && (prev_label == -1 || n - prev_step > suppression_steps),
+ *            and when is_new: prev_label = top, prev_step = n;
+ *       then n += 1.
+ * reset (uint8 [S], may be NULL): the marked streams return to the initial state -- audio, window, ring, detector -- BEFORE this
+ * step's samples are appended.  Streams are independent.
+ * Configurations: the front-end's n_coef x T must be the net's input; 1 <= k <= T; the front-end must be one frontend_pk3_kernel
+ * covers (mfcc / log-mel; the float64 deploy path, method 2, and windows pk3 declines are refused: no other kernel gives the
+ * offline features bitwise).  State and workspace are caller-owned device memory of the sizes below (0: invalid arguments, see
+ * tcr_last_error); tcr_stream_init fills the state (every stream = a silent clip) and must run once before the first step; the
+ * state belongs to one (cfg, net, n_streams, k, det) and the same values must be passed to every step. */
+typedef struct tcr_detect_cfg {
+    int32_t average_steps;      /* W: probability vectors averaged (average_window_ms / step) */
+    int32_t min_count;          /* 1..W: no result before this many vectors since the reset */
+    int32_t suppression_steps;  /* a new detection needs more than this many steps since the last one (unless the first) */
+    float threshold;            /* the smoothed score must exceed it */
+} tcr_detect_cfg;
+
+size_t tcr_stream_state_bytes(const tcr_frontend_cfg* cfg, const tcr_net* net, int n_streams, int k, const tcr_detect_cfg* det);
+size_t tcr_stream_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_net* net, int n_streams, int k);
+int tcr_stream_init(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, int n_streams, int k,
+                    const tcr_detect_cfg* det, void* state, void* workspace, size_t ws_bytes, void* stream);
+/* One step, one host call: stage / shift, front-end (k frames per stream), network, detector.  samples [S][k * hop] float32;
+ * smoothed [S][num_classes], top / score / is_new [S]. */
+int tcr_stream_step(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params,
+                    const float* frozen_ss, int n_streams, int k, const tcr_detect_cfg* det, const float* samples,
+                    const uint8_t* reset, void* state, void* workspace, size_t ws_bytes, float* logits, float* probs,
+                    float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Instrumentation                                                                             */
 /* ------------------------------------------------------------------------------------------ */
 /* Name of the n-th kernel family in this library (NULL past the end); used by bench.py to match

@@ -41,6 +41,10 @@ class DSCNNCfg(C.Structure):
                 ("bn_eps", C.c_float)]
 
 
+class DetectCfg(C.Structure):
+    _fields_ = [("average_steps", C.c_int32), ("min_count", C.c_int32), ("suppression_steps", C.c_int32), ("threshold", C.c_float)]
+
+
 class TensorInfo(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("kind", C.c_int32), ("arena", C.c_int32), ("offset", C.c_int64),
                 ("size", C.c_int64), ("shape", C.c_int32 * 4), ("rank", C.c_int32)]
@@ -148,6 +152,11 @@ _PROTOTYPES = {
     "tcr_ema_step": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P]),
     "tcr_l2_loss": (C.c_int, [_P, C.c_int64, C.c_float, _P, _P]),
     "tcr_xent_loss_sum": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
+    "tcr_stream_state_bytes": (C.c_size_t, [C.POINTER(FrontendCfg), _P, C.c_int, C.c_int, C.POINTER(DetectCfg)]),
+    "tcr_stream_workspace_bytes": (C.c_size_t, [C.POINTER(FrontendCfg), _P, C.c_int, C.c_int]),
+    "tcr_stream_init": (C.c_int, [C.POINTER(FrontendCfg), _P, _P, C.c_int, C.c_int, C.POINTER(DetectCfg), _P, _P, C.c_size_t, _P]),
+    "tcr_stream_step": (C.c_int, [C.POINTER(FrontendCfg), _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(DetectCfg), _P, _P, _P, _P,
+                                  C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 ABI_SYMBOLS = tuple(_PROTOTYPES.keys())

@@ -390,6 +390,23 @@ __global__ __launch_bounds__(256) void from_planar_kernel(const float* __restric
     }
 }
 
+void frontend_plan_args(const tcr_frontend_cfg* cfg, const void* plan_dev, FrontendArgs& a) {
+    const FrontendPlanLayout L = frontend_plan_layout(*cfg);
+    const float* p = static_cast<const float*>(plan_dev);
+    a.window = p + L.window;
+    a.window_sgn = p + L.window_sgn;
+    a.tw256 = reinterpret_cast<const float2*>(p + L.tw256);
+    a.tw_combine = reinterpret_cast<const float2*>(p + L.tw_combine);
+    a.tw_real = reinterpret_cast<const float2*>(p + L.tw_real);
+    a.seg_start = reinterpret_cast<const int*>(p + L.seg_start);
+    a.wud = reinterpret_cast<const float2*>(p + L.wud);
+    a.dcth = p + L.dcth;
+    a.mel_items = reinterpret_cast<const int*>(p + L.mel_items);
+    a.mel_ifirst = reinterpret_cast<const int*>(p + L.mel_ifirst);
+    a.mel_wit = reinterpret_cast<const float2*>(p + L.mel_wit);
+    a.dct_tab = p + L.dct_tab;
+}
+
 }  // namespace tcr
 
 using namespace tcr;
@@ -405,23 +422,10 @@ extern "C" int tcr_frontend_fwd_rounds(const tcr_frontend_cfg* cfg, const void* 
     TCR_REQUIRE(batch > 0, "tcr_frontend_fwd: batch must be positive (got %d)", batch);
     TCR_REQUIRE(cfg->nfft == 512 || cfg->nfft == 1024, "tcr_frontend_fwd: unresolved or unsupported configuration (nfft=%d)", cfg->nfft);
     TCR_REQUIRE((int64_t)batch * cfg->n_frames < (int64_t)1 << 31, "tcr_frontend_fwd: batch too large");
-    const FrontendPlanLayout L = frontend_plan_layout(*cfg);
-    const float* p = static_cast<const float*>(plan_dev);
     FrontendArgs a;
+    frontend_plan_args(cfg, plan_dev, a);
     a.wav = wav;
     a.out = feat;
-    a.window = p + L.window;
-    a.window_sgn = p + L.window_sgn;
-    a.tw256 = reinterpret_cast<const float2*>(p + L.tw256);
-    a.tw_combine = reinterpret_cast<const float2*>(p + L.tw_combine);
-    a.tw_real = reinterpret_cast<const float2*>(p + L.tw_real);
-    a.seg_start = reinterpret_cast<const int*>(p + L.seg_start);
-    a.wud = reinterpret_cast<const float2*>(p + L.wud);
-    a.dcth = p + L.dcth;
-    a.mel_items = reinterpret_cast<const int*>(p + L.mel_items);
-    a.mel_ifirst = reinterpret_cast<const int*>(p + L.mel_ifirst);
-    a.mel_wit = reinterpret_cast<const float2*>(p + L.mel_wit);
-    a.dct_tab = p + L.dct_tab;
     a.n_samples = cfg->n_samples;
     a.win = cfg->win;
     a.hop = cfg->hop;

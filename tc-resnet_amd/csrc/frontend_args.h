@@ -29,9 +29,16 @@ struct FrontendArgs {
     int rounds;         // packed kernel: rounds of (4096 / nc) frames per workgroup (set by launch_frontend_pk)
 };
 
+// the plan's table pointers of `a` (frontend.hip)
+void frontend_plan_args(const tcr_frontend_cfg* cfg, const void* plan_dev, FrontendArgs& a);
 // packed-FP32 kernel; nc = nfft / 2 (256 or 512); returns 1 when the general kernel must be used
 int launch_frontend_pk(int nc, const FrontendArgs& a, hipStream_t s);
 // the same at three waves per SIMD (frontend_pk3.hip); n_items: frontend_mel_item_count() of the configuration
 int launch_frontend_pk3(int nc, const FrontendArgs& a, int n_items, hipStream_t s);
+// streaming instance (stream.hip): `a.n_frames` = k new frames per stream, `a.n_samples` = the staging row stride, `a.tp` = the
+// window's padded length T + 2 kHalo; frame t of stream n goes to window column T - k + t; returns 1 when pk3 declines the configuration
+int launch_frontend_pk3_stream(int nc, const FrontendArgs& a, int n_items, hipStream_t s);
+// 1 when launch_frontend_pk3(_stream) takes a configuration of this window / filterbank with aligned frames (nothing launched)
+int frontend_pk3_supports(int nc, int win, int n_items);
 
 }  // namespace tcr

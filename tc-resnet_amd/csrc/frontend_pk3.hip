@@ -72,7 +72,11 @@ __device__ __forceinline__ void pk3_real_pair_power(v2 zk, v2 zn, v2 wmi, float&
 // LDS of one workgroup (bytes): 4 waves x (tile / power 4608 + item sums FPWV x 832 + log-mel 4096) + slopes + items
 //   nfft 1024: 18432 + 6656 + 16384 + 6144       = 47616      nfft 512: 18432 + 13312 + 16384 + 3072 + 768 = 51968
 // three workgroups per CU: <= 54613.
-template <int NC, int QV, bool MAG>
+// STREAM (stream.hip): the k = a.n_frames new frames of each stream of a streaming detector -- frame g is frame t = g % k of stream
+// g / k, read from the stream's staging row (a.wav, row stride a.n_samples) at t * hop like an utterance's, and written to window
+// column T - k + t of a window of a.tp = T + 2 kHalo columns; the halo zeroing keys on the window column.  Per-frame arithmetic
+// unchanged, and the argument block is the same (the column offset is derived from tp), so the other instances compile as before.
+template <int NC, int QV, bool MAG, bool STREAM>
 __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs a) {
     constexpr int LPF = NC / 16;            // lanes per frame
     constexpr int FPR = 256 / LPF;          // frames per round (workgroup)
@@ -351,13 +355,15 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
         const int gg = valid ? g : a.total_frames - 1;
         const int n = gg / a.n_frames;
         const int t = gg - n * a.n_frames;
-        float* dst = a.out + (size_t)n * a.n_coef * a.tp + kHalo + t;
+        const int col0 = STREAM ? a.tp - 2 * kHalo - a.n_frames : 0;       // window column of the stream's first new frame (halo: column 0
+                                                                            // is new only when k == T)
+        float* dst = a.out + (size_t)n * a.n_coef * a.tp + kHalo + col0 + t;
         if (a.no_dct) {
             for (int m = kq; m < a.n_coef; m += 4) {
                 if (valid) {
                     float* row = dst + (size_t)m * a.tp;
                     row[0] = LM[m * 16 + (col ^ ((m >> 1) & 15))];
-                    if (t == 0) { row[-4] = 0.f; row[-3] = 0.f; row[-2] = 0.f; row[-1] = 0.f; }
+                    if (t == 0 && (!STREAM || col0 == 0)) { row[-4] = 0.f; row[-3] = 0.f; row[-2] = 0.f; row[-1] = 0.f; }
                     if (t == a.n_frames - 1) { row[1] = 0.f; row[2] = 0.f; row[3] = 0.f; row[4] = 0.f; }
                 }
             }
@@ -384,7 +390,7 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
                             if (c < a.n_coef) {
                                 float* row = dst + (size_t)c * a.tp;
                                 row[0] = acc[rr];
-                                if (t == 0) { row[-4] = 0.f; row[-3] = 0.f; row[-2] = 0.f; row[-1] = 0.f; }
+                                if (t == 0 && (!STREAM || col0 == 0)) { row[-4] = 0.f; row[-3] = 0.f; row[-2] = 0.f; row[-1] = 0.f; }
                                 if (t == a.n_frames - 1) { row[1] = 0.f; row[2] = 0.f; row[3] = 0.f; row[4] = 0.f; }
                             }
                         }
@@ -397,10 +403,20 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
     }
 }
 
+// the launcher's own tests below, for a caller that needs to know before it launches (stream.hip refuses what pk3 would decline)
+int frontend_pk3_supports(int nc, int win, int n_items) {
+    const int sub = nc / 256;
+    if ((nc != 256 && nc != 512) || (win & 1) || (win / 2) % (16 * sub) != 0) return 0;
+    if (n_items < 0 || n_items > mel_items_fast(nc)) return 0;
+    const int qv = win / (32 * sub);
+    return (qv == 10 || qv == 15 || qv == 16) ? 1 : 0;     // the instances of TCR_FPK3 below
+}
+
 // returns 1 (nothing launched) when the configuration needs another kernel: unaligned frames, a window whose valid radix-16 inputs
 // differ from lane to lane, or a filterbank with more items than the unrolled trips take / with a segment of more items than the log
 // phase reads (n_items < 0: frontend_mel_item_count)
-int launch_frontend_pk3(int nc, const FrontendArgs& a0, int n_items, hipStream_t s) {
+template <bool STREAM>
+static int launch_pk3(int nc, const FrontendArgs& a0, int n_items, hipStream_t s) {
     const int sub = nc / 256;
     if (!a0.aligned || (a0.win & 1) || (a0.win / 2) % (16 * sub) != 0) return 1;
     if (a0.total_frames >= (1 << 23)) return 1;                // (the frame -> utterance split uses a float reciprocal)
@@ -434,8 +450,8 @@ int launch_frontend_pk3(int nc, const FrontendArgs& a0, int n_items, hipStream_t
     }
 #define TCR_FPK3(NC_, QV_)                                                                                          \
     if (nc == NC_ && qv == QV_) {                                                                                   \
-        if (a.magnitude) hipLaunchKernelGGL((frontend_pk3_kernel<NC_, QV_, true>), dim3(grid), dim3(256), 0, s, a); \
-        else hipLaunchKernelGGL((frontend_pk3_kernel<NC_, QV_, false>), dim3(grid), dim3(256), 0, s, a);            \
+        if (a.magnitude) hipLaunchKernelGGL((frontend_pk3_kernel<NC_, QV_, true, STREAM>), dim3(grid), dim3(256), 0, s, a); \
+        else hipLaunchKernelGGL((frontend_pk3_kernel<NC_, QV_, false, STREAM>), dim3(grid), dim3(256), 0, s, a);            \
         return check_launch("frontend_pk3_kernel");                                                                 \
     }
     TCR_FPK3(512, 10)   // 40 ms window @ 16 kHz, FFT 1024
@@ -448,4 +464,10 @@ int launch_frontend_pk3(int nc, const FrontendArgs& a0, int n_items, hipStream_t
     return 1;
 }
 
+int launch_frontend_pk3(int nc, const FrontendArgs& a, int n_items, hipStream_t s) { return launch_pk3<false>(nc, a, n_items, s); }
+int launch_frontend_pk3_stream(int nc, const FrontendArgs& a, int n_items, hipStream_t s) { return launch_pk3<true>(nc, a, n_items, s); }
+
 }  // namespace tcr
+
+// The streaming detector (tcr_stream_*) that drives the STREAM instances is compiled in this translation unit.
+#include "stream.hip"

@@ -57,6 +57,12 @@ struct tcr_net {
 
 namespace tcr {
 
+void net_io_shape(const tcr_net* net, int* in_channels, int* t_in, int* num_classes) {
+    *in_channels = net->cfg.in_channels;
+    *t_in = net->cfg.t_in;
+    *num_classes = net->cfg.num_classes;
+}
+
 static int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
 // filter gradients that get the finer split-K grid (mfma.hip: wgrad_chunks_for)

@@ -1,0 +1,349 @@
+// Streaming keyword spotting over many concurrent audio streams (tcr_stream_*): per step, every stream hears k * hop new samples,
+// only the k new MFCC / log-mel frames are computed, the network runs on the window kept on the device, and the posteriors are
+// smoothed into detections there.
+//
+// Each stream conceptually carries audio = zeros(n_samples) ++ everything pushed since its last reset; after a step its window is
+// bitwise the ordinary front-end's features of audio[-n_samples:], because
+//   * a window column is a pure function of its frame's samples (frontend_pk3.hip: the same operations on every frame), so the
+//     columns that survive a step move left by k unchanged, and
+//   * the k new frames are computed by frontend_pk3_kernel's streaming instance from a staging row that holds exactly the samples
+//     they cover: tail ++ new, where tail = the last  win - hop + ((n_samples - win) mod hop)  samples heard (the new clip ends
+//     (n_samples - win) mod hop samples behind its last frame, so the staging row's first sample is the first new frame's first).
+// Nothing is accumulated: every column comes from raw samples, so the window does not drift however long a stream runs.
+//
+// Kernels of a step: stream_stage_kernel (reset, staging row, tail, window shift; one workgroup per stream, so the in-place shift has
+// no cross-workgroup hazard), frontend_pk3_kernel<.., STREAM = true>, the network (tcr_net_forward_frozen, untouched), then
+// stream_detect_kernel (a lane per stream and class: the smoothing / detection rule of the header, a ring of the last W probability
+// vectors).
+//
+// State (caller-owned device memory, tcr_stream_state_bytes), regions 256-byte aligned:
+//   window [S][n_coef][T + 2 TCR_HALO] | zero window [n_coef][Tp] (the features of a silent clip: what a reset window is)
+//   | tail [S][tail_len] | ring [W][S][classes] | detector integers [5][S] (head, count, prev_label, prev_step, n)
+// Workspace (tcr_stream_workspace_bytes): staging rows [S][stage_stride] (>= n_samples floats) | the network's workspace at batch S.
+//
+// Compiled as part of frontend_pk3.hip's translation unit (included at its end, next to the streaming front-end's launcher).
+#pragma once
+#include <algorithm>
+
+#include "frontend_plan.h"
+#include "frontend_args.h"
+
+namespace tcr {
+
+namespace {
+
+constexpr int kMaxTail = 1024;          // tail_len <= win - 1 < nfft <= 1024
+constexpr int kShiftRegs = 8;           // window elements per thread and pass of the shift
+
+struct StreamGeom {
+    int S, k, T, tp, n_coef, classes, W;
+    int tail_len, stage_stride;
+    int64_t win_off, zw_off, tail_off, ring_off, ist_off, state_floats;         // state offsets in floats
+    int64_t stage_floats, net_ws_off, ws_floats;                                // workspace
+};
+
+int64_t align64(int64_t v) { return (v + 63) / 64 * 64; }     // floats -> 256 bytes
+
+StreamGeom stream_geom(const tcr_frontend_cfg& cfg, const tcr_net* net, int S, int k, int W) {
+    StreamGeom g{};
+    int cin = 0, t_in = 0, classes = 0;
+    net_io_shape(net, &cin, &t_in, &classes);
+    g.S = S; g.k = k; g.T = cfg.n_frames; g.tp = tcr_padded_len(cfg.n_frames); g.n_coef = cfg.n_coef; g.classes = classes; g.W = W;
+    g.tail_len = cfg.win - cfg.hop + (cfg.n_samples - cfg.win) % cfg.hop;
+    g.stage_stride = (g.tail_len + k * cfg.hop + 3) / 4 * 4;
+    int64_t o = 0;
+    g.win_off = o; o = align64(o + (int64_t)S * g.n_coef * g.tp);
+    g.zw_off = o; o = align64(o + (int64_t)g.n_coef * g.tp);
+    g.tail_off = o; o = align64(o + (int64_t)S * g.tail_len);
+    g.ring_off = o; o = align64(o + (int64_t)W * classes * S);
+    g.ist_off = o; o = align64(o + 5 * (int64_t)S);
+    g.state_floats = o;
+    g.stage_floats = align64(std::max((int64_t)S * g.stage_stride, (int64_t)cfg.n_samples));
+    g.net_ws_off = g.stage_floats;
+    g.ws_floats = g.stage_floats + (int64_t)(tcr_net_workspace_bytes(net, S, 0) / sizeof(float));
+    return g;
+}
+
+// Everything the create / step calls refuse, with the reason.
+int stream_check(const tcr_frontend_cfg* cfg, const tcr_net* net, int S, int k, const tcr_detect_cfg* det, const char* what) {
+    TCR_REQUIRE(cfg && net, "%s: null front-end configuration or network", what);
+    TCR_REQUIRE(cfg->nfft == 512 || cfg->nfft == 1024, "%s: unresolved or unsupported front-end configuration (nfft=%d)", what, cfg->nfft);
+    TCR_REQUIRE(cfg->method != 2, "%s: the float64 deploy front-end (method 2, mfcc_deploy) has no streaming instance", what);
+    int cin = 0, t_in = 0, classes = 0;
+    net_io_shape(net, &cin, &t_in, &classes);
+    TCR_REQUIRE(cfg->n_coef == cin && cfg->n_frames == t_in, "%s: the front-end yields %d x %d features, the network expects %d x %d", what,
+                cfg->n_coef, cfg->n_frames, cin, t_in);
+    TCR_REQUIRE(S > 0, "%s: the number of streams must be positive (got %d)", what, S);
+    TCR_REQUIRE(classes <= 256, "%s: the detector takes at most 256 classes (got %d)", what, classes);
+    TCR_REQUIRE(k >= 1 && k <= cfg->n_frames, "%s: frames per step k = %d outside 1..T = %d", what, k, cfg->n_frames);
+    TCR_REQUIRE((int64_t)S * k < (1 << 23) && (int64_t)S * cfg->n_frames < ((int64_t)1 << 31), "%s: %d streams x %d frames is too large", what, S, k);
+    TCR_REQUIRE((cfg->hop & 1) == 0 && frontend_pk3_supports(cfg->nfft / 2, cfg->win, frontend_mel_item_count(*cfg)),
+                "%s: the streaming front-end (frontend_pk3_kernel) does not cover window %d / hop %d / %d mel bands at nfft %d; another "
+                "kernel would not give the offline features bitwise", what, cfg->win, cfg->hop, cfg->n_mel, cfg->nfft);
+    TCR_REQUIRE(cfg->win - cfg->hop + (cfg->n_samples - cfg->win) % cfg->hop <= kMaxTail, "%s: window %d / hop %d leave a tail of more "
+                "than %d samples", what, cfg->win, cfg->hop, kMaxTail);
+    if (det) {
+        TCR_REQUIRE(det->average_steps >= 1, "%s: average_steps (the ring of probability vectors) must be >= 1 (got %d)", what, det->average_steps);
+        TCR_REQUIRE(det->min_count >= 1 && det->min_count <= det->average_steps, "%s: min_count %d outside 1..average_steps = %d", what,
+                    det->min_count, det->average_steps);
+        TCR_REQUIRE(det->suppression_steps >= 0, "%s: suppression_steps must be >= 0 (got %d)", what, det->suppression_steps);
+    }
+    return TCR_OK;
+}
+
+}  // namespace
+
+struct StageArgs {
+    const float* samples;       // [S][k hop]
+    const uint8_t* reset;       // [S] or null
+    float* window;              // [S][n_coef][tp]
+    const float* zw;            // [n_coef][tp]
+    float* tail;                // [S][tail_len]
+    float* stage;               // [S][stage_stride]
+    int khop, tail_len, stage_stride, n_coef, tp, T, k;
+};
+
+// One workgroup per stream: reset, staging row tail ++ new samples, the new tail, the window's columns k..T-1 moved to 0..T-k-1 (the
+// front-end then writes columns T-k..T-1).  The old tail is read into LDS before the new one is written; the shift moves the window
+// in passes of 256 x kShiftRegs elements in row order, each read into registers before a barrier and written behind it -- a later
+// pass only reads columns (>= t + k of a row) that no earlier pass writes.
+__global__ __launch_bounds__(256) void stream_stage_kernel(const StageArgs a) {
+    __shared__ float s_tail[kMaxTail];
+    const int s = blockIdx.x;
+    const int tid = threadIdx.x;
+    const bool rst = a.reset && a.reset[s];
+    float* tail = a.tail + (size_t)s * a.tail_len;
+    const float* src = a.samples + (size_t)s * a.khop;
+    for (int i = tid; i < a.tail_len; i += 256) s_tail[i] = rst ? 0.f : tail[i];
+    __syncthreads();
+    float* stage = a.stage + (size_t)s * a.stage_stride;
+    for (int i = tid; i < a.tail_len + a.khop; i += 256) stage[i] = i < a.tail_len ? s_tail[i] : src[i - a.tail_len];
+    for (int i = tid; i < a.tail_len; i += 256) {
+        const int j = i + a.khop;
+        tail[i] = j < a.tail_len ? s_tail[j] : src[j - a.tail_len];
+    }
+    const int keep = a.T - a.k;                 // surviving columns per row
+    const int n = a.n_coef * keep;
+    const float inv_keep = keep > 0 ? 1.0f / (float)keep : 0.f;
+    float* win = a.window + (size_t)s * a.n_coef * a.tp + kHalo;
+    const float* zw = a.zw + kHalo;
+    for (int base = 0; base < n; base += 256 * kShiftRegs) {
+        float v[kShiftRegs];
+#pragma unroll
+        for (int m = 0; m < kShiftRegs; ++m) {
+            const int i = base + m * 256 + tid;
+            if (i < n) {
+                const int c = fast_div(i, keep, inv_keep), t = i - c * keep;
+                const int at = c * a.tp + t + a.k;
+                v[m] = rst ? zw[at] : win[at];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < kShiftRegs; ++m) {
+            const int i = base + m * 256 + tid;
+            if (i < n) {
+                const int c = fast_div(i, keep, inv_keep), t = i - c * keep;
+                win[c * a.tp + t] = v[m];
+            }
+        }
+    }
+}
+
+// Every stream = the silent clip: window = the zero window, tail zero, detector state fresh.
+__global__ __launch_bounds__(256) void stream_init_kernel(float* window, const float* zw, int win_elems, int S, float* tail, int tail_len,
+                                                          int* ist) {
+    const int64_t total = (int64_t)S * win_elems;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) window[i] = zw[i % win_elems];
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (int64_t)S * tail_len; i += (int64_t)gridDim.x * 256) tail[i] = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < S; i += (int64_t)gridDim.x * 256) {
+        ist[i] = 0;                 // head
+        ist[S + i] = 0;             // count
+        ist[2 * S + i] = -1;        // prev_label
+        ist[3 * S + i] = 0;         // prev_step
+        ist[4 * S + i] = 0;         // n
+    }
+}
+
+struct DetectArgs {
+    const float* probs;         // [S][C]
+    const uint8_t* reset;
+    float* ring;                // [W][S][C]
+    int* ist;                   // [5][S]
+    float* smoothed;            // [S][C]
+    int* top;
+    float* score;
+    int* is_new;
+    int S, C, W, min_count, suppression;
+    float threshold;
+};
+
+// A lane per (stream, class): a workgroup holds 256 / C streams.  Each lane stores its class's probability into the ring slot and
+// sums the ring oldest to newest in float32 (the loads requested eight at a time, the adds in ring order); the stream's first lane
+// takes the argmax (lowest index on ties) from LDS and runs the detection rule of tcr_stream_step's documentation.  Ring
+// [W][S][C]: a wave's accesses are contiguous.
+__global__ __launch_bounds__(256) void stream_detect_kernel(const DetectArgs a) {
+    __shared__ float s_sm[256];
+    const int S = a.S, C = a.C, W = a.W;
+    const int per = 256 / C;                    // streams per workgroup
+    const int ls = threadIdx.x / C, c = threadIdx.x - ls * C;
+    const int s = blockIdx.x * per + ls;
+    const bool live = ls < per && s < S;
+    int head = 0, count = 0, prev_label = -1, prev_step = 0, n = 0;
+    if (live) {
+        head = a.ist[s]; count = a.ist[S + s]; prev_label = a.ist[2 * S + s]; prev_step = a.ist[3 * S + s]; n = a.ist[4 * S + s];
+        if (a.reset && a.reset[s]) { head = 0; count = 0; prev_label = -1; prev_step = 0; n = 0; }
+        const size_t sc = (size_t)s * C + c, ring_row = (size_t)S * C;
+        a.ring[head * ring_row + sc] = a.probs[sc];
+        head = head + 1 == W ? 0 : head + 1;
+        count = min(count + 1, W);
+        int slot = head - count < 0 ? head - count + W : head - count;        // oldest
+        float acc = 0.f;
+        int i = 0;
+        for (; i + 8 <= count; i += 8) {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                v[j] = a.ring[slot * ring_row + sc];
+                slot = slot + 1 == W ? 0 : slot + 1;
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc += v[j];
+        }
+        for (; i < count; ++i) {
+            acc += a.ring[slot * ring_row + sc];
+            slot = slot + 1 == W ? 0 : slot + 1;
+        }
+        const float v = acc * (1.0f / (float)count);
+        a.smoothed[sc] = v;
+        s_sm[threadIdx.x] = v;
+    }
+    __syncthreads();
+    if (!live || c != 0) return;
+    int best = 0;
+    float best_v = s_sm[threadIdx.x];
+    for (int cc = 1; cc < C; ++cc) {
+        const float v = s_sm[threadIdx.x + cc];
+        if (v > best_v) { best = cc; best_v = v; }
+    }
+    int top = -1, fired = 0;
+    float score = 0.f;
+    if (count >= a.min_count) {
+        top = best;
+        score = best_v;
+        fired = score > a.threshold && top != prev_label && (prev_label == -1 || n - prev_step > a.suppression);
+        if (fired) { prev_label = top; prev_step = n; }
+    }
+    n += 1;
+    a.top[s] = top;
+    a.score[s] = score;
+    a.is_new[s] = fired;
+    a.ist[s] = head; a.ist[S + s] = count; a.ist[2 * S + s] = prev_label; a.ist[3 * S + s] = prev_step; a.ist[4 * S + s] = n;
+}
+
+namespace {
+
+// the streaming front-end over `rows` staging rows of `stride` floats, k frames each, into window columns T - k .. T - 1
+int stream_frontend(const tcr_frontend_cfg& cfg, const void* plan_dev, const float* stage, int stride, int rows, int k, float* out,
+                    hipStream_t s) {
+    FrontendArgs a;
+    frontend_plan_args(&cfg, plan_dev, a);
+    a.wav = stage;
+    a.out = out;
+    a.n_samples = stride;
+    a.win = cfg.win;
+    a.hop = cfg.hop;
+    a.n_frames = k;
+    a.n_coef = cfg.n_coef;
+    a.tp = tcr_padded_len(cfg.n_frames);
+    a.total_frames = rows * k;
+    a.magnitude = cfg.method != 0;
+    a.no_dct = cfg.method == 1;
+    a.log_floor = 0;
+    // one round of frames per persistent-workgroup chunk while the chunks fit one generation of the CUs' slots (a step's few frames:
+    // as many workgroups as there are rounds); otherwise the launcher's cost model.  The features do not depend on it.
+    a.rounds = ceil_div(a.total_frames, 4096 / (cfg.nfft / 2)) <= 3 * device_cus() ? 1 : 0;
+    a.stagger = 0;
+    a.stagger_div = 1;
+    a.aligned = (stride & 1) == 0 && (cfg.hop & 1) == 0 && (reinterpret_cast<uintptr_t>(stage) & 7) == 0;
+    const int rc = launch_frontend_pk3_stream(cfg.nfft / 2, a, frontend_mel_item_count(cfg), s);
+    TCR_REQUIRE(rc != 1, "tcr_stream: frontend_pk3_kernel declined the configuration");
+    return rc;
+}
+
+}  // namespace
+
+}  // namespace tcr
+
+using namespace tcr;
+
+extern "C" size_t tcr_stream_state_bytes(const tcr_frontend_cfg* cfg, const tcr_net* net, int n_streams, int k, const tcr_detect_cfg* det) {
+    if (!det) { set_error("tcr_stream_state_bytes: null detector configuration"); return 0; }
+    if (stream_check(cfg, net, n_streams, k, det, "tcr_stream_state_bytes") != TCR_OK) return 0;
+    return (size_t)stream_geom(*cfg, net, n_streams, k, det->average_steps).state_floats * sizeof(float);
+}
+
+extern "C" size_t tcr_stream_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_net* net, int n_streams, int k) {
+    if (stream_check(cfg, net, n_streams, k, nullptr, "tcr_stream_workspace_bytes") != TCR_OK) return 0;
+    return (size_t)stream_geom(*cfg, net, n_streams, k, 1).ws_floats * sizeof(float);
+}
+
+extern "C" int tcr_stream_init(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, int n_streams, int k,
+                               const tcr_detect_cfg* det, void* state, void* workspace, size_t ws_bytes, void* stream) {
+    TCR_REQUIRE(plan_dev && det && state && workspace, "tcr_stream_init: null argument");
+    TCR_TRY(stream_check(cfg, net, n_streams, k, det, "tcr_stream_init"));
+    const StreamGeom g = stream_geom(*cfg, net, n_streams, k, det->average_steps);
+    if ((size_t)g.ws_floats * sizeof(float) > ws_bytes) {
+        set_error("tcr_stream_init: workspace %zu bytes < required %zu", ws_bytes, (size_t)g.ws_floats * sizeof(float));
+        return TCR_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* st = static_cast<float*>(state);
+    float* ws = static_cast<float*>(workspace);
+    // the zero window: the streaming front-end over one silent clip (all T frames, columns 0..T-1) -- the offline kernel's arithmetic
+    if (hipMemsetAsync(ws, 0, (size_t)cfg->n_samples * sizeof(float), s) != hipSuccess) {
+        set_error("tcr_stream_init: hipMemsetAsync failed");
+        return TCR_ERR_HIP;
+    }
+    TCR_TRY(stream_frontend(*cfg, plan_dev, ws, cfg->n_samples, 1, cfg->n_frames, st + g.zw_off, s));
+    if (hipMemsetAsync(st + g.ring_off, 0, (size_t)g.W * g.classes * g.S * sizeof(float), s) != hipSuccess) {
+        set_error("tcr_stream_init: hipMemsetAsync failed");
+        return TCR_ERR_HIP;
+    }
+    const int64_t work = (int64_t)g.S * g.n_coef * g.tp;
+    const int grid = (int)std::min<int64_t>(ceil_div64(work, 256), 4 * (int64_t)device_cus());
+    hipLaunchKernelGGL(stream_init_kernel, dim3(grid), dim3(256), 0, s, st + g.win_off, st + g.zw_off, g.n_coef * g.tp, g.S,
+                       st + g.tail_off, g.tail_len, reinterpret_cast<int*>(st + g.ist_off));
+    return check_launch("stream_init_kernel");
+}
+
+extern "C" int tcr_stream_step(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params,
+                               const float* frozen_ss, int n_streams, int k, const tcr_detect_cfg* det, const float* samples,
+                               const uint8_t* reset, void* state, void* workspace, size_t ws_bytes, float* logits, float* probs,
+                               float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream) {
+    TCR_REQUIRE(plan_dev && params && frozen_ss && det && samples && state && workspace && logits && probs && smoothed && top && score && is_new,
+                "tcr_stream_step: null argument");
+    TCR_TRY(stream_check(cfg, net, n_streams, k, det, "tcr_stream_step"));
+    const StreamGeom g = stream_geom(*cfg, net, n_streams, k, det->average_steps);
+    if ((size_t)g.ws_floats * sizeof(float) > ws_bytes) {
+        set_error("tcr_stream_step: workspace %zu bytes < required %zu", ws_bytes, (size_t)g.ws_floats * sizeof(float));
+        return TCR_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* st = static_cast<float*>(state);
+    float* ws = static_cast<float*>(workspace);
+    StageArgs sa;
+    sa.samples = samples; sa.reset = reset; sa.window = st + g.win_off; sa.zw = st + g.zw_off; sa.tail = st + g.tail_off; sa.stage = ws;
+    sa.khop = k * cfg->hop; sa.tail_len = g.tail_len; sa.stage_stride = g.stage_stride; sa.n_coef = g.n_coef; sa.tp = g.tp; sa.T = g.T; sa.k = k;
+    hipLaunchKernelGGL(stream_stage_kernel, dim3(g.S), dim3(256), 0, s, sa);
+    TCR_TRY(check_launch("stream_stage_kernel"));
+    TCR_TRY(stream_frontend(*cfg, plan_dev, ws, g.stage_stride, g.S, k, st + g.win_off, s));
+    TCR_TRY(tcr_net_forward_frozen(net, params, frozen_ss, st + g.win_off, g.S, ws + g.net_ws_off, ws_bytes - (size_t)g.net_ws_off * sizeof(float),
+                                   logits, probs, nullptr, stream));
+    DetectArgs da;
+    da.probs = probs; da.reset = reset; da.ring = st + g.ring_off; da.ist = reinterpret_cast<int*>(st + g.ist_off);
+    da.smoothed = smoothed; da.top = top; da.score = score; da.is_new = is_new;
+    da.S = g.S; da.C = g.classes; da.W = g.W; da.min_count = det->min_count; da.suppression = det->suppression_steps; da.threshold = det->threshold;
+    hipLaunchKernelGGL(stream_detect_kernel, dim3(ceil_div(g.S, 256 / g.classes)), dim3(256), 0, s, da);
+    return check_launch("stream_detect_kernel");
+}

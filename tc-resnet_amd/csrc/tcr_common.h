@@ -31,6 +31,7 @@ hipStream_t shared_stream(int idx, hipStream_t caller);
 unsigned internal_event_flags();
 int tune_get(int knob);                  // process-wide tuning knobs (tcr_tune)
 int device_cus();                        // compute units of the current device (cached per device; 256 on MI355X)
+void net_io_shape(const tcr_net* net, int* in_channels, int* t_in, int* num_classes);      // (net.cpp: the opaque handle's input / output shape)
 
 #define TCR_REQUIRE(cond, ...)                 \
     do {                                       \

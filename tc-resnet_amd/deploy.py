@@ -95,6 +95,17 @@ class FrozenModel:
             return self.engine.forward_frozen(planar, self.frozen_ss)[1]
         return self.engine.forward_infer(planar)[1]
 
+    def streaming(self, n_streams: int, **kw):
+        """A `streaming.StreamingDetector` of n_streams over this artifact (TC-ResNet with `include_preprocess` only): the frozen
+        front-end settings, the conv / fc constants and the folded BN table as exported.  kw: frames_per_step, average_window_ms,
+        min_count, detection_threshold, suppression_ms."""
+        if self.meta["family"] != "tcresnet":
+            raise ValueError(f"streaming detection runs TC-ResNet artifacts only (this one is {self.meta['family']})")
+        if self.frontend is None:
+            raise ValueError("streaming detection needs an artifact exported with include_preprocess (it consumes raw audio)")
+        from .streaming import StreamingDetector
+        return StreamingDetector(self.engine, self.frontend, n_streams, frozen_ss=self.frozen_ss, **kw)
+
     # ---- file format ----------------------------------------------------------------------------------------------
     def save(self, path: str) -> str:
         out = {"__meta__": np.frombuffer(json.dumps(self.meta, sort_keys=True).encode(), dtype=np.uint8)}

@@ -1,0 +1,195 @@
+"""Streaming keyword spotting over many concurrent audio streams, on the device (tcr_stream_* of include/tcresnet_hip.h).
+
+A `StreamingDetector` holds S streams.  Each starts as if it had heard one clip of digital silence; every `push` appends
+k * hop samples to every stream (k = frames_per_step), computes only the k new front-end frames, runs the network on the
+one-second window kept on the device and smooths the posteriors into detections (the speech-commands "recognize commands"
+rule, stated in steps: see tcr_stream_step).  After a push, `window()` is bitwise the ordinary `Frontend` of each stream's last
+n_samples samples, and the logits / probs are bitwise `TCResNet.forward_frozen` of those windows at batch S.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Iterable, NamedTuple, Optional, Union
+
+import numpy as np
+import torch
+
+from ._lib import DetectCfg, TcrError, padded_len
+from .engine import Frontend, TCResNet
+
+
+class StreamOutput(NamedTuple):
+    """Results of one step, all on the device: logits / probs / smoothed [S, classes] float32, top [S] int32 (-1 before
+    min_count vectors), score [S] float32, is_new [S] int32 (1: a new detection of `top` at this step)."""
+    logits: torch.Tensor
+    probs: torch.Tensor
+    smoothed: torch.Tensor
+    top: torch.Tensor
+    score: torch.Tensor
+    is_new: torch.Tensor
+
+
+def ms_to_steps(ms: float, step_ms: float) -> int:
+    """Milliseconds -> whole steps (nearest)."""
+    return int(round(float(ms) / step_ms))
+
+
+class StreamingDetector:
+    """S concurrent streams through `frontend` and `net`, k = frames_per_step new frames per stream and step.
+
+    average_window_ms / suppression_ms become steps of k * hop / sample_rate seconds (the nearest whole number; the averaging
+    ring holds at least one vector).  Silence / unknown classes get no special case: callers filter labels.
+
+    Weights: without `frozen_ss` the detector runs on the net's folded BN table (`TCResNet._folded_table`): `push` refolds when
+    the variables or moving statistics changed since the last fold, a `prepared` call refuses to run (prepare it again).  With
+    `frozen_ss` (a frozen artifact's table, `FrozenModel.streaming`) that table is used as it is; the net's arena then only
+    supplies the conv / fc weights, and both forms refuse to run once the arena changed.
+
+    The output tensors are the detector's own and are overwritten by the next step (copy what must survive it)."""
+
+    def __init__(self, net: TCResNet, frontend: Frontend, n_streams: int, frames_per_step: int = 1, average_window_ms: float = 1000,
+                 min_count: int = 3, detection_threshold: float = 0.5, suppression_ms: float = 1500,
+                 frozen_ss: Optional[torch.Tensor] = None):
+        if not isinstance(net, TCResNet):
+            raise TcrError(f"StreamingDetector runs TC-ResNet models only, got {type(net).__name__}")
+        if net.lib is not frontend.lib or net.device != frontend.device:
+            raise TcrError("the network and the front-end must use the same library and device")
+        self.net, self.frontend, self.lib, self.device = net, frontend, net.lib, net.device
+        self.n_streams, self.k = int(n_streams), int(frames_per_step)
+        cfg = frontend.cfg
+        if not 1 <= self.k <= cfg.n_frames:
+            raise TcrError(f"StreamingDetector: frames per step k = {self.k} outside 1..T = {cfg.n_frames}")
+        self.step_samples = self.k * cfg.hop
+        self.step_ms = 1000.0 * self.step_samples / cfg.sample_rate
+        self.det = DetectCfg(max(1, ms_to_steps(average_window_ms, self.step_ms)), int(min_count),
+                             max(0, ms_to_steps(suppression_ms, self.step_ms)), float(detection_threshold))
+        S, lib = self.n_streams, self.lib
+        if S <= 0:
+            raise TcrError(f"StreamingDetector: n_streams must be positive (got {S})")
+        nstate = lib.tcr_stream_state_bytes(C.byref(cfg), net._h, S, self.k, C.byref(self.det))
+        if nstate == 0:
+            raise TcrError(f"StreamingDetector: {lib.tcr_last_error().decode()}")
+        nws = lib.tcr_stream_workspace_bytes(C.byref(cfg), net._h, S, self.k)
+        if nws == 0:
+            raise TcrError(f"StreamingDetector: {lib.tcr_last_error().decode()}")
+        if frozen_ss is not None:
+            net._check_tensor(frozen_ss, "frozen table")
+        self._frozen = frozen_ss
+        self._frozen_ver = (net.params._version, net._kver, net.params.data_ptr())
+        dev, ncls = self.device, net.num_classes
+        self.state = torch.empty(nstate // 4, dtype=torch.float32, device=dev)
+        self.workspace = torch.empty(nws // 4, dtype=torch.float32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.out = StreamOutput(torch.empty((S, ncls), **f32), torch.empty((S, ncls), **f32), torch.empty((S, ncls), **f32),
+                                torch.empty(S, **i32), torch.empty(S, **f32), torch.empty(S, **i32))
+        self._reset_dev = torch.zeros(S, dtype=torch.uint8, device=dev)
+        self._pending: Optional[np.ndarray] = None
+        lib.check(lib.tcr_stream_init(C.byref(cfg), frontend.plan.data_ptr(), net._h, S, self.k, C.byref(self.det),
+                                      self.state.data_ptr(), self.workspace.data_ptr(), self.workspace.numel() * 4, net._stream()),
+                  "tcr_stream_init")
+
+    # ---- detector settings in steps ------------------------------------------------------------------------------------
+    @property
+    def average_steps(self) -> int:
+        return self.det.average_steps
+
+    @property
+    def suppression_steps(self) -> int:
+        return self.det.suppression_steps
+
+    # ---- stream control -----------------------------------------------------------------------------------------------
+    def reset(self, mask_or_indices: Union[np.ndarray, torch.Tensor, Iterable[int]]) -> None:
+        """Return streams to the initial state (a silent clip, empty ring, no detection yet) at the NEXT push, before its samples
+        are appended.  A bool / uint8 mask of S entries, or stream indices (any other integer type)."""
+        if isinstance(mask_or_indices, torch.Tensor):
+            mask_or_indices = mask_or_indices.cpu().numpy()
+        arr = np.asarray(mask_or_indices if not isinstance(mask_or_indices, (set, frozenset)) else sorted(mask_or_indices))
+        if arr.dtype in (np.bool_, np.uint8):
+            if arr.shape != (self.n_streams,):
+                raise TcrError(f"reset mask must have {self.n_streams} entries, got shape {arr.shape}")
+            mask = arr.astype(bool)
+        else:
+            idx = arr.astype(np.int64).reshape(-1)
+            if idx.size and (idx.min() < 0 or idx.max() >= self.n_streams):
+                raise TcrError(f"reset: stream index outside 0..{self.n_streams - 1}")
+            mask = np.zeros(self.n_streams, bool)
+            mask[idx] = True
+        self._pending = mask if self._pending is None else (self._pending | mask)
+
+    def _take_reset(self) -> Optional[int]:
+        if self._pending is None:
+            return None
+        self._reset_dev.copy_(torch.from_numpy(self._pending.astype(np.uint8)))
+        self._pending = None
+        return self._reset_dev.data_ptr()
+
+    def window(self) -> torch.Tensor:
+        """The streams' current window features, planar [S, n_coef, T + 2*HALO] (a view of the state)."""
+        cfg = self.frontend.cfg
+        n = self.n_streams * cfg.n_coef * padded_len(cfg.n_frames)
+        return self.state[:n].view(self.n_streams, cfg.n_coef, padded_len(cfg.n_frames))
+
+    # ---- steps --------------------------------------------------------------------------------------------------------
+    def _check_samples(self, samples: torch.Tensor) -> None:
+        if samples.dim() != 2 or tuple(samples.shape) != (self.n_streams, self.step_samples):
+            raise TcrError(f"push expects samples [{self.n_streams}, {self.step_samples}] (k * hop per stream), got {tuple(samples.shape)}")
+        self.net._check_tensor(samples, "stream samples")
+
+    def _table(self) -> torch.Tensor:
+        return self._frozen if self._frozen is not None else self.net._folded_table()
+
+    def _args(self, samples: torch.Tensor, ss: torch.Tensor, reset_ptr, stream):
+        o, fe, net = self.out, self.frontend, self.net
+        return (C.byref(fe.cfg), fe.plan.data_ptr(), net._h, net.params.data_ptr(), ss.data_ptr(), self.n_streams, self.k, C.byref(self.det),
+                samples.data_ptr(), reset_ptr, self.state.data_ptr(), self.workspace.data_ptr(), self.workspace.numel() * 4,
+                o.logits.data_ptr(), o.probs.data_ptr(), o.smoothed.data_ptr(), o.top.data_ptr(), o.score.data_ptr(), o.is_new.data_ptr(),
+                stream)
+
+    def push(self, samples: torch.Tensor) -> StreamOutput:
+        """Append samples [S, k * hop] (float32, on the device) to every stream; one step.  Refolds BN first when the net's weights
+        changed (without `frozen_ss`); with `frozen_ss`, raises once the conv / fc arena changed since construction."""
+        self._check_samples(samples)
+        if self._frozen is not None:
+            self._check_frozen_arena()
+        ss = self._table()
+        self.lib.check(self.lib.tcr_stream_step(*self._args(samples, ss, self._take_reset(), self.net._stream())), "tcr_stream_step")
+        self.net._note_fold_reader()
+        return self.out
+
+    def _check_frozen_arena(self):
+        if (self.net.params._version, self.net._kver, self.net.params.data_ptr()) != self._frozen_ver:
+            raise TcrError("StreamingDetector: the network's weights changed since the frozen table was bound; build a new detector")
+
+    def prepared(self, samples_buffer: torch.Tensor):
+        """A zero-argument callable that runs one step on `samples_buffer` (fill it in place between calls) with every pointer bound,
+        on the stream current now: the per-step cost a C / C++ host of the ABI sees.  Like `TCResNet.waveform_call` it refuses to
+        run once the variables / moving statistics (or, with `frozen_ss`, the arena) changed since it was prepared: prepare it again.
+        Resets requested with `reset` are applied by the next call."""
+        self._check_samples(samples_buffer)
+        if self._frozen is not None:
+            self._check_frozen_arena()
+            ss = self._frozen
+        else:
+            ss = self.net._folded_table()
+            self.net._note_fold_reader()
+        net = self.net
+        stream = net._stream()
+        args = self._args(samples_buffer, ss, None, stream)
+        args_reset = self._args(samples_buffer, ss, self._reset_dev.data_ptr(), stream)
+        fn, check, out = self.lib.tcr_stream_step, self.lib.check, self.out
+        kver = (net.params._version, net.stats._version, net._kver)
+        keep = (samples_buffer, ss)
+
+        def call(_keep=keep):
+            if (net.params._version, net.stats._version, net._kver) != kver:
+                raise TcrError("StreamingDetector.prepared: the weights changed since the call was prepared; prepare it again")
+            bound = args
+            if self._pending is not None:
+                self._take_reset()
+                bound = args_reset
+            rc = fn(*bound)
+            if rc:
+                check(rc, "tcr_stream_step")
+            return out
+        return call
