@@ -1,15 +1,18 @@
 #!/usr/bin/env python
 """bench.py -- utterances/s of the TC-ResNet keyword-spotting hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one eval-mode pass of the hot path over one batch of synthetic 1 s @ 16 kHz waveforms
 (waveform -> MFCC -> TCResNet8-1.0 -> softmax), BASELINE.json configs[1]: batch 4096 per GPU, 40/20 ms
 front-end (49x40 MFCC, the shape BASELINE.json names).  Inputs are resident in HBM before the timed region.
-N > 1 shards utterances across ranks with no collective (weak scaling).  The same JSON line also carries the
-training step (configs[2]: train-mode BN + backward + momentum, with the RCCL gradient all-reduce when N > 1),
-the 30/10 ms front-end variant, the roofline of the dominant kernel and the CPU baseline.
+N > 1 shards utterances across ranks with no collective (weak scaling).  A plain run times the headline alone:
+set-up, the untimed pre-warm, W warm-up steps, K timed steps, the optional dump and the JSON line.  With --full
+the line also carries what takes runs of its own: the cold and one-stream figures, the roofline of the dominant
+kernel, the secondary legs (batch-1 latency; training steps such as configs[2]: train-mode BN + backward +
+momentum, with the RCCL gradient all-reduce when N > 1; the 30/10 ms front-end; DS-CNN-L; the input stage) and
+the CPU baseline.
 """
 from __future__ import annotations
 
@@ -119,15 +122,22 @@ def main():
     ap.add_argument("--prewarm", type=int, default=100, help="untimed launches of the headline step BEFORE the warm-up steps: the first ~50 "
                     "launches on an idle GPU run ~15 %% slower while the clocks ramp, whatever --warmup says (reported as pre_warm_launches)")
     ap.add_argument("--batch", type=int, default=BATCH, help="utterances per GPU per step (BASELINE config: 4096)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the train / 3010 legs (profiling runs); same as --legs none")
-    ap.add_argument("--legs", default="all", help="secondary legs to run next to the headline: 'all', 'none' or a comma list of " + ", ".join(LEGS))
+    ap.add_argument("--full", action="store_true", help="besides the headline, measure what takes runs of its own: the cold and one-stream "
+                    "figures, the dominant kernel's roofline, the secondary legs (--legs) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the train / 3010 legs (profiling runs); same as --legs none")
+    ap.add_argument("--legs", default=None, help="with --full: secondary legs to run next to the headline: 'all' (the default), 'none' or a "
+                    "comma list of " + ", ".join(LEGS))
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the (logits, probs) of the last timed headline step to "
                     "DIR/logits.npy and DIR/probs.npy (float32; with N > 1 ranks: logits_rank<r>.npy ...), to compare two builds output for output")
     args = ap.parse_args()
-    if args.no_extras or args.legs == "none":
+    if not args.full:
+        if args.legs not in (None, "none"):
+            ap.error("--legs: the secondary legs run with --full")
         legs = set()
-    elif args.legs == "all":
+    elif args.no_extras or args.legs == "none":
+        legs = set()
+    elif args.legs in (None, "all"):
         legs = set(LEGS) if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and os.environ.get("TCR_BENCH_FORCE_DIST") != "1" else {"train", "train14", "train14_3010"}      # (several ranks: the two legs whose gradient all-reduce crosses xGMI -- configs[2] and configs[3], TCResNet14-1.5 at global batch 4096 N; see "secondary legs" below)
     else:
         legs = set(x for x in args.legs.split(",") if x)
@@ -221,16 +231,16 @@ def main():
     # (0) the COLD figure: the headline schedule's first 20 steps after 5 warm-up steps, ahead of every pre-warm launch of
     #     this process -- what `--steps 20 --warmup 5 --prewarm 0` sees on an idle GPU whose clocks have not ramped.  Reported, never `value`.
     cold_ms = None
-    if not EMU and args.prewarm > 0:
+    if args.full and not EMU and args.prewarm > 0:
         cold_fn = (lambda: pipe.submit(wav)) if pipelined else (lambda: seq_step())
         dt_cold = timed(cold_fn, 20, 5, dist_on)
         cold_ms = round(dt_cold / 20 * 1e3, 4)
-    # (1) clock pre-warm + the one-stream sequence: labelled, untimed by the contract (outside the K timed steps and the W warm-up steps).
-    #     The first ~50 launches on an idle GPU run ~15 % slower whatever --warmup says; the sequence's sampled events give the solo kernels.
+    # (1) clock pre-warm + (--full) the one-stream sequence: labelled, untimed by the contract (outside the K timed steps and the W warm-up
+    #     steps).  The first ~50 launches on an idle GPU run ~15 % slower whatever --warmup says; the sequence's sampled events give the solo kernels.
     for _ in range(max(0, args.prewarm)):
         seq_step()
     sync()
-    nseq = 0 if EMU else max(64, args.steps)
+    nseq = max(64, args.steps) if args.full and not EMU else 0
     sev = {i: [new_event() for _ in range(3)] for i in range(nseq) if i % EV_EVERY == 2}
     c_seq = [0]
 
@@ -261,46 +271,8 @@ def main():
         dump_outputs(args.dump_outputs, {"logits": last_out[0][0], "probs": last_out[0][1]}, rank, world)
     value = world * B * args.steps / dt
     timed_ev = [ev[i] for i in range(args.warmup, args.warmup + args.steps) if i in ev]
-    fe_in = sum(e[0].elapsed_time(e[1]) for e in timed_ev) / len(timed_ev)          # inside the timed region (co-running when pipelined)
-    net_in = sum(e[1].elapsed_time(e[2]) for e in timed_ev) / len(timed_ev)
     per_step = sorted(e[0].elapsed_time(e[2]) for e in timed_ev)
     pct = lambda q: round(per_step[min(len(per_step) - 1, int(q * len(per_step)))], 4)
-    if sev:
-        fe_ms = sum(e[0].elapsed_time(e[1]) for e in sev.values()) / len(sev)       # solo: the one-stream sequence
-        net_ms = sum(e[1].elapsed_time(e[2]) for e in sev.values()) / len(sev)
-    else:
-        fe_ms, net_ms = fe_in, net_in
-    bitwise = None
-    if pipelined:
-        sync()
-        ref_logits = net.forward_infer(fe(wav))[0]
-        bitwise = bool(all(torch.equal(o[0], ref_logits) for o in step_out))
-
-    # dominant kernel = the fused front-end (one launch per step): waveform read once, [40][49] tile written once
-    fe_bytes = B * (16000 * 4 + 40 * w["frames"] * 4)
-    fe_flops = B * w["mfcc_flops"]
-    fe_gbs = fe_bytes / (fe_ms * 1e-3) / 1e9
-    fe_tf = fe_flops / (fe_ms * 1e-3) / 1e12
-    hbm_frac, fp_frac = fe_gbs / HBM_PEAK_GBS, fe_tf / FP32_PEAK_TFLOPS
-    if fp_frac >= hbm_frac:
-        # ("valu": the kernel's flops issue on the packed-FP32 vector pipe, not on the matrix cores -- the f32 peak of both pipes is the
-        #  same 157.3 TFLOP/s, so `peak` is what the contract's "mfma" bound would carry)
-        roof = {"bound": "valu", "achieved": round(fe_tf, 3), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(fp_frac, 4)}
-    else:
-        roof = {"bound": "hbm", "achieved": round(fe_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(hbm_frac, 4)}
-    traffic, traffic_src = pmc_traffic("frontend_pk3_kernel<512,")
-    prof_avg_us, prof_src = profile_avg_us("frontend_pk3_kernel<512,")
-    roof.update({"traffic": traffic, "traffic_source": traffic_src, "profile_avg_us": prof_avg_us, "profile_source": prof_src, "kernel": "frontend_pk3_kernel<512, 10, false>", "kernel_ms": round(fe_ms, 4),
-                 "kernel_ms_in_timed_region": round(fe_in, 4),
-                 "note": "f32 VALU pipe; its 157.3 TFLOP/s peak equals the exact-f32 MFMA peak. kernel_ms: HIP-event-bracketed launches on the launch "
-                         "stream in the one-stream sequence of this run (the kernel alone on the chip; every 8th step: an event record costs ~4 us of "
-                         "dispatch gap); kernel_ms_in_timed_region: the same brackets inside the timed region, where the kernel shares the chip with the "
-                         "other stream's network kernel -- see pair_roofline for the co-running pair",
-                 "hbm_gbs": round(fe_gbs, 1), "hbm_frac": round(hbm_frac, 4), "fp32_tflops": round(fe_tf, 3), "fp32_frac": round(fp_frac, 4),
-                 "algorithmic_bytes_per_launch": fe_bytes, "algorithmic_flops_per_launch": fe_flops})
-    if prof_avg_us and abs(prof_avg_us - fe_ms * 1e3) > 0.05 * fe_ms * 1e3:
-        roof["profile_stale_warning"] = (f"committed profile says {prof_avg_us} us per launch, this run measured {round(fe_ms * 1e3, 1)} us (> 5 % apart): "
-                                         f"{prof_src} (and the PMC traffic beside it) describes another build or another clock state")
     whole_tf = value / world * (w["mfcc_flops"] + w["net_flops"]) / 1e12
     out = {
         "metric": "utterances/sec (1 s@16 kHz) TCResNet8-1.0 forward", "value": round(value, 1), "unit": "utterances/s",
@@ -310,28 +282,70 @@ def main():
                    "global_batch": world * B, "parallelism": f"dp{world} (utterance shards, no collective)", "collective_backend": dist.get_backend() if dist_on else None,
                    "schedule": "whole batches alternating between three streams, three in flight (InferencePipeline 'alternate', ways 3)" if pipelined else "one stream"},
         "collective_backend": coll, "collectives_per_step": {"forward": 0},       # (eval forward: replicas only; the training legs add theirs below)
-        "roofline": roof,
         # the co-running pair: algorithmic flops of BOTH kernels of a step / the step time of the timed region
         "pair_roofline": {"bound": "mfma", "achieved": round(whole_tf, 3), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(whole_tf / FP32_PEAK_TFLOPS, 4),
                           "kernels": ["frontend_pk3_kernel<512, 10, false>", "net_fused_tc8_kernel<8, 49, 0, 3>"],
                           "algorithmic_flops_per_step": B * (w["mfcc_flops"] + w["net_flops"])},
-        "phases_ms": {"frontend": round(fe_ms, 4), "net": round(net_ms, 4), "frontend_in_timed_region": round(fe_in, 4), "net_in_timed_region": round(net_in, 4)},
-        "sequential": {"ms_per_step": round(dt_seq / nseq * 1e3, 4) if nseq else None, "steps": nseq,
-                       "what": "the same batches on ONE stream (front-end, network back to back), timed in this run ahead of the warm-up steps"},
-        "bitwise_equal_to_sequential": bitwise,
         ("batch_latency_ms_p10_p50_p90" if pipelined else "step_ms_p10_p50_p90"): [pct(0.1), pct(0.5), pct(0.9)],     # (pipelined: e0 -> e2 of a batch on its own stream, three batches in flight)
         "event_timed_steps": len(timed_ev),
         "pre_warm_launches": max(0, args.prewarm) + (max(0, args.prewarm) // 2 if pipelined else 0),
-        "cold_ms_per_step": cold_ms,        # (steps 6..25 of this process's headline schedule, ahead of the pre-warm; None with --prewarm 0, where ms_per_step IS the cold figure)
         "whole_path_fp32_frac": round(whole_tf / FP32_PEAK_TFLOPS, 4),
         "whole_path_hbm_frac": round(value / world * 64048 / 1e9 / HBM_PEAK_GBS, 4),
     }
+
+    if args.full:
+        fe_in = sum(e[0].elapsed_time(e[1]) for e in timed_ev) / len(timed_ev)          # inside the timed region (co-running when pipelined)
+        net_in = sum(e[1].elapsed_time(e[2]) for e in timed_ev) / len(timed_ev)
+        if sev:
+            fe_ms = sum(e[0].elapsed_time(e[1]) for e in sev.values()) / len(sev)       # solo: the one-stream sequence
+            net_ms = sum(e[1].elapsed_time(e[2]) for e in sev.values()) / len(sev)
+        else:
+            fe_ms, net_ms = fe_in, net_in
+        bitwise = None
+        if pipelined:
+            sync()
+            ref_logits = net.forward_infer(fe(wav))[0]
+            bitwise = bool(all(torch.equal(o[0], ref_logits) for o in step_out))
+
+        # dominant kernel = the fused front-end (one launch per step): waveform read once, [40][49] tile written once
+        fe_bytes = B * (16000 * 4 + 40 * w["frames"] * 4)
+        fe_flops = B * w["mfcc_flops"]
+        fe_gbs = fe_bytes / (fe_ms * 1e-3) / 1e9
+        fe_tf = fe_flops / (fe_ms * 1e-3) / 1e12
+        hbm_frac, fp_frac = fe_gbs / HBM_PEAK_GBS, fe_tf / FP32_PEAK_TFLOPS
+        if fp_frac >= hbm_frac:
+            # ("valu": the kernel's flops issue on the packed-FP32 vector pipe, not on the matrix cores -- the f32 peak of both pipes is the
+            #  same 157.3 TFLOP/s, so `peak` is what the contract's "mfma" bound would carry)
+            roof = {"bound": "valu", "achieved": round(fe_tf, 3), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(fp_frac, 4)}
+        else:
+            roof = {"bound": "hbm", "achieved": round(fe_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(hbm_frac, 4)}
+        traffic, traffic_src = pmc_traffic("frontend_pk3_kernel<512,")
+        prof_avg_us, prof_src = profile_avg_us("frontend_pk3_kernel<512,")
+        roof.update({"traffic": traffic, "traffic_source": traffic_src, "profile_avg_us": prof_avg_us, "profile_source": prof_src, "kernel": "frontend_pk3_kernel<512, 10, false>", "kernel_ms": round(fe_ms, 4),
+                     "kernel_ms_in_timed_region": round(fe_in, 4),
+                     "note": "f32 VALU pipe; its 157.3 TFLOP/s peak equals the exact-f32 MFMA peak. kernel_ms: HIP-event-bracketed launches on the launch "
+                             "stream in the one-stream sequence of this run (the kernel alone on the chip; every 8th step: an event record costs ~4 us of "
+                             "dispatch gap); kernel_ms_in_timed_region: the same brackets inside the timed region, where the kernel shares the chip with the "
+                             "other stream's network kernel -- see pair_roofline for the co-running pair",
+                     "hbm_gbs": round(fe_gbs, 1), "hbm_frac": round(hbm_frac, 4), "fp32_tflops": round(fe_tf, 3), "fp32_frac": round(fp_frac, 4),
+                     "algorithmic_bytes_per_launch": fe_bytes, "algorithmic_flops_per_launch": fe_flops})
+        if prof_avg_us and abs(prof_avg_us - fe_ms * 1e3) > 0.05 * fe_ms * 1e3:
+            roof["profile_stale_warning"] = (f"committed profile says {prof_avg_us} us per launch, this run measured {round(fe_ms * 1e3, 1)} us (> 5 % apart): "
+                                             f"{prof_src} (and the PMC traffic beside it) describes another build or another clock state")
+        out.update({
+            "roofline": roof,
+            "phases_ms": {"frontend": round(fe_ms, 4), "net": round(net_ms, 4), "frontend_in_timed_region": round(fe_in, 4), "net_in_timed_region": round(net_in, 4)},
+            "sequential": {"ms_per_step": round(dt_seq / nseq * 1e3, 4) if nseq else None, "steps": nseq,
+                           "what": "the same batches on ONE stream (front-end, network back to back), timed in this run ahead of the warm-up steps"},
+            "bitwise_equal_to_sequential": bitwise,
+            "cold_ms_per_step": cold_ms,        # (steps 6..25 of this process's headline schedule, ahead of the pre-warm; None with --prewarm 0, where ms_per_step IS the cold figure)
+        })
 
     if EMU:
         out["rehearsal"] = "CPU emulator build of the kernel sources (TCR_BENCH_EMU): control flow only, NOT a measurement"
         out["data"] = "synthetic (CPU rehearsal)"
 
-    # ---------------- secondary legs ----------------
+    # ---------------- secondary legs (--full) ----------------
     # The headline above is complete at this point.  The legs below never ran on more than one GPU before the driver's scaling runs, so
     # with several ranks (a) only the training leg runs by default -- the one whose gradient all-reduce crosses xGMI --, (b) an exception
     # in a leg is recorded as {"error": ...} under "secondary_legs" instead of losing the line, and (c) a watchdog prints the line as it
@@ -584,14 +598,15 @@ def main():
                               "algorithmic_bytes_per_launch": aug_bytes,
                               "workload": f"tcr_augment_fwd: int16 PCM -> float, +-1600-sample shift, background mix (80 % of utterances), clip; batch {B}/GPU"}
 
-    try:
-        secondary()
-    except Exception as e:                          # (one rank: let it surface -- the GPU tests and the driver's N = 1 run want the traceback)
-        if not dist_on:
-            raise
-        out["secondary_legs"] = {"error": f"{type(e).__name__}: {e}"[:400]}
+    if args.full:
+        try:
+            secondary()
+        except Exception as e:                          # (one rank: let it surface -- the GPU tests and the driver's N = 1 run want the traceback)
+            if not dist_on:
+                raise
+            out["secondary_legs"] = {"error": f"{type(e).__name__}: {e}"[:400]}
     legs_done.set()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not EMU:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not EMU:
         out["cpu_baseline"] = cpu_baseline()
     emit()
     if dist_on:
@@ -636,7 +651,7 @@ def pmc_traffic(kernel: str):
 
 def profile_avg_us(kernel: str):
     """Average launch duration of `kernel` in the committed forward-only rocprofv3 --kernel-trace --stats summary of this command
-    (`bench.py --no-extras --no-cpu-baseline` under scripts/gpu_prof.sh -> profiles/*_fwd_kernel_stats.csv): the file the
+    (`bench.py --full --no-extras --no-cpu-baseline` under scripts/gpu_prof.sh -> profiles/*_fwd_kernel_stats.csv): the file the
     roofline's `kernel_ms` can be recomputed from."""
     import csv
     import glob

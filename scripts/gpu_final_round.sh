@@ -4,5 +4,6 @@
 TAG=${1:-final}
 cd $GRAFT_REPO_ROOT
 bash scripts/gpu_round.sh $TAG
-timeout 500 python bench.py --steps 20 --warmup 5 > gpurun_out/$TAG/bench_driver_flags.json 2> gpurun_out/$TAG/bench_driver_flags.err; echo "bench (driver flags) rc=$?"
+OUT=${OUT:-results/$TAG}; mkdir -p $OUT
+timeout 500 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_flags.json 2> $OUT/bench_driver_flags.err; echo "bench (driver flags) rc=$?"
 bash scripts/gpu_prof_train_all.sh

@@ -244,7 +244,7 @@ BENCH_COLLECTIVES = {"forward": 0, "train": 1.0, "train_tcresnet14_1.5": 1.0, "t
 
 
 def _bench_plain_command(env_extra, batch, legs_ok=True, ranks=2):
-    """`python bench.py --gpus N ...` as a PLAIN command (no launcher, WORLD_SIZE unset): bench.py launches its own N ranks under
+    """`python bench.py --gpus N --full ...` with no launcher (WORLD_SIZE unset): bench.py launches its own N ranks under
     torch.distributed.run, rank 0 prints the one JSON line."""
     import json
     import subprocess
@@ -252,7 +252,7 @@ def _bench_plain_command(env_extra, batch, legs_ok=True, ranks=2):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(env_extra)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--prewarm", "0", "--batch", str(batch),
-           "--no-cpu-baseline"]           # (several ranks: the default legs are the training legs, configs[2] and configs[3] at 49 and 98 frames)
+           "--full", "--no-cpu-baseline"]           # (several ranks: the default legs are the training legs, configs[2] and configs[3] at 49 and 98 frames)
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -319,7 +319,7 @@ def test_bench_single_rank_goes_through_rccl(hip_lib):
     env.update({"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port),
                 "TCR_BENCH_FORCE_DIST": "1", "TCR_DP_FORCE": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--prewarm", "4", "--batch", "512",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
