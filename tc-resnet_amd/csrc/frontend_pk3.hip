@@ -24,6 +24,16 @@ namespace tcr {
 
 namespace {
 
+// One LDS read that the compiler does not pair with the next one.  Two 8-byte reads a few slots apart become one ds_read2_b64
+// (two 4 x 16-lane accesses: 8 LDS-array cycles) where two ds_read_b64 (2 x 32 lanes each) take 2 + 2; the empty asm orders memory
+// accesses, so neither the IR load vectoriser nor the DS load/store optimiser merges across it.  No instruction of its own (plain C++
+// on the host emulator too); the compiler still counts the read on lgkmcnt and waits for it where the value is used.
+template <class T> __device__ __forceinline__ T lds_read_unpaired(const T* p) {
+    const T v = *p;
+    asm volatile("" ::: "memory");
+    return v;
+}
+
 // 4-point forward DFT (W4 = -i), in place: 8 packed instructions.
 __device__ __forceinline__ void pk3_dft4(v2& a, v2& b, v2& c, v2& d) {
     const v2 t0 = a + c, t1 = a - c, t2 = b + d, t3 = b - d;
@@ -100,7 +110,7 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
     __shared__ v2 s_t[4 * TILEW];
     __shared__ v2 s_ud[4 * FPWV * USZ];
     __shared__ float s_lm[4 * NMEL * 16];
-    __shared__ v2 s_wit[kMelItemBins * NIT];
+    __shared__ v4 s_wit[kMelItemBins / 2 * NIT];    // [bin pair][item]: the slopes of bins 2 bp and 2 bp + 1 in one ds_read_b128
     __shared__ int s_items[kItemsLds ? NIT : 1];
     constexpr bool kBandsLds = true;                // the bands' item ranges from LDS (one ds_read_b32 per band and round instead of 2 - 4 registers)
     __shared__ int s_band[kBandsLds ? NMEL : 1];
@@ -111,7 +121,11 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
     {
         const float fold = MAG ? 0.5f : 0.25f;
         const v2* wit = reinterpret_cast<const v2*>(a.mel_wit);
-        for (int i = tid; i < kMelItemBins * NIT; i += 256) s_wit[i] = wit[i] * fold;
+        for (int i = tid; i < kMelItemBins / 2 * NIT; i += 256) {
+            const int bp = i / NIT, it = i % NIT;
+            const v2 w0 = wit[2 * bp * NIT + it] * fold, w1 = wit[(2 * bp + 1) * NIT + it] * fold;
+            s_wit[i] = (v4){w0.x, w0.y, w1.x, w1.y};
+        }
         if (kItemsLds)
             for (int i = tid; i < NIT; i += 256) s_items[i] = a.mel_items[i];
         if (kBandsLds && tid < NMEL) s_band[tid] = a.mel_ifirst[tid] | (a.mel_ifirst[tid + 1] << 8) | (a.mel_ifirst[tid + 2] << 16);
@@ -204,7 +218,7 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
             const v2* wsrc = s_wnd + lf;
             v2 wnd[QV];
 #pragma unroll
-            for (int q = 0; q < QV; ++q) wnd[q] = wsrc[q * LPF];
+            for (int q = 0; q < QV; ++q) wnd[q] = lds_read_unpaired(wsrc + q * LPF);     // (ds_read_b64 each)
 #pragma unroll
             for (int q = 0; q < 16; ++q) v[q] = q < QV ? xa[q] * wnd[q] : (v2){0.f, 0.f};
         }
@@ -220,13 +234,13 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
             for (int j = 0; j < 8; ++j) wa[j * RS] = v[j];
             wave_sync();
 #pragma unroll
-            for (int c = 0; c < 8; ++c) v[c] = rd[c];
+            for (int c = 0; c < 8; ++c) v[c] = lds_read_unpaired(rd + c);           // (RS odd: 32 distinct 8-byte slots per 32 lanes)
             wave_sync();
 #pragma unroll
             for (int j = 0; j < 8; ++j) wb[j * RS] = v[8 + j];
             wave_sync();
 #pragma unroll
-            for (int c = 0; c < 8; ++c) v[8 + c] = rd[c];
+            for (int c = 0; c < 8; ++c) v[8 + c] = lds_read_unpaired(rd + c);
         }
         // ---------------- second radix-16 pass: register n holds input n ^ 8h -> odd outputs carry (-1)^h ----------------
         pk3_dft16(v);
@@ -301,13 +315,16 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
                     for (int q = 1; q < TRIPS; ++q) d = tr == q ? item_d[kItemsLds ? 0 : q] : d;
                 }
                 const float* pk = P + (d & 1023);
-                const v2* wk = s_wit + it;
+                const v4* wk = s_wit + it;
                 float p[kMelItemBins];
                 v2 wv[kMelItemBins];
 #pragma unroll
-                for (int b = 0; b < kMelItemBins; ++b) {
-                    p[b] = pk[b];
-                    wv[b] = wk[b * NIT];
+                for (int b = 0; b < kMelItemBins; ++b) p[b] = pk[b];
+#pragma unroll
+                for (int bp = 0; bp < kMelItemBins / 2; ++bp) {    // (ds_read_b128, 16 consecutive lanes on 256 consecutive bytes: 4 cycles, no conflicts)
+                    const v4 w = wk[bp * NIT];
+                    wv[2 * bp] = (v2){w.x, w.y};
+                    wv[2 * bp + 1] = (v2){w.z, w.w};
                 }
                 v2 ud = (v2){0.f, 0.f};
 #pragma unroll
@@ -319,26 +336,32 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
         // ---------------- log(mel + 1e-6) -> [mel][frame ^ swizzle] ----------------
         {
             const int c = r * FPWV + fw;                    // column of the wave's DCT tile
+            constexpr int NB = NMEL / LPF;
+            constexpr int MAXC = NC == 512 ? 3 : 2;
+            float up[NB][MAXC], dn[NB][MAXC];
 #pragma unroll
-            for (int i = 0; i < NMEL / LPF; ++i) {
+            for (int i = 0; i < NB; ++i) {                  // every band's cells first (single ds_read_b64 each), the sums behind them
+                const int bi = kBandsLds ? bi_pre[i] : band_i[kBandsLds ? 0 : i];
+                const int i0 = bi & 255, i1 = (bi >> 8) & 255;
+#pragma unroll
+                for (int cc = 0; cc < MAXC; ++cc) {
+                    up[i][cc] = lds_read_unpaired(UD + i0 + cc).x;      // (i0, i1 <= NIT: inside the row; cells past the band's items are read and dropped)
+                    dn[i][cc] = lds_read_unpaired(UD + i1 + cc).y;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < NB; ++i) {
                 const int m = lf + LPF * i;
                 const int bi = kBandsLds ? bi_pre[i] : band_i[kBandsLds ? 0 : i];
                 const int i0 = bi & 255, i1 = (bi >> 8) & 255, i2 = bi >> 16;
-                constexpr int MAXC = NC == 512 ? 3 : 2;
-                float up[MAXC], dn[MAXC];
-#pragma unroll
-                for (int cc = 0; cc < MAXC; ++cc) {
-                    up[cc] = UD[i0 + cc].x;                 // (i0, i1 <= NIT: inside the row; cells past the band's items are read and dropped)
-                    dn[cc] = UD[i1 + cc].y;
-                }
                 // (nfft 1024: a segment has <= MAXC items -- the launcher sends other filterbanks to frontend_pk.hip --, so no loop behind
                 //  the unconditional reads; nfft 512: the reference filterbank has a few 3-item segments, the loops stay)
                 float mel = 0.f;
 #pragma unroll
-                for (int cc = 0; cc < MAXC; ++cc) mel += i0 + cc < i1 ? up[cc] : 0.f;
+                for (int cc = 0; cc < MAXC; ++cc) mel += i0 + cc < i1 ? up[i][cc] : 0.f;
                 if (NC != 512) for (int it = i0 + MAXC; it < i1; ++it) mel += UD[it].x;
 #pragma unroll
-                for (int cc = 0; cc < MAXC; ++cc) mel += i1 + cc < i2 ? dn[cc] : 0.f;
+                for (int cc = 0; cc < MAXC; ++cc) mel += i1 + cc < i2 ? dn[i][cc] : 0.f;
                 if (NC != 512) for (int it = i1 + MAXC; it < i2; ++it) mel += UD[it].y;
                 LM[m * 16 + (c ^ ((m >> 1) & 15))] = fast_log(a.log_floor ? fmaxf(mel, 1e-12f) : mel + 1e-6f);
             }
