@@ -435,6 +435,21 @@ int tcr_stream_step(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr
                     const uint8_t* reset, void* state, void* workspace, size_t ws_bytes, float* logits, float* probs,
                     float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream);
 
+/* Offline scanning: every step of N signals of equal length L (samples [N][L] float32, L a positive multiple of k * hop) in one
+ * call.  For signal n and step i = 0 .. L / (k * hop) - 1, logits / probs / smoothed [N][steps][num_classes] and top / score /
+ * is_new [N][steps] are bitwise what a fresh stream (tcr_stream_init, then steps without resets) returns from its (i + 1)-th step
+ * when fed signal n k * hop samples at a time, with the same cfg, frozen_ss, k and det: the window of step i is frames
+ * [(i + 1) k, (i + 1) k + T) of the signal with n_samples zeros in front, and the detector rule is tcr_stream_step's.
+ * Configurations: those tcr_stream_* accept (the same refusals, the same messages).  The workspace does not depend on L:
+ * tcr_scan_workspace_bytes sizes one for chunks of up to max_windows windows (0: invalid arguments, see tcr_last_error), and
+ * tcr_scan runs the largest chunks the bytes passed hold (TCR_ERR_WORKSPACE below one window).  Outputs are caller-owned device
+ * memory sized by L; everything is enqueued on `stream`. */
+size_t tcr_scan_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_net* net, int k, int max_windows);
+int tcr_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params, const float* frozen_ss,
+             int n_signals, int64_t n_samples, int k, const tcr_detect_cfg* det, const float* samples /* [N][L] */,
+             void* workspace, size_t ws_bytes, float* logits, float* probs, float* smoothed /* [N][steps][C] */,
+             int32_t* top, float* score, int32_t* is_new /* [N][steps] */, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Instrumentation                                                                             */
 /* ------------------------------------------------------------------------------------------ */

@@ -492,5 +492,7 @@ int launch_frontend_pk3_stream(int nc, const FrontendArgs& a, int n_items, hipSt
 
 }  // namespace tcr
 
-// The streaming detector (tcr_stream_*) that drives the STREAM instances is compiled in this translation unit.
+// The streaming detector (tcr_stream_*) and the offline scan (tcr_scan) that drive the STREAM instances are compiled in this
+// translation unit.
 #include "stream.hip"
+#include "scan.hip"

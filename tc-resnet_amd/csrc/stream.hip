@@ -165,6 +165,24 @@ __global__ __launch_bounds__(256) void stream_init_kernel(float* window, const f
     }
 }
 
+// The detector's smoothing (tcr_stream_step): `count` values of one class, oldest to newest (next() yields them in that order), summed
+// in float32 -- the loads requested eight at a time, the adds in order -- times (1.0f / count).  stream_detect_kernel and
+// scan_smooth_kernel (scan.hip) both call it, so an offline scan smooths with the streaming detector's expression.
+template <class Next>
+__device__ __forceinline__ float smooth_mean(int count, Next next) {
+    float acc = 0.f;
+    int i = 0;
+    for (; i + 8 <= count; i += 8) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = next();
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc += v[j];
+    }
+    for (; i < count; ++i) acc += next();
+    return acc * (1.0f / (float)count);
+}
+
 struct DetectArgs {
     const float* probs;         // [S][C]
     const uint8_t* reset;
@@ -198,23 +216,11 @@ __global__ __launch_bounds__(256) void stream_detect_kernel(const DetectArgs a) 
         head = head + 1 == W ? 0 : head + 1;
         count = min(count + 1, W);
         int slot = head - count < 0 ? head - count + W : head - count;        // oldest
-        float acc = 0.f;
-        int i = 0;
-        for (; i + 8 <= count; i += 8) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                v[j] = a.ring[slot * ring_row + sc];
-                slot = slot + 1 == W ? 0 : slot + 1;
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc += v[j];
-        }
-        for (; i < count; ++i) {
-            acc += a.ring[slot * ring_row + sc];
+        const float v = smooth_mean(count, [&]() {
+            const float x = a.ring[slot * ring_row + sc];
             slot = slot + 1 == W ? 0 : slot + 1;
-        }
-        const float v = acc * (1.0f / (float)count);
+            return x;
+        });
         a.smoothed[sc] = v;
         s_sm[threadIdx.x] = v;
     }
@@ -243,9 +249,10 @@ __global__ __launch_bounds__(256) void stream_detect_kernel(const DetectArgs a) 
 
 namespace {
 
-// the streaming front-end over `rows` staging rows of `stride` floats, k frames each, into window columns T - k .. T - 1
+// the streaming front-end over `rows` staging rows of `stride` floats, k frames each, into columns tp - 8 - k .. tp - 9 of rows of tp
+// columns (tp = 0: the window's T + 2 TCR_HALO, i.e. columns T - k .. T - 1; tcr_scan passes k + 2 TCR_HALO: columns 0 .. k - 1)
 int stream_frontend(const tcr_frontend_cfg& cfg, const void* plan_dev, const float* stage, int stride, int rows, int k, float* out,
-                    hipStream_t s) {
+                    hipStream_t s, int tp = 0) {
     FrontendArgs a;
     frontend_plan_args(&cfg, plan_dev, a);
     a.wav = stage;
@@ -255,7 +262,7 @@ int stream_frontend(const tcr_frontend_cfg& cfg, const void* plan_dev, const flo
     a.hop = cfg.hop;
     a.n_frames = k;
     a.n_coef = cfg.n_coef;
-    a.tp = tcr_padded_len(cfg.n_frames);
+    a.tp = tp > 0 ? tp : tcr_padded_len(cfg.n_frames);
     a.total_frames = rows * k;
     a.magnitude = cfg.method != 0;
     a.no_dct = cfg.method == 1;

@@ -106,6 +106,16 @@ class FrozenModel:
         from .streaming import StreamingDetector
         return StreamingDetector(self.engine, self.frontend, n_streams, frozen_ss=self.frozen_ss, **kw)
 
+    def scanner(self, **kw):
+        """A `scanning.KeywordScanner` over this artifact, like `streaming` (TC-ResNet with `include_preprocess` only).  kw:
+        frames_per_step, average_window_ms, min_count, detection_threshold, suppression_ms, max_windows."""
+        if self.meta["family"] != "tcresnet":
+            raise ValueError(f"keyword scanning runs TC-ResNet artifacts only (this one is {self.meta['family']})")
+        if self.frontend is None:
+            raise ValueError("keyword scanning needs an artifact exported with include_preprocess (it consumes raw audio)")
+        from .scanning import KeywordScanner
+        return KeywordScanner(self.engine, self.frontend, frozen_ss=self.frozen_ss, **kw)
+
     # ---- file format ----------------------------------------------------------------------------------------------
     def save(self, path: str) -> str:
         out = {"__meta__": np.frombuffer(json.dumps(self.meta, sort_keys=True).encode(), dtype=np.uint8)}

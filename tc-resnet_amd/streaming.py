@@ -34,7 +34,53 @@ def ms_to_steps(ms: float, step_ms: float) -> int:
     return int(round(float(ms) / step_ms))
 
 
-class StreamingDetector:
+class _Detection:
+    """What `StreamingDetector` and `scanning.KeywordScanner` share: the argument checks, the detector settings in steps and the
+    weight / fold rules (see `StreamingDetector`)."""
+
+    def _setup(self, what: str, noun: str, net: TCResNet, frontend: Frontend, frames_per_step: int, average_window_ms: float,
+               min_count: int, detection_threshold: float, suppression_ms: float) -> None:
+        if not isinstance(net, TCResNet):
+            raise TcrError(f"{what} runs TC-ResNet models only, got {type(net).__name__}")
+        if net.lib is not frontend.lib or net.device != frontend.device:
+            raise TcrError("the network and the front-end must use the same library and device")
+        self.net, self.frontend, self.lib, self.device = net, frontend, net.lib, net.device
+        self.k = int(frames_per_step)
+        cfg = frontend.cfg
+        if not 1 <= self.k <= cfg.n_frames:
+            raise TcrError(f"{what}: frames per step k = {self.k} outside 1..T = {cfg.n_frames}")
+        self.step_samples = self.k * cfg.hop
+        self.step_ms = 1000.0 * self.step_samples / cfg.sample_rate
+        self.det = DetectCfg(max(1, ms_to_steps(average_window_ms, self.step_ms)), int(min_count),
+                             max(0, ms_to_steps(suppression_ms, self.step_ms)), float(detection_threshold))
+        self._what, self._noun = what, noun
+
+    def _bind_frozen(self, frozen_ss: Optional[torch.Tensor]) -> None:
+        net = self.net
+        if frozen_ss is not None:
+            net._check_tensor(frozen_ss, "frozen table")
+        self._frozen = frozen_ss
+        self._frozen_ver = (net.params._version, net._kver, net.params.data_ptr())
+
+    # ---- detector settings in steps ------------------------------------------------------------------------------------
+    @property
+    def average_steps(self) -> int:
+        return self.det.average_steps
+
+    @property
+    def suppression_steps(self) -> int:
+        return self.det.suppression_steps
+
+    # ---- weights ------------------------------------------------------------------------------------------------------
+    def _table(self) -> torch.Tensor:
+        return self._frozen if self._frozen is not None else self.net._folded_table()
+
+    def _check_frozen_arena(self):
+        if (self.net.params._version, self.net._kver, self.net.params.data_ptr()) != self._frozen_ver:
+            raise TcrError(f"{self._what}: the network's weights changed since the frozen table was bound; build a new {self._noun}")
+
+
+class StreamingDetector(_Detection):
     """S concurrent streams through `frontend` and `net`, k = frames_per_step new frames per stream and step.
 
     average_window_ms / suppression_ms become steps of k * hop / sample_rate seconds (the nearest whole number; the averaging
@@ -50,19 +96,10 @@ class StreamingDetector:
     def __init__(self, net: TCResNet, frontend: Frontend, n_streams: int, frames_per_step: int = 1, average_window_ms: float = 1000,
                  min_count: int = 3, detection_threshold: float = 0.5, suppression_ms: float = 1500,
                  frozen_ss: Optional[torch.Tensor] = None):
-        if not isinstance(net, TCResNet):
-            raise TcrError(f"StreamingDetector runs TC-ResNet models only, got {type(net).__name__}")
-        if net.lib is not frontend.lib or net.device != frontend.device:
-            raise TcrError("the network and the front-end must use the same library and device")
-        self.net, self.frontend, self.lib, self.device = net, frontend, net.lib, net.device
-        self.n_streams, self.k = int(n_streams), int(frames_per_step)
+        self._setup("StreamingDetector", "detector", net, frontend, frames_per_step, average_window_ms, min_count, detection_threshold,
+                    suppression_ms)
+        self.n_streams = int(n_streams)
         cfg = frontend.cfg
-        if not 1 <= self.k <= cfg.n_frames:
-            raise TcrError(f"StreamingDetector: frames per step k = {self.k} outside 1..T = {cfg.n_frames}")
-        self.step_samples = self.k * cfg.hop
-        self.step_ms = 1000.0 * self.step_samples / cfg.sample_rate
-        self.det = DetectCfg(max(1, ms_to_steps(average_window_ms, self.step_ms)), int(min_count),
-                             max(0, ms_to_steps(suppression_ms, self.step_ms)), float(detection_threshold))
         S, lib = self.n_streams, self.lib
         if S <= 0:
             raise TcrError(f"StreamingDetector: n_streams must be positive (got {S})")
@@ -72,10 +109,7 @@ class StreamingDetector:
         nws = lib.tcr_stream_workspace_bytes(C.byref(cfg), net._h, S, self.k)
         if nws == 0:
             raise TcrError(f"StreamingDetector: {lib.tcr_last_error().decode()}")
-        if frozen_ss is not None:
-            net._check_tensor(frozen_ss, "frozen table")
-        self._frozen = frozen_ss
-        self._frozen_ver = (net.params._version, net._kver, net.params.data_ptr())
+        self._bind_frozen(frozen_ss)
         dev, ncls = self.device, net.num_classes
         self.state = torch.empty(nstate // 4, dtype=torch.float32, device=dev)
         self.workspace = torch.empty(nws // 4, dtype=torch.float32, device=dev)
@@ -88,15 +122,6 @@ class StreamingDetector:
         lib.check(lib.tcr_stream_init(C.byref(cfg), frontend.plan.data_ptr(), net._h, S, self.k, C.byref(self.det),
                                       self.state.data_ptr(), self.workspace.data_ptr(), self.workspace.numel() * 4, net._stream()),
                   "tcr_stream_init")
-
-    # ---- detector settings in steps ------------------------------------------------------------------------------------
-    @property
-    def average_steps(self) -> int:
-        return self.det.average_steps
-
-    @property
-    def suppression_steps(self) -> int:
-        return self.det.suppression_steps
 
     # ---- stream control -----------------------------------------------------------------------------------------------
     def reset(self, mask_or_indices: Union[np.ndarray, torch.Tensor, Iterable[int]]) -> None:
@@ -136,9 +161,6 @@ class StreamingDetector:
             raise TcrError(f"push expects samples [{self.n_streams}, {self.step_samples}] (k * hop per stream), got {tuple(samples.shape)}")
         self.net._check_tensor(samples, "stream samples")
 
-    def _table(self) -> torch.Tensor:
-        return self._frozen if self._frozen is not None else self.net._folded_table()
-
     def _args(self, samples: torch.Tensor, ss: torch.Tensor, reset_ptr, stream):
         o, fe, net = self.out, self.frontend, self.net
         return (C.byref(fe.cfg), fe.plan.data_ptr(), net._h, net.params.data_ptr(), ss.data_ptr(), self.n_streams, self.k, C.byref(self.det),
@@ -156,10 +178,6 @@ class StreamingDetector:
         self.lib.check(self.lib.tcr_stream_step(*self._args(samples, ss, self._take_reset(), self.net._stream())), "tcr_stream_step")
         self.net._note_fold_reader()
         return self.out
-
-    def _check_frozen_arena(self):
-        if (self.net.params._version, self.net._kver, self.net.params.data_ptr()) != self._frozen_ver:
-            raise TcrError("StreamingDetector: the network's weights changed since the frozen table was bound; build a new detector")
 
     def prepared(self, samples_buffer: torch.Tensor):
         """A zero-argument callable that runs one step on `samples_buffer` (fill it in place between calls) with every pointer bound,
