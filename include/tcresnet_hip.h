@@ -450,6 +450,31 @@ int tcr_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* n
              void* workspace, size_t ws_bytes, float* logits, float* probs, float* smoothed /* [N][steps][C] */,
              int32_t* top, float* score, int32_t* is_new /* [N][steps] */, void* stream);
 
+/* Detection sweep: tcr_stream_step's suppression rule for T thresholds at once, with the detections scored against labelled events.
+ * top int32 / score float32 [N][steps] are what tcr_scan writes (or streaming steps stacked over steps).  For every signal n and
+ * threshold t, starting from prev_label = -1, prev_step = 0, the steps i = 0 .. valid_steps[n] - 1 are walked in order:
+ *     is_new = top >= 0 && score > thresholds[t] && top != prev_label && (prev_label == -1 || i - prev_step > suppression_steps),
+ *     and when is_new: prev_label = top, prev_step = i.
+ * So at thresholds[t] the steps that fire are exactly those a tcr_scan with det->threshold = thresholds[t] (and the same
+ * suppression_steps) marks in is_new.  valid_steps [N] (NULL: all steps) ends each signal's walk early (clamped to 0..steps); the
+ * rule is causal, so this is the walk of the signal cut there.  Steps whose top is outside 0 .. num_classes - 1 never fire.
+ * Events, per signal sorted by step: CSR event_offsets [N + 1] into event_first / event_last (int64, an inclusive step range) and
+ * event_label (int32).  Precondition: within a signal, event_first[j + 1] > event_last[j] (disjoint, in order); when it is broken
+ * the counts are unspecified (the call stays memory-safe).  A detection at step i with label c is a hit when an event j with
+ * first <= i <= last has label c and no earlier detection hit j, a duplicate when one did; every other detection is a false accept
+ * (one inside another label's event too).  Events labelled outside 0 .. num_classes - 1 are never hit.
+ * Outputs, caller-owned device memory: detections / hits / duplicates int32 [N][T][num_classes] (per detection label); false
+ * accepts = detections - hits - duplicates, misses = events - hits.  event_offsets NULL: no events (hits and duplicates may then
+ * be NULL; when given they are zeroed).  fired uint8 [T][N][steps] (NULL: not written) is 1 at the steps that fire, 0 elsewhere.
+ * Every pointer is device memory; everything is enqueued on `stream`.  Refused (TCR_ERR_ARG, tcr_last_error): null top / score /
+ * thresholds / detections, events without their arrays or hits / duplicates, N, T, steps or num_classes <= 0, num_classes > 256,
+ * suppression_steps < 0, N x steps or N x T x num_classes >= 2^31. */
+int tcr_detect_sweep(int n_signals, int64_t steps, int num_classes, const int32_t* top, const float* score,
+                     const int64_t* valid_steps, int32_t suppression_steps, int n_thresholds, const float* thresholds,
+                     const int32_t* event_offsets, const int64_t* event_first, const int64_t* event_last,
+                     const int32_t* event_label, int32_t* detections, int32_t* hits, int32_t* duplicates,
+                     uint8_t* fired, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Instrumentation                                                                             */
 /* ------------------------------------------------------------------------------------------ */

@@ -4,14 +4,21 @@ A `KeywordScanner` takes a batch of N signals of equal length and returns, for e
 `streaming.StreamingDetector` with the same settings returns from its (i + 1)-th `push` when fed that signal k * hop samples at a
 time: logits, probs, smoothed, top, score and is_new, bitwise.  One call computes every window at the network's batch throughput;
 only the suppression rule runs in step order, over the candidate steps.
+
+`KeywordScanner.sweep` (and `detection_sweep` over raw top / score tensors) then runs that rule for many thresholds at once on the
+device and scores the detections against labelled keyword events: a DET curve (false rejects against false accepts per hour) for
+the cost of one scan and a pass over its top / score.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import NamedTuple, Optional
+import math
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
+from . import _lib
 from ._lib import TcrError
 from .engine import Frontend, TCResNet
 from .streaming import _Detection
@@ -73,3 +80,212 @@ class KeywordScanner(_Detection):
                                          *(t.data_ptr() for t in out), net._stream()), "tcr_scan")
         net._note_fold_reader()
         return out
+
+    def sweep(self, out: ScanOutput, thresholds, events=None, lengths=None, tolerance_ms: float = 1000.0, return_fired: bool = False,
+              labels: Optional[Sequence[str]] = None) -> SweepResult:
+        """The detections of `out` (this scanner's scan) at every threshold, with this scanner's suppression_steps: for thresholds[t]
+        exactly the steps a scanner built with detection_threshold = thresholds[t] marks in is_new (float32 thresholds; -inf and
+        +inf allowed, NaN refused).  See `detection_sweep` and `SweepResult`.
+
+        lengths: per signal, its true length in samples (None: the whole scan); only its whole steps count, so signals of several
+        lengths can share one zero-padded scan.  events: per signal, a list of (start_ms, end_ms, label), label a class index or
+        one of `labels`.  A detection at step i is stamped at  t_i = 1000 * (i + 1) * step_samples / sample_rate  ms (the end of
+        the window that fired, scan_audio.py's time) and hits an event of its label when  start_ms <= t_i <= end_ms + tolerance_ms;
+        each event becomes the inclusive step range of those i, computed in float64.  Refused: events that overlap once the
+        tolerance is added (start of the next <= end + tolerance_ms), that end before they start or start past the signal's
+        length, unknown labels."""
+        N, steps = int(out.top.shape[0]), int(out.top.shape[1])
+        step, sr = self.step_samples, self.frontend.cfg.sample_rate
+        if lengths is None:
+            valid = np.full(N, steps, np.int64)
+        else:
+            lens = np.asarray(lengths, np.int64).reshape(-1)
+            if lens.shape != (N,):
+                raise TcrError(f"sweep: {lens.size} lengths for {N} signals")
+            if (lens < 0).any() or (lens // step > steps).any():
+                raise TcrError(f"sweep: lengths outside 0..{steps * step} samples (the scan's): {lens.tolist()}")
+            valid = lens // step
+        ev_steps = None
+        if events is not None:
+            if len(events) != N:
+                raise TcrError(f"sweep: events for {len(events)} signals, the scan has {N}")
+            names = {str(x): c for c, x in enumerate(labels)} if labels is not None else {}
+            ncls, tol = self.net.num_classes, float(tolerance_ms)
+            ev_steps = []
+            for n, evs in enumerate(events):
+                length_ms = 1000.0 * (float(lengths[n]) if lengths is not None else float(steps * step)) / sr
+                cls = [names.get(e[2]) if isinstance(e[2], str) else int(e[2]) for e in evs]
+                for e, c in zip(evs, cls):
+                    if c is None or not 0 <= c < ncls:
+                        raise TcrError(f"sweep: signal {n}: event {tuple(e)} has an unknown label {e[2]!r}")
+                se = np.array([(float(e[0]), float(e[1])) for e in evs], np.float64).reshape(-1, 2)
+                bad = np.flatnonzero(~(se[:, 1] >= se[:, 0]))
+                if bad.size:
+                    raise TcrError(f"sweep: signal {n}: event {tuple(evs[bad[0]])} ends before it starts")
+                bad = np.flatnonzero(se[:, 0] > length_ms)
+                if bad.size:
+                    raise TcrError(f"sweep: signal {n}: event {tuple(evs[bad[0]])} starts past the signal's end ({length_ms:g} ms)")
+                order = np.lexsort((se[:, 1], se[:, 0]))
+                se, cls = se[order], np.asarray(cls, np.int64).reshape(-1)[order]
+                ov = np.flatnonzero(se[1:, 0] <= se[:-1, 1] + tol)
+                if ov.size:
+                    a, b = evs[order[ov[0]]], evs[order[ov[0] + 1]]
+                    raise TcrError(f"sweep: signal {n}: events {tuple(a)} and {tuple(b)} overlap with tolerance_ms = {tol:g}")
+                ev_steps.append(np.stack([_first_steps(se[:, 0], step, sr), _last_steps(se[:, 1] + tol, step, sr), cls], axis=1))
+        return detection_sweep(out.top, out.score, thresholds, self.suppression_steps, self.net.num_classes, ev_steps, valid,
+                               step / sr, return_fired, self.lib)
+
+
+# ---- detection sweeps ------------------------------------------------------------------------------------------------------------
+class SweepResult(NamedTuple):
+    """Results of a detection sweep (tcr_detect_sweep) over N signals, T thresholds and C classes.
+
+    detections / hits / duplicates [N, T, C] int32 on the device, per detection label (hits / duplicates are zero without events);
+    fired [T, N, steps] uint8 on the device or None (1 at the steps that fire at thresholds[t]); thresholds [T] float32 (host);
+    events [N, C] int64 (host): the labelled events per signal and label; hours [N] float64 (host): each signal's valid steps in
+    hours (NaN when the step length is unknown)."""
+    detections: torch.Tensor
+    hits: torch.Tensor
+    duplicates: torch.Tensor
+    fired: Optional[torch.Tensor]
+    thresholds: np.ndarray
+    events: np.ndarray
+    hours: np.ndarray
+
+    def false_accepts(self) -> torch.Tensor:
+        """[N, T, C] int32: detections that hit no event of their label for the first time or again."""
+        return self.detections - self.hits - self.duplicates
+
+    def curve(self, classes: Optional[Sequence[int]] = None) -> Dict[str, np.ndarray]:
+        """The DET curve over every signal and the chosen classes (default: all), one entry per threshold: threshold, hits,
+        events, false_accepts, duplicates, frr = 1 - hits / events (NaN without events), fa_per_hour = false_accepts / hours."""
+        cls = list(range(self.detections.shape[2])) if classes is None else [int(c) for c in classes]
+        det = self.detections.cpu().numpy().astype(np.int64)[:, :, cls].sum(axis=(0, 2))
+        hits = self.hits.cpu().numpy().astype(np.int64)[:, :, cls].sum(axis=(0, 2))
+        dup = self.duplicates.cpu().numpy().astype(np.int64)[:, :, cls].sum(axis=(0, 2))
+        events = int(self.events[:, cls].sum())
+        fa = det - hits - dup
+        hours = float(self.hours.sum())
+        with np.errstate(divide="ignore", invalid="ignore"):
+            frr = 1.0 - hits / events if events > 0 else np.full(len(hits), np.nan)
+            fa_h = fa / hours if hours > 0 else np.full(len(fa), np.nan)
+        return {"threshold": self.thresholds.astype(np.float64), "hits": hits, "events": np.full(len(hits), events, np.int64),
+                "false_accepts": fa, "duplicates": dup, "frr": np.asarray(frr, np.float64), "fa_per_hour": np.asarray(fa_h, np.float64)}
+
+    def operating_point(self, max_fa_per_hour: float, classes: Optional[Sequence[int]] = None) -> Optional[Dict[str, float]]:
+        """The threshold of the lowest FRR among those with fa_per_hour <= max_fa_per_hour (ties: fewer false accepts per hour,
+        then the higher threshold), as {threshold, frr, fa_per_hour, hits, events, false_accepts}; None when none is in budget."""
+        cv = self.curve(classes)
+        best = None
+        for t in range(len(cv["threshold"])):
+            if not cv["fa_per_hour"][t] <= max_fa_per_hour:
+                continue
+            frr = cv["frr"][t]
+            key = (0.0 if np.isnan(frr) else frr, cv["fa_per_hour"][t], -cv["threshold"][t])
+            if best is None or key < best[0]:
+                best = (key, t)
+        if best is None:
+            return None
+        t = best[1]
+        return {"threshold": float(cv["threshold"][t]), "frr": float(cv["frr"][t]), "fa_per_hour": float(cv["fa_per_hour"][t]),
+                "hits": int(cv["hits"][t]), "events": int(cv["events"][t]), "false_accepts": int(cv["false_accepts"][t])}
+
+
+def _step_ms(i: np.ndarray, step: int, sr: int) -> np.ndarray:
+    return 1000.0 * (i + 1) * step / sr
+
+
+def _first_steps(start_ms: np.ndarray, step: int, sr: int) -> np.ndarray:
+    """Per entry, the first step i >= 0 with _step_ms(i) >= start_ms."""
+    i = np.maximum(0, np.ceil(start_ms * sr / (1000.0 * step)) - 1).astype(np.int64)
+    while (m := _step_ms(i, step, sr) < start_ms).any():
+        i[m] += 1
+    while (m := (i > 0) & (_step_ms(i - 1, step, sr) >= start_ms)).any():
+        i[m] -= 1
+    return i
+
+
+def _last_steps(end_ms: np.ndarray, step: int, sr: int) -> np.ndarray:
+    """Per entry, the last step i with _step_ms(i) <= end_ms (-1: none)."""
+    i = np.maximum(-1, np.floor(end_ms * sr / (1000.0 * step)) - 1).astype(np.int64)
+    while (m := (i >= 0) & (_step_ms(i, step, sr) > end_ms)).any():
+        i[m] -= 1
+    while (m := _step_ms(i + 1, step, sr) <= end_ms).any():
+        i[m] += 1
+    return i
+
+
+def _thresholds(thresholds) -> np.ndarray:
+    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1).astype(np.float32))
+    if thr.size == 0:
+        raise TcrError("detection sweep: no thresholds")
+    if np.isnan(thr).any():
+        raise TcrError(f"detection sweep: NaN thresholds at positions {np.flatnonzero(np.isnan(thr)).tolist()}")
+    return thr
+
+
+def detection_sweep(top: torch.Tensor, score: torch.Tensor, thresholds, suppression_steps: int, num_classes: int,
+                    events: Optional[Sequence[Sequence[Tuple[int, int, int]]]] = None, valid_steps=None,
+                    step_seconds: Optional[float] = None, return_fired: bool = False, lib=None) -> SweepResult:
+    """The streaming detector's suppression rule (include/tcresnet_hip.h, tcr_detect_sweep) for every threshold at once, over top
+    int32 / score float32 [N, steps] on the device (a scan's, or streaming outputs stacked over steps), scored against events.
+
+    events: per signal, a list of (first_step, last_step, label) or an integer array [E, 3] of them (no conversion then): inclusive
+    step ranges, disjoint within a signal (checked);
+    valid_steps: per signal, the steps that count (None: all); step_seconds: one step's duration, for SweepResult.hours."""
+    if lib is None:
+        lib = _lib.get()
+    if top.dim() != 2 or score.shape != top.shape:
+        raise TcrError(f"detection sweep expects top and score [N, steps], got {tuple(top.shape)} and {tuple(score.shape)}")
+    if top.dtype != torch.int32 or score.dtype != torch.float32 or not top.is_contiguous() or not score.is_contiguous():
+        raise TcrError("detection sweep expects contiguous int32 top and float32 score")
+    if top.device != score.device:
+        raise TcrError("detection sweep: top and score are on different devices")
+    dev = top.device
+    N, steps, ncls = int(top.shape[0]), int(top.shape[1]), int(num_classes)
+    thr = _thresholds(thresholds)
+    T = int(thr.size)
+    vs = np.full(N, steps, np.int64) if valid_steps is None else np.asarray(valid_steps, np.int64).reshape(-1)
+    if vs.shape != (N,):
+        raise TcrError(f"detection sweep: {vs.size} valid_steps for {N} signals")
+    if (vs < 0).any() or (vs > steps).any():
+        raise TcrError(f"detection sweep: valid_steps outside 0..{steps}: {vs.tolist()}")
+    i32 = dict(dtype=torch.int32, device=dev)
+    detections = torch.empty((N, T, ncls), **i32)
+    hits = torch.zeros((N, T, ncls), **i32)
+    dups = torch.zeros((N, T, ncls), **i32)
+    fired = torch.empty((T, N, steps), dtype=torch.uint8, device=dev) if return_fired else None
+    counts = np.zeros((N, ncls), np.int64)
+    ev_args = [None, None, None, None]
+    keep = []
+    if events is not None:
+        if len(events) != N:
+            raise TcrError(f"detection sweep: events for {len(events)} signals, the scan has {N}")
+        off, rows = np.zeros(N + 1, np.int32), []
+        for n, evs in enumerate(events):
+            a = np.asarray(evs, dtype=np.int64).reshape(-1, 3)
+            a = a[np.lexsort((a[:, 1], a[:, 0]))]
+            bad = np.flatnonzero((a[:, 2] < 0) | (a[:, 2] >= ncls))
+            if bad.size:
+                raise TcrError(f"detection sweep: signal {n}: event {tuple(a[bad[0]].tolist())} has an unknown label "
+                               f"(classes 0..{ncls - 1})")
+            ov = np.flatnonzero(a[1:, 0] <= a[:-1, 1])
+            if ov.size:
+                raise TcrError(f"detection sweep: signal {n}: events {tuple(a[ov[0]].tolist())} and {tuple(a[ov[0] + 1].tolist())} overlap")
+            counts[n] = np.bincount(a[:, 2], minlength=ncls)
+            rows.append(a)
+            off[n + 1] = off[n] + len(a)
+        a = np.concatenate(rows) if rows else np.zeros((0, 3), np.int64)
+        if len(a) == 0:
+            a = np.zeros((1, 3), np.int64)              # (never read: every signal's range is empty)
+        host = [off, np.ascontiguousarray(a[:, 0]), np.ascontiguousarray(a[:, 1]), np.ascontiguousarray(a[:, 2].astype(np.int32))]
+        keep = [torch.from_numpy(x).to(dev) for x in host]
+        ev_args = [t.data_ptr() for t in keep]
+    thr_dev = torch.from_numpy(thr).to(dev)
+    vs_dev = torch.from_numpy(vs).to(dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+    lib.check(lib.tcr_detect_sweep(N, steps, ncls, top.data_ptr(), score.data_ptr(), vs_dev.data_ptr(), int(suppression_steps), T,
+                                   thr_dev.data_ptr(), *ev_args, detections.data_ptr(), hits.data_ptr(), dups.data_ptr(),
+                                   None if fired is None else fired.data_ptr(), stream), "tcr_detect_sweep")
+    hours = vs * float(step_seconds) / 3600.0 if step_seconds is not None else np.full(N, np.nan)
+    return SweepResult(detections, hits, dups, fired, thr, counts, hours)

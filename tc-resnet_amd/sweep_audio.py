@@ -1,0 +1,134 @@
+"""Detection-threshold sweep of a frozen TC-ResNet artifact (deploy.FrozenModel, include_preprocess) over labelled WAV files: a DET
+curve (false rejects against false accepts per hour) from one scan.
+
+    python sweep_audio.py --frozen MODEL.npz --wav a.wav [b.wav ...] --events EVENTS.csv [--thresholds LO:HI:STEP | t0,t1,...]
+                          [--tolerance_ms MS] [--keywords l0,l1,...] [--per_label] [--target_fa_per_hour F]
+                          [--frames_per_step k] [--labels l0,l1,...] [--average_window_ms MS] [--suppression_ms MS]
+                          [--min_count N] [--max_windows B]
+
+The files are read as scan_audio.py reads them (16-bit PCM at the model's sample rate, only whole steps), zero-padded to the
+longest and scanned in one call; one `KeywordScanner.sweep` then walks the detector's suppression rule at every threshold over
+each file's true length (--detection_threshold is not an input: the thresholds are).  EVENTS.csv has a header and the columns
+file,start_ms,end_ms,label  (file as given to --wav, label one of --labels or a class index).  A detection at time t (the end of
+the window that fired, scan_audio.py's time) hits an event of its label when  start_ms <= t <= end_ms + tolerance_ms; the first
+hit of an event counts as a hit, later ones as duplicates, every other detection as a false accept.
+
+stdout: CSV with a header, one row per threshold over the --keywords (default: every label that does not start with '_'):
+threshold,hits,events,false_accepts,duplicates,frr,fa_per_hour  (frr = 1 - hits / events); --per_label: one row per keyword and
+threshold, with a leading label column.  stderr: one JSON line, the hours scanned and the operating point: the threshold of the
+lowest FRR with fa_per_hour <= --target_fa_per_hour (null when none is)."""
+from __future__ import annotations
+
+import argparse
+import csv
+import json
+import os
+import sys
+from typing import List, Optional
+
+import numpy as np
+
+if __package__ in (None, ""):           # run as a script: import the package through the repository's shim
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from tcresnet_amd.datasets.augmentation_factory import read_wav_pcm16
+    from tcresnet_amd.deploy import FrozenModel
+else:
+    from .datasets.augmentation_factory import read_wav_pcm16
+    from .deploy import FrozenModel
+
+COLUMNS = ("threshold", "hits", "events", "false_accepts", "duplicates", "frr", "fa_per_hour")
+
+
+def parse_thresholds(spec: str) -> np.ndarray:
+    """LO:HI:STEP (LO, LO + STEP, ... up to HI inclusive) or a comma list."""
+    if ":" in spec:
+        lo, hi, step = (float(x) for x in spec.split(":"))
+        if not step > 0 or hi < lo:
+            raise ValueError(f"--thresholds {spec}: expected LO:HI:STEP with STEP > 0 and HI >= LO")
+        return np.arange(lo, hi + step * 1e-6, step)
+    return np.array([float(x) for x in spec.split(",")])
+
+
+def parse_arguments(arguments: Optional[List[str]] = None):
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--frozen", required=True, help="frozen TC-ResNet artifact (.npz) exported with include_preprocess")
+    p.add_argument("--wav", required=True, nargs="+", help="16-bit PCM WAV files, one signal each")
+    p.add_argument("--events", required=True, help="CSV of labelled keyword events: file,start_ms,end_ms,label")
+    p.add_argument("--thresholds", default="0:0.99:0.01", help="LO:HI:STEP or a comma-separated list")
+    p.add_argument("--tolerance_ms", type=float, default=1000.0, help="a detection up to this long after an event's end still hits it")
+    p.add_argument("--keywords", default=None, help="comma-separated labels scored (default: labels not starting with '_')")
+    p.add_argument("--per_label", action="store_true", help="one row per keyword and threshold")
+    p.add_argument("--target_fa_per_hour", type=float, default=0.5, help="false-accept budget of the operating point")
+    p.add_argument("--frames_per_step", type=int, default=1, help="new front-end frames per step (k)")
+    p.add_argument("--labels", default=None, help="comma-separated class names (default: class indices)")
+    p.add_argument("--average_window_ms", type=float, default=1000.0)
+    p.add_argument("--suppression_ms", type=float, default=1500.0)
+    p.add_argument("--min_count", type=int, default=3)
+    p.add_argument("--max_windows", type=int, default=None, help="windows per network launch (the workspace's size)")
+    return p.parse_args(arguments)
+
+
+def read_events(path: str, wavs: List[str]):
+    out = [[] for _ in wavs]
+    index = {w: n for n, w in enumerate(wavs)}
+    with open(path, newline="") as fh:
+        for row in csv.DictReader(fh):
+            f = row["file"]
+            if f not in index:
+                raise SystemExit(f"{path}: event of {f!r}, which is not one of --wav")
+            lab = row["label"].strip()
+            out[index[f]].append((float(row["start_ms"]), float(row["end_ms"]), lab))
+    return out
+
+
+def main(args) -> int:
+    import torch
+    model = FrozenModel.load(args.frozen)
+    scanner = model.scanner(frames_per_step=args.frames_per_step, average_window_ms=args.average_window_ms, min_count=args.min_count,
+                            suppression_ms=args.suppression_ms, max_windows=args.max_windows)
+    ncls = scanner.net.num_classes
+    names = args.labels.split(",") if args.labels else [str(c) for c in range(ncls)]
+    keywords = args.keywords.split(",") if args.keywords else [x for x in names if not x.startswith("_")]
+    unknown = [k for k in keywords if k not in names]
+    if unknown:
+        raise SystemExit(f"--keywords {unknown} are not labels")
+    classes = [names.index(k) for k in keywords]
+    thresholds = parse_thresholds(args.thresholds)
+    step = scanner.step_samples
+    audio = []
+    for path in args.wav:
+        pcm = read_wav_pcm16(path).astype(np.float32) * (1.0 / 32768.0)
+        if len(pcm) % step:
+            print(f"{path}: dropping the last {len(pcm) % step} samples (not a whole step of {step})", file=sys.stderr)
+        audio.append(pcm[:len(pcm) // step * step])
+    n_steps = max(len(a) for a in audio) // step
+    if n_steps == 0:
+        raise SystemExit("no whole step of audio in the files")
+    events = read_events(args.events, args.wav)
+    host = np.zeros((len(audio), n_steps * step), np.float32)
+    for s, a in enumerate(audio):
+        host[s, :len(a)] = a
+    out = scanner.scan(torch.from_numpy(host).to(scanner.device))
+    res = scanner.sweep(out, thresholds, events=events, lengths=[len(a) for a in audio], tolerance_ms=args.tolerance_ms, labels=names)
+    w = csv.writer(sys.stdout, lineterminator="\n")
+    fmt = lambda cv, t: [f"{cv['threshold'][t]:.6g}", *(int(cv[k][t]) for k in COLUMNS[1:5]), f"{cv['frr'][t]:.6g}",
+                         f"{cv['fa_per_hour'][t]:.9g}"]
+    if args.per_label:
+        w.writerow(("label",) + COLUMNS)
+        for k, c in zip(keywords, classes):
+            cv = res.curve([c])
+            for t in range(len(thresholds)):
+                w.writerow([k] + fmt(cv, t))
+    else:
+        w.writerow(COLUMNS)
+        cv = res.curve(classes)
+        for t in range(len(thresholds)):
+            w.writerow(fmt(cv, t))
+    sys.stdout.flush()
+    print(json.dumps({"hours": float(res.hours.sum()), "keywords": keywords, "target_fa_per_hour": args.target_fa_per_hour,
+                      "operating_point": res.operating_point(args.target_fa_per_hour, classes)}), file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(parse_arguments()))
