@@ -416,7 +416,8 @@ int tcr_augment_fwd(const int16_t* pcm, const int64_t* clip_off, const int32_t* 
  * covers (mfcc / log-mel; the float64 deploy path, method 2, and windows pk3 declines are refused: no other kernel gives the
  * offline features bitwise).  State and workspace are caller-owned device memory of the sizes below (0: invalid arguments, see
  * tcr_last_error); tcr_stream_init fills the state (every stream = a silent clip) and must run once before the first step; the
- * state belongs to one (cfg, net, n_streams, k, det) and the same values must be passed to every step. */
+ * state belongs to one (cfg, net, n_streams, k, det) and the same values must be passed to every step.  tcr_stream_scan (below,
+ * after tcr_scan) advances the same state by many steps in one call, bitwise these steps. */
 typedef struct tcr_detect_cfg {
     int32_t average_steps;      /* W: probability vectors averaged (average_window_ms / step) */
     int32_t min_count;          /* 1..W: no result before this many vectors since the reset */
@@ -443,12 +444,27 @@ int tcr_stream_step(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr
  * Configurations: those tcr_stream_* accept (the same refusals, the same messages).  The workspace does not depend on L:
  * tcr_scan_workspace_bytes sizes one for chunks of up to max_windows windows (0: invalid arguments, see tcr_last_error), and
  * tcr_scan runs the largest chunks the bytes passed hold (TCR_ERR_WORKSPACE below one window).  Outputs are caller-owned device
- * memory sized by L; everything is enqueued on `stream`. */
+ * memory sized by L; everything is enqueued on `stream`.  Every signal starts from a silent clip: to scan a recording in pieces,
+ * or to continue a stream, use tcr_stream_scan, which starts from and updates a stream state. */
 size_t tcr_scan_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_net* net, int k, int max_windows);
 int tcr_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params, const float* frozen_ss,
              int n_signals, int64_t n_samples, int k, const tcr_detect_cfg* det, const float* samples /* [N][L] */,
              void* workspace, size_t ws_bytes, float* logits, float* probs, float* smoothed /* [N][steps][C] */,
              int32_t* top, float* score, int32_t* is_new /* [N][steps] */, void* stream);
+
+/* m = n_samples / (k * hop) steps of tcr_stream_step for every stream, in one call, at tcr_scan's throughput.  samples [S][n_samples]
+ * float32 (n_samples a positive multiple of k * hop); reset [S] uint8 or NULL, applied before the first step only (as
+ * tcr_stream_step applies it); state: a tcr_stream_state_bytes region from tcr_stream_init / _step / _scan with the same (cfg, net,
+ * S, k, det).  logits / probs / smoothed [S][m][C], top / score / is_new [S][m]: step i of stream s is bitwise what the (i + 1)-th
+ * of m tcr_stream_step calls returns; afterwards `state` is what those m calls leave: the window, the tail, the five detector
+ * integers and the ring slots of the last min(count, W) vectors bitwise (the other ring slots are never read).  workspace:
+ * tcr_scan_workspace_bytes(cfg, net, k, max_windows) bytes (TCR_ERR_WORKSPACE below one window).  Precondition: every stream's
+ * step counter stays below 2^31 (n + m < 2^31 steps since its reset).  Configurations and refusals: tcr_stream_step's.  Calls of
+ * tcr_stream_step and tcr_stream_scan may be mixed on one state in any order; everything is enqueued on `stream`. */
+int tcr_stream_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params,
+                    const float* frozen_ss, int n_streams, int64_t n_samples, int k, const tcr_detect_cfg* det,
+                    const float* samples, const uint8_t* reset, void* state, void* workspace, size_t ws_bytes,
+                    float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream);
 
 /* Detection sweep: tcr_stream_step's suppression rule for T thresholds at once, with the detections scored against labelled events.
  * top int32 / score float32 [N][steps] are what tcr_scan writes (or streaming steps stacked over steps).  For every signal n and

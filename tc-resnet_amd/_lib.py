@@ -160,6 +160,8 @@ _PROTOTYPES = {
     "tcr_scan_workspace_bytes": (C.c_size_t, [C.POINTER(FrontendCfg), _P, C.c_int, C.c_int]),
     "tcr_scan": (C.c_int, [C.POINTER(FrontendCfg), _P, _P, _P, _P, C.c_int, C.c_int64, C.c_int, C.POINTER(DetectCfg), _P, _P, C.c_size_t,
                            _P, _P, _P, _P, _P, _P, _P]),
+    "tcr_stream_scan": (C.c_int, [C.POINTER(FrontendCfg), _P, _P, _P, _P, C.c_int, C.c_int64, C.c_int, C.POINTER(DetectCfg), _P, _P, _P, _P,
+                                  C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
     "tcr_detect_sweep": (C.c_int, [C.c_int, C.c_int64, C.c_int, _P, _P, _P, C.c_int32, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 

@@ -262,6 +262,27 @@ int scan_group(int64_t steps, int cap) {
     return (int)ceil_div64(steps, groups);
 }
 
+// The largest chunk the workspace holds for n_signals x steps: G = the balanced group (smaller when even one row of it does not fit),
+// R rows (TCR_ERR_WORKSPACE below one window).
+int scan_chunking(const tcr_frontend_cfg& cfg, const tcr_net* net, int k, int64_t steps, int n_signals, size_t ws_bytes, const char* what,
+                  ScanGeom& out) {
+    int G = scan_group(steps, kScanGroup);
+    while (G > 1 && (size_t)scan_geom(cfg, net, k, G, 1).ws_floats * sizeof(float) > ws_bytes) G = scan_group(steps, G / 2);
+    if ((size_t)scan_geom(cfg, net, k, G, 1).ws_floats * sizeof(float) > ws_bytes) {
+        set_error("%s: workspace %zu bytes < one window's %zu", what, ws_bytes, (size_t)scan_geom(cfg, net, k, 1, 1).ws_floats * sizeof(float));
+        return TCR_ERR_WORKSPACE;
+    }
+    const int64_t total_groups = ceil_div64(steps, G) * n_signals;
+    int64_t lo = 1, hi = total_groups;                  // R: the largest that fits (binary search; the size grows with R)
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) / 2;
+        if (scan_geom_ok(k, cfg.n_frames, G, mid) && (size_t)scan_geom(cfg, net, k, G, (int)mid).ws_floats * sizeof(float) <= ws_bytes) lo = mid;
+        else hi = mid - 1;
+    }
+    out = scan_geom(cfg, net, k, G, (int)lo);
+    return TCR_OK;
+}
+
 }  // namespace
 
 }  // namespace tcr
@@ -293,21 +314,10 @@ extern "C" int tcr_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const
     net_io_shape(net, &cin, &t_in, &classes);
     TCR_REQUIRE((int64_t)n_signals * steps * classes < ((int64_t)1 << 31), "tcr_scan: %d signals x %lld steps is too large", n_signals,
                 (long long)steps);
-    // the largest chunk the workspace holds: G = the balanced group (smaller when even one row of it does not fit), R rows
-    int G = scan_group(steps, kScanGroup);
-    while (G > 1 && (size_t)scan_geom(*cfg, net, k, G, 1).ws_floats * sizeof(float) > ws_bytes) G = scan_group(steps, G / 2);
-    if ((size_t)scan_geom(*cfg, net, k, G, 1).ws_floats * sizeof(float) > ws_bytes) {
-        set_error("tcr_scan: workspace %zu bytes < one window's %zu", ws_bytes, (size_t)scan_geom(*cfg, net, k, 1, 1).ws_floats * sizeof(float));
-        return TCR_ERR_WORKSPACE;
-    }
+    ScanGeom g;
+    TCR_TRY(scan_chunking(*cfg, net, k, steps, n_signals, ws_bytes, "tcr_scan", g));
+    const int G = g.G;
     const int64_t groups = ceil_div64(steps, G), total_groups = groups * n_signals;
-    int64_t lo = 1, hi = total_groups;                  // R: the largest that fits (binary search; the size grows with R)
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) / 2;
-        if (scan_geom_ok(k, cfg->n_frames, G, mid) && (size_t)scan_geom(*cfg, net, k, G, (int)mid).ws_floats * sizeof(float) <= ws_bytes) lo = mid;
-        else hi = mid - 1;
-    }
-    const ScanGeom g = scan_geom(*cfg, net, k, G, (int)lo);
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* ws = static_cast<float*>(workspace);
     const int ftp = tcr_padded_len(g.F);

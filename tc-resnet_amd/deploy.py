@@ -98,7 +98,7 @@ class FrozenModel:
     def streaming(self, n_streams: int, **kw):
         """A `streaming.StreamingDetector` of n_streams over this artifact (TC-ResNet with `include_preprocess` only): the frozen
         front-end settings, the conv / fc constants and the folded BN table as exported.  kw: frames_per_step, average_window_ms,
-        min_count, detection_threshold, suppression_ms."""
+        min_count, detection_threshold, suppression_ms, max_windows (push_many's windows per network launch)."""
         if self.meta["family"] != "tcresnet":
             raise ValueError(f"streaming detection runs TC-ResNet artifacts only (this one is {self.meta['family']})")
         if self.frontend is None:

@@ -2,10 +2,12 @@
 
     python scan_audio.py --frozen MODEL.npz --wav a.wav [b.wav ...] [--frames_per_step k] [--labels l0,l1,...]
                          [--average_window_ms MS] [--detection_threshold P] [--suppression_ms MS] [--min_count N]
-                         [--max_windows B] [--summary]
+                         [--max_windows B] [--summary] [--chunk_seconds X]
 
 The files are scanned in one `scanning.KeywordScanner` call (16-bit PCM at the model's sample rate), zero-padded to the longest;
-samples that do not fill a whole step are dropped (noted on stderr).  The output is stream_audio.py's, line for line: one line per
+samples that do not fill a whole step are dropped (noted on stderr).  With --chunk_seconds, the files are read X seconds at a time
+(rounded down to whole steps) and fed to one `streaming.StreamingDetector` by `push_many`, so host memory holds one chunk per file;
+a file that has ended reads as zeros until the longest ends, and the output is the one-call output, byte for byte.  The output is stream_audio.py's, line for line: one line per
 detection on stdout,  file,time_ms,label,score,  in step order and, within a step, in file order -- time_ms is the end of the
 window that fired (every file starts as if it had heard one clip of silence).  --summary adds one JSON line on stderr: the hours
 of audio scanned (each file's whole steps), the detections per label and the detections per hour."""
@@ -14,8 +16,9 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import struct
 import sys
-from typing import List, Optional
+from typing import Iterator, List, Optional, Tuple
 
 import numpy as np
 
@@ -42,10 +45,79 @@ def parse_arguments(arguments: Optional[List[str]] = None):
     p.add_argument("--min_count", type=int, default=3)
     p.add_argument("--max_windows", type=int, default=None, help="windows per network launch (the workspace's size)")
     p.add_argument("--summary", action="store_true", help="one JSON line of totals on stderr")
+    p.add_argument("--chunk_seconds", type=float, default=None, help="read and scan the files this many seconds at a time")
     return p.parse_args(arguments)
 
 
+class WavReader:
+    """Channel 0 of a 16-bit PCM WAV file (read_wav_pcm16's parsing), read sequentially without loading the file: `read(n)` returns
+    the next n samples as float32 / 32768, zeros past the end."""
+
+    def __init__(self, path: str):
+        self.fh = open(path, "rb")
+        size = os.fstat(self.fh.fileno()).st_size
+        head = self.fh.read(12)
+        if head[:4] != b"RIFF" or head[8:12] != b"WAVE":
+            raise ValueError(f"{path}: not a RIFF/WAVE file")
+        pos, self.channels, data = 12, 1, None
+        while pos + 8 <= size:
+            self.fh.seek(pos)
+            tag, n = self.fh.read(4), struct.unpack("<I", self.fh.read(4))[0]
+            if tag == b"fmt ":
+                fmt, self.channels, _rate, _br, _align, bits = struct.unpack("<HHIIHH", self.fh.read(16))
+                if fmt != 1 or bits != 16:
+                    raise ValueError(f"{path}: only 16-bit PCM is supported (format {fmt}, {bits} bits)")
+            elif tag == b"data":
+                data = (pos + 8, min(n, size - pos - 8))
+            pos += 8 + n + (n & 1)
+        if data is None:
+            raise ValueError(f"{path}: no data chunk")
+        self.start, self.length, self.pos = data[0], data[1] // 2 // self.channels, 0
+
+    def read(self, n: int) -> np.ndarray:
+        out = np.zeros(n, np.float32)
+        m = max(0, min(n, self.length - self.pos))
+        if m:
+            self.fh.seek(self.start + self.pos * 2 * self.channels)
+            pcm = np.frombuffer(self.fh.read(m * 2 * self.channels), dtype="<i2").reshape(-1, self.channels)[:, 0]
+            out[:m] = pcm.astype(np.float32) * (1.0 / 32768.0)
+        self.pos += n
+        return out
+
+
+def whole_step_lengths(paths: List[str], step: int) -> List[int]:
+    """Each file's length in whole steps' samples; the dropped samples are noted on stderr (as the one-call path notes them)."""
+    lengths = []
+    for path in paths:
+        n = WavReader(path).length
+        if n % step:
+            print(f"{path}: dropping the last {n % step} samples (not a whole step of {step})", file=sys.stderr)
+        lengths.append(n // step * step)
+    return lengths
+
+
+def wav_chunks(paths: List[str], step: int, chunk_seconds: float, sample_rate: int) -> Iterator[Tuple[int, np.ndarray]]:
+    """(first step, samples [N, m * step]) of the files chunk by chunk, chunk_seconds rounded down to whole steps, up to the longest
+    file's last whole step; a file that has ended (or ends inside its last partial step) reads as zeros."""
+    chunk_steps = int(chunk_seconds * sample_rate) // step
+    if chunk_steps < 1:
+        raise SystemExit(f"--chunk_seconds {chunk_seconds:g} is shorter than one step ({step} samples)")
+    readers = [WavReader(p) for p in paths]
+    lengths = [r.length // step * step for r in readers]
+    n_steps = max(lengths) // step
+    for i0 in range(0, n_steps, chunk_steps):
+        m = min(chunk_steps, n_steps - i0)
+        host = np.zeros((len(paths), m * step), np.float32)
+        for s, r in enumerate(readers):
+            x = r.read(m * step)
+            keep = max(0, min(m * step, lengths[s] - i0 * step))
+            host[s, :keep] = x[:keep]
+        yield i0, host
+
+
 def main(args) -> int:
+    if args.chunk_seconds is not None:
+        return main_chunked(args)
     import torch
     model = FrozenModel.load(args.frozen)
     scanner = model.scanner(frames_per_step=args.frames_per_step, average_window_ms=args.average_window_ms, min_count=args.min_count,
@@ -77,6 +149,34 @@ def main(args) -> int:
             print(f"{args.wav[s]},{format_time_ms(1000.0 * (i + 1) * step / sr)},{name},{float(score[s, i]):.6f}", flush=True)
     if args.summary:
         hours = sum(len(a) for a in audio) / sr / 3600.0
+        total = sum(counts.values())
+        print(json.dumps({"hours": hours, "detections": total, "detections_per_label": counts,
+                          "detections_per_hour": total / hours if hours > 0 else None}), file=sys.stderr)
+    return 0
+
+
+def main_chunked(args) -> int:
+    import torch
+    model = FrozenModel.load(args.frozen)
+    det = model.streaming(len(args.wav), frames_per_step=args.frames_per_step, average_window_ms=args.average_window_ms,
+                          min_count=args.min_count, detection_threshold=args.detection_threshold, suppression_ms=args.suppression_ms,
+                          max_windows=args.max_windows)
+    labels = args.labels.split(",") if args.labels else None
+    step, sr = det.step_samples, det.frontend.cfg.sample_rate
+    names = labels if labels else [str(c) for c in range(det.net.num_classes)]
+    lengths = whole_step_lengths(args.wav, step)
+    counts = {}
+    for i0, host in wav_chunks(args.wav, step, args.chunk_seconds, sr):
+        out = det.push_many(torch.from_numpy(host).to(det.device))
+        fired = out.is_new.cpu().numpy()
+        top, score = out.top.cpu().numpy(), out.score.cpu().numpy()
+        sig, at = np.nonzero(fired.T)                 # step-major within the chunk; chunks come in step order
+        for i, s in zip(sig, at):
+            name = names[top[s, i]]
+            counts[name] = counts.get(name, 0) + 1
+            print(f"{args.wav[s]},{format_time_ms(1000.0 * (i0 + i + 1) * step / sr)},{name},{float(score[s, i]):.6f}", flush=True)
+    if args.summary:
+        hours = sum(lengths) / sr / 3600.0
         total = sum(counts.values())
         print(json.dumps({"hours": hours, "detections": total, "detections_per_label": counts,
                           "detections_per_hour": total / hours if hours > 0 else None}), file=sys.stderr)

@@ -81,60 +81,6 @@ class KeywordScanner(_Detection):
         net._note_fold_reader()
         return out
 
-    def sweep(self, out: ScanOutput, thresholds, events=None, lengths=None, tolerance_ms: float = 1000.0, return_fired: bool = False,
-              labels: Optional[Sequence[str]] = None) -> SweepResult:
-        """The detections of `out` (this scanner's scan) at every threshold, with this scanner's suppression_steps: for thresholds[t]
-        exactly the steps a scanner built with detection_threshold = thresholds[t] marks in is_new (float32 thresholds; -inf and
-        +inf allowed, NaN refused).  See `detection_sweep` and `SweepResult`.
-
-        lengths: per signal, its true length in samples (None: the whole scan); only its whole steps count, so signals of several
-        lengths can share one zero-padded scan.  events: per signal, a list of (start_ms, end_ms, label), label a class index or
-        one of `labels`.  A detection at step i is stamped at  t_i = 1000 * (i + 1) * step_samples / sample_rate  ms (the end of
-        the window that fired, scan_audio.py's time) and hits an event of its label when  start_ms <= t_i <= end_ms + tolerance_ms;
-        each event becomes the inclusive step range of those i, computed in float64.  Refused: events that overlap once the
-        tolerance is added (start of the next <= end + tolerance_ms), that end before they start or start past the signal's
-        length, unknown labels."""
-        N, steps = int(out.top.shape[0]), int(out.top.shape[1])
-        step, sr = self.step_samples, self.frontend.cfg.sample_rate
-        if lengths is None:
-            valid = np.full(N, steps, np.int64)
-        else:
-            lens = np.asarray(lengths, np.int64).reshape(-1)
-            if lens.shape != (N,):
-                raise TcrError(f"sweep: {lens.size} lengths for {N} signals")
-            if (lens < 0).any() or (lens // step > steps).any():
-                raise TcrError(f"sweep: lengths outside 0..{steps * step} samples (the scan's): {lens.tolist()}")
-            valid = lens // step
-        ev_steps = None
-        if events is not None:
-            if len(events) != N:
-                raise TcrError(f"sweep: events for {len(events)} signals, the scan has {N}")
-            names = {str(x): c for c, x in enumerate(labels)} if labels is not None else {}
-            ncls, tol = self.net.num_classes, float(tolerance_ms)
-            ev_steps = []
-            for n, evs in enumerate(events):
-                length_ms = 1000.0 * (float(lengths[n]) if lengths is not None else float(steps * step)) / sr
-                cls = [names.get(e[2]) if isinstance(e[2], str) else int(e[2]) for e in evs]
-                for e, c in zip(evs, cls):
-                    if c is None or not 0 <= c < ncls:
-                        raise TcrError(f"sweep: signal {n}: event {tuple(e)} has an unknown label {e[2]!r}")
-                se = np.array([(float(e[0]), float(e[1])) for e in evs], np.float64).reshape(-1, 2)
-                bad = np.flatnonzero(~(se[:, 1] >= se[:, 0]))
-                if bad.size:
-                    raise TcrError(f"sweep: signal {n}: event {tuple(evs[bad[0]])} ends before it starts")
-                bad = np.flatnonzero(se[:, 0] > length_ms)
-                if bad.size:
-                    raise TcrError(f"sweep: signal {n}: event {tuple(evs[bad[0]])} starts past the signal's end ({length_ms:g} ms)")
-                order = np.lexsort((se[:, 1], se[:, 0]))
-                se, cls = se[order], np.asarray(cls, np.int64).reshape(-1)[order]
-                ov = np.flatnonzero(se[1:, 0] <= se[:-1, 1] + tol)
-                if ov.size:
-                    a, b = evs[order[ov[0]]], evs[order[ov[0] + 1]]
-                    raise TcrError(f"sweep: signal {n}: events {tuple(a)} and {tuple(b)} overlap with tolerance_ms = {tol:g}")
-                ev_steps.append(np.stack([_first_steps(se[:, 0], step, sr), _last_steps(se[:, 1] + tol, step, sr), cls], axis=1))
-        return detection_sweep(out.top, out.score, thresholds, self.suppression_steps, self.net.num_classes, ev_steps, valid,
-                               step / sr, return_fired, self.lib)
-
 
 # ---- detection sweeps ------------------------------------------------------------------------------------------------------------
 class SweepResult(NamedTuple):

@@ -4,12 +4,13 @@ A `StreamingDetector` holds S streams.  Each starts as if it had heard one clip 
 k * hop samples to every stream (k = frames_per_step), computes only the k new front-end frames, runs the network on the
 one-second window kept on the device and smooths the posteriors into detections (the speech-commands "recognize commands"
 rule, stated in steps: see tcr_stream_step).  After a push, `window()` is bitwise the ordinary `Frontend` of each stream's last
-n_samples samples, and the logits / probs are bitwise `TCResNet.forward_frozen` of those windows at batch S.
+n_samples samples, and the logits / probs are bitwise `TCResNet.forward_frozen` of those windows at batch S.  `push_many` (tcr_stream_scan)
+appends many steps at once at the offline scan's throughput, bitwise the same pushes.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Iterable, NamedTuple, Optional, Union
+from typing import Iterable, NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -79,6 +80,64 @@ class _Detection:
         if (self.net.params._version, self.net._kver, self.net.params.data_ptr()) != self._frozen_ver:
             raise TcrError(f"{self._what}: the network's weights changed since the frozen table was bound; build a new {self._noun}")
 
+    # ---- detection sweeps ---------------------------------------------------------------------------------------------
+    def sweep(self, out, thresholds, events=None, lengths=None, tolerance_ms: float = 1000.0, return_fired: bool = False,
+              labels: Optional[Sequence[str]] = None):
+        """The detections of `out` at every threshold, with these settings' suppression_steps: for thresholds[t] exactly the steps
+        a scanner built with detection_threshold = thresholds[t] marks in is_new (float32 thresholds; -inf and +inf allowed, NaN
+        refused).  `out`: a scanning.ScanOutput of these settings (a KeywordScanner's scan, or StreamingDetector.push_many
+        outputs concatenated over steps from a fresh detector); only its top / score are read.  See `scanning.detection_sweep`
+        and `scanning.SweepResult`.
+
+        lengths: per signal, its true length in samples (None: the whole scan); only its whole steps count, so signals of several
+        lengths can share one zero-padded scan.  events: per signal, a list of (start_ms, end_ms, label), label a class index or
+        one of `labels`.  A detection at step i is stamped at  t_i = 1000 * (i + 1) * step_samples / sample_rate  ms (the end of
+        the window that fired, scan_audio.py's time) and hits an event of its label when  start_ms <= t_i <= end_ms + tolerance_ms;
+        each event becomes the inclusive step range of those i, computed in float64.  Refused: events that overlap once the
+        tolerance is added (start of the next <= end + tolerance_ms), that end before they start or start past the signal's
+        length, unknown labels."""
+        from .scanning import _first_steps, _last_steps, detection_sweep
+        N, steps = int(out.top.shape[0]), int(out.top.shape[1])
+        step, sr = self.step_samples, self.frontend.cfg.sample_rate
+        if lengths is None:
+            valid = np.full(N, steps, np.int64)
+        else:
+            lens = np.asarray(lengths, np.int64).reshape(-1)
+            if lens.shape != (N,):
+                raise TcrError(f"sweep: {lens.size} lengths for {N} signals")
+            if (lens < 0).any() or (lens // step > steps).any():
+                raise TcrError(f"sweep: lengths outside 0..{steps * step} samples (the scan's): {lens.tolist()}")
+            valid = lens // step
+        ev_steps = None
+        if events is not None:
+            if len(events) != N:
+                raise TcrError(f"sweep: events for {len(events)} signals, the scan has {N}")
+            names = {str(x): c for c, x in enumerate(labels)} if labels is not None else {}
+            ncls, tol = self.net.num_classes, float(tolerance_ms)
+            ev_steps = []
+            for n, evs in enumerate(events):
+                length_ms = 1000.0 * (float(lengths[n]) if lengths is not None else float(steps * step)) / sr
+                cls = [names.get(e[2]) if isinstance(e[2], str) else int(e[2]) for e in evs]
+                for e, c in zip(evs, cls):
+                    if c is None or not 0 <= c < ncls:
+                        raise TcrError(f"sweep: signal {n}: event {tuple(e)} has an unknown label {e[2]!r}")
+                se = np.array([(float(e[0]), float(e[1])) for e in evs], np.float64).reshape(-1, 2)
+                bad = np.flatnonzero(~(se[:, 1] >= se[:, 0]))
+                if bad.size:
+                    raise TcrError(f"sweep: signal {n}: event {tuple(evs[bad[0]])} ends before it starts")
+                bad = np.flatnonzero(se[:, 0] > length_ms)
+                if bad.size:
+                    raise TcrError(f"sweep: signal {n}: event {tuple(evs[bad[0]])} starts past the signal's end ({length_ms:g} ms)")
+                order = np.lexsort((se[:, 1], se[:, 0]))
+                se, cls = se[order], np.asarray(cls, np.int64).reshape(-1)[order]
+                ov = np.flatnonzero(se[1:, 0] <= se[:-1, 1] + tol)
+                if ov.size:
+                    a, b = evs[order[ov[0]]], evs[order[ov[0] + 1]]
+                    raise TcrError(f"sweep: signal {n}: events {tuple(a)} and {tuple(b)} overlap with tolerance_ms = {tol:g}")
+                ev_steps.append(np.stack([_first_steps(se[:, 0], step, sr), _last_steps(se[:, 1] + tol, step, sr), cls], axis=1))
+        return detection_sweep(out.top, out.score, thresholds, self.suppression_steps, self.net.num_classes, ev_steps, valid,
+                               step / sr, return_fired, self.lib)
+
 
 class StreamingDetector(_Detection):
     """S concurrent streams through `frontend` and `net`, k = frames_per_step new frames per stream and step.
@@ -91,14 +150,23 @@ class StreamingDetector(_Detection):
     `frozen_ss` (a frozen artifact's table, `FrozenModel.streaming`) that table is used as it is; the net's arena then only
     supplies the conv / fc weights, and both forms refuse to run once the arena changed.
 
-    The output tensors are the detector's own and are overwritten by the next step (copy what must survive it)."""
+    The output tensors are the detector's own and are overwritten by the next step (copy what must survive it).
+
+    `push_many` advances every stream by many steps in one call at the offline scan's throughput (tcr_stream_scan), bitwise the
+    same pushes; max_windows (default scanning.DEFAULT_MAX_WINDOWS) bounds its windows per network launch and sizes the scan
+    workspace it allocates on first use."""
 
     def __init__(self, net: TCResNet, frontend: Frontend, n_streams: int, frames_per_step: int = 1, average_window_ms: float = 1000,
                  min_count: int = 3, detection_threshold: float = 0.5, suppression_ms: float = 1500,
-                 frozen_ss: Optional[torch.Tensor] = None):
+                 frozen_ss: Optional[torch.Tensor] = None, max_windows: Optional[int] = None):
         self._setup("StreamingDetector", "detector", net, frontend, frames_per_step, average_window_ms, min_count, detection_threshold,
                     suppression_ms)
         self.n_streams = int(n_streams)
+        if max_windows is None:
+            from .scanning import DEFAULT_MAX_WINDOWS
+            max_windows = DEFAULT_MAX_WINDOWS
+        self.max_windows = int(max_windows)
+        self._scan_ws: Optional[torch.Tensor] = None
         cfg = frontend.cfg
         S, lib = self.n_streams, self.lib
         if S <= 0:
@@ -178,6 +246,39 @@ class StreamingDetector(_Detection):
         self.lib.check(self.lib.tcr_stream_step(*self._args(samples, ss, self._take_reset(), self.net._stream())), "tcr_stream_step")
         self.net._note_fold_reader()
         return self.out
+
+    def push_many(self, samples: torch.Tensor):
+        """Append samples [S, m * k * hop] (float32, on the device) to every stream: m steps in one call (tcr_stream_scan), at the
+        offline scan's throughput.  Returns a scanning.ScanOutput of new tensors, [S, m, ...]: step i is bitwise what the (i + 1)-th
+        of m `push` calls returns, and the detector is left as those pushes leave it, so `push` and `push_many` mix freely.  Pending
+        `reset`s apply at the first step; `out` is not touched.  The weight / fold rules are `push`'s.  The scan workspace (sized
+        by max_windows) is allocated on the first call."""
+        from .scanning import ScanOutput
+        S, step = self.n_streams, self.step_samples
+        if samples.dim() != 2 or int(samples.shape[0]) != S:
+            raise TcrError(f"push_many expects samples [{S}, m * {step}] (m steps of k * hop per stream), got {tuple(samples.shape)}")
+        self.net._check_tensor(samples, "stream samples")
+        lib, fe, net = self.lib, self.frontend, self.net
+        if self._scan_ws is None:
+            nws = lib.tcr_scan_workspace_bytes(C.byref(fe.cfg), net._h, self.k, self.max_windows)
+            if nws == 0:
+                raise TcrError(f"StreamingDetector.push_many: {lib.tcr_last_error().decode()}")
+            self._scan_ws = torch.empty(nws // 4, dtype=torch.float32, device=self.device)
+        if self._frozen is not None:
+            self._check_frozen_arena()
+        ss = self._table()
+        L = int(samples.shape[1])
+        steps, ncls = max(L // step, 0), net.num_classes
+        f32 = dict(dtype=torch.float32, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        out = ScanOutput(torch.empty((S, steps, ncls), **f32), torch.empty((S, steps, ncls), **f32), torch.empty((S, steps, ncls), **f32),
+                         torch.empty((S, steps), **i32), torch.empty((S, steps), **f32), torch.empty((S, steps), **i32))
+        ws = self._scan_ws
+        lib.check(lib.tcr_stream_scan(C.byref(fe.cfg), fe.plan.data_ptr(), net._h, net.params.data_ptr(), ss.data_ptr(), S, L, self.k,
+                                      C.byref(self.det), samples.data_ptr(), self._take_reset(), self.state.data_ptr(), ws.data_ptr(),
+                                      ws.numel() * 4, *(t.data_ptr() for t in out), net._stream()), "tcr_stream_scan")
+        net._note_fold_reader()
+        return out
 
     def prepared(self, samples_buffer: torch.Tensor):
         """A zero-argument callable that runs one step on `samples_buffer` (fill it in place between calls) with every pointer bound,

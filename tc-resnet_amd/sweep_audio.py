@@ -4,11 +4,13 @@ curve (false rejects against false accepts per hour) from one scan.
     python sweep_audio.py --frozen MODEL.npz --wav a.wav [b.wav ...] --events EVENTS.csv [--thresholds LO:HI:STEP | t0,t1,...]
                           [--tolerance_ms MS] [--keywords l0,l1,...] [--per_label] [--target_fa_per_hour F]
                           [--frames_per_step k] [--labels l0,l1,...] [--average_window_ms MS] [--suppression_ms MS]
-                          [--min_count N] [--max_windows B]
+                          [--min_count N] [--max_windows B] [--chunk_seconds X]
 
 The files are read as scan_audio.py reads them (16-bit PCM at the model's sample rate, only whole steps), zero-padded to the
 longest and scanned in one call; one `KeywordScanner.sweep` then walks the detector's suppression rule at every threshold over
-each file's true length (--detection_threshold is not an input: the thresholds are).  EVENTS.csv has a header and the columns
+each file's true length (--detection_threshold is not an input: the thresholds are).  With --chunk_seconds the files are read and scanned chunk by
+chunk (scan_audio.py's --chunk_seconds: `StreamingDetector.push_many`), the chunks' top / score are concatenated on the device
+and swept once: the output is the one-call output, byte for byte.  EVENTS.csv has a header and the columns
 file,start_ms,end_ms,label  (file as given to --wav, label one of --labels or a class index).  A detection at time t (the end of
 the window that fired, scan_audio.py's time) hits an event of its label when  start_ms <= t <= end_ms + tolerance_ms; the first
 hit of an event counts as a hit, later ones as duplicates, every other detection as a false accept.
@@ -32,9 +34,13 @@ if __package__ in (None, ""):           # run as a script: import the package th
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from tcresnet_amd.datasets.augmentation_factory import read_wav_pcm16
     from tcresnet_amd.deploy import FrozenModel
+    from tcresnet_amd.scan_audio import wav_chunks, whole_step_lengths
+    from tcresnet_amd.scanning import ScanOutput
 else:
     from .datasets.augmentation_factory import read_wav_pcm16
     from .deploy import FrozenModel
+    from .scan_audio import wav_chunks, whole_step_lengths
+    from .scanning import ScanOutput
 
 COLUMNS = ("threshold", "hits", "events", "false_accepts", "duplicates", "frr", "fa_per_hour")
 
@@ -65,6 +71,7 @@ def parse_arguments(arguments: Optional[List[str]] = None):
     p.add_argument("--suppression_ms", type=float, default=1500.0)
     p.add_argument("--min_count", type=int, default=3)
     p.add_argument("--max_windows", type=int, default=None, help="windows per network launch (the workspace's size)")
+    p.add_argument("--chunk_seconds", type=float, default=None, help="read and scan the files this many seconds at a time")
     return p.parse_args(arguments)
 
 
@@ -84,8 +91,9 @@ def read_events(path: str, wavs: List[str]):
 def main(args) -> int:
     import torch
     model = FrozenModel.load(args.frozen)
-    scanner = model.scanner(frames_per_step=args.frames_per_step, average_window_ms=args.average_window_ms, min_count=args.min_count,
-                            suppression_ms=args.suppression_ms, max_windows=args.max_windows)
+    settings = dict(frames_per_step=args.frames_per_step, average_window_ms=args.average_window_ms, min_count=args.min_count,
+                    suppression_ms=args.suppression_ms, max_windows=args.max_windows)
+    scanner = model.scanner(**settings) if args.chunk_seconds is None else model.streaming(len(args.wav), **settings)
     ncls = scanner.net.num_classes
     names = args.labels.split(",") if args.labels else [str(c) for c in range(ncls)]
     keywords = args.keywords.split(",") if args.keywords else [x for x in names if not x.startswith("_")]
@@ -95,21 +103,33 @@ def main(args) -> int:
     classes = [names.index(k) for k in keywords]
     thresholds = parse_thresholds(args.thresholds)
     step = scanner.step_samples
-    audio = []
-    for path in args.wav:
-        pcm = read_wav_pcm16(path).astype(np.float32) * (1.0 / 32768.0)
-        if len(pcm) % step:
-            print(f"{path}: dropping the last {len(pcm) % step} samples (not a whole step of {step})", file=sys.stderr)
-        audio.append(pcm[:len(pcm) // step * step])
-    n_steps = max(len(a) for a in audio) // step
+    if args.chunk_seconds is None:
+        audio = []
+        for path in args.wav:
+            pcm = read_wav_pcm16(path).astype(np.float32) * (1.0 / 32768.0)
+            if len(pcm) % step:
+                print(f"{path}: dropping the last {len(pcm) % step} samples (not a whole step of {step})", file=sys.stderr)
+            audio.append(pcm[:len(pcm) // step * step])
+        lengths = [len(a) for a in audio]
+    else:
+        lengths = whole_step_lengths(args.wav, step)
+    n_steps = max(lengths) // step
     if n_steps == 0:
         raise SystemExit("no whole step of audio in the files")
     events = read_events(args.events, args.wav)
-    host = np.zeros((len(audio), n_steps * step), np.float32)
-    for s, a in enumerate(audio):
-        host[s, :len(a)] = a
-    out = scanner.scan(torch.from_numpy(host).to(scanner.device))
-    res = scanner.sweep(out, thresholds, events=events, lengths=[len(a) for a in audio], tolerance_ms=args.tolerance_ms, labels=names)
+    if args.chunk_seconds is None:
+        host = np.zeros((len(audio), n_steps * step), np.float32)
+        for s, a in enumerate(audio):
+            host[s, :len(a)] = a
+        out = scanner.scan(torch.from_numpy(host).to(scanner.device))
+    else:
+        tops, scores = [], []                           # (only what the sweep reads stays on the device)
+        for _, host in wav_chunks(args.wav, step, args.chunk_seconds, scanner.frontend.cfg.sample_rate):
+            o = scanner.push_many(torch.from_numpy(host).to(scanner.device))
+            tops.append(o.top)
+            scores.append(o.score)
+        out = ScanOutput(None, None, None, torch.cat(tops, dim=1), torch.cat(scores, dim=1), None)
+    res = scanner.sweep(out, thresholds, events=events, lengths=lengths, tolerance_ms=args.tolerance_ms, labels=names)
     w = csv.writer(sys.stdout, lineterminator="\n")
     fmt = lambda cv, t: [f"{cv['threshold'][t]:.6g}", *(int(cv[k][t]) for k in COLUMNS[1:5]), f"{cv['frr'][t]:.6g}",
                          f"{cv['fa_per_hour'][t]:.9g}"]
