@@ -466,6 +466,46 @@ int tcr_stream_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr
                     const float* samples, const uint8_t* reset, void* state, void* workspace, size_t ws_bytes,
                     float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream);
 
+/* The detection entries above for every model family: each _m twin takes a model reference in place of (net, params, frozen_ss)
+ * and is otherwise the entry it is named after (arguments, layouts, refusals, bitwise contracts).  The window stays the planar
+ * front-end output [n_coef][T + 2*TCR_HALO] in the state whatever the family; the network call is
+ *   TCR_FAMILY_TCRESNET  tcr_net_forward_frozen(handle, params, aux = the folded table of tcr_net_fold_bn, windows);
+ *   TCR_FAMILY_DSCNN     tcr_dscnn_forward_infer(handle, params, aux = the moving statistics, windows): w_in = n_coef, h_in = T;
+ *   TCR_FAMILY_G2D       tcr_g2d_forward_infer(handle, params, aux = the moving statistics, planes): a finalized graph of a
+ *                        single-channel h = T frames x w = n_coef input; the windows are laid out as tcr_g2d_input_from_features
+ *                        lays them out (a pure copy).
+ * So logits / probs of a step are bitwise that call on the S windows at batch S (DS-CNN: S <= 65535 * 16, the batch range of one
+ * kernel path; tcr_scan_m keeps its launches in it).  DS-CNN and 2-D graphs fold their BN inside every call: in-place updates to
+ * params / aux are seen by the next one.  A state belongs to one (cfg, model, n_streams, k, det), as above.  Refused, with a
+ * message: an unknown family, a null handle, a graph that is not finalized, a front-end that does not yield the input shape,
+ * more than 256 classes.  The entries without _m are these with a TCR_FAMILY_TCRESNET reference. */
+#define TCR_FAMILY_TCRESNET 0
+#define TCR_FAMILY_DSCNN 1
+#define TCR_FAMILY_G2D 2
+typedef struct tcr_model_ref {
+    int family;                 /* TCR_FAMILY_* */
+    const void* handle;         /* tcr_net* / tcr_dscnn* / finalized tcr_g2d* */
+    const float* params;        /* the trainable arena */
+    const float* aux;           /* TC-ResNet: frozen_ss (tcr_net_fold_bn); DS-CNN, 2-D graph: the moving-statistics arena */
+} tcr_model_ref;
+
+size_t tcr_stream_state_bytes_m(const tcr_frontend_cfg* cfg, const tcr_model_ref* model, int n_streams, int k, const tcr_detect_cfg* det);
+size_t tcr_stream_workspace_bytes_m(const tcr_frontend_cfg* cfg, const tcr_model_ref* model, int n_streams, int k);
+int tcr_stream_init_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_streams, int k,
+                      const tcr_detect_cfg* det, void* state, void* workspace, size_t ws_bytes, void* stream);
+int tcr_stream_step_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_streams, int k,
+                      const tcr_detect_cfg* det, const float* samples, const uint8_t* reset, void* state, void* workspace,
+                      size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new,
+                      void* stream);
+size_t tcr_scan_workspace_bytes_m(const tcr_frontend_cfg* cfg, const tcr_model_ref* model, int k, int max_windows);
+int tcr_scan_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_signals, int64_t n_samples, int k,
+               const tcr_detect_cfg* det, const float* samples, void* workspace, size_t ws_bytes, float* logits, float* probs,
+               float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream);
+int tcr_stream_scan_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_streams, int64_t n_samples,
+                      int k, const tcr_detect_cfg* det, const float* samples, const uint8_t* reset, void* state, void* workspace,
+                      size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new,
+                      void* stream);
+
 /* Detection sweep: tcr_stream_step's suppression rule for T thresholds at once, with the detections scored against labelled events.
  * top int32 / score float32 [N][steps] are what tcr_scan writes (or streaming steps stacked over steps).  For every signal n and
  * threshold t, starting from prev_label = -1, prev_step = 0, the steps i = 0 .. valid_steps[n] - 1 are walked in order:

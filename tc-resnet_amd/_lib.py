@@ -45,6 +45,14 @@ class DetectCfg(C.Structure):
     _fields_ = [("average_steps", C.c_int32), ("min_count", C.c_int32), ("suppression_steps", C.c_int32), ("threshold", C.c_float)]
 
 
+FAMILY_TCRESNET, FAMILY_DSCNN, FAMILY_G2D = 0, 1, 2
+
+
+class ModelRef(C.Structure):
+    """tcr_model_ref: the network of the detection entries (tcr_stream_*_m, tcr_scan_m, tcr_stream_scan_m)."""
+    _fields_ = [("family", C.c_int), ("handle", C.c_void_p), ("params", C.c_void_p), ("aux", C.c_void_p)]
+
+
 class TensorInfo(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("kind", C.c_int32), ("arena", C.c_int32), ("offset", C.c_int64),
                 ("size", C.c_int64), ("shape", C.c_int32 * 4), ("rank", C.c_int32)]
@@ -162,6 +170,17 @@ _PROTOTYPES = {
                            _P, _P, _P, _P, _P, _P, _P]),
     "tcr_stream_scan": (C.c_int, [C.POINTER(FrontendCfg), _P, _P, _P, _P, C.c_int, C.c_int64, C.c_int, C.POINTER(DetectCfg), _P, _P, _P, _P,
                                   C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
+    "tcr_stream_state_bytes_m": (C.c_size_t, [C.POINTER(FrontendCfg), C.POINTER(ModelRef), C.c_int, C.c_int, C.POINTER(DetectCfg)]),
+    "tcr_stream_workspace_bytes_m": (C.c_size_t, [C.POINTER(FrontendCfg), C.POINTER(ModelRef), C.c_int, C.c_int]),
+    "tcr_stream_init_m": (C.c_int, [C.POINTER(FrontendCfg), _P, C.POINTER(ModelRef), C.c_int, C.c_int, C.POINTER(DetectCfg), _P, _P, C.c_size_t,
+                                    _P]),
+    "tcr_stream_step_m": (C.c_int, [C.POINTER(FrontendCfg), _P, C.POINTER(ModelRef), C.c_int, C.c_int, C.POINTER(DetectCfg), _P, _P, _P, _P,
+                                    C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
+    "tcr_scan_workspace_bytes_m": (C.c_size_t, [C.POINTER(FrontendCfg), C.POINTER(ModelRef), C.c_int, C.c_int]),
+    "tcr_scan_m": (C.c_int, [C.POINTER(FrontendCfg), _P, C.POINTER(ModelRef), C.c_int, C.c_int64, C.c_int, C.POINTER(DetectCfg), _P, _P,
+                             C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
+    "tcr_stream_scan_m": (C.c_int, [C.POINTER(FrontendCfg), _P, C.POINTER(ModelRef), C.c_int, C.c_int64, C.c_int, C.POINTER(DetectCfg), _P, _P,
+                                    _P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
     "tcr_detect_sweep": (C.c_int, [C.c_int, C.c_int64, C.c_int, _P, _P, _P, C.c_int32, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 

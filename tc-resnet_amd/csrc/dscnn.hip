@@ -1124,6 +1124,12 @@ struct tcr_dscnn {
 
 namespace tcr {
 static int64_t ds_align(int64_t v) { return (v + 63) / 64 * 64; }
+
+void dscnn_io_shape(const tcr_dscnn* net, int* w_in, int* h_in, int* num_classes) {
+    *w_in = net->cfg.w_in;
+    *h_in = net->cfg.h_in;
+    *num_classes = net->cfg.num_classes;
+}
 }
 
 extern "C" int tcr_dscnn_create(const tcr_dscnn_cfg* cfg, tcr_dscnn** out) {

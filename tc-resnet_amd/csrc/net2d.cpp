@@ -326,6 +326,11 @@ extern "C" int64_t tcr_g2d_decay_floats(const tcr_g2d* g) { return g ? g->decay_
 extern "C" int64_t tcr_g2d_stat_floats(const tcr_g2d* g) { return g ? g->stat_floats : 0; }
 extern "C" int tcr_g2d_num_tensors(const tcr_g2d* g) { return g ? (int)g->tensors.size() : 0; }
 extern "C" int tcr_g2d_num_classes(const tcr_g2d* g) { return g ? g->num_classes : 0; }
+
+bool tcr::g2d_io_shape(const tcr_g2d* g, int* c, int* h, int* w, int* num_classes) {
+    *c = g->in_c; *h = g->in_h; *w = g->in_w; *num_classes = g->num_classes;
+    return g->finalized;
+}
 extern "C" int tcr_g2d_tensor_info(const tcr_g2d* g, int index, tcr_tensor_info* out) {
     TCR_REQUIRE(g && out && index >= 0 && index < (int)g->tensors.size(), "tcr_g2d_tensor_info: bad argument");
     *out = g->tensors[index];

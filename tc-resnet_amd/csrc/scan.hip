@@ -12,15 +12,17 @@
 // starting at frame (g G + 1) k.  A chunk is R consecutive groups (flattened over signals) = R G window slots:
 //   scan_stage_kernel     the R staging rows (zero prefix ++ signal, zeros past its end);
 //   frontend_pk3_kernel   <.., STREAM = true> over R rows of F frames into frame rows [R][n_coef][F + 2 TCR_HALO] (column 0 on);
-//   scan_gather_kernel    the planar windows [R G][n_coef][T + 2 TCR_HALO] (zero halo) from the frame rows;
-//   tcr_net_forward_frozen at batch R G (unchanged);
+//   scan_gather_kernel    the planar windows [R G][n_coef][T + 2 TCR_HALO] (zero halo) from the frame rows; for a 2-D graph
+//                         scan_gather_plane_kernel writes its [R G][1][T n_coef + 2 TCR_HALO] planes from them instead;
+//   the network at batch R G (detect_model.h: tcr_net_forward_frozen, tcr_dscnn_forward_infer or tcr_g2d_forward_infer, unchanged);
 //   scan_scatter_kernel   logits / probs of the slots that are steps (g G + j < steps) into the caller's [N][steps][C].
 // Slots past a signal's last step (the last group of a signal may be short) are computed and dropped.  Then, once per call:
 //   scan_smooth_kernel    a lane per (signal, step, class): smoothed, top, score and the candidate flag (is_new = top + 1 or 0);
 //   scan_suppress_kernel  a workgroup per signal finds the detections in step order and rewrites is_new with them.
 //
 // Workspace (tcr_scan_workspace_bytes), regions 256-byte aligned:
-//   staging [R][stage_stride] | frame rows [R][n_coef][F + 8] | windows [R G][n_coef][Tp] | logits, probs [R G][C] | network at R G.
+//   staging [R][stage_stride] | frame rows [R][n_coef][F + 8] | windows [R G][n_coef][Tp] (2-D graph: planes [R G][T n_coef + 8])
+//   | logits, probs [R G][C] | network at R G.
 // It does not depend on the signals' length; R and G are derived from the bytes the caller passes.
 //
 // Compiled as part of frontend_pk3.hip's translation unit (included at its end, after stream.hip).
@@ -39,13 +41,16 @@ constexpr int kSuppressPer = 32;         // steps per thread and pass of scan_su
 
 struct ScanGeom {
     int G, R, F, T, tp, n_coef, classes, stage_stride;
+    bool planes;                // the windows are the 2-D graph's planes
+    int64_t win_floats;         // floats of one window (detect_model.h)
     int64_t stage_off, frames_off, win_off, logits_off, probs_off, net_off, ws_floats;     // floats
 };
 
-ScanGeom scan_geom(const tcr_frontend_cfg& cfg, const tcr_net* net, int k, int G, int R) {
+ScanGeom scan_geom(const tcr_frontend_cfg& cfg, const tcr_model_ref& m, const ModelIO& io, int k, int G, int R) {
     ScanGeom g{};
-    int cin = 0, t_in = 0, classes = 0;
-    net_io_shape(net, &cin, &t_in, &classes);
+    const int classes = io.classes;
+    g.planes = io.planes;
+    g.win_floats = model_window_floats(io);
     g.G = G; g.R = R; g.T = cfg.n_frames; g.tp = tcr_padded_len(cfg.n_frames); g.n_coef = cfg.n_coef; g.classes = classes;
     g.F = G * k + g.T - k;
     g.stage_stride = ((g.F - 1) * cfg.hop + cfg.win + 3) / 4 * 4;
@@ -53,17 +58,18 @@ ScanGeom scan_geom(const tcr_frontend_cfg& cfg, const tcr_net* net, int k, int G
     int64_t o = 0;
     g.stage_off = o; o = align64(o + (int64_t)R * g.stage_stride);
     g.frames_off = o; o = align64(o + (int64_t)R * g.n_coef * tcr_padded_len(g.F));
-    g.win_off = o; o = align64(o + B * g.n_coef * g.tp);
+    g.win_off = o; o = align64(o + B * g.win_floats);
     g.logits_off = o; o = align64(o + B * classes);
     g.probs_off = o; o = align64(o + B * classes);
     g.net_off = o;
-    g.ws_floats = o + (int64_t)(tcr_net_workspace_bytes(net, (int)B, 0) / sizeof(float));
+    g.ws_floats = o + (int64_t)(model_workspace_bytes(m, (int)B) / sizeof(float));
     return g;
 }
 
-// a chunk's slots and frames stay inside the int ranges of the kernels below and of the front-end's launcher
-bool scan_geom_ok(int k, int T, int G, int64_t R) {
-    return R >= 1 && R * G < (1 << 24) && R * (G * (int64_t)k + T - k) < (1 << 23);
+// a chunk's slots and frames stay inside the int ranges of the kernels below and of the front-end's launcher, and its R G windows
+// inside the batches one network call runs on one kernel path (ModelIO::max_batch: DS-CNN's kDscnnMaxBatch)
+bool scan_geom_ok(int k, int T, int G, int64_t R, int max_batch) {
+    return R >= 1 && R * G < (1 << 24) && R * G <= max_batch && R * (G * (int64_t)k + T - k) < (1 << 23);
 }
 
 }  // namespace
@@ -108,6 +114,26 @@ __global__ __launch_bounds__(256) void scan_gather_kernel(const ScanGatherArgs a
         c += dc;
         x += dx;
         if (x >= a.tp) { x -= a.tp; ++c; }
+    }
+}
+
+// scan_gather_kernel for a 2-D graph: the window of slot b as its [T x n_coef] plane, written in plane order (coalesced): plane
+// offset t n_coef + c <- frame-row column j k + t, coefficient c (features_to_plane_kernel's map, net2d_kernels.hip), zero halo.
+// A pure copy: bitwise scan_gather_kernel followed by features_to_plane_kernel.
+__global__ __launch_bounds__(256) void scan_gather_plane_kernel(const ScanGatherArgs a) {
+    const int b = blockIdx.x;
+    const int r = b / a.G, j = b - r * a.G;
+    const float* src = a.frames + (size_t)r * a.n_coef * a.ftp + j * a.k + kHalo;      // column t <- frame-row column j k + t
+    const int n = a.T * a.n_coef, pp = n + 2 * kHalo;
+    float* dst = a.windows + (size_t)b * pp;
+    for (int i = threadIdx.x; i < pp; i += 256) {
+        const int o = i - kHalo;
+        float v = 0.f;
+        if (o >= 0 && o < n) {
+            const int t = o / a.n_coef, c = o - t * a.n_coef;
+            v = src[(size_t)c * a.ftp + t];
+        }
+        dst[i] = v;
     }
 }
 
@@ -263,59 +289,56 @@ int scan_group(int64_t steps, int cap) {
 }
 
 // The largest chunk the workspace holds for n_signals x steps: G = the balanced group (smaller when even one row of it does not fit),
-// R rows (TCR_ERR_WORKSPACE below one window).
-int scan_chunking(const tcr_frontend_cfg& cfg, const tcr_net* net, int k, int64_t steps, int n_signals, size_t ws_bytes, const char* what,
-                  ScanGeom& out) {
+// R rows (TCR_ERR_WORKSPACE below one window).  R G also stays within io.max_batch (scan_geom_ok; G <= kScanGroup is far below
+// every family's bound), so that every window of a DS-CNN scan runs on the kernel path a stream step of up to kDscnnMaxBatch
+// streams runs: the result does not depend on the chunking.
+int scan_chunking(const tcr_frontend_cfg& cfg, const tcr_model_ref& m, const ModelIO& io, int k, int64_t steps, int n_signals,
+                  size_t ws_bytes, const char* what, ScanGeom& out) {
     int G = scan_group(steps, kScanGroup);
-    while (G > 1 && (size_t)scan_geom(cfg, net, k, G, 1).ws_floats * sizeof(float) > ws_bytes) G = scan_group(steps, G / 2);
-    if ((size_t)scan_geom(cfg, net, k, G, 1).ws_floats * sizeof(float) > ws_bytes) {
-        set_error("%s: workspace %zu bytes < one window's %zu", what, ws_bytes, (size_t)scan_geom(cfg, net, k, 1, 1).ws_floats * sizeof(float));
+    while (G > 1 && (size_t)scan_geom(cfg, m, io, k, G, 1).ws_floats * sizeof(float) > ws_bytes) G = scan_group(steps, G / 2);
+    if ((size_t)scan_geom(cfg, m, io, k, G, 1).ws_floats * sizeof(float) > ws_bytes) {
+        set_error("%s: workspace %zu bytes < one window's %zu", what, ws_bytes,
+                  (size_t)scan_geom(cfg, m, io, k, 1, 1).ws_floats * sizeof(float));
         return TCR_ERR_WORKSPACE;
     }
     const int64_t total_groups = ceil_div64(steps, G) * n_signals;
     int64_t lo = 1, hi = total_groups;                  // R: the largest that fits (binary search; the size grows with R)
     while (lo < hi) {
         const int64_t mid = (lo + hi + 1) / 2;
-        if (scan_geom_ok(k, cfg.n_frames, G, mid) && (size_t)scan_geom(cfg, net, k, G, (int)mid).ws_floats * sizeof(float) <= ws_bytes) lo = mid;
+        if (scan_geom_ok(k, cfg.n_frames, G, mid, io.max_batch) &&
+            (size_t)scan_geom(cfg, m, io, k, G, (int)mid).ws_floats * sizeof(float) <= ws_bytes) lo = mid;
         else hi = mid - 1;
     }
-    out = scan_geom(cfg, net, k, G, (int)lo);
+    out = scan_geom(cfg, m, io, k, G, (int)lo);
     return TCR_OK;
 }
 
-}  // namespace
-
-}  // namespace tcr
-
-using namespace tcr;
-
-extern "C" size_t tcr_scan_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_net* net, int k, int max_windows) {
-    if (stream_check(cfg, net, 1, k, nullptr, "tcr_scan_workspace_bytes") != TCR_OK) return 0;
-    if (max_windows < 1) { set_error("tcr_scan_workspace_bytes: max_windows must be >= 1 (got %d)", max_windows); return 0; }
+size_t scan_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_model_ref* m, int k, int max_windows, const char* what) {
+    ModelIO io;
+    if (stream_check(cfg, m, 1, k, nullptr, what, io) != TCR_OK) return 0;
+    if (max_windows < 1) { set_error("%s: max_windows must be >= 1 (got %d)", what, max_windows); return 0; }
     const int G = std::min(kScanGroup, max_windows);
     const int R = max_windows / G;
-    if (!scan_geom_ok(k, cfg->n_frames, G, R)) { set_error("tcr_scan_workspace_bytes: %d windows is too large", max_windows); return 0; }
-    return (size_t)scan_geom(*cfg, net, k, G, R).ws_floats * sizeof(float);
+    if (!scan_geom_ok(k, cfg->n_frames, G, R, io.max_batch)) { set_error("%s: %d windows is too large", what, max_windows); return 0; }
+    return (size_t)scan_geom(*cfg, *m, io, k, G, R).ws_floats * sizeof(float);
 }
 
-extern "C" int tcr_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params, const float* frozen_ss,
-                        int n_signals, int64_t n_samples, int k, const tcr_detect_cfg* det, const float* samples, void* workspace,
-                        size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new,
-                        void* stream) {
-    TCR_REQUIRE(plan_dev && params && frozen_ss && det && samples && workspace && logits && probs && smoothed && top && score && is_new,
-                "tcr_scan: null argument");
-    TCR_REQUIRE(n_signals > 0, "tcr_scan: the number of signals must be positive (got %d)", n_signals);
-    TCR_TRY(stream_check(cfg, net, n_signals, k, det, "tcr_scan"));
+int scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* m, int n_signals, int64_t n_samples, int k,
+         const tcr_detect_cfg* det, const float* samples, void* workspace, size_t ws_bytes, float* logits, float* probs, float* smoothed,
+         int32_t* top, float* score, int32_t* is_new, void* stream, const char* what) {
+    TCR_REQUIRE(plan_dev && m && m->params && m->aux && det && samples && workspace && logits && probs && smoothed && top && score && is_new,
+                "%s: null argument", what);
+    TCR_REQUIRE(n_signals > 0, "%s: the number of signals must be positive (got %d)", what, n_signals);
+    ModelIO io;
+    TCR_TRY(stream_check(cfg, m, n_signals, k, det, what, io, false));
     const int64_t khop = (int64_t)k * cfg->hop;
-    TCR_REQUIRE(n_samples > 0 && n_samples % khop == 0, "tcr_scan: the signal length %lld is not a positive multiple of k * hop = %lld",
+    TCR_REQUIRE(n_samples > 0 && n_samples % khop == 0, "%s: the signal length %lld is not a positive multiple of k * hop = %lld", what,
                 (long long)n_samples, (long long)khop);
     const int64_t steps = n_samples / khop;
-    int cin = 0, t_in = 0, classes = 0;
-    net_io_shape(net, &cin, &t_in, &classes);
-    TCR_REQUIRE((int64_t)n_signals * steps * classes < ((int64_t)1 << 31), "tcr_scan: %d signals x %lld steps is too large", n_signals,
+    TCR_REQUIRE((int64_t)n_signals * steps * io.classes < ((int64_t)1 << 31), "%s: %d signals x %lld steps is too large", what, n_signals,
                 (long long)steps);
     ScanGeom g;
-    TCR_TRY(scan_chunking(*cfg, net, k, steps, n_signals, ws_bytes, "tcr_scan", g));
+    TCR_TRY(scan_chunking(*cfg, *m, io, k, steps, n_signals, ws_bytes, what, g));
     const int G = g.G;
     const int64_t groups = ceil_div64(steps, G), total_groups = groups * n_signals;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -335,10 +358,15 @@ extern "C" int tcr_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const
         ScanGatherArgs ga;
         ga.frames = ws + g.frames_off; ga.windows = ws + g.win_off; ga.G = G; ga.k = k; ga.T = g.T; ga.tp = g.tp; ga.n_coef = g.n_coef;
         ga.ftp = ftp;
-        hipLaunchKernelGGL(scan_gather_kernel, dim3(slots), dim3(256), 0, s, ga);
-        TCR_TRY(check_launch("scan_gather_kernel"));
-        TCR_TRY(tcr_net_forward_frozen(net, params, frozen_ss, ws + g.win_off, slots, ws + g.net_off, ws_bytes - (size_t)g.net_off * sizeof(float),
-                                       ws + g.logits_off, ws + g.probs_off, nullptr, stream));
+        if (g.planes) {
+            hipLaunchKernelGGL(scan_gather_plane_kernel, dim3(slots), dim3(256), 0, s, ga);
+            TCR_TRY(check_launch("scan_gather_plane_kernel"));
+        } else {
+            hipLaunchKernelGGL(scan_gather_kernel, dim3(slots), dim3(256), 0, s, ga);
+            TCR_TRY(check_launch("scan_gather_kernel"));
+        }
+        TCR_TRY(model_forward(*m, ws + g.win_off, slots, ws + g.net_off, ws_bytes - (size_t)g.net_off * sizeof(float), ws + g.logits_off,
+                              ws + g.probs_off, stream));
         ScanScatterArgs xa;
         xa.logits_in = ws + g.logits_off; xa.probs_in = ws + g.probs_off; xa.logits = logits; xa.probs = probs; xa.q0 = q0;
         xa.groups = groups; xa.steps = steps; xa.G = G; xa.C = g.classes; xa.slots = slots;
@@ -352,4 +380,35 @@ extern "C" int tcr_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const
     TCR_TRY(check_launch("scan_smooth_kernel"));
     hipLaunchKernelGGL(scan_suppress_kernel, dim3(n_signals), dim3(256), 0, s, is_new, steps, det->suppression_steps);
     return check_launch("scan_suppress_kernel");
+}
+
+}  // namespace
+
+}  // namespace tcr
+
+using namespace tcr;
+
+extern "C" size_t tcr_scan_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_net* net, int k, int max_windows) {
+    const tcr_model_ref m = tcresnet_ref(net, nullptr, nullptr);
+    return scan_workspace_bytes(cfg, &m, k, max_windows, "tcr_scan_workspace_bytes");
+}
+
+extern "C" size_t tcr_scan_workspace_bytes_m(const tcr_frontend_cfg* cfg, const tcr_model_ref* model, int k, int max_windows) {
+    return scan_workspace_bytes(cfg, model, k, max_windows, "tcr_scan_workspace_bytes_m");
+}
+
+extern "C" int tcr_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params, const float* frozen_ss,
+                        int n_signals, int64_t n_samples, int k, const tcr_detect_cfg* det, const float* samples, void* workspace,
+                        size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new,
+                        void* stream) {
+    const tcr_model_ref m = tcresnet_ref(net, params, frozen_ss);
+    return scan(cfg, plan_dev, &m, n_signals, n_samples, k, det, samples, workspace, ws_bytes, logits, probs, smoothed, top, score, is_new,
+                stream, "tcr_scan");
+}
+
+extern "C" int tcr_scan_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_signals, int64_t n_samples,
+                          int k, const tcr_detect_cfg* det, const float* samples, void* workspace, size_t ws_bytes, float* logits,
+                          float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream) {
+    return scan(cfg, plan_dev, model, n_signals, n_samples, k, det, samples, workspace, ws_bytes, logits, probs, smoothed, top, score, is_new,
+                stream, "tcr_scan_m");
 }

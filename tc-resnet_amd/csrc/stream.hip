@@ -12,14 +12,17 @@
 // Nothing is accumulated: every column comes from raw samples, so the window does not drift however long a stream runs.
 //
 // Kernels of a step: stream_stage_kernel (reset, staging row, tail, window shift; one workgroup per stream, so the in-place shift has
-// no cross-workgroup hazard), frontend_pk3_kernel<.., STREAM = true>, the network (tcr_net_forward_frozen, untouched), then
+// no cross-workgroup hazard), frontend_pk3_kernel<.., STREAM = true>, the network (detect_model.h: tcr_net_forward_frozen,
+// tcr_dscnn_forward_infer on the planar windows, or tcr_g2d_forward_infer on planes that features_to_plane_kernel lays out from them
+// in the workspace; the state keeps the planar window whatever the family, the front-end writes its new columns there), then
 // stream_detect_kernel (a lane per stream and class: the smoothing / detection rule of the header, a ring of the last W probability
 // vectors).
 //
 // State (caller-owned device memory, tcr_stream_state_bytes), regions 256-byte aligned:
 //   window [S][n_coef][T + 2 TCR_HALO] | zero window [n_coef][Tp] (the features of a silent clip: what a reset window is)
 //   | tail [S][tail_len] | ring [W][S][classes] | detector integers [5][S] (head, count, prev_label, prev_step, n)
-// Workspace (tcr_stream_workspace_bytes): staging rows [S][stage_stride] (>= n_samples floats) | the network's workspace at batch S.
+// Workspace (tcr_stream_workspace_bytes): staging rows [S][stage_stride] (>= n_samples floats) | 2-D graph: the planes
+//   [S][T n_coef + 2 TCR_HALO] | the network's workspace at batch S.
 //
 // Compiled as part of frontend_pk3.hip's translation unit (included at its end, next to the streaming front-end's launcher).
 #pragma once
@@ -27,6 +30,7 @@
 
 #include "frontend_plan.h"
 #include "frontend_args.h"
+#include "detect_model.h"
 
 namespace tcr {
 
@@ -39,15 +43,14 @@ struct StreamGeom {
     int S, k, T, tp, n_coef, classes, W;
     int tail_len, stage_stride;
     int64_t win_off, zw_off, tail_off, ring_off, ist_off, state_floats;         // state offsets in floats
-    int64_t stage_floats, net_ws_off, ws_floats;                                // workspace
+    int64_t stage_floats, plane_off, net_ws_off, ws_floats;                     // workspace
 };
 
 int64_t align64(int64_t v) { return (v + 63) / 64 * 64; }     // floats -> 256 bytes
 
-StreamGeom stream_geom(const tcr_frontend_cfg& cfg, const tcr_net* net, int S, int k, int W) {
+StreamGeom stream_geom(const tcr_frontend_cfg& cfg, const tcr_model_ref& m, const ModelIO& io, int S, int k, int W) {
     StreamGeom g{};
-    int cin = 0, t_in = 0, classes = 0;
-    net_io_shape(net, &cin, &t_in, &classes);
+    const int classes = io.classes;
     g.S = S; g.k = k; g.T = cfg.n_frames; g.tp = tcr_padded_len(cfg.n_frames); g.n_coef = cfg.n_coef; g.classes = classes; g.W = W;
     g.tail_len = cfg.win - cfg.hop + (cfg.n_samples - cfg.win) % cfg.hop;
     g.stage_stride = (g.tail_len + k * cfg.hop + 3) / 4 * 4;
@@ -59,22 +62,26 @@ StreamGeom stream_geom(const tcr_frontend_cfg& cfg, const tcr_net* net, int S, i
     g.ist_off = o; o = align64(o + 5 * (int64_t)S);
     g.state_floats = o;
     g.stage_floats = align64(std::max((int64_t)S * g.stage_stride, (int64_t)cfg.n_samples));
-    g.net_ws_off = g.stage_floats;
-    g.ws_floats = g.stage_floats + (int64_t)(tcr_net_workspace_bytes(net, S, 0) / sizeof(float));
+    g.plane_off = g.stage_floats;
+    g.net_ws_off = g.plane_off + (io.planes ? align64((int64_t)S * model_window_floats(io)) : 0);
+    g.ws_floats = g.net_ws_off + (int64_t)(model_workspace_bytes(m, S) / sizeof(float));
     return g;
 }
 
-// Everything the create / step calls refuse, with the reason.
-int stream_check(const tcr_frontend_cfg* cfg, const tcr_net* net, int S, int k, const tcr_detect_cfg* det, const char* what) {
-    TCR_REQUIRE(cfg && net, "%s: null front-end configuration or network", what);
+// Everything the create / step calls refuse, with the reason; io: the network's shape.  S is a batch of the network (the streams of
+// tcr_stream_*), or not (the signals of tcr_scan: streams_are_batch = false).
+int stream_check(const tcr_frontend_cfg* cfg, const tcr_model_ref* m, int S, int k, const tcr_detect_cfg* det, const char* what, ModelIO& io,
+                 bool streams_are_batch = true) {
+    TCR_REQUIRE(cfg && m && m->handle, "%s: null front-end configuration or network", what);
+    TCR_TRY(model_io(*m, what, io));
     TCR_REQUIRE(cfg->nfft == 512 || cfg->nfft == 1024, "%s: unresolved or unsupported front-end configuration (nfft=%d)", what, cfg->nfft);
     TCR_REQUIRE(cfg->method != 2, "%s: the float64 deploy front-end (method 2, mfcc_deploy) has no streaming instance", what);
-    int cin = 0, t_in = 0, classes = 0;
-    net_io_shape(net, &cin, &t_in, &classes);
-    TCR_REQUIRE(cfg->n_coef == cin && cfg->n_frames == t_in, "%s: the front-end yields %d x %d features, the network expects %d x %d", what,
-                cfg->n_coef, cfg->n_frames, cin, t_in);
+    TCR_REQUIRE(cfg->n_coef == io.n_coef && cfg->n_frames == io.t, "%s: the front-end yields %d x %d features, the network expects %d x %d",
+                what, cfg->n_coef, cfg->n_frames, io.n_coef, io.t);
     TCR_REQUIRE(S > 0, "%s: the number of streams must be positive (got %d)", what, S);
-    TCR_REQUIRE(classes <= 256, "%s: the detector takes at most 256 classes (got %d)", what, classes);
+    TCR_REQUIRE(!streams_are_batch || S <= io.max_batch, "%s: %d streams exceed the %d windows one call of this network runs", what, S,
+                io.max_batch);
+    TCR_REQUIRE(io.classes <= 256, "%s: the detector takes at most 256 classes (got %d)", what, io.classes);
     TCR_REQUIRE(k >= 1 && k <= cfg->n_frames, "%s: frames per step k = %d outside 1..T = %d", what, k, cfg->n_frames);
     TCR_REQUIRE((int64_t)S * k < (1 << 23) && (int64_t)S * cfg->n_frames < ((int64_t)1 << 31), "%s: %d streams x %d frames is too large", what, S, k);
     TCR_REQUIRE((cfg->hop & 1) == 0 && frontend_pk3_supports(cfg->nfft / 2, cfg->win, frontend_mel_item_count(*cfg)),
@@ -278,30 +285,28 @@ int stream_frontend(const tcr_frontend_cfg& cfg, const void* plan_dev, const flo
     return rc;
 }
 
-}  // namespace
-
-}  // namespace tcr
-
-using namespace tcr;
-
-extern "C" size_t tcr_stream_state_bytes(const tcr_frontend_cfg* cfg, const tcr_net* net, int n_streams, int k, const tcr_detect_cfg* det) {
-    if (!det) { set_error("tcr_stream_state_bytes: null detector configuration"); return 0; }
-    if (stream_check(cfg, net, n_streams, k, det, "tcr_stream_state_bytes") != TCR_OK) return 0;
-    return (size_t)stream_geom(*cfg, net, n_streams, k, det->average_steps).state_floats * sizeof(float);
+size_t stream_state_bytes(const tcr_frontend_cfg* cfg, const tcr_model_ref* m, int n_streams, int k, const tcr_detect_cfg* det,
+                          const char* what) {
+    if (!det) { set_error("%s: null detector configuration", what); return 0; }
+    ModelIO io;
+    if (stream_check(cfg, m, n_streams, k, det, what, io) != TCR_OK) return 0;
+    return (size_t)stream_geom(*cfg, *m, io, n_streams, k, det->average_steps).state_floats * sizeof(float);
 }
 
-extern "C" size_t tcr_stream_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_net* net, int n_streams, int k) {
-    if (stream_check(cfg, net, n_streams, k, nullptr, "tcr_stream_workspace_bytes") != TCR_OK) return 0;
-    return (size_t)stream_geom(*cfg, net, n_streams, k, 1).ws_floats * sizeof(float);
+size_t stream_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_model_ref* m, int n_streams, int k, const char* what) {
+    ModelIO io;
+    if (stream_check(cfg, m, n_streams, k, nullptr, what, io) != TCR_OK) return 0;
+    return (size_t)stream_geom(*cfg, *m, io, n_streams, k, 1).ws_floats * sizeof(float);
 }
 
-extern "C" int tcr_stream_init(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, int n_streams, int k,
-                               const tcr_detect_cfg* det, void* state, void* workspace, size_t ws_bytes, void* stream) {
-    TCR_REQUIRE(plan_dev && det && state && workspace, "tcr_stream_init: null argument");
-    TCR_TRY(stream_check(cfg, net, n_streams, k, det, "tcr_stream_init"));
-    const StreamGeom g = stream_geom(*cfg, net, n_streams, k, det->average_steps);
+int stream_init(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* m, int n_streams, int k, const tcr_detect_cfg* det,
+                void* state, void* workspace, size_t ws_bytes, void* stream, const char* what) {
+    TCR_REQUIRE(plan_dev && det && state && workspace, "%s: null argument", what);
+    ModelIO io;
+    TCR_TRY(stream_check(cfg, m, n_streams, k, det, what, io));
+    const StreamGeom g = stream_geom(*cfg, *m, io, n_streams, k, det->average_steps);
     if ((size_t)g.ws_floats * sizeof(float) > ws_bytes) {
-        set_error("tcr_stream_init: workspace %zu bytes < required %zu", ws_bytes, (size_t)g.ws_floats * sizeof(float));
+        set_error("%s: workspace %zu bytes < required %zu", what, ws_bytes, (size_t)g.ws_floats * sizeof(float));
         return TCR_ERR_WORKSPACE;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -309,12 +314,12 @@ extern "C" int tcr_stream_init(const tcr_frontend_cfg* cfg, const void* plan_dev
     float* ws = static_cast<float*>(workspace);
     // the zero window: the streaming front-end over one silent clip (all T frames, columns 0..T-1) -- the offline kernel's arithmetic
     if (hipMemsetAsync(ws, 0, (size_t)cfg->n_samples * sizeof(float), s) != hipSuccess) {
-        set_error("tcr_stream_init: hipMemsetAsync failed");
+        set_error("%s: hipMemsetAsync failed", what);
         return TCR_ERR_HIP;
     }
     TCR_TRY(stream_frontend(*cfg, plan_dev, ws, cfg->n_samples, 1, cfg->n_frames, st + g.zw_off, s));
     if (hipMemsetAsync(st + g.ring_off, 0, (size_t)g.W * g.classes * g.S * sizeof(float), s) != hipSuccess) {
-        set_error("tcr_stream_init: hipMemsetAsync failed");
+        set_error("%s: hipMemsetAsync failed", what);
         return TCR_ERR_HIP;
     }
     const int64_t work = (int64_t)g.S * g.n_coef * g.tp;
@@ -324,16 +329,16 @@ extern "C" int tcr_stream_init(const tcr_frontend_cfg* cfg, const void* plan_dev
     return check_launch("stream_init_kernel");
 }
 
-extern "C" int tcr_stream_step(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params,
-                               const float* frozen_ss, int n_streams, int k, const tcr_detect_cfg* det, const float* samples,
-                               const uint8_t* reset, void* state, void* workspace, size_t ws_bytes, float* logits, float* probs,
-                               float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream) {
-    TCR_REQUIRE(plan_dev && params && frozen_ss && det && samples && state && workspace && logits && probs && smoothed && top && score && is_new,
-                "tcr_stream_step: null argument");
-    TCR_TRY(stream_check(cfg, net, n_streams, k, det, "tcr_stream_step"));
-    const StreamGeom g = stream_geom(*cfg, net, n_streams, k, det->average_steps);
+int stream_step(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* m, int n_streams, int k, const tcr_detect_cfg* det,
+                const float* samples, const uint8_t* reset, void* state, void* workspace, size_t ws_bytes, float* logits, float* probs,
+                float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream, const char* what) {
+    TCR_REQUIRE(plan_dev && m && m->params && m->aux && det && samples && state && workspace && logits && probs && smoothed && top && score &&
+                is_new, "%s: null argument", what);
+    ModelIO io;
+    TCR_TRY(stream_check(cfg, m, n_streams, k, det, what, io));
+    const StreamGeom g = stream_geom(*cfg, *m, io, n_streams, k, det->average_steps);
     if ((size_t)g.ws_floats * sizeof(float) > ws_bytes) {
-        set_error("tcr_stream_step: workspace %zu bytes < required %zu", ws_bytes, (size_t)g.ws_floats * sizeof(float));
+        set_error("%s: workspace %zu bytes < required %zu", what, ws_bytes, (size_t)g.ws_floats * sizeof(float));
         return TCR_ERR_WORKSPACE;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -345,12 +350,69 @@ extern "C" int tcr_stream_step(const tcr_frontend_cfg* cfg, const void* plan_dev
     hipLaunchKernelGGL(stream_stage_kernel, dim3(g.S), dim3(256), 0, s, sa);
     TCR_TRY(check_launch("stream_stage_kernel"));
     TCR_TRY(stream_frontend(*cfg, plan_dev, ws, g.stage_stride, g.S, k, st + g.win_off, s));
-    TCR_TRY(tcr_net_forward_frozen(net, params, frozen_ss, st + g.win_off, g.S, ws + g.net_ws_off, ws_bytes - (size_t)g.net_ws_off * sizeof(float),
-                                   logits, probs, nullptr, stream));
+    const float* x = st + g.win_off;
+    if (io.planes) {            // the 2-D graph's planes, relaid out from the windows (a pure copy)
+        TCR_TRY(tcr_g2d_input_from_features(x, g.S, g.T, g.n_coef, ws + g.plane_off, stream));
+        x = ws + g.plane_off;
+    }
+    TCR_TRY(model_forward(*m, x, g.S, ws + g.net_ws_off, ws_bytes - (size_t)g.net_ws_off * sizeof(float), logits, probs, stream));
     DetectArgs da;
     da.probs = probs; da.reset = reset; da.ring = st + g.ring_off; da.ist = reinterpret_cast<int*>(st + g.ist_off);
     da.smoothed = smoothed; da.top = top; da.score = score; da.is_new = is_new;
     da.S = g.S; da.C = g.classes; da.W = g.W; da.min_count = det->min_count; da.suppression = det->suppression_steps; da.threshold = det->threshold;
     hipLaunchKernelGGL(stream_detect_kernel, dim3(ceil_div(g.S, 256 / g.classes)), dim3(256), 0, s, da);
     return check_launch("stream_detect_kernel");
+}
+
+}  // namespace
+
+}  // namespace tcr
+
+using namespace tcr;
+
+extern "C" size_t tcr_stream_state_bytes(const tcr_frontend_cfg* cfg, const tcr_net* net, int n_streams, int k, const tcr_detect_cfg* det) {
+    const tcr_model_ref m = tcresnet_ref(net, nullptr, nullptr);
+    return stream_state_bytes(cfg, &m, n_streams, k, det, "tcr_stream_state_bytes");
+}
+
+extern "C" size_t tcr_stream_state_bytes_m(const tcr_frontend_cfg* cfg, const tcr_model_ref* model, int n_streams, int k,
+                                           const tcr_detect_cfg* det) {
+    return stream_state_bytes(cfg, model, n_streams, k, det, "tcr_stream_state_bytes_m");
+}
+
+extern "C" size_t tcr_stream_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_net* net, int n_streams, int k) {
+    const tcr_model_ref m = tcresnet_ref(net, nullptr, nullptr);
+    return stream_workspace_bytes(cfg, &m, n_streams, k, "tcr_stream_workspace_bytes");
+}
+
+extern "C" size_t tcr_stream_workspace_bytes_m(const tcr_frontend_cfg* cfg, const tcr_model_ref* model, int n_streams, int k) {
+    return stream_workspace_bytes(cfg, model, n_streams, k, "tcr_stream_workspace_bytes_m");
+}
+
+extern "C" int tcr_stream_init(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, int n_streams, int k,
+                               const tcr_detect_cfg* det, void* state, void* workspace, size_t ws_bytes, void* stream) {
+    const tcr_model_ref m = tcresnet_ref(net, nullptr, nullptr);
+    return stream_init(cfg, plan_dev, &m, n_streams, k, det, state, workspace, ws_bytes, stream, "tcr_stream_init");
+}
+
+extern "C" int tcr_stream_init_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_streams, int k,
+                                 const tcr_detect_cfg* det, void* state, void* workspace, size_t ws_bytes, void* stream) {
+    return stream_init(cfg, plan_dev, model, n_streams, k, det, state, workspace, ws_bytes, stream, "tcr_stream_init_m");
+}
+
+extern "C" int tcr_stream_step(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params,
+                               const float* frozen_ss, int n_streams, int k, const tcr_detect_cfg* det, const float* samples,
+                               const uint8_t* reset, void* state, void* workspace, size_t ws_bytes, float* logits, float* probs,
+                               float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream) {
+    const tcr_model_ref m = tcresnet_ref(net, params, frozen_ss);
+    return stream_step(cfg, plan_dev, &m, n_streams, k, det, samples, reset, state, workspace, ws_bytes, logits, probs, smoothed, top, score,
+                       is_new, stream, "tcr_stream_step");
+}
+
+extern "C" int tcr_stream_step_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_streams, int k,
+                                 const tcr_detect_cfg* det, const float* samples, const uint8_t* reset, void* state, void* workspace,
+                                 size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new,
+                                 void* stream) {
+    return stream_step(cfg, plan_dev, model, n_streams, k, det, samples, reset, state, workspace, ws_bytes, logits, probs, smoothed, top, score,
+                       is_new, stream, "tcr_stream_step_m");
 }

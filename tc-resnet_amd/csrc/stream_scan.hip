@@ -10,11 +10,13 @@
 // carried window in place of its silent prefix.  Frames of negative index are computed from zeros and never gathered.  Per chunk:
 //   stream_scan_stage_kernel   the staging rows (tail ++ samples, zeros outside);
 //   frontend_pk3_kernel        <.., STREAM = true>, as in tcr_scan;
-//   stream_scan_gather_kernel  the planar windows: frame-row columns, or carried columns for negative frames;
+//   stream_scan_gather_kernel  the planar windows: frame-row columns, or carried columns for negative frames (2-D graph:
+//                              stream_scan_gather_plane_kernel writes the same values as its planes);
 //   stream_scan_carry_kernel   window and tail write-back of the streams whose last group is in this chunk (their last step's
 //                              window, gathered just before; the last tail_len samples of x, the old tail read before it is written);
-//                              a stream's groups are consecutive, so no later chunk reads its window or tail;
-//   tcr_net_forward_frozen, scan_scatter_kernel (tcr_scan's).
+//                              a stream's groups are consecutive, so no later chunk reads its window or tail (2-D graph:
+//                              stream_scan_carry_plane_kernel, the planar state window read back from the plane);
+//   the network (detect_model.h), scan_scatter_kernel (tcr_scan's).
 // Once per call:
 //   stream_scan_smooth_kernel    scan_smooth_kernel with the ring in front: count_i = min(count0 + i + 1, W), the vectors of steps
 //                                before the call from ring slots (head0 - d) mod W, oldest first, through smooth_mean;
@@ -91,6 +93,30 @@ __global__ __launch_bounds__(256) void stream_scan_gather_kernel(const StreamSca
     }
 }
 
+// stream_scan_gather_kernel for a 2-D graph: slot b's window as its [T x n_coef] plane, written in plane order: plane offset
+// t n_coef + c <- window column t, coefficient c (features_to_plane_kernel's map, net2d_kernels.hip), zero halo.  A pure copy:
+// bitwise stream_scan_gather_kernel followed by features_to_plane_kernel.
+__global__ __launch_bounds__(256) void stream_scan_gather_plane_kernel(const StreamScanGatherArgs a) {
+    const int b = blockIdx.x;
+    const int r = b / a.G, j = b - r * a.G;
+    const int64_t q = a.q0 + r, s = q / a.groups, g = q - s * a.groups;
+    const int64_t i1 = (g * a.G + j + 1) * a.k;                                 // (i + 1) k
+    const int sh = i1 < a.T ? (int)i1 : a.T;                                    // carried columns: t < T - sh
+    const float* src = a.frames + (size_t)r * a.n_coef * a.ftp + j * a.k;      // window column x <- frame-row column j k + x
+    const float* old = (a.reset && a.reset[s] ? a.zw : a.window + (size_t)s * a.n_coef * a.tp) + sh;
+    const int n = a.T * a.n_coef, pp = n + 2 * kHalo;
+    float* dst = a.windows + (size_t)b * pp;
+    for (int i = threadIdx.x; i < pp; i += 256) {
+        const int o = i - kHalo;
+        float v = 0.f;
+        if (o >= 0 && o < n) {
+            const int t = o / a.n_coef, c = o - t * a.n_coef, x = t + kHalo;
+            v = t + sh < a.T ? old[c * a.tp + x] : src[(size_t)c * a.ftp + x];
+        }
+        dst[i] = v;
+    }
+}
+
 struct StreamScanCarryArgs {
     const float* windows;       // the chunk's [R G][n_coef][tp]
     const float* samples;       // [S][L]
@@ -112,6 +138,35 @@ __global__ __launch_bounds__(256) void stream_scan_carry_kernel(const StreamScan
     const float* wsrc = a.windows + b * a.win_elems;
     float* wdst = a.window + s * a.win_elems;
     for (int i = tid; i < a.win_elems; i += 256) wdst[i] = wsrc[i];
+    const bool rst = a.reset && a.reset[s];
+    float* tail = a.tail + s * a.tail_len;
+    const float* src = a.samples + s * a.L;
+    const int keep = a.L < a.tail_len ? (int)(a.tail_len - a.L) : 0;          // old tail samples L .. tail_len - 1 stay
+    for (int i = tid; i < keep; i += 256) s_tail[i] = rst ? 0.f : tail[a.L + i];
+    __syncthreads();
+    for (int i = tid; i < a.tail_len; i += 256) tail[i] = i < keep ? s_tail[i] : src[a.L - a.tail_len + i];
+}
+
+struct StreamScanCarryPlaneArgs {
+    StreamScanCarryArgs c;      // c.win_elems: the state's n_coef tp floats per stream
+    int T, n_coef, tp;
+};
+
+// stream_scan_carry_kernel for a 2-D graph: the chunk's windows are planes [R G][T n_coef + 2 TCR_HALO]; the state's planar window
+// is read back from the last step's plane (column t, coefficient c <- plane offset t n_coef + c; zero halo).  The tail as there.
+__global__ __launch_bounds__(256) void stream_scan_carry_plane_kernel(const StreamScanCarryPlaneArgs p) {
+    __shared__ float s_tail[kMaxTail];
+    const StreamScanCarryArgs& a = p.c;
+    const int64_t s = a.s0 + blockIdx.x;
+    const int tid = threadIdx.x;
+    const int64_t b = (s * a.groups + a.groups - 1 - a.q0) * a.G + a.steps - 1 - (a.groups - 1) * a.G;
+    const int pp = p.T * p.n_coef + 2 * kHalo;
+    const float* wsrc = a.windows + b * pp + kHalo;
+    float* wdst = a.window + s * a.win_elems;
+    for (int i = tid; i < a.win_elems; i += 256) {
+        const int c = i / p.tp, t = i - c * p.tp - kHalo;
+        wdst[i] = t >= 0 && t < p.T ? wsrc[t * p.n_coef + c] : 0.f;
+    }
     const bool rst = a.reset && a.reset[s];
     float* tail = a.tail + s * a.tail_len;
     const float* src = a.samples + s * a.L;
@@ -283,26 +338,24 @@ __global__ __launch_bounds__(256) void stream_scan_suppress_kernel(const StreamS
     }
 }
 
-}  // namespace tcr
+namespace {
 
-using namespace tcr;
-
-extern "C" int tcr_stream_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params,
-                               const float* frozen_ss, int n_streams, int64_t n_samples, int k, const tcr_detect_cfg* det,
-                               const float* samples, const uint8_t* reset, void* state, void* workspace, size_t ws_bytes, float* logits,
-                               float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream) {
-    TCR_REQUIRE(plan_dev && params && frozen_ss && det && samples && state && workspace && logits && probs && smoothed && top && score && is_new,
-                "tcr_stream_scan: null argument");
-    TCR_TRY(stream_check(cfg, net, n_streams, k, det, "tcr_stream_scan"));
+int stream_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* m, int n_streams, int64_t n_samples, int k,
+                const tcr_detect_cfg* det, const float* samples, const uint8_t* reset, void* state, void* workspace, size_t ws_bytes,
+                float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream, const char* what) {
+    TCR_REQUIRE(plan_dev && m && m->params && m->aux && det && samples && state && workspace && logits && probs && smoothed && top && score &&
+                is_new, "%s: null argument", what);
+    ModelIO io;
+    TCR_TRY(stream_check(cfg, m, n_streams, k, det, what, io));
     const int64_t khop = (int64_t)k * cfg->hop;
-    TCR_REQUIRE(n_samples > 0 && n_samples % khop == 0, "tcr_stream_scan: the signal length %lld is not a positive multiple of k * hop = %lld",
+    TCR_REQUIRE(n_samples > 0 && n_samples % khop == 0, "%s: the signal length %lld is not a positive multiple of k * hop = %lld", what,
                 (long long)n_samples, (long long)khop);
     const int64_t steps = n_samples / khop;
-    const StreamGeom sg = stream_geom(*cfg, net, n_streams, k, det->average_steps);
+    const StreamGeom sg = stream_geom(*cfg, *m, io, n_streams, k, det->average_steps);
     TCR_REQUIRE((int64_t)n_streams * steps * sg.classes < ((int64_t)1 << 31),
-                "tcr_stream_scan: %d streams x %lld steps is too large", n_streams, (long long)steps);
+                "%s: %d streams x %lld steps is too large", what, n_streams, (long long)steps);
     ScanGeom g;
-    TCR_TRY(scan_chunking(*cfg, net, k, steps, n_streams, ws_bytes, "tcr_stream_scan", g));
+    TCR_TRY(scan_chunking(*cfg, *m, io, k, steps, n_streams, ws_bytes, what, g));
     const int G = g.G;
     const int64_t groups = ceil_div64(steps, G), total_groups = groups * n_streams;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -325,8 +378,13 @@ extern "C" int tcr_stream_scan(const tcr_frontend_cfg* cfg, const void* plan_dev
         StreamScanGatherArgs ga;
         ga.frames = ws + g.frames_off; ga.windows = ws + g.win_off; ga.window = st + sg.win_off; ga.zw = st + sg.zw_off; ga.reset = reset;
         ga.q0 = q0; ga.groups = groups; ga.G = G; ga.k = k; ga.T = g.T; ga.tp = g.tp; ga.n_coef = g.n_coef; ga.ftp = ftp;
-        hipLaunchKernelGGL(stream_scan_gather_kernel, dim3(slots), dim3(256), 0, s, ga);
-        TCR_TRY(check_launch("stream_scan_gather_kernel"));
+        if (g.planes) {
+            hipLaunchKernelGGL(stream_scan_gather_plane_kernel, dim3(slots), dim3(256), 0, s, ga);
+            TCR_TRY(check_launch("stream_scan_gather_plane_kernel"));
+        } else {
+            hipLaunchKernelGGL(stream_scan_gather_kernel, dim3(slots), dim3(256), 0, s, ga);
+            TCR_TRY(check_launch("stream_scan_gather_kernel"));
+        }
         // the streams whose last group (s groups + groups - 1) is one of this chunk's rows
         const int64_t s_lo = (q0 + 1 + groups - 1) / groups - 1, s_hi = (q0 + rows) / groups - 1;
         if (s_hi >= s_lo) {
@@ -334,11 +392,18 @@ extern "C" int tcr_stream_scan(const tcr_frontend_cfg* cfg, const void* plan_dev
             ca.windows = ws + g.win_off; ca.samples = samples; ca.reset = reset; ca.window = st + sg.win_off; ca.tail = st + sg.tail_off;
             ca.L = n_samples; ca.q0 = q0; ca.groups = groups; ca.steps = steps; ca.s0 = s_lo; ca.G = G; ca.win_elems = g.n_coef * g.tp;
             ca.tail_len = sg.tail_len;
-            hipLaunchKernelGGL(stream_scan_carry_kernel, dim3((unsigned)(s_hi - s_lo + 1)), dim3(256), 0, s, ca);
-            TCR_TRY(check_launch("stream_scan_carry_kernel"));
+            if (g.planes) {
+                StreamScanCarryPlaneArgs pa;
+                pa.c = ca; pa.T = g.T; pa.n_coef = g.n_coef; pa.tp = g.tp;
+                hipLaunchKernelGGL(stream_scan_carry_plane_kernel, dim3((unsigned)(s_hi - s_lo + 1)), dim3(256), 0, s, pa);
+                TCR_TRY(check_launch("stream_scan_carry_plane_kernel"));
+            } else {
+                hipLaunchKernelGGL(stream_scan_carry_kernel, dim3((unsigned)(s_hi - s_lo + 1)), dim3(256), 0, s, ca);
+                TCR_TRY(check_launch("stream_scan_carry_kernel"));
+            }
         }
-        TCR_TRY(tcr_net_forward_frozen(net, params, frozen_ss, ws + g.win_off, slots, ws + g.net_off, ws_bytes - (size_t)g.net_off * sizeof(float),
-                                       ws + g.logits_off, ws + g.probs_off, nullptr, stream));
+        TCR_TRY(model_forward(*m, ws + g.win_off, slots, ws + g.net_off, ws_bytes - (size_t)g.net_off * sizeof(float), ws + g.logits_off,
+                              ws + g.probs_off, stream));
         ScanScatterArgs xa;
         xa.logits_in = ws + g.logits_off; xa.probs_in = ws + g.probs_off; xa.logits = logits; xa.probs = probs; xa.q0 = q0;
         xa.groups = groups; xa.steps = steps; xa.G = G; xa.C = g.classes; xa.slots = slots;
@@ -356,4 +421,27 @@ extern "C" int tcr_stream_scan(const tcr_frontend_cfg* cfg, const void* plan_dev
     pa.C = g.classes; pa.W = det->average_steps; pa.suppression = det->suppression_steps;
     hipLaunchKernelGGL(stream_scan_suppress_kernel, dim3(n_streams), dim3(256), 0, s, pa);
     return check_launch("stream_scan_suppress_kernel");
+}
+
+}  // namespace
+
+}  // namespace tcr
+
+using namespace tcr;
+
+extern "C" int tcr_stream_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params,
+                               const float* frozen_ss, int n_streams, int64_t n_samples, int k, const tcr_detect_cfg* det,
+                               const float* samples, const uint8_t* reset, void* state, void* workspace, size_t ws_bytes, float* logits,
+                               float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream) {
+    const tcr_model_ref m = tcresnet_ref(net, params, frozen_ss);
+    return stream_scan(cfg, plan_dev, &m, n_streams, n_samples, k, det, samples, reset, state, workspace, ws_bytes, logits, probs, smoothed,
+                       top, score, is_new, stream, "tcr_stream_scan");
+}
+
+extern "C" int tcr_stream_scan_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_streams,
+                                 int64_t n_samples, int k, const tcr_detect_cfg* det, const float* samples, const uint8_t* reset, void* state,
+                                 void* workspace, size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score,
+                                 int32_t* is_new, void* stream) {
+    return stream_scan(cfg, plan_dev, model, n_streams, n_samples, k, det, samples, reset, state, workspace, ws_bytes, logits, probs,
+                       smoothed, top, score, is_new, stream, "tcr_stream_scan_m");
 }

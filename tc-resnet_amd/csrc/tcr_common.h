@@ -32,6 +32,9 @@ unsigned internal_event_flags();
 int tune_get(int knob);                  // process-wide tuning knobs (tcr_tune)
 int device_cus();                        // compute units of the current device (cached per device; 256 on MI355X)
 void net_io_shape(const tcr_net* net, int* in_channels, int* t_in, int* num_classes);      // (net.cpp: the opaque handle's input / output shape)
+void dscnn_io_shape(const tcr_dscnn* net, int* w_in, int* h_in, int* num_classes);          // (dscnn.hip: the same for DS-CNN)
+// (net2d.cpp: the input's c / h / w, the classes; false while the graph is not finalized)
+bool g2d_io_shape(const tcr_g2d* g, int* c, int* h, int* w, int* num_classes);
 
 #define TCR_REQUIRE(cond, ...)                 \
     do {                                       \

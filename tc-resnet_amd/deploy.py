@@ -95,26 +95,30 @@ class FrozenModel:
             return self.engine.forward_frozen(planar, self.frozen_ss)[1]
         return self.engine.forward_infer(planar)[1]
 
-    def streaming(self, n_streams: int, **kw):
-        """A `streaming.StreamingDetector` of n_streams over this artifact (TC-ResNet with `include_preprocess` only): the frozen
-        front-end settings, the conv / fc constants and the folded BN table as exported.  kw: frames_per_step, average_window_ms,
-        min_count, detection_threshold, suppression_ms, max_windows (push_many's windows per network launch)."""
-        if self.meta["family"] != "tcresnet":
-            raise ValueError(f"streaming detection runs TC-ResNet artifacts only (this one is {self.meta['family']})")
+    def _detection_inputs(self, what: str):
+        # (the front-end first: an artifact without one is refused before its engine is touched)
         if self.frontend is None:
-            raise ValueError("streaming detection needs an artifact exported with include_preprocess (it consumes raw audio)")
+            raise ValueError(f"{what} runs TC-ResNet, DS-CNN and 2-D graph artifacts exported with include_preprocess (this "
+                             f"{self.meta['family']} artifact has none: it consumes features, the detector raw audio)")
+        if self.meta["family"] not in ("tcresnet", "dscnn", "graph2d"):
+            raise ValueError(f"{what} runs TC-ResNet, DS-CNN and 2-D graph artifacts (this one is {self.meta['family']})")
+        return self.engine, self.frontend
+
+    def streaming(self, n_streams: int, **kw):
+        """A `streaming.StreamingDetector` of n_streams over this artifact (any family, exported with `include_preprocess`): the
+        frozen front-end settings and the constants as exported (TC-ResNet: the conv / fc weights and the folded BN table; DS-CNN
+        and 2-D graphs: every variable).  kw: frames_per_step, average_window_ms, min_count, detection_threshold, suppression_ms,
+        max_windows (push_many's windows per network launch)."""
+        net, fe = FrozenModel._detection_inputs(self, "streaming detection")
         from .streaming import StreamingDetector
-        return StreamingDetector(self.engine, self.frontend, n_streams, frozen_ss=self.frozen_ss, **kw)
+        return StreamingDetector(net, fe, n_streams, frozen_ss=self.frozen_ss, **kw)
 
     def scanner(self, **kw):
-        """A `scanning.KeywordScanner` over this artifact, like `streaming` (TC-ResNet with `include_preprocess` only).  kw:
+        """A `scanning.KeywordScanner` over this artifact, like `streaming` (any family, exported with `include_preprocess`).  kw:
         frames_per_step, average_window_ms, min_count, detection_threshold, suppression_ms, max_windows."""
-        if self.meta["family"] != "tcresnet":
-            raise ValueError(f"keyword scanning runs TC-ResNet artifacts only (this one is {self.meta['family']})")
-        if self.frontend is None:
-            raise ValueError("keyword scanning needs an artifact exported with include_preprocess (it consumes raw audio)")
+        net, fe = FrozenModel._detection_inputs(self, "keyword scanning")
         from .scanning import KeywordScanner
-        return KeywordScanner(self.engine, self.frontend, frozen_ss=self.frozen_ss, **kw)
+        return KeywordScanner(net, fe, frozen_ss=self.frozen_ss, **kw)
 
     # ---- file format ----------------------------------------------------------------------------------------------
     def save(self, path: str) -> str:

@@ -1,4 +1,4 @@
-"""Streaming keyword detection over long WAV files with a frozen TC-ResNet artifact (deploy.FrozenModel, include_preprocess):
+"""Streaming keyword detection over long WAV files with a frozen artifact (TC-ResNet, DS-CNN or 2-D graph; deploy.FrozenModel, include_preprocess):
 
     python stream_audio.py --frozen MODEL.npz --wav a.wav [b.wav ...] [--frames_per_step k] [--labels l0,l1,...]
                            [--average_window_ms MS] [--detection_threshold P] [--suppression_ms MS] [--min_count N]
@@ -27,7 +27,7 @@ else:
 
 def parse_arguments(arguments: Optional[List[str]] = None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--frozen", required=True, help="frozen TC-ResNet artifact (.npz) exported with include_preprocess")
+    p.add_argument("--frozen", required=True, help="frozen artifact (.npz) of any model family exported with include_preprocess")
     p.add_argument("--wav", required=True, nargs="+", help="16-bit PCM WAV files, one stream each")
     p.add_argument("--frames_per_step", type=int, default=1, help="new front-end frames per step (k)")
     p.add_argument("--labels", default=None, help="comma-separated class names (default: class indices)")

@@ -4,8 +4,10 @@ A `StreamingDetector` holds S streams.  Each starts as if it had heard one clip 
 k * hop samples to every stream (k = frames_per_step), computes only the k new front-end frames, runs the network on the
 one-second window kept on the device and smooths the posteriors into detections (the speech-commands "recognize commands"
 rule, stated in steps: see tcr_stream_step).  After a push, `window()` is bitwise the ordinary `Frontend` of each stream's last
-n_samples samples, and the logits / probs are bitwise `TCResNet.forward_frozen` of those windows at batch S.  `push_many` (tcr_stream_scan)
-appends many steps at once at the offline scan's throughput, bitwise the same pushes.
+n_samples samples, and the logits / probs are bitwise the network's eval forward of those windows at batch S
+(`TCResNet.forward_frozen`, `DSCNN.forward_infer`, `Graph2D.forward_infer`).  `push_many` (tcr_stream_scan) appends many steps at
+once at the offline scan's throughput, bitwise the same pushes.  Every model family runs: TC-ResNet, DS-CNN and the 2-D graphs
+(tcr_model_ref of include/tcresnet_hip.h).
 """
 from __future__ import annotations
 
@@ -15,8 +17,10 @@ from typing import Iterable, NamedTuple, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from ._lib import DetectCfg, TcrError, padded_len
-from .engine import Frontend, TCResNet
+from ._lib import FAMILY_DSCNN, FAMILY_G2D, FAMILY_TCRESNET, DetectCfg, ModelRef, TcrError, padded_len
+from .engine import DSCNN, Frontend, Graph2D, TCResNet
+
+Network = Union[TCResNet, DSCNN, Graph2D]
 
 
 class StreamOutput(NamedTuple):
@@ -36,13 +40,21 @@ def ms_to_steps(ms: float, step_ms: float) -> int:
 
 
 class _Detection:
-    """What `StreamingDetector` and `scanning.KeywordScanner` share: the argument checks, the detector settings in steps and the
-    weight / fold rules (see `StreamingDetector`)."""
+    """What `StreamingDetector` and `scanning.KeywordScanner` share: the argument checks, the detector settings in steps, the model
+    reference of the C calls and the weight / fold rules (see `StreamingDetector`)."""
 
-    def _setup(self, what: str, noun: str, net: TCResNet, frontend: Frontend, frames_per_step: int, average_window_ms: float,
+    def _setup(self, what: str, noun: str, net: Network, frontend: Frontend, frames_per_step: int, average_window_ms: float,
                min_count: int, detection_threshold: float, suppression_ms: float) -> None:
-        if not isinstance(net, TCResNet):
-            raise TcrError(f"{what} runs TC-ResNet models only, got {type(net).__name__}")
+        if isinstance(net, TCResNet):
+            self._family = FAMILY_TCRESNET
+        elif isinstance(net, DSCNN):
+            self._family = FAMILY_DSCNN
+        elif isinstance(net, Graph2D):
+            if not net.finalized:
+                raise TcrError(f"{what}: the 2-D graph is not finalized")
+            self._family = FAMILY_G2D
+        else:
+            raise TcrError(f"{what} runs TC-ResNet, DS-CNN and 2-D graph models, got {type(net).__name__}")
         if net.lib is not frontend.lib or net.device != frontend.device:
             raise TcrError("the network and the front-end must use the same library and device")
         self.net, self.frontend, self.lib, self.device = net, frontend, net.lib, net.device
@@ -59,9 +71,32 @@ class _Detection:
     def _bind_frozen(self, frozen_ss: Optional[torch.Tensor]) -> None:
         net = self.net
         if frozen_ss is not None:
+            if self._family != FAMILY_TCRESNET:
+                raise TcrError(f"{self._what}: frozen_ss is a TC-ResNet folded BN table; {type(net).__name__} folds its BN from params / "
+                               "stats in every call")
             net._check_tensor(frozen_ss, "frozen table")
         self._frozen = frozen_ss
         self._frozen_ver = (net.params._version, net._kver, net.params.data_ptr())
+
+    def _ref(self, aux: Optional[torch.Tensor] = None) -> ModelRef:
+        """The tcr_model_ref of a call: TC-ResNet with `aux` = its BN table (None for the size queries and init), DS-CNN / 2-D graph
+        with the arenas the net holds now."""
+        net = self.net
+        if self._family == FAMILY_TCRESNET:
+            return ModelRef(self._family, net._h.value, net.params.data_ptr(), aux.data_ptr() if aux is not None else None)
+        return ModelRef(self._family, net._h.value, net.params.data_ptr(), net.stats.data_ptr())
+
+    def _call_ref(self) -> ModelRef:
+        """The reference of a push / scan, after the weight rules: TC-ResNet refolds (or checks the frozen table's arena)."""
+        if self._family != FAMILY_TCRESNET:
+            return self._ref()
+        if self._frozen is not None:
+            self._check_frozen_arena()
+        return self._ref(self._table())
+
+    def _after_call(self) -> None:
+        if self._family == FAMILY_TCRESNET:
+            self.net._note_fold_reader()
 
     # ---- detector settings in steps ------------------------------------------------------------------------------------
     @property
@@ -140,7 +175,8 @@ class _Detection:
 
 
 class StreamingDetector(_Detection):
-    """S concurrent streams through `frontend` and `net`, k = frames_per_step new frames per stream and step.
+    """S concurrent streams through `frontend` and `net` (a TCResNet, DSCNN or finalized Graph2D whose input is the front-end's
+    n_coef x T features), k = frames_per_step new frames per stream and step.
 
     average_window_ms / suppression_ms become steps of k * hop / sample_rate seconds (the nearest whole number; the averaging
     ring holds at least one vector).  Silence / unknown classes get no special case: callers filter labels.
@@ -148,7 +184,9 @@ class StreamingDetector(_Detection):
     Weights: without `frozen_ss` the detector runs on the net's folded BN table (`TCResNet._folded_table`): `push` refolds when
     the variables or moving statistics changed since the last fold, a `prepared` call refuses to run (prepare it again).  With
     `frozen_ss` (a frozen artifact's table, `FrozenModel.streaming`) that table is used as it is; the net's arena then only
-    supplies the conv / fc weights, and both forms refuse to run once the arena changed.
+    supplies the conv / fc weights, and both forms refuse to run once the arena changed.  DS-CNN and 2-D graphs have no fold:
+    every call folds from the net's `params` / `stats` as they are then (in-place updates are seen by the next call), `frozen_ss`
+    is refused, and a `prepared` call refuses to run once `params` or `stats` were rebound to other tensors.
 
     The output tensors are the detector's own and are overwritten by the next step (copy what must survive it).
 
@@ -156,7 +194,7 @@ class StreamingDetector(_Detection):
     same pushes; max_windows (default scanning.DEFAULT_MAX_WINDOWS) bounds its windows per network launch and sizes the scan
     workspace it allocates on first use."""
 
-    def __init__(self, net: TCResNet, frontend: Frontend, n_streams: int, frames_per_step: int = 1, average_window_ms: float = 1000,
+    def __init__(self, net: Network, frontend: Frontend, n_streams: int, frames_per_step: int = 1, average_window_ms: float = 1000,
                  min_count: int = 3, detection_threshold: float = 0.5, suppression_ms: float = 1500,
                  frozen_ss: Optional[torch.Tensor] = None, max_windows: Optional[int] = None):
         self._setup("StreamingDetector", "detector", net, frontend, frames_per_step, average_window_ms, min_count, detection_threshold,
@@ -171,10 +209,11 @@ class StreamingDetector(_Detection):
         S, lib = self.n_streams, self.lib
         if S <= 0:
             raise TcrError(f"StreamingDetector: n_streams must be positive (got {S})")
-        nstate = lib.tcr_stream_state_bytes(C.byref(cfg), net._h, S, self.k, C.byref(self.det))
+        ref = self._ref()
+        nstate = lib.tcr_stream_state_bytes_m(C.byref(cfg), C.byref(ref), S, self.k, C.byref(self.det))
         if nstate == 0:
             raise TcrError(f"StreamingDetector: {lib.tcr_last_error().decode()}")
-        nws = lib.tcr_stream_workspace_bytes(C.byref(cfg), net._h, S, self.k)
+        nws = lib.tcr_stream_workspace_bytes_m(C.byref(cfg), C.byref(ref), S, self.k)
         if nws == 0:
             raise TcrError(f"StreamingDetector: {lib.tcr_last_error().decode()}")
         self._bind_frozen(frozen_ss)
@@ -187,8 +226,8 @@ class StreamingDetector(_Detection):
                                 torch.empty(S, **i32), torch.empty(S, **f32), torch.empty(S, **i32))
         self._reset_dev = torch.zeros(S, dtype=torch.uint8, device=dev)
         self._pending: Optional[np.ndarray] = None
-        lib.check(lib.tcr_stream_init(C.byref(cfg), frontend.plan.data_ptr(), net._h, S, self.k, C.byref(self.det),
-                                      self.state.data_ptr(), self.workspace.data_ptr(), self.workspace.numel() * 4, net._stream()),
+        lib.check(lib.tcr_stream_init_m(C.byref(cfg), frontend.plan.data_ptr(), C.byref(ref), S, self.k, C.byref(self.det),
+                                        self.state.data_ptr(), self.workspace.data_ptr(), self.workspace.numel() * 4, net._stream()),
                   "tcr_stream_init")
 
     # ---- stream control -----------------------------------------------------------------------------------------------
@@ -229,22 +268,19 @@ class StreamingDetector(_Detection):
             raise TcrError(f"push expects samples [{self.n_streams}, {self.step_samples}] (k * hop per stream), got {tuple(samples.shape)}")
         self.net._check_tensor(samples, "stream samples")
 
-    def _args(self, samples: torch.Tensor, ss: torch.Tensor, reset_ptr, stream):
-        o, fe, net = self.out, self.frontend, self.net
-        return (C.byref(fe.cfg), fe.plan.data_ptr(), net._h, net.params.data_ptr(), ss.data_ptr(), self.n_streams, self.k, C.byref(self.det),
-                samples.data_ptr(), reset_ptr, self.state.data_ptr(), self.workspace.data_ptr(), self.workspace.numel() * 4,
+    def _args(self, samples: torch.Tensor, ref: ModelRef, reset_ptr, stream):
+        o, fe = self.out, self.frontend
+        return (C.byref(fe.cfg), fe.plan.data_ptr(), C.byref(ref), self.n_streams, self.k, C.byref(self.det), samples.data_ptr(), reset_ptr, self.state.data_ptr(), self.workspace.data_ptr(), self.workspace.numel() * 4,
                 o.logits.data_ptr(), o.probs.data_ptr(), o.smoothed.data_ptr(), o.top.data_ptr(), o.score.data_ptr(), o.is_new.data_ptr(),
                 stream)
 
     def push(self, samples: torch.Tensor) -> StreamOutput:
-        """Append samples [S, k * hop] (float32, on the device) to every stream; one step.  Refolds BN first when the net's weights
-        changed (without `frozen_ss`); with `frozen_ss`, raises once the conv / fc arena changed since construction."""
+        """Append samples [S, k * hop] (float32, on the device) to every stream; one step.  TC-ResNet: refolds BN first when the net's
+        weights changed (without `frozen_ss`); with `frozen_ss`, raises once the conv / fc arena changed since construction."""
         self._check_samples(samples)
-        if self._frozen is not None:
-            self._check_frozen_arena()
-        ss = self._table()
-        self.lib.check(self.lib.tcr_stream_step(*self._args(samples, ss, self._take_reset(), self.net._stream())), "tcr_stream_step")
-        self.net._note_fold_reader()
+        ref = self._call_ref()
+        self.lib.check(self.lib.tcr_stream_step_m(*self._args(samples, ref, self._take_reset(), self.net._stream())), "tcr_stream_step")
+        self._after_call()
         return self.out
 
     def push_many(self, samples: torch.Tensor):
@@ -260,13 +296,11 @@ class StreamingDetector(_Detection):
         self.net._check_tensor(samples, "stream samples")
         lib, fe, net = self.lib, self.frontend, self.net
         if self._scan_ws is None:
-            nws = lib.tcr_scan_workspace_bytes(C.byref(fe.cfg), net._h, self.k, self.max_windows)
+            nws = lib.tcr_scan_workspace_bytes_m(C.byref(fe.cfg), C.byref(self._ref()), self.k, self.max_windows)
             if nws == 0:
                 raise TcrError(f"StreamingDetector.push_many: {lib.tcr_last_error().decode()}")
             self._scan_ws = torch.empty(nws // 4, dtype=torch.float32, device=self.device)
-        if self._frozen is not None:
-            self._check_frozen_arena()
-        ss = self._table()
+        ref = self._call_ref()
         L = int(samples.shape[1])
         steps, ncls = max(L // step, 0), net.num_classes
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -274,35 +308,50 @@ class StreamingDetector(_Detection):
         out = ScanOutput(torch.empty((S, steps, ncls), **f32), torch.empty((S, steps, ncls), **f32), torch.empty((S, steps, ncls), **f32),
                          torch.empty((S, steps), **i32), torch.empty((S, steps), **f32), torch.empty((S, steps), **i32))
         ws = self._scan_ws
-        lib.check(lib.tcr_stream_scan(C.byref(fe.cfg), fe.plan.data_ptr(), net._h, net.params.data_ptr(), ss.data_ptr(), S, L, self.k,
-                                      C.byref(self.det), samples.data_ptr(), self._take_reset(), self.state.data_ptr(), ws.data_ptr(),
-                                      ws.numel() * 4, *(t.data_ptr() for t in out), net._stream()), "tcr_stream_scan")
-        net._note_fold_reader()
+        lib.check(lib.tcr_stream_scan_m(C.byref(fe.cfg), fe.plan.data_ptr(), C.byref(ref), S, L, self.k, C.byref(self.det),
+                                        samples.data_ptr(), self._take_reset(), self.state.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                        *(t.data_ptr() for t in out), net._stream()), "tcr_stream_scan")
+        self._after_call()
         return out
 
     def prepared(self, samples_buffer: torch.Tensor):
         """A zero-argument callable that runs one step on `samples_buffer` (fill it in place between calls) with every pointer bound,
-        on the stream current now: the per-step cost a C / C++ host of the ABI sees.  Like `TCResNet.waveform_call` it refuses to
-        run once the variables / moving statistics (or, with `frozen_ss`, the arena) changed since it was prepared: prepare it again.
-        Resets requested with `reset` are applied by the next call."""
+        on the stream current now: the per-step cost a C / C++ host of the ABI sees.  TC-ResNet: like `TCResNet.waveform_call` it
+        refuses to run once the variables / moving statistics (or, with `frozen_ss`, the arena) changed since it was prepared.
+        DS-CNN / 2-D graph: in-place weight updates are seen by the next call (push's rule), and it refuses to run once `params` or
+        `stats` were rebound to other tensors.  Prepare it again then.  Resets requested with `reset` are applied by the next call."""
         self._check_samples(samples_buffer)
-        if self._frozen is not None:
-            self._check_frozen_arena()
-            ss = self._frozen
-        else:
-            ss = self.net._folded_table()
-            self.net._note_fold_reader()
         net = self.net
+        if self._family != FAMILY_TCRESNET:
+            ref = self._ref()
+            keep = (samples_buffer, net.params, net.stats, ref)
+            bound_ptrs = (net.params.data_ptr(), net.stats.data_ptr())
+
+            def stale():
+                return (net.params.data_ptr(), net.stats.data_ptr()) != bound_ptrs
+            why = "the network's params / stats were rebound since the call was prepared"
+        else:
+            if self._frozen is not None:
+                self._check_frozen_arena()
+                ss = self._frozen
+            else:
+                ss = net._folded_table()
+                net._note_fold_reader()
+            ref = self._ref(ss)
+            keep = (samples_buffer, ss, ref)
+            kver = (net.params._version, net.stats._version, net._kver)
+
+            def stale():
+                return (net.params._version, net.stats._version, net._kver) != kver
+            why = "the weights changed since the call was prepared"
         stream = net._stream()
-        args = self._args(samples_buffer, ss, None, stream)
-        args_reset = self._args(samples_buffer, ss, self._reset_dev.data_ptr(), stream)
-        fn, check, out = self.lib.tcr_stream_step, self.lib.check, self.out
-        kver = (net.params._version, net.stats._version, net._kver)
-        keep = (samples_buffer, ss)
+        args = self._args(samples_buffer, ref, None, stream)
+        args_reset = self._args(samples_buffer, ref, self._reset_dev.data_ptr(), stream)
+        fn, check, out = self.lib.tcr_stream_step_m, self.lib.check, self.out
 
         def call(_keep=keep):
-            if (net.params._version, net.stats._version, net._kver) != kver:
-                raise TcrError("StreamingDetector.prepared: the weights changed since the call was prepared; prepare it again")
+            if stale():
+                raise TcrError(f"StreamingDetector.prepared: {why}; prepare it again")
             bound = args
             if self._pending is not None:
                 self._take_reset()

@@ -1,4 +1,4 @@
-"""Detection-threshold sweep of a frozen TC-ResNet artifact (deploy.FrozenModel, include_preprocess) over labelled WAV files: a DET
+"""Detection-threshold sweep of a frozen artifact (TC-ResNet, DS-CNN or 2-D graph; deploy.FrozenModel, include_preprocess) over labelled WAV files: a DET
 curve (false rejects against false accepts per hour) from one scan.
 
     python sweep_audio.py --frozen MODEL.npz --wav a.wav [b.wav ...] --events EVENTS.csv [--thresholds LO:HI:STEP | t0,t1,...]
@@ -57,7 +57,7 @@ def parse_thresholds(spec: str) -> np.ndarray:
 
 def parse_arguments(arguments: Optional[List[str]] = None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--frozen", required=True, help="frozen TC-ResNet artifact (.npz) exported with include_preprocess")
+    p.add_argument("--frozen", required=True, help="frozen artifact (.npz) of any model family exported with include_preprocess")
     p.add_argument("--wav", required=True, nargs="+", help="16-bit PCM WAV files, one signal each")
     p.add_argument("--events", required=True, help="CSV of labelled keyword events: file,start_ms,end_ms,label")
     p.add_argument("--thresholds", default="0:0.99:0.01", help="LO:HI:STEP or a comma-separated list")
