@@ -1,6 +1,6 @@
 // The network of the detection entries (tcr_stream_*, tcr_scan, tcr_stream_scan and their _m twins): one dispatch point per
-// model family for the input shape, the workspace at a batch and the forward, so that stream.hip / scan.hip / stream_scan.hip
-// never name a family's entry themselves.
+// model family for the input shape, the workspace at a batch and the forward, so that stream.hip / scan.hip never
+// name a family's entry themselves.
 //
 // The windows a detection call hands the network are always the front-end's planar [n_coef][T + 2 TCR_HALO] rows, except for the
 // 2-D graph, which reads one [T x n_coef] plane per window ([B][1][T n_coef + 2 TCR_HALO], tcr_g2d_input_from_features's layout:

@@ -492,10 +492,8 @@ int launch_frontend_pk3_stream(int nc, const FrontendArgs& a, int n_items, hipSt
 
 }  // namespace tcr
 
-// The streaming detector (tcr_stream_*) and the offline scan (tcr_scan) that drive the STREAM instances are compiled in this
-// translation unit, and the detection sweep over a scan's outputs (tcr_detect_sweep) next to the scan; then the many-step streaming
-// call (tcr_stream_scan), which runs the scan's chunks on a stream state.
+// The streaming detector (tcr_stream_*) and the many-step calls (tcr_scan, tcr_stream_scan) that drive the STREAM instances are
+// compiled in this translation unit, and the detection sweep over a scan's outputs (tcr_detect_sweep) next to the scan.
 #include "stream.hip"
 #include "scan.hip"
 #include "sweep.hip"
-#include "stream_scan.hip"

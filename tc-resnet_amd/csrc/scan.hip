@@ -1,24 +1,35 @@
-// Offline keyword scanning of long recordings (tcr_scan): every step of N signals in one call, bitwise what a fresh streaming
-// detector (stream.hip) returns push by push.
+// Many detector steps in one call: tcr_stream_scan advances S streams by m steps from their stream state (stream.hip) and writes the
+// state back, bitwise m calls of tcr_stream_step -- outputs and state; tcr_scan is the same call from a fresh state without the
+// write-back: every step of N recordings, bitwise what a fresh streaming detector returns push by push.  One pipeline runs both; the
+// state (ScanState) is its variable part, and "fresh" is what reset[s] != 0 means as well.
 //
-// In frames of a signal with n_samples zeros in front (frame f covers padded samples [f hop, f hop + win)), the window of step i is
-// frames [(i + 1) k, (i + 1) k + T): tcr_stream_step's window after i + 1 pushes.  A frame is a pure function of its samples
-// (frontend_pk3.hip), the network's result for a window does not depend on its batch (DESIGN, net_small_tc8_kernel), the smoothing of
-// step i reads the probabilities of steps i - W + 1 .. i only, and the suppression state changes only at candidate steps
-// (count >= min_count && score > threshold).  So the windows are computed at the network's batch throughput and only the
-// suppression is sequential.
+// In frames of  x = tail ++ samples  (the stream's tail, zeros when fresh, then the call's L = m k hop samples), new frame j covers
+// x[j hop, j hop + win): the samples tcr_stream_step's staging rows hold for the same frame, and a frame is a pure function of its
+// samples (frontend_pk3.hip).  Column t of step i's window is new frame (i + 1) k - T + t; a negative index -e is column T - e of the
+// carried window.  For a fresh signal the frames of negative index cover zeros only and are computed like any other frame, which is
+// how the zero window itself was computed, so its windows need no carried column.  The network's result for a window does not depend
+// on its batch (DESIGN, net_small_tc8_kernel), the smoothing of step i reads the probabilities of steps i - W + 1 .. i only, and the
+// suppression state changes only at candidate steps (count >= min_count && score > threshold).  So the windows are computed at the
+// network's batch throughput and only the suppression is sequential.
 //
 // Steps are cut into groups of G consecutive steps of one signal; group g of signal n is one front-end row of F = G k + T - k frames
-// starting at frame (g G + 1) k.  A chunk is R consecutive groups (flattened over signals) = R G window slots:
-//   scan_stage_kernel     the R staging rows (zero prefix ++ signal, zeros past its end);
+// from new frame g G k + k - T on.  A chunk is R consecutive groups (flattened over signals) = R G window slots:
+//   scan_stage_kernel     the R staging rows (tail ++ samples, zeros outside);
 //   frontend_pk3_kernel   <.., STREAM = true> over R rows of F frames into frame rows [R][n_coef][F + 2 TCR_HALO] (column 0 on);
-//   scan_gather_kernel    the planar windows [R G][n_coef][T + 2 TCR_HALO] (zero halo) from the frame rows; for a 2-D graph
-//                         scan_gather_plane_kernel writes its [R G][1][T n_coef + 2 TCR_HALO] planes from them instead;
+//   scan_gather_kernel    the windows from the frame rows, or from carried columns for negative frames: planar
+//                         [R G][n_coef][T + 2 TCR_HALO] (zero halo), or the 2-D graph's planes [R G][1][T n_coef + 2 TCR_HALO];
+//   scan_carry_kernel     with a state: window and tail write-back of the streams whose last group is in this chunk (their last
+//                         step's window, gathered just before; the last tail_len samples of x, the old tail read before it is
+//                         written); a stream's groups are consecutive, so no later chunk reads its window or tail;
 //   the network at batch R G (detect_model.h: tcr_net_forward_frozen, tcr_dscnn_forward_infer or tcr_g2d_forward_infer, unchanged);
 //   scan_scatter_kernel   logits / probs of the slots that are steps (g G + j < steps) into the caller's [N][steps][C].
 // Slots past a signal's last step (the last group of a signal may be short) are computed and dropped.  Then, once per call:
-//   scan_smooth_kernel    a lane per (signal, step, class): smoothed, top, score and the candidate flag (is_new = top + 1 or 0);
-//   scan_suppress_kernel  a workgroup per signal finds the detections in step order and rewrites is_new with them.
+//   scan_smooth_kernel    a lane per (signal, step, class): smoothed over count_i = min(count0 + i + 1, W) vectors, those of steps
+//                         before the call from ring slots (head0 - d) mod W, oldest first; top, score and the candidate flag
+//                         (is_new = top + 1 or 0);
+//   scan_suppress_kernel  a workgroup per signal: the ring write-back (the last min(W, m) vectors at slots (head0 + i) mod W: the
+//                         smoothing has read the old ones), the detections in step order from the carried prev_label and
+//                         prev_step - n0, rewritten into is_new, then the five detector integers.
 //
 // Workspace (tcr_scan_workspace_bytes), regions 256-byte aligned:
 //   staging [R][stage_stride] | frame rows [R][n_coef][F + 8] | windows [R G][n_coef][Tp] (2-D graph: planes [R G][T n_coef + 8])
@@ -74,67 +85,126 @@ bool scan_geom_ok(int k, int T, int G, int64_t R, int max_batch) {
 
 }  // namespace
 
-struct ScanStageArgs {
-    const float* samples;       // [N][L]
-    float* stage;               // [R][stride]
-    int64_t L, stride, q0, rows, groups, n_prefix, step_hop;    // step_hop = G k hop (samples between two rows' starts)
-    int64_t k_hop;
+// The stream state a call starts from and writes back (StreamGeom's regions, stream.hip).  All null: no state, every signal is fresh
+// and nothing is written back (tcr_scan).  reset[s] != 0 makes stream s fresh for this call; its state is written all the same.
+struct ScanState {
+    float* window;              // [S][n_coef][tp]
+    float* tail;                // [S][tail_len]
+    float* ring;                // [W][S][C]
+    int* ist;                   // [5][S]: head, count, prev_label, prev_step, n
+    const uint8_t* reset;       // [S] or null
+    int tail_len;
 };
 
-// Staging row r = group q0 + r (signal q / groups, group q % groups): padded samples from frame (g G + 1) k on, i.e. from sample
-// (g G + 1) k hop of  zeros(n_prefix) ++ signal ++ zeros.  One thread per staged sample.
-__global__ __launch_bounds__(256) void scan_stage_kernel(const ScanStageArgs a) {
+__device__ __forceinline__ bool scan_fresh(const ScanState& st, int64_t s) { return !st.window || (st.reset && st.reset[s]); }
+
+// a chunk: rows q0 .. q0 + rows - 1 of the call's groups (signal q / groups, group q % groups)
+struct ScanChunkArgs {
+    const float* samples;       // [N][L]
+    float* stage;               // [R][stride]
+    float* frames;              // [R][n_coef][ftp]
+    float* windows;             // [R G][n_coef][tp] (planes: [R G][T n_coef + 2 kHalo])
+    ScanState st;
+    int64_t L, stride, q0, rows, groups, steps, n_prefix, k_hop;
+    int64_t s0;                 // scan_carry_kernel: the first stream whose last group is in the chunk
+    int G, k, T, tp, n_coef, ftp;
+};
+
+// Staging row r = group q0 + r: x from new frame g G k + k - T on, i.e. from sample (g G + 1) k hop of  zeros(n_prefix) ++ signal ++
+// zeros  (n_prefix = the clip's n_samples = T hop + tail_len), with the stream's tail in the last tail_len samples of the prefix.
+// One thread per staged sample.
+__global__ __launch_bounds__(256) void scan_stage_kernel(const ScanChunkArgs a) {
     const int64_t total = a.rows * a.stride;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
         const int64_t r = e / a.stride, x = e - r * a.stride;
         const int64_t q = a.q0 + r, n = q / a.groups, g = q - n * a.groups;
-        const int64_t pos = g * a.step_hop + a.k_hop + x - a.n_prefix;          // sample of the signal
-        a.stage[e] = pos >= 0 && pos < a.L ? a.samples[n * a.L + pos] : 0.f;
+        const int64_t pos = (g * a.G + 1) * a.k_hop + x - a.n_prefix;           // sample of the signal; < 0: before the call
+        float v = 0.f;
+        if (pos >= 0) {
+            if (pos < a.L) v = a.samples[n * a.L + pos];
+        } else if (pos + a.st.tail_len >= 0 && !scan_fresh(a.st, n)) {
+            v = a.st.tail[n * a.st.tail_len + pos + a.st.tail_len];
+        }
+        a.stage[e] = v;
     }
 }
 
-struct ScanGatherArgs {
-    const float* frames;        // [R][n_coef][F + 2 kHalo]
-    float* windows;             // [R G][n_coef][tp]
-    int G, k, T, tp, n_coef, ftp;
-};
-
-// One workgroup per window slot b = r G + j: column t of its window is column j k + t of frame row r; the halo is zero.
-__global__ __launch_bounds__(256) void scan_gather_kernel(const ScanGatherArgs a) {
+// One workgroup per window slot b = r G + j (step i = g G + j): column t is column j k + t of frame row r when new frame
+// (i + 1) k - T + t >= 0 or the signal is fresh, else column (i + 1) k + t of the carried window; the halo is zero.  PLANES (2-D
+// graph): the same window as its [T x n_coef] plane, written in plane order (coalesced): plane offset t n_coef + c <- window column t,
+// coefficient c (features_to_plane_kernel's map, net2d_kernels.hip).  A pure copy: bitwise the planar gather followed by
+// features_to_plane_kernel.  CARRIED: the call has a state; without one no column is carried, and the instance is the plain copy
+// (the test at run time cost tcr_scan 5 % of this kernel, profiles/scan_unify_kernel_stats.csv).
+template <bool PLANES, bool CARRIED>
+__global__ __launch_bounds__(256) void scan_gather_kernel(const ScanChunkArgs a) {
     const int b = blockIdx.x;
     const int r = b / a.G, j = b - r * a.G;
     const float* src = a.frames + (size_t)r * a.n_coef * a.ftp + j * a.k;      // window column x <- frame-row column j k + x
-    float* dst = a.windows + (size_t)b * a.n_coef * a.tp;
-    const int n = a.n_coef * a.tp;
-    const int dc = 256 / a.tp, dx = 256 - dc * a.tp;
-    int c = threadIdx.x / a.tp, x = threadIdx.x - c * a.tp;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int t = x - kHalo;
-        dst[i] = t >= 0 && t < a.T ? src[(size_t)c * a.ftp + x] : 0.f;
-        c += dc;
-        x += dx;
-        if (x >= a.tp) { x -= a.tp; ++c; }
+    const float* old = src;                                                     // (not read while sh = T)
+    int sh = a.T;                                                               // carried columns: t < T - sh
+    if constexpr (CARRIED) {
+        const int64_t q = a.q0 + r, s = q / a.groups, g = q - s * a.groups;
+        const int64_t i1 = (g * a.G + j + 1) * a.k;                             // (i + 1) k
+        if (i1 < a.T && !scan_fresh(a.st, s)) sh = (int)i1;
+        old = a.st.window + (size_t)s * a.n_coef * a.tp + sh;
+    }
+    if constexpr (PLANES) {
+        const int n = a.T * a.n_coef, pp = n + 2 * kHalo;
+        float* dst = a.windows + (size_t)b * pp;
+        for (int i = threadIdx.x; i < pp; i += 256) {
+            const int o = i - kHalo;
+            float v = 0.f;
+            if (o >= 0 && o < n) {
+                const int t = o / a.n_coef, c = o - t * a.n_coef, x = t + kHalo;
+                v = CARRIED && t + sh < a.T ? old[c * a.tp + x] : src[(size_t)c * a.ftp + x];
+            }
+            dst[i] = v;
+        }
+    } else {
+        float* dst = a.windows + (size_t)b * a.n_coef * a.tp;
+        const int n = a.n_coef * a.tp;
+        const int dc = 256 / a.tp, dx = 256 - dc * a.tp;
+        int c = threadIdx.x / a.tp, x = threadIdx.x - c * a.tp;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const int t = x - kHalo;
+            dst[i] = t >= 0 && t < a.T ? (CARRIED && t + sh < a.T ? old[c * a.tp + x] : src[(size_t)c * a.ftp + x]) : 0.f;
+            c += dc;
+            x += dx;
+            if (x >= a.tp) { x -= a.tp; ++c; }
+        }
     }
 }
 
-// scan_gather_kernel for a 2-D graph: the window of slot b as its [T x n_coef] plane, written in plane order (coalesced): plane
-// offset t n_coef + c <- frame-row column j k + t, coefficient c (features_to_plane_kernel's map, net2d_kernels.hip), zero halo.
-// A pure copy: bitwise scan_gather_kernel followed by features_to_plane_kernel.
-__global__ __launch_bounds__(256) void scan_gather_plane_kernel(const ScanGatherArgs a) {
-    const int b = blockIdx.x;
-    const int r = b / a.G, j = b - r * a.G;
-    const float* src = a.frames + (size_t)r * a.n_coef * a.ftp + j * a.k + kHalo;      // column t <- frame-row column j k + t
-    const int n = a.T * a.n_coef, pp = n + 2 * kHalo;
-    float* dst = a.windows + (size_t)b * pp;
-    for (int i = threadIdx.x; i < pp; i += 256) {
-        const int o = i - kHalo;
-        float v = 0.f;
-        if (o >= 0 && o < n) {
-            const int t = o / a.n_coef, c = o - t * a.n_coef;
-            v = src[(size_t)c * a.ftp + t];
+// One workgroup per stream s0 + blockIdx.x whose last group is in the chunk: window = its last step's gathered window (planar, zero
+// halo: the state's layout; PLANES: read back from the last step's plane, column t, coefficient c <- plane offset t n_coef + c);
+// tail = the last tail_len samples of  tail ++ samples  (old samples that survive a short call are read into LDS before the tail is
+// written).
+template <bool PLANES>
+__global__ __launch_bounds__(256) void scan_carry_kernel(const ScanChunkArgs a) {
+    __shared__ float s_tail[kMaxTail];
+    const int64_t s = a.s0 + blockIdx.x;
+    const int tid = threadIdx.x;
+    const int64_t b = (s * a.groups + a.groups - 1 - a.q0) * a.G + a.steps - 1 - (a.groups - 1) * a.G;
+    const int win_elems = a.n_coef * a.tp;
+    float* wdst = a.st.window + s * win_elems;
+    if constexpr (PLANES) {
+        const float* wsrc = a.windows + b * (a.T * a.n_coef + 2 * kHalo) + kHalo;
+        for (int i = tid; i < win_elems; i += 256) {
+            const int c = i / a.tp, t = i - c * a.tp - kHalo;
+            wdst[i] = t >= 0 && t < a.T ? wsrc[t * a.n_coef + c] : 0.f;
         }
-        dst[i] = v;
+    } else {
+        const float* wsrc = a.windows + b * win_elems;
+        for (int i = tid; i < win_elems; i += 256) wdst[i] = wsrc[i];
     }
+    const int tail_len = a.st.tail_len;
+    const bool rst = scan_fresh(a.st, s);
+    float* tail = a.st.tail + s * tail_len;
+    const float* src = a.samples + s * a.L;
+    const int keep = a.L < tail_len ? (int)(tail_len - a.L) : 0;               // old tail samples L .. tail_len - 1 stay
+    for (int i = tid; i < keep; i += 256) s_tail[i] = rst ? 0.f : tail[a.L + i];
+    __syncthreads();
+    for (int i = tid; i < tail_len; i += 256) tail[i] = i < keep ? s_tail[i] : src[a.L - tail_len + i];
 }
 
 struct ScanScatterArgs {
@@ -160,35 +230,50 @@ __global__ __launch_bounds__(256) void scan_scatter_kernel(const ScanScatterArgs
     a.probs[o] = a.probs_in[e];
 }
 
-struct ScanSmoothArgs {
+struct ScanDetectArgs {
     const float* probs;         // [N][steps][C]
     float* smoothed;
     int32_t* top;               // [N][steps]
     float* score;
-    int32_t* is_new;            // here: the candidate flag, top + 1 (candidate) or 0
-    int64_t windows, steps;
-    int C, W, min_count;
+    int32_t* is_new;            // scan_smooth_kernel writes the candidate flag, top + 1 (candidate) or 0; scan_suppress_kernel the detections
+    ScanState st;
+    int64_t steps;
+    int N, C, W, min_count, suppression;
     float threshold;
 };
 
-// A lane per (signal, step, class), 256 / C steps per workgroup: the streaming detector's smoothing over the last min(i + 1, W)
-// probability vectors (smooth_mean, stream.hip: the same expression), the argmax from LDS by the step's first lane, top / score
-// (-1 / 0 below min_count) and the candidate flag.  Consecutive lanes read consecutive floats.
-__global__ __launch_bounds__(256) void scan_smooth_kernel(const ScanSmoothArgs a) {
+// A lane per (signal, step, class), 256 / C steps per workgroup: the streaming detector's smoothing over the last
+// count = min(count0 + i + 1, W) probability vectors (smooth_mean, stream.hip: the same expression), those of steps before the call
+// from ring slot (head0 + j) mod W (j < 0, oldest first); the argmax from LDS by the step's first lane, top / score (-1 / 0 below
+// min_count) and the candidate flag.  Consecutive lanes read consecutive floats.  CARRIED: the call has a state; without one the
+// ring is never read, and the instance has no test for it (at run time it doubled this kernel's time for tcr_scan).
+template <bool CARRIED>
+__global__ __launch_bounds__(256) void scan_smooth_kernel(const ScanDetectArgs a) {
     __shared__ float s_sm[256];
-    const int C = a.C;
+    const int C = a.C, W = a.W;
     const int per = 256 / C;
     const int ls = threadIdx.x / C, c = threadIdx.x - ls * C;
-    const int64_t w = (int64_t)blockIdx.x * per + ls;                   // window = n steps + i
-    const bool live = ls < per && w < a.windows;
+    const int64_t w = (int64_t)blockIdx.x * per + ls;                   // window = s steps + i
+    const bool live = ls < per && w < a.N * a.steps;
     int count = 0;
     if (live) {
-        const int64_t i = w % a.steps;
-        count = i + 1 < a.W ? (int)(i + 1) : a.W;
-        const float* p = a.probs + (w - count + 1) * C + c;             // oldest
+        const int64_t s = w / a.steps, i = w - s * a.steps;
+        const bool fresh = !CARRIED || scan_fresh(a.st, s);
+        const int head0 = fresh ? 0 : a.st.ist[s], count0 = fresh ? 0 : a.st.ist[a.N + s];
+        count = count0 + i + 1 < W ? (int)(count0 + i + 1) : W;
+        int64_t jj = i - count + 1;                                     // oldest step (< 0: before the call)
+        int slot = jj < 0 ? (head0 + (int)jj < 0 ? head0 + (int)jj + W : head0 + (int)jj) : 0;
+        const float* p = a.probs + s * a.steps * C + c;
+        const size_t ring_row = (size_t)a.N * C, sc = (size_t)s * C + c;
         const float v = smooth_mean(count, [&]() {
-            const float x = *p;
-            p += C;
+            float x;
+            if (CARRIED && jj < 0) {
+                x = a.st.ring[slot * ring_row + sc];
+                slot = slot + 1 == W ? 0 : slot + 1;
+            } else {
+                x = p[jj * C];
+            }
+            ++jj;
             return x;
         });
         a.smoothed[w * C + c] = v;
@@ -196,8 +281,8 @@ __global__ __launch_bounds__(256) void scan_smooth_kernel(const ScanSmoothArgs a
     }
     __syncthreads();
     if (!live || c != 0) return;
-    int best = 0;                                                       // (stream_detect_kernel's argmax, written out: as a shared
-    float best_v = s_sm[threadIdx.x];                                   // function it reorders that kernel's instructions)
+    int best = 0;
+    float best_v = s_sm[threadIdx.x];
     for (int cc = 1; cc < C; ++cc) {
         const float v = s_sm[threadIdx.x + cc];
         if (v > best_v) { best = cc; best_v = v; }
@@ -208,21 +293,37 @@ __global__ __launch_bounds__(256) void scan_smooth_kernel(const ScanSmoothArgs a
     a.is_new[w] = warm && best_v > a.threshold ? best + 1 : 0;
 }
 
-// One workgroup per signal walks its steps in passes of 256 x kSuppressPer flags, read coalesced into LDS.  A pass without a candidate
-// costs its loads and two barriers.  Otherwise wave 0 looks for the next detection: fired = top != prev_label && (prev_label == -1 ||
-// i - prev_step > suppression), so after a detection the walk jumps past the suppressed steps, and from there the first candidate whose
-// label differs from prev_label fires -- 256 steps per probe (four per lane, the lowest index by a butterfly minimum), one probe per
-// detection or per 256 steps.  A detection is marked -1 in LDS; then the candidates' flags are rewritten as 0 / 1.  Non-candidates
-// never fire and never change the state.
-__global__ __launch_bounds__(256) void scan_suppress_kernel(int32_t* is_new, int64_t steps, int suppression) {
+// One workgroup per signal: the ring write-back, the suppression walk from the carried detector, the detector integers.  The walk goes
+// over the signal's flags in passes of 256 x kSuppressPer, read coalesced into LDS.  A pass without a candidate costs its loads and
+// two barriers.  Otherwise wave 0 looks for the next detection: fired = top != prev_label && (prev_label == -1 || i - prev_step >
+// suppression), so after a detection the walk jumps past the suppressed steps, and from there the first candidate whose label differs
+// from prev_label fires -- 256 steps per probe (four per lane, the lowest index by a butterfly minimum), one probe per detection or
+// per 256 steps.  A detection is marked -1 in LDS; then the candidates' flags are rewritten as 0 / 1.  Non-candidates never fire and
+// never change the state.
+__global__ __launch_bounds__(256) void scan_suppress_kernel(const ScanDetectArgs a) {
     constexpr int PASS = 256 * kSuppressPer;
     constexpr int NONE = 0x7fffffff;
     __shared__ int s_val[PASS];
     __shared__ int s_any[2];
-    const int tid = threadIdx.x;
-    int32_t* fl = is_new + (int64_t)blockIdx.x * steps;
-    int prev_label = -1;                                // (wave 0's, the same in its lanes)
-    int64_t prev_step = 0;
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int N = a.N, C = a.C, W = a.W;
+    const int64_t steps = a.steps;
+    int* ist = a.st.ist;
+    const bool fresh = scan_fresh(a.st, s);
+    const int head0 = fresh ? 0 : ist[s], count0 = fresh ? 0 : ist[N + s];
+    const int n0 = fresh ? 0 : ist[4 * N + s];
+    int prev_label = fresh ? -1 : ist[2 * N + s];                       // (wave 0's, the same in its lanes)
+    int64_t prev_step = fresh ? 0 : (int64_t)ist[3 * N + s] - n0;       // relative to the call's first step: may be negative
+    if (a.st.ring) {
+        const int nw = steps < W ? (int)steps : W;                      // the last nw vectors stay in the ring
+        const int64_t i0 = steps - nw;
+        for (int e = tid; e < nw * C; e += 256) {
+            const int d = e / C, c = e - d * C;
+            const int slot = (int)((head0 + i0 + d) % W);
+            a.st.ring[(size_t)slot * N * C + (size_t)s * C + c] = a.probs[((int64_t)s * steps + i0 + d) * C + c];
+        }
+    }
+    int32_t* fl = a.is_new + (int64_t)s * steps;
     if (tid == 0) s_any[0] = 0;
     __syncthreads();
     int it = 0;
@@ -248,7 +349,7 @@ __global__ __launch_bounds__(256) void scan_suppress_kernel(int32_t* is_new, int
             int cur = 0;
             while (cur < n) {
                 if (prev_label != -1) {
-                    const int64_t lo = prev_step + suppression + 1 - base;
+                    const int64_t lo = prev_step + a.suppression + 1 - base;
                     if (lo > cur) cur = lo < n ? (int)lo : n;
                     if (cur >= n) break;
                 }
@@ -275,6 +376,13 @@ __global__ __launch_bounds__(256) void scan_suppress_kernel(int32_t* is_new, int
             const int64_t idx = base + e * 256 + tid;
             if (v[e] != 0) fl[idx] = s_val[e * 256 + tid] == -1 ? 1 : 0;
         }
+    }
+    if (ist && tid == 0) {                                              // (every thread read the integers before the walk's barriers)
+        ist[s] = (int)((head0 + steps) % W);
+        ist[N + s] = count0 + steps < W ? (int)(count0 + steps) : W;
+        ist[2 * N + s] = prev_label;
+        ist[3 * N + s] = (int)(n0 + prev_step);
+        ist[4 * N + s] = (int)(n0 + steps);
     }
 }
 
@@ -323,6 +431,61 @@ size_t scan_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_model_ref* m,
     return (size_t)scan_geom(*cfg, *m, io, k, G, R).ws_floats * sizeof(float);
 }
 
+// The pipeline of the header comment over n_signals x steps checked by the caller, from and to the state st (all null: none).
+int scan_run(const tcr_frontend_cfg& cfg, const void* plan_dev, const tcr_model_ref& m, const ModelIO& io, int n_signals, int64_t steps,
+             int k, const tcr_detect_cfg& det, const float* samples, const ScanState& st, void* workspace, size_t ws_bytes, float* logits,
+             float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream, const char* what) {
+    ScanGeom g;
+    TCR_TRY(scan_chunking(cfg, m, io, k, steps, n_signals, ws_bytes, what, g));
+    const int G = g.G;
+    const int64_t groups = ceil_div64(steps, G), total_groups = groups * n_signals;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* ws = static_cast<float*>(workspace);
+    ScanChunkArgs ca;
+    ca.samples = samples; ca.stage = ws + g.stage_off; ca.frames = ws + g.frames_off; ca.windows = ws + g.win_off; ca.st = st;
+    ca.k_hop = (int64_t)k * cfg.hop; ca.L = steps * ca.k_hop; ca.stride = g.stage_stride; ca.groups = groups; ca.steps = steps;
+    ca.n_prefix = cfg.n_samples; ca.G = G; ca.k = k; ca.T = g.T; ca.tp = g.tp; ca.n_coef = g.n_coef; ca.ftp = tcr_padded_len(g.F);
+    const bool carried = st.window != nullptr;
+    const auto gather = g.planes ? (carried ? scan_gather_kernel<true, true> : scan_gather_kernel<true, false>)
+                                 : (carried ? scan_gather_kernel<false, true> : scan_gather_kernel<false, false>);
+    for (int64_t q0 = 0; q0 < total_groups; q0 += g.R) {
+        const int rows = (int)std::min<int64_t>(g.R, total_groups - q0);
+        const int slots = rows * G;
+        ca.q0 = q0; ca.rows = rows;
+        // the streams whose last group (s groups + groups - 1) is one of this chunk's rows
+        const int64_t s_lo = (q0 + 1 + groups - 1) / groups - 1, s_hi = (q0 + rows) / groups - 1;
+        ca.s0 = s_lo;
+        const int64_t staged = (int64_t)rows * g.stage_stride;
+        hipLaunchKernelGGL(scan_stage_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(staged, 256), 8 * (int64_t)device_cus())), dim3(256), 0,
+                           s, ca);
+        TCR_TRY(check_launch("scan_stage_kernel"));
+        TCR_TRY(stream_frontend(cfg, plan_dev, ca.stage, g.stage_stride, rows, g.F, ca.frames, s, ca.ftp));
+        hipLaunchKernelGGL(gather, dim3(slots), dim3(256), 0, s, ca);
+        TCR_TRY(check_launch("scan_gather_kernel"));
+        if (carried && s_hi >= s_lo) {
+            if (g.planes) hipLaunchKernelGGL(scan_carry_kernel<true>, dim3((unsigned)(s_hi - s_lo + 1)), dim3(256), 0, s, ca);
+            else hipLaunchKernelGGL(scan_carry_kernel<false>, dim3((unsigned)(s_hi - s_lo + 1)), dim3(256), 0, s, ca);
+            TCR_TRY(check_launch("scan_carry_kernel"));
+        }
+        TCR_TRY(model_forward(m, ca.windows, slots, ws + g.net_off, ws_bytes - (size_t)g.net_off * sizeof(float), ws + g.logits_off,
+                              ws + g.probs_off, stream));
+        ScanScatterArgs xa;
+        xa.logits_in = ws + g.logits_off; xa.probs_in = ws + g.probs_off; xa.logits = logits; xa.probs = probs; xa.q0 = q0;
+        xa.groups = groups; xa.steps = steps; xa.G = G; xa.C = g.classes; xa.slots = slots;
+        hipLaunchKernelGGL(scan_scatter_kernel, dim3(ceil_div(slots * g.classes, 256)), dim3(256), 0, s, xa);
+        TCR_TRY(check_launch("scan_scatter_kernel"));
+    }
+    ScanDetectArgs da;
+    da.probs = probs; da.smoothed = smoothed; da.top = top; da.score = score; da.is_new = is_new; da.st = st; da.steps = steps;
+    da.N = n_signals; da.C = g.classes; da.W = det.average_steps; da.min_count = det.min_count; da.suppression = det.suppression_steps;
+    da.threshold = det.threshold;
+    hipLaunchKernelGGL(carried ? scan_smooth_kernel<true> : scan_smooth_kernel<false>, dim3((unsigned)ceil_div64(n_signals * steps, 256 / g.classes)),
+                       dim3(256), 0, s, da);
+    TCR_TRY(check_launch("scan_smooth_kernel"));
+    hipLaunchKernelGGL(scan_suppress_kernel, dim3(n_signals), dim3(256), 0, s, da);
+    return check_launch("scan_suppress_kernel");
+}
+
 int scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* m, int n_signals, int64_t n_samples, int k,
          const tcr_detect_cfg* det, const float* samples, void* workspace, size_t ws_bytes, float* logits, float* probs, float* smoothed,
          int32_t* top, float* score, int32_t* is_new, void* stream, const char* what) {
@@ -337,49 +500,28 @@ int scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref*
     const int64_t steps = n_samples / khop;
     TCR_REQUIRE((int64_t)n_signals * steps * io.classes < ((int64_t)1 << 31), "%s: %d signals x %lld steps is too large", what, n_signals,
                 (long long)steps);
-    ScanGeom g;
-    TCR_TRY(scan_chunking(*cfg, *m, io, k, steps, n_signals, ws_bytes, what, g));
-    const int G = g.G;
-    const int64_t groups = ceil_div64(steps, G), total_groups = groups * n_signals;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float* ws = static_cast<float*>(workspace);
-    const int ftp = tcr_padded_len(g.F);
-    for (int64_t q0 = 0; q0 < total_groups; q0 += g.R) {
-        const int rows = (int)std::min<int64_t>(g.R, total_groups - q0);
-        const int slots = rows * G;
-        ScanStageArgs sa;
-        sa.samples = samples; sa.stage = ws + g.stage_off; sa.L = n_samples; sa.stride = g.stage_stride; sa.q0 = q0; sa.rows = rows;
-        sa.groups = groups; sa.n_prefix = cfg->n_samples; sa.step_hop = (int64_t)G * khop; sa.k_hop = khop;
-        const int64_t staged = (int64_t)rows * g.stage_stride;
-        hipLaunchKernelGGL(scan_stage_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(staged, 256), 8 * (int64_t)device_cus())), dim3(256), 0,
-                           s, sa);
-        TCR_TRY(check_launch("scan_stage_kernel"));
-        TCR_TRY(stream_frontend(*cfg, plan_dev, ws + g.stage_off, g.stage_stride, rows, g.F, ws + g.frames_off, s, ftp));
-        ScanGatherArgs ga;
-        ga.frames = ws + g.frames_off; ga.windows = ws + g.win_off; ga.G = G; ga.k = k; ga.T = g.T; ga.tp = g.tp; ga.n_coef = g.n_coef;
-        ga.ftp = ftp;
-        if (g.planes) {
-            hipLaunchKernelGGL(scan_gather_plane_kernel, dim3(slots), dim3(256), 0, s, ga);
-            TCR_TRY(check_launch("scan_gather_plane_kernel"));
-        } else {
-            hipLaunchKernelGGL(scan_gather_kernel, dim3(slots), dim3(256), 0, s, ga);
-            TCR_TRY(check_launch("scan_gather_kernel"));
-        }
-        TCR_TRY(model_forward(*m, ws + g.win_off, slots, ws + g.net_off, ws_bytes - (size_t)g.net_off * sizeof(float), ws + g.logits_off,
-                              ws + g.probs_off, stream));
-        ScanScatterArgs xa;
-        xa.logits_in = ws + g.logits_off; xa.probs_in = ws + g.probs_off; xa.logits = logits; xa.probs = probs; xa.q0 = q0;
-        xa.groups = groups; xa.steps = steps; xa.G = G; xa.C = g.classes; xa.slots = slots;
-        hipLaunchKernelGGL(scan_scatter_kernel, dim3(ceil_div(slots * g.classes, 256)), dim3(256), 0, s, xa);
-        TCR_TRY(check_launch("scan_scatter_kernel"));
-    }
-    ScanSmoothArgs ma;
-    ma.probs = probs; ma.smoothed = smoothed; ma.top = top; ma.score = score; ma.is_new = is_new; ma.windows = (int64_t)n_signals * steps;
-    ma.steps = steps; ma.C = g.classes; ma.W = det->average_steps; ma.min_count = det->min_count; ma.threshold = det->threshold;
-    hipLaunchKernelGGL(scan_smooth_kernel, dim3((unsigned)ceil_div64(ma.windows, 256 / g.classes)), dim3(256), 0, s, ma);
-    TCR_TRY(check_launch("scan_smooth_kernel"));
-    hipLaunchKernelGGL(scan_suppress_kernel, dim3(n_signals), dim3(256), 0, s, is_new, steps, det->suppression_steps);
-    return check_launch("scan_suppress_kernel");
+    return scan_run(*cfg, plan_dev, *m, io, n_signals, steps, k, *det, samples, ScanState{}, workspace, ws_bytes, logits, probs, smoothed,
+                    top, score, is_new, stream, what);
+}
+
+int stream_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* m, int n_streams, int64_t n_samples, int k,
+                const tcr_detect_cfg* det, const float* samples, const uint8_t* reset, void* state, void* workspace, size_t ws_bytes,
+                float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream, const char* what) {
+    TCR_REQUIRE(plan_dev && m && m->params && m->aux && det && samples && state && workspace && logits && probs && smoothed && top && score &&
+                is_new, "%s: null argument", what);
+    ModelIO io;
+    TCR_TRY(stream_check(cfg, m, n_streams, k, det, what, io));
+    const int64_t khop = (int64_t)k * cfg->hop;
+    TCR_REQUIRE(n_samples > 0 && n_samples % khop == 0, "%s: the signal length %lld is not a positive multiple of k * hop = %lld", what,
+                (long long)n_samples, (long long)khop);
+    const int64_t steps = n_samples / khop;
+    TCR_REQUIRE((int64_t)n_streams * steps * io.classes < ((int64_t)1 << 31), "%s: %d streams x %lld steps is too large", what, n_streams,
+                (long long)steps);
+    const StreamGeom sg = stream_geom(*cfg, *m, io, n_streams, k, det->average_steps);
+    float* st = static_cast<float*>(state);
+    const ScanState carried{st + sg.win_off, st + sg.tail_off, st + sg.ring_off, reinterpret_cast<int*>(st + sg.ist_off), reset, sg.tail_len};
+    return scan_run(*cfg, plan_dev, *m, io, n_streams, steps, k, *det, samples, carried, workspace, ws_bytes, logits, probs, smoothed, top,
+                    score, is_new, stream, what);
 }
 
 }  // namespace
@@ -411,4 +553,21 @@ extern "C" int tcr_scan_m(const tcr_frontend_cfg* cfg, const void* plan_dev, con
                           float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream) {
     return scan(cfg, plan_dev, model, n_signals, n_samples, k, det, samples, workspace, ws_bytes, logits, probs, smoothed, top, score, is_new,
                 stream, "tcr_scan_m");
+}
+
+extern "C" int tcr_stream_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params,
+                               const float* frozen_ss, int n_streams, int64_t n_samples, int k, const tcr_detect_cfg* det,
+                               const float* samples, const uint8_t* reset, void* state, void* workspace, size_t ws_bytes, float* logits,
+                               float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream) {
+    const tcr_model_ref m = tcresnet_ref(net, params, frozen_ss);
+    return stream_scan(cfg, plan_dev, &m, n_streams, n_samples, k, det, samples, reset, state, workspace, ws_bytes, logits, probs, smoothed,
+                       top, score, is_new, stream, "tcr_stream_scan");
+}
+
+extern "C" int tcr_stream_scan_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_streams,
+                                 int64_t n_samples, int k, const tcr_detect_cfg* det, const float* samples, const uint8_t* reset, void* state,
+                                 void* workspace, size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score,
+                                 int32_t* is_new, void* stream) {
+    return stream_scan(cfg, plan_dev, model, n_streams, n_samples, k, det, samples, reset, state, workspace, ws_bytes, logits, probs,
+                       smoothed, top, score, is_new, stream, "tcr_stream_scan_m");
 }

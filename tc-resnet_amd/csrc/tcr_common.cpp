@@ -163,10 +163,8 @@ extern "C" const char* tcr_kernel_name(int index) {
         "net_fused_tc8_kernel", "net_fused_tc14w_kernel", "train_phase_s_kernel", "bwd_lazy_kernel", "conv_wgrad_mfma4_kernel", "conv_wgrad_lds_kernel",
         "conv1x1_lds_kernel", "bn_bwd_finalize_kernel", "bn_bwd_finalize2_kernel", "wgrad_reduce_multi_kernel", "frontend_pk3_kernel", "pw_wgrad_glds_kernel", "pw_wgrad_lds_p_kernel", "frontend_deploy_f64_kernel", "net_small_tc8_kernel", "bn_bwd_apply4x_kernel", "dscnn_dw_dgrad_rows_kernel", "dscnn_dw_dgrad_rows_s2_kernel", "dscnn_dw_wgrad_rows_kernel", "dscnn_dw_wgrad_rows_s2_kernel", "dscnn_depthwise_rows_kernel", "dscnn_depthwise_rows_s2_kernel", "plane_mean_block_kernel", "dscnn_conv1_dw_loop_kernel",
         "stream_stage_kernel", "stream_init_kernel", "stream_detect_kernel",
-        "scan_stage_kernel", "scan_gather_kernel", "scan_scatter_kernel", "scan_smooth_kernel", "scan_suppress_kernel",
+        "scan_stage_kernel", "scan_gather_kernel", "scan_carry_kernel", "scan_scatter_kernel", "scan_smooth_kernel", "scan_suppress_kernel",
         "sweep_kernel",
-        "stream_scan_stage_kernel", "stream_scan_gather_kernel", "stream_scan_carry_kernel", "stream_scan_smooth_kernel",
-        "stream_scan_suppress_kernel",
     };
     const int n = (int)(sizeof(names) / sizeof(names[0]));
     return (index >= 0 && index < n) ? names[index] : nullptr;
