@@ -531,6 +531,40 @@ int tcr_detect_sweep(int n_signals, int64_t steps, int num_classes, const int32_
                      const int32_t* event_label, int32_t* detections, int32_t* hits, int32_t* duplicates,
                      uint8_t* fired, void* stream);
 
+/* Sample-rate conversion: a rational-ratio polyphase FIR in front of the detectors (which take float32 at the model's rate).
+ * in_rate -> out_rate, g = gcd: up = L = out_rate / g, down = M = in_rate / g; taps = P per phase (even, or 1); table float32
+ * [up][taps], designed on the host (tcresnet_amd.resampling.design_table: windowed sinc, fc = rolloff / max(1, M / L), Kaiser
+ * window over zero_crossings * max(1, M / L) input samples each side, every phase row divided by its sum: unit DC gain).
+ * Output j >= 0 (global index, int64):
+ *     n_j = floor(j M / L),  phi_j = (j M) mod L,  lead = P / 2 - 1 (0 when P == 1),
+ *     y[j] = sum over p = 0 .. P - 1, in this order, as one fmaf chain starting from 0:  table[phi_j][p] * x[n_j - lead + p].
+ * x[i] is the decoded input at global index i: float32 as is, int16 as (float)v * (1.0f / 32768.0f) (exact); x[i] = 0 for every i
+ * outside the span the caller passed, so the start of a signal, its end and a final flush need no special case.  A signal of n_in
+ * samples has ceil(n_in L / M) outputs.  The order of the chain is part of the contract: a sample's value does not depend on the
+ * tile, the chunk or the call that computed it, so converting a range of outputs in pieces is bitwise converting it at once.  With
+ * up = down = taps = 1 and the table {1.0f} the result is bitwise the decoded input.  Positions are 64-bit on host and device
+ * (j M passes 2^32 within an hour of 44.1 kHz audio).
+ * Live audio: keep the last `taps` input samples of each stream next to the new ones in one buffer, call tcr_resample with the
+ * buffer's global index as in_first and the outputs whose span (tcr_resample_span) has arrived; at the end call once more for the
+ * remaining outputs up to ceil(n_total L / M) - 1: the future reads as zeros. */
+typedef struct {
+    int32_t up, down, taps;
+    int32_t in_format;          /* 0 float32, 1 int16 */
+    int32_t in_step;            /* elements between consecutive samples of a row: the channel count of interleaved PCM (channel 0 is read) */
+} tcr_resample_cfg;
+/* in: S rows; row s starts at in + s * in_pitch elements and holds n_in samples (in_step elements apart), the first of which has
+ * global index in_first (which may be negative).  out[s * out_pitch + (j - out_first)] = y[j] for j in [out_first, out_first + n_out).
+ * table: device float32 [up][taps].  Stateless; nothing is read outside the rows, nothing written outside out's n_out columns.
+ * Every pointer is device memory; the launch is enqueued on `stream`.  n_out == 0 or S == 0: a successful no-op.  Refused
+ * (TCR_ERR_ARG, tcr_last_error, no launch): null pointers, up / down / taps < 1, odd taps other than 1, unknown in_format,
+ * in_step < 1, negative counts, in_pitch < (n_in - 1) in_step + 1, out_pitch < n_out, positions past 2^61 / down, and filters of
+ * more taps than a workgroup stages (taps > 6143, or taps + down beyond 14336 samples). */
+int tcr_resample(const tcr_resample_cfg* cfg, const float* table, int n_streams, const void* in, int64_t in_pitch, int64_t in_first,
+                 int64_t n_in, int64_t out_first, int64_t n_out, float* out, int64_t out_pitch, void* stream);
+/* The input span [first, first + n) that outputs [out_first, out_first + n_out) read: first = floor(out_first M / L) - lead,
+ * first + n - 1 = floor((out_first + n_out - 1) M / L) - lead + taps - 1 (n = 0 when n_out == 0).  Host arithmetic only. */
+int tcr_resample_span(const tcr_resample_cfg* cfg, int64_t out_first, int64_t n_out, int64_t* first, int64_t* n);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Instrumentation                                                                             */
 /* ------------------------------------------------------------------------------------------ */

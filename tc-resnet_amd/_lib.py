@@ -45,6 +45,11 @@ class DetectCfg(C.Structure):
     _fields_ = [("average_steps", C.c_int32), ("min_count", C.c_int32), ("suppression_steps", C.c_int32), ("threshold", C.c_float)]
 
 
+class ResampleCfg(C.Structure):
+    """tcr_resample_cfg."""
+    _fields_ = [("up", C.c_int32), ("down", C.c_int32), ("taps", C.c_int32), ("in_format", C.c_int32), ("in_step", C.c_int32)]
+
+
 FAMILY_TCRESNET, FAMILY_DSCNN, FAMILY_G2D = 0, 1, 2
 
 
@@ -182,6 +187,9 @@ _PROTOTYPES = {
     "tcr_stream_scan_m": (C.c_int, [C.POINTER(FrontendCfg), _P, C.POINTER(ModelRef), C.c_int, C.c_int64, C.c_int, C.POINTER(DetectCfg), _P, _P,
                                     _P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
     "tcr_detect_sweep": (C.c_int, [C.c_int, C.c_int64, C.c_int, _P, _P, _P, C.c_int32, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "tcr_resample": (C.c_int, [C.POINTER(ResampleCfg), _P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64,
+                               _P]),
+    "tcr_resample_span": (C.c_int, [C.POINTER(ResampleCfg), C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
 ABI_SYMBOLS = tuple(_PROTOTYPES.keys())

@@ -120,6 +120,14 @@ class FrozenModel:
         from .scanning import KeywordScanner
         return KeywordScanner(net, fe, frozen_ss=self.frozen_ss, **kw)
 
+    def resampler(self, in_rate: int, n_streams: int, **kw):
+        """A `resampling.Resampler` from in_rate to this artifact's sample rate (exported with `include_preprocess`), on the
+        artifact's device: what turns recordings at another rate into the audio `streaming` / `scanner` take.  kw: dtype, channels,
+        zero_crossings, beta, rolloff."""
+        _, fe = FrozenModel._detection_inputs(self, "resampling to the model's rate")
+        from .resampling import Resampler
+        return Resampler(in_rate, int(fe.cfg.sample_rate), n_streams, device=fe.device, lib=fe.lib, **kw)
+
     # ---- file format ----------------------------------------------------------------------------------------------
     def save(self, path: str) -> str:
         out = {"__meta__": np.frombuffer(json.dumps(self.meta, sort_keys=True).encode(), dtype=np.uint8)}

@@ -3,7 +3,8 @@
     python stream_audio.py --frozen MODEL.npz --wav a.wav [b.wav ...] [--frames_per_step k] [--labels l0,l1,...]
                            [--average_window_ms MS] [--detection_threshold P] [--suppression_ms MS] [--min_count N]
 
-Each file is one stream of a `streaming.StreamingDetector` (16-bit PCM at the model's sample rate); the files are fed in lockstep,
+Each file is one stream of a `streaming.StreamingDetector` (16-bit PCM; a file at another sample rate than the model's is converted
+whole on the device first, `resampling.Resampler`, and noted on stderr); the files are fed in lockstep,
 k * hop samples per step, and a file that has ended is fed zeros until every file is done.  Samples that do not fill a whole step
 are dropped (noted on stderr).  One line per detection on stdout:  file,time_ms,label,score  -- time_ms is the end of the window
 that fired (every stream starts as if it had heard one clip of silence)."""
@@ -18,11 +19,13 @@ import numpy as np
 
 if __package__ in (None, ""):           # run as a script: import the package through the repository's shim
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from tcresnet_amd.datasets.augmentation_factory import read_wav_pcm16
+    from tcresnet_amd.datasets.augmentation_factory import read_wav_pcm16_rate
     from tcresnet_amd.deploy import FrozenModel
+    from tcresnet_amd.resampling import Resampler
 else:
-    from .datasets.augmentation_factory import read_wav_pcm16
+    from .datasets.augmentation_factory import read_wav_pcm16_rate
     from .deploy import FrozenModel
+    from .resampling import Resampler
 
 
 def parse_arguments(arguments: Optional[List[str]] = None):
@@ -42,6 +45,27 @@ def format_time_ms(ms: float) -> str:
     return f"{round(ms, 3):g}"
 
 
+def load_streams(paths: List[str], det) -> List[np.ndarray]:
+    """Each file as float32 at the model's rate, cut to whole steps (host arrays): decoded on the host at the model's rate, converted
+    whole on the device otherwise."""
+    import torch
+    step, sr = det.step_samples, det.frontend.cfg.sample_rate
+    audio, resamplers = [], {}
+    for path in paths:
+        pcm, rate = read_wav_pcm16_rate(path)
+        if rate == sr:
+            pcm = pcm.astype(np.float32) * (1.0 / 32768.0)
+        else:
+            print(f"{path}: {rate} Hz -> {sr} Hz", file=sys.stderr)
+            if rate not in resamplers:
+                resamplers[rate] = Resampler(rate, sr, 1, device=det.device, lib=det.lib)
+            pcm = resamplers[rate].resample(torch.from_numpy(np.array(pcm[None, :])).to(det.device))[0].cpu().numpy()
+        if len(pcm) % step:
+            print(f"{path}: dropping the last {len(pcm) % step} samples (not a whole step of {step})", file=sys.stderr)
+        audio.append(pcm[:len(pcm) // step * step])
+    return audio
+
+
 def main(args) -> int:
     import torch
     model = FrozenModel.load(args.frozen)
@@ -49,12 +73,7 @@ def main(args) -> int:
                           min_count=args.min_count, detection_threshold=args.detection_threshold, suppression_ms=args.suppression_ms)
     labels = args.labels.split(",") if args.labels else None
     step = det.step_samples
-    audio = []
-    for path in args.wav:
-        pcm = read_wav_pcm16(path).astype(np.float32) * (1.0 / 32768.0)
-        if len(pcm) % step:
-            print(f"{path}: dropping the last {len(pcm) % step} samples (not a whole step of {step})", file=sys.stderr)
-        audio.append(pcm[:len(pcm) // step * step])
+    audio = load_streams(args.wav, det)
     n_steps = max(len(a) for a in audio) // step
     host = np.zeros((len(audio), step), np.float32)
     buf = torch.zeros((len(audio), step), dtype=torch.float32, device=det.device)

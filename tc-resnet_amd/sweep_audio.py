@@ -32,14 +32,12 @@ import numpy as np
 
 if __package__ in (None, ""):           # run as a script: import the package through the repository's shim
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from tcresnet_amd.datasets.augmentation_factory import read_wav_pcm16
     from tcresnet_amd.deploy import FrozenModel
-    from tcresnet_amd.scan_audio import wav_chunks, whole_step_lengths
+    from tcresnet_amd.scan_audio import load_signals, signal_chunks, whole_step_lengths
     from tcresnet_amd.scanning import ScanOutput
 else:
-    from .datasets.augmentation_factory import read_wav_pcm16
     from .deploy import FrozenModel
-    from .scan_audio import wav_chunks, whole_step_lengths
+    from .scan_audio import load_signals, signal_chunks, whole_step_lengths
     from .scanning import ScanOutput
 
 COLUMNS = ("threshold", "hits", "events", "false_accepts", "duplicates", "frr", "fa_per_hour")
@@ -104,28 +102,19 @@ def main(args) -> int:
     thresholds = parse_thresholds(args.thresholds)
     step = scanner.step_samples
     if args.chunk_seconds is None:
-        audio = []
-        for path in args.wav:
-            pcm = read_wav_pcm16(path).astype(np.float32) * (1.0 / 32768.0)
-            if len(pcm) % step:
-                print(f"{path}: dropping the last {len(pcm) % step} samples (not a whole step of {step})", file=sys.stderr)
-            audio.append(pcm[:len(pcm) // step * step])
-        lengths = [len(a) for a in audio]
+        samples, lengths = load_signals(args.wav, scanner)
     else:
-        lengths = whole_step_lengths(args.wav, step)
+        lengths = whole_step_lengths(args.wav, step, scanner.frontend.cfg.sample_rate)
     n_steps = max(lengths) // step
     if n_steps == 0:
         raise SystemExit("no whole step of audio in the files")
     events = read_events(args.events, args.wav)
     if args.chunk_seconds is None:
-        host = np.zeros((len(audio), n_steps * step), np.float32)
-        for s, a in enumerate(audio):
-            host[s, :len(a)] = a
-        out = scanner.scan(torch.from_numpy(host).to(scanner.device))
+        out = scanner.scan(samples)
     else:
         tops, scores = [], []                           # (only what the sweep reads stays on the device)
-        for _, host in wav_chunks(args.wav, step, args.chunk_seconds, scanner.frontend.cfg.sample_rate):
-            o = scanner.push_many(torch.from_numpy(host).to(scanner.device))
+        for _, samples in signal_chunks(args.wav, scanner, args.chunk_seconds):
+            o = scanner.push_many(samples)
             tops.append(o.top)
             scores.append(o.score)
         out = ScanOutput(None, None, None, torch.cat(tops, dim=1), torch.cat(scores, dim=1), None)
