@@ -60,7 +60,7 @@ def make_frontend():
                             win=cfg.win, hop=cfg.hop)
 
 
-def edge_waveforms() -> np.ndarray:
+def edge_waveforms(n_samples: int = 16000) -> np.ndarray:
     """The reference's low-amplitude workload and two spectral extremes, where log(mel + 1e-6) amplifies error most:
     rows 0-2: a SILENT clip (label `_silence_`: empty file -> zeros, datasets/audio_data_wrapper.py:164-174) mixed with a
               background recording at volume 0.01 / 0.05 / 0.1 (augmentation_factory.py:92-97: clip(bg * volume + fg); the
@@ -70,13 +70,13 @@ def edge_waveforms() -> np.ndarray:
     row 5:    a 30 Hz sine at 0.5 (energy only BELOW the first mel filter: every band near the log offset)."""
     from . import augment_ref as A
     rng = np.random.RandomState(77)
-    bg = rng.randint(-32768, 32768, 3 * 16000).astype(np.int16)
+    bg = rng.randint(-32768, 32768, 3 * n_samples).astype(np.int16)
     rows = []
     for i, vol in enumerate((0.01, 0.05, 0.1)):
-        crop = bg[i * 16000:(i + 1) * 16000].astype(np.float32) * np.float32(1.0 / 32768.0)
-        rows.append(A.mix_background(np.zeros(16000, np.float32), crop, vol))
-    rows.append((rng.uniform(-1.0, 1.0, 16000) * 1e-4).astype(np.float32))
-    t = np.arange(16000, dtype=np.float64) / 16000.0
+        crop = bg[i * n_samples:(i + 1) * n_samples].astype(np.float32) * np.float32(1.0 / 32768.0)
+        rows.append(A.mix_background(np.zeros(n_samples, np.float32), crop, vol))
+    rows.append((rng.uniform(-1.0, 1.0, n_samples) * 1e-4).astype(np.float32))
+    t = np.arange(n_samples, dtype=np.float64) / 16000.0
     rows.append(np.sin(2.0 * np.pi * 1000.0 * t).astype(np.float32))
     rows.append((0.5 * np.sin(2.0 * np.pi * 30.0 * t)).astype(np.float32))
     return np.stack(rows)

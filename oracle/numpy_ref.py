@@ -187,6 +187,29 @@ def mfcc_deploy(wav: np.ndarray, cfg: FrontendCfg, dtype=np.float64) -> np.ndarr
     return logmel @ dct.T
 
 
+def deploy_mel_weight_matrix(cfg: FrontendCfg) -> np.ndarray:
+    """The filterbank mfcc_deploy applies bin by bin, as a dense [n_bins, num_mel_bins] matrix on the MAGNITUDE spectrum
+    (sqrt(power) @ matrix is mfcc_deploy's `out`, up to the order of the sums)."""
+    nbins, nch = cfg.n_bins, cfg.num_mel_bins
+    mel_low, mel_hi = hertz_to_mel(cfg.lower_edge_hertz), hertz_to_mel(cfg.upper_edge_hertz)
+    center = mel_low + (mel_hi - mel_low) / (nch + 1) * (np.arange(nch + 1) + 1)
+    hz_per_sbin = 0.5 * cfg.sample_rate / (nbins - 1)
+    start, end = int(1.5 + cfg.lower_edge_hertz / hz_per_sbin), int(cfg.upper_edge_hertz / hz_per_sbin)
+    m = np.zeros((nbins, nch))
+    channel = 0
+    for i in range(start, min(end, nbins - 1) + 1):
+        melf = hertz_to_mel(i * hz_per_sbin)
+        while channel < nch and center[channel] < melf:
+            channel += 1
+        b = channel - 1
+        w = (center[b + 1] - melf) / (center[b + 1] - center[b]) if b >= 0 else (center[0] - melf) / (center[0] - mel_low)
+        if b >= 0:
+            m[i, b] += w
+        if b + 1 < nch:
+            m[i, b + 1] += 1.0 - w
+    return m
+
+
 @dataclass
 class ConvSpec:
     name: str            # TF variable scope under the model scope, e.g. "block0/conv0_0"

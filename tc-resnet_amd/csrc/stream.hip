@@ -27,6 +27,7 @@
 // Compiled as part of frontend_pk3.hip's translation unit (included at its end, next to the streaming front-end's launcher).
 #pragma once
 #include <algorithm>
+#include <cstdio>
 
 #include "frontend_plan.h"
 #include "frontend_args.h"
@@ -84,9 +85,23 @@ int stream_check(const tcr_frontend_cfg* cfg, const tcr_model_ref* m, int S, int
     TCR_REQUIRE(io.classes <= 256, "%s: the detector takes at most 256 classes (got %d)", what, io.classes);
     TCR_REQUIRE(k >= 1 && k <= cfg->n_frames, "%s: frames per step k = %d outside 1..T = %d", what, k, cfg->n_frames);
     TCR_REQUIRE((int64_t)S * k < (1 << 23) && (int64_t)S * cfg->n_frames < ((int64_t)1 << 31), "%s: %d streams x %d frames is too large", what, S, k);
-    TCR_REQUIRE((cfg->hop & 1) == 0 && frontend_pk3_supports(cfg->nfft / 2, cfg->win, frontend_mel_item_count(*cfg)),
+    // (n_items = 0: the window / hop part of the launcher's test alone, so that the two causes are told apart)
+    TCR_REQUIRE((cfg->hop & 1) == 0 && frontend_pk3_supports(cfg->nfft / 2, cfg->win, 0),
                 "%s: the streaming front-end (frontend_pk3_kernel) does not cover window %d / hop %d / %d mel bands at nfft %d; another "
                 "kernel would not give the offline features bitwise", what, cfg->win, cfg->hop, cfg->n_mel, cfg->nfft);
+    {
+        const int n_items = frontend_mel_item_count(*cfg), n_fast = mel_items_fast(cfg->nfft / 2);
+        char why[160];
+        if (n_items < 0)
+            std::snprintf(why, sizeof(why), "a mel-edge segment of more than %d bins (three work items; the kernel's log phase reads no more)",
+                          3 * mel_item_bins(cfg->nfft / 2));
+        else
+            std::snprintf(why, sizeof(why), "%d work items, its unrolled trips take %d", n_items, n_fast);
+        TCR_REQUIRE(frontend_pk3_supports(cfg->nfft / 2, cfg->win, n_items),
+                    "%s: the streaming front-end (frontend_pk3_kernel) does not cover the mel filterbank %g - %g Hz at sample rate %d / "
+                    "nfft %d (%s); another kernel would not give the offline features bitwise", what, cfg->lower_hz, cfg->upper_hz,
+                    cfg->sample_rate, cfg->nfft, why);
+    }
     TCR_REQUIRE(cfg->win - cfg->hop + (cfg->n_samples - cfg->win) % cfg->hop <= kMaxTail, "%s: window %d / hop %d leave a tail of more "
                 "than %d samples", what, cfg->win, cfg->hop, kMaxTail);
     if (det) {

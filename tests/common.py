@@ -31,9 +31,30 @@ def frontend_cfg(win, hop, num_mfccs=40):
     return dataclasses.replace(R.FRONTEND_3010, window_size_ms=win / 16.0, window_stride_ms=hop / 16.0, num_mfccs=num_mfccs)
 
 
-def make_frontend(lib, win, hop, num_mfccs=40, method="mfcc"):
-    return T.Frontend(window_size_samples=int(win), window_stride_samples=int(hop), num_mfccs=num_mfccs, method=method,
+def make_frontend(lib, win, hop, num_mfccs=40, method="mfcc", sample_rate=16000, clip_ms=1000, lower_hz=80.0, upper_hz=7600.0):
+    return T.Frontend(sample_rate=int(sample_rate), clip_duration_ms=clip_ms, window_size_samples=int(win), window_stride_samples=int(hop),
+                      num_mfccs=num_mfccs, lower_edge_hertz=lower_hz, upper_edge_hertz=upper_hz, method=method,
                       lib=lib, device=device_of(lib))
+
+
+def oracle_frontend_cfg(sample_rate, clip_ms, win, hop, lower_hz, upper_hz, num_mfccs):
+    """The oracle's FrontendCfg of a front-end given in samples (the oracle takes window and stride in ms and truncates: half a sample
+    is added so that every sample rate lands on `win` / `hop`)."""
+    cfg = R.FrontendCfg(sample_rate=int(sample_rate), clip_duration_ms=clip_ms, window_size_ms=(win + 0.5) * 1000.0 / sample_rate,
+                        window_stride_ms=(hop + 0.5) * 1000.0 / sample_rate, lower_edge_hertz=float(lower_hz),
+                        upper_edge_hertz=float(upper_hz), num_mfccs=int(num_mfccs))
+    assert (cfg.win, cfg.hop) == (win, hop), (cfg.win, cfg.hop)
+    return cfg
+
+
+def config_waveforms(n_samples, batch, seed=1234):
+    """The inputs of the configuration sweep at a clip length: R.synth_waveforms rows, then digital silence and the four low-noise rows
+    of oracle.make_golden.edge_waveforms regenerated at that length (pure tones have their own float32 bound and tests); the ordinary
+    rows repeat (new seeds) until `batch` is reached."""
+    from oracle.make_golden import edge_waveforms
+    edge = np.concatenate([np.zeros((1, n_samples), np.float32), edge_waveforms(n_samples)[:4]], axis=0)
+    n_syn = max(batch - edge.shape[0], 1)
+    return np.concatenate([R.synth_waveforms(n_syn, n_samples, seed=seed), edge], axis=0)
 
 
 def fixture_params(fx, name, width):
