@@ -1,0 +1,162 @@
+"""What scan_audio.py, stream_audio.py and sweep_audio.py share: the WAV parser (`WavFile`, the package's only one), the files as the
+detector takes them (`Recordings`: whole steps at the model's rate, on its device, chunk by chunk or whole), the detection lines and
+the --summary line, and the flags the tools have in common."""
+from __future__ import annotations
+
+import json
+import os
+import struct
+import sys
+from typing import Dict, Iterator, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from .resampling import Resampler
+
+
+class WavFile:
+    """The header of a 16-bit PCM RIFF/WAVE file: `rate`, `channels`, `length` (frames).  `read_pcm(first, n)` returns channel 0 of
+    the frames [first, first + n) as int16, zeros outside the file.  A data chunk that ends inside a frame counts its whole frames."""
+
+    def __init__(self, path: str):
+        self.path = path
+        with open(path, "rb") as fh:
+            size = os.fstat(fh.fileno()).st_size
+            head = fh.read(12)
+            if head[:4] != b"RIFF" or head[8:12] != b"WAVE":
+                raise ValueError(f"{path}: not a RIFF/WAVE file")
+            pos, self.channels, self.rate, data = 12, 1, 0, None
+            while pos + 8 <= size:
+                fh.seek(pos)
+                tag, n = fh.read(4), struct.unpack("<I", fh.read(4))[0]
+                if tag == b"fmt ":
+                    fmt, self.channels, self.rate, _br, _align, bits = struct.unpack("<HHIIHH", fh.read(16))
+                    if fmt != 1 or bits != 16:
+                        raise ValueError(f"{path}: only 16-bit PCM is supported (format {fmt}, {bits} bits)")
+                elif tag == b"data":
+                    data = (pos + 8, min(n, size - pos - 8))
+                pos += 8 + n + (n & 1)
+        if data is None:
+            raise ValueError(f"{path}: no data chunk")
+        self.start, self.length = data[0], data[1] // 2 // self.channels
+
+    def read_pcm(self, first: int, n: int) -> np.ndarray:
+        out = np.zeros(n, np.int16)
+        lo, hi = max(first, 0), min(first + n, self.length)
+        if hi > lo:
+            with open(self.path, "rb") as fh:
+                fh.seek(self.start + lo * 2 * self.channels)
+                out[lo - first:hi - first] = np.frombuffer(fh.read((hi - lo) * 2 * self.channels), dtype="<i2").reshape(-1, self.channels)[:, 0]
+        return out
+
+
+class Recordings:
+    """The files as `det` (a KeywordScanner or StreamingDetector) takes them.  Each file is parsed once; `lengths` are the files'
+    lengths at the model's rate in whole steps' samples (a file at another rate counts with its converted length,
+    ceil(n sample_rate / rate)), `n_steps` the longest's steps.  The conversions and the dropped samples are noted on stderr."""
+
+    def __init__(self, paths: List[str], det):
+        self.paths, self.det, self.step, self.rate = list(paths), det, det.step_samples, det.frontend.cfg.sample_rate
+        self.files, self.lengths, self.resamplers = [WavFile(p) for p in paths], [], {}
+        for f in self.files:
+            n = f.length
+            if f.rate != self.rate:
+                print(f"{f.path}: {f.rate} Hz -> {self.rate} Hz", file=sys.stderr)
+                n = -(-n * self.rate // f.rate)
+            if n % self.step:
+                print(f"{f.path}: dropping the last {n % self.step} samples (not a whole step of {self.step})", file=sys.stderr)
+            self.lengths.append(n // self.step * self.step)
+        self.n_steps = max(self.lengths) // self.step
+
+    def resampler(self, rate: int) -> Resampler:
+        """One `Resampler` per input rate, built when a file first needs it."""
+        if rate not in self.resamplers:
+            self.resamplers[rate] = Resampler(rate, self.rate, 1, device=self.det.device, lib=self.det.lib)
+        return self.resamplers[rate]
+
+    def chunks(self, chunk_seconds: Optional[float] = None) -> Iterator[Tuple[int, torch.Tensor]]:
+        """(first step, float32 [N, m * step] on det's device) up to the longest file's last whole step, chunk_seconds (rounded down
+        to whole steps) at a time; None: the whole recordings as one chunk.  A file that has ended reads as zeros.  A file at the
+        model's rate is decoded on the host; of a file at another rate each chunk reads exactly the input span its outputs need
+        (zeros outside the file) and converts it by global position on the device, so the chunks are the whole buffer's columns,
+        bitwise, and no resampler state is kept."""
+        chunk_steps = max(self.n_steps, 1) if chunk_seconds is None else int(chunk_seconds * self.rate) // self.step
+        if chunk_steps < 1:
+            raise SystemExit(f"--chunk_seconds {chunk_seconds:g} is shorter than one step ({self.step} samples)")
+        dev = self.det.device
+        for i0 in range(0, self.n_steps, chunk_steps):
+            m, at = min(chunk_steps, self.n_steps - i0), i0 * self.step
+            buf = torch.zeros((len(self.files), m * self.step), dtype=torch.float32, device=dev)
+            for s, f in enumerate(self.files):
+                keep = max(0, min(m * self.step, self.lengths[s] - at))
+                if keep == 0:
+                    continue
+                if f.rate == self.rate:
+                    buf[s, :keep] = torch.from_numpy(f.read_pcm(at, keep).astype(np.float32) * (1.0 / 32768.0)).to(dev)
+                else:
+                    rs = self.resampler(f.rate)
+                    first, n = rs.span(at, keep)
+                    rs.convert(torch.from_numpy(f.read_pcm(first, n)[None, :]).to(dev), first, at, keep, out=buf[s:s + 1, :keep])
+            yield i0, buf
+
+
+def format_time_ms(ms: float) -> str:
+    return f"{round(ms, 3):g}"
+
+
+def print_detections(rec: Recordings, out, i0: int, names: List[str], counts: Dict[str, int]) -> None:
+    """One line per detection of `out` (is_new / top / score [N, m], or [N] for one step: a ScanOutput or StreamOutput) on stdout,
+    file,time_ms,label,score,  in step order and, within a step, in file order; `i0` is out's first step, time_ms the end of the
+    window that fired.  `counts` gains the detections per label."""
+    fired = out.is_new.cpu().numpy().reshape(len(rec.paths), -1)
+    if not fired.any():
+        return
+    top, score = out.top.cpu().numpy().reshape(fired.shape), out.score.cpu().numpy().reshape(fired.shape)
+    for i, s in zip(*np.nonzero(fired.T)):
+        name = names[top[s, i]]
+        counts[name] = counts.get(name, 0) + 1
+        print(f"{rec.paths[s]},{format_time_ms(1000.0 * (i0 + i + 1) * rec.step / rec.rate)},{name},{float(score[s, i]):.6f}", flush=True)
+
+
+def summary_line(rec: Recordings, counts: Dict[str, int]) -> str:
+    """--summary's JSON: the hours of audio (each file's whole steps), the detections per label and per hour."""
+    hours, total = sum(rec.lengths) / rec.rate / 3600.0, sum(counts.values())
+    return json.dumps({"hours": hours, "detections": total, "detections_per_label": counts,
+                       "detections_per_hour": total / hours if hours > 0 else None})
+
+
+def add_detector_flags(p, each: str = "signal", threshold: bool = True, offline: bool = True) -> None:
+    """The model, input and detector flags of the three tools; `offline`: the scanning tools' --max_windows and --chunk_seconds."""
+    p.add_argument("--frozen", required=True, help="frozen artifact (.npz) of any model family exported with include_preprocess")
+    p.add_argument("--wav", required=True, nargs="+", help=f"16-bit PCM WAV files, one {each} each")
+    p.add_argument("--frames_per_step", type=int, default=1, help="new front-end frames per step (k)")
+    p.add_argument("--labels", default=None, help="comma-separated class names (default: class indices)")
+    p.add_argument("--average_window_ms", type=float, default=1000.0)
+    if threshold:
+        p.add_argument("--detection_threshold", type=float, default=0.5)
+    p.add_argument("--suppression_ms", type=float, default=1500.0)
+    p.add_argument("--min_count", type=int, default=3)
+    if offline:
+        p.add_argument("--max_windows", type=int, default=None, help="windows per network launch (the workspace's size)")
+        p.add_argument("--chunk_seconds", type=float, default=None, help="read and scan the files this many seconds at a time")
+
+
+def detector_settings(args) -> dict:
+    """FrozenModel.scanner's / .streaming's keyword arguments from the flags the tool has."""
+    keys = ("frames_per_step", "average_window_ms", "min_count", "detection_threshold", "suppression_ms", "max_windows")
+    return {k: getattr(args, k) for k in keys if hasattr(args, k)}
+
+
+def open_detector(model, args):
+    """(detector, its call on one chunk): a KeywordScanner and `scan` for the one-call run, which allocates no stream state; with
+    --chunk_seconds a StreamingDetector over the files and `push_many`, which carries the state from chunk to chunk."""
+    if args.chunk_seconds is None:
+        det = model.scanner(**detector_settings(args))
+        return det, det.scan
+    det = model.streaming(len(args.wav), **detector_settings(args))
+    return det, det.push_many
+
+
+def label_names(args, det) -> List[str]:
+    return args.labels.split(",") if args.labels else [str(c) for c in range(det.net.num_classes)]

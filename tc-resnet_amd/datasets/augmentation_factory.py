@@ -7,13 +7,13 @@ inside its graph come from a seeded host generator, in the same per-element orde
 """
 from __future__ import annotations
 
-import struct
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from .. import runtime
+from ..audio_input import WavFile
 from ..engine import _resolve
 
 _available_audio_augmentation_methods = [
@@ -33,24 +33,8 @@ def read_wav_pcm16(path: str) -> np.ndarray:
 
 def read_wav_pcm16_rate(path: str) -> Tuple[np.ndarray, int]:
     """read_wav_pcm16's samples and the sample rate of the file's `fmt ` chunk."""
-    with open(path, "rb") as fh:
-        data = fh.read()
-    if data[:4] != b"RIFF" or data[8:12] != b"WAVE":
-        raise ValueError(f"{path}: not a RIFF/WAVE file")
-    pos, channels, rate, bits, pcm = 12, 1, 0, 16, None
-    while pos + 8 <= len(data):
-        tag, size = data[pos:pos + 4], struct.unpack("<I", data[pos + 4:pos + 8])[0]
-        body = data[pos + 8:pos + 8 + size]
-        if tag == b"fmt ":
-            fmt, channels, rate, _br, _align, bits = struct.unpack("<HHIIHH", body[:16])
-            if fmt != 1 or bits != 16:
-                raise ValueError(f"{path}: only 16-bit PCM is supported (format {fmt}, {bits} bits)")
-        elif tag == b"data":
-            pcm = np.frombuffer(body[:len(body) // 2 * 2], dtype="<i2")
-        pos += 8 + size + (size & 1)
-    if pcm is None:
-        raise ValueError(f"{path}: no data chunk")
-    return np.ascontiguousarray(pcm.reshape(-1, channels)[:, 0]), int(rate)
+    wav = WavFile(path)
+    return wav.read_pcm(0, wav.length), int(wav.rate)
 
 
 class PcmPool:

@@ -6,11 +6,12 @@ curve (false rejects against false accepts per hour) from one scan.
                           [--frames_per_step k] [--labels l0,l1,...] [--average_window_ms MS] [--suppression_ms MS]
                           [--min_count N] [--max_windows B] [--chunk_seconds X]
 
-The files are read as scan_audio.py reads them (16-bit PCM at the model's sample rate, only whole steps), zero-padded to the
-longest and scanned in one call; one `KeywordScanner.sweep` then walks the detector's suppression rule at every threshold over
-each file's true length (--detection_threshold is not an input: the thresholds are).  With --chunk_seconds the files are read and scanned chunk by
-chunk (scan_audio.py's --chunk_seconds: `StreamingDetector.push_many`), the chunks' top / score are concatenated on the device
-and swept once: the output is the one-call output, byte for byte.  EVENTS.csv has a header and the columns
+The files are read as scan_audio.py reads them (`audio_input.Recordings`: 16-bit PCM, converted to the model's sample rate on the
+device where it differs, only whole steps), zero-padded to the longest and scanned in one call; one `KeywordScanner.sweep` then
+walks the detector's suppression rule at every threshold over each file's true length (--detection_threshold is not an input: the
+thresholds are).  With --chunk_seconds the files are read and scanned chunk by chunk (scan_audio.py's --chunk_seconds:
+`StreamingDetector.push_many`); either way the chunks' top / score are concatenated on the device and swept once: the output is the
+one-call output, byte for byte.  EVENTS.csv has a header and the columns
 file,start_ms,end_ms,label  (file as given to --wav, label one of --labels or a class index).  A detection at time t (the end of
 the window that fired, scan_audio.py's time) hits an event of its label when  start_ms <= t <= end_ms + tolerance_ms; the first
 hit of an event counts as a hit, later ones as duplicates, every other detection as a false accept.
@@ -32,12 +33,12 @@ import numpy as np
 
 if __package__ in (None, ""):           # run as a script: import the package through the repository's shim
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from tcresnet_amd.audio_input import Recordings, add_detector_flags, label_names, open_detector
     from tcresnet_amd.deploy import FrozenModel
-    from tcresnet_amd.scan_audio import load_signals, signal_chunks, whole_step_lengths
     from tcresnet_amd.scanning import ScanOutput
 else:
+    from .audio_input import Recordings, add_detector_flags, label_names, open_detector
     from .deploy import FrozenModel
-    from .scan_audio import load_signals, signal_chunks, whole_step_lengths
     from .scanning import ScanOutput
 
 COLUMNS = ("threshold", "hits", "events", "false_accepts", "duplicates", "frr", "fa_per_hour")
@@ -55,21 +56,13 @@ def parse_thresholds(spec: str) -> np.ndarray:
 
 def parse_arguments(arguments: Optional[List[str]] = None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--frozen", required=True, help="frozen artifact (.npz) of any model family exported with include_preprocess")
-    p.add_argument("--wav", required=True, nargs="+", help="16-bit PCM WAV files, one signal each")
+    add_detector_flags(p, threshold=False)
     p.add_argument("--events", required=True, help="CSV of labelled keyword events: file,start_ms,end_ms,label")
     p.add_argument("--thresholds", default="0:0.99:0.01", help="LO:HI:STEP or a comma-separated list")
     p.add_argument("--tolerance_ms", type=float, default=1000.0, help="a detection up to this long after an event's end still hits it")
     p.add_argument("--keywords", default=None, help="comma-separated labels scored (default: labels not starting with '_')")
     p.add_argument("--per_label", action="store_true", help="one row per keyword and threshold")
     p.add_argument("--target_fa_per_hour", type=float, default=0.5, help="false-accept budget of the operating point")
-    p.add_argument("--frames_per_step", type=int, default=1, help="new front-end frames per step (k)")
-    p.add_argument("--labels", default=None, help="comma-separated class names (default: class indices)")
-    p.add_argument("--average_window_ms", type=float, default=1000.0)
-    p.add_argument("--suppression_ms", type=float, default=1500.0)
-    p.add_argument("--min_count", type=int, default=3)
-    p.add_argument("--max_windows", type=int, default=None, help="windows per network launch (the workspace's size)")
-    p.add_argument("--chunk_seconds", type=float, default=None, help="read and scan the files this many seconds at a time")
     return p.parse_args(arguments)
 
 
@@ -88,37 +81,25 @@ def read_events(path: str, wavs: List[str]):
 
 def main(args) -> int:
     import torch
-    model = FrozenModel.load(args.frozen)
-    settings = dict(frames_per_step=args.frames_per_step, average_window_ms=args.average_window_ms, min_count=args.min_count,
-                    suppression_ms=args.suppression_ms, max_windows=args.max_windows)
-    scanner = model.scanner(**settings) if args.chunk_seconds is None else model.streaming(len(args.wav), **settings)
-    ncls = scanner.net.num_classes
-    names = args.labels.split(",") if args.labels else [str(c) for c in range(ncls)]
+    scanner, run = open_detector(FrozenModel.load(args.frozen), args)
+    names = label_names(args, scanner)
     keywords = args.keywords.split(",") if args.keywords else [x for x in names if not x.startswith("_")]
     unknown = [k for k in keywords if k not in names]
     if unknown:
         raise SystemExit(f"--keywords {unknown} are not labels")
     classes = [names.index(k) for k in keywords]
     thresholds = parse_thresholds(args.thresholds)
-    step = scanner.step_samples
-    if args.chunk_seconds is None:
-        samples, lengths = load_signals(args.wav, scanner)
-    else:
-        lengths = whole_step_lengths(args.wav, step, scanner.frontend.cfg.sample_rate)
-    n_steps = max(lengths) // step
-    if n_steps == 0:
+    rec = Recordings(args.wav, scanner)
+    if rec.n_steps == 0:
         raise SystemExit("no whole step of audio in the files")
     events = read_events(args.events, args.wav)
-    if args.chunk_seconds is None:
-        out = scanner.scan(samples)
-    else:
-        tops, scores = [], []                           # (only what the sweep reads stays on the device)
-        for _, samples in signal_chunks(args.wav, scanner, args.chunk_seconds):
-            o = scanner.push_many(samples)
-            tops.append(o.top)
-            scores.append(o.score)
-        out = ScanOutput(None, None, None, torch.cat(tops, dim=1), torch.cat(scores, dim=1), None)
-    res = scanner.sweep(out, thresholds, events=events, lengths=lengths, tolerance_ms=args.tolerance_ms, labels=names)
+    tops, scores = [], []                               # (only what the sweep reads stays on the device)
+    for _, samples in rec.chunks(args.chunk_seconds):
+        o = run(samples)
+        tops.append(o.top)
+        scores.append(o.score)
+    out = ScanOutput(None, None, None, torch.cat(tops, dim=1), torch.cat(scores, dim=1), None)
+    res = scanner.sweep(out, thresholds, events=events, lengths=rec.lengths, tolerance_ms=args.tolerance_ms, labels=names)
     w = csv.writer(sys.stdout, lineterminator="\n")
     fmt = lambda cv, t: [f"{cv['threshold'][t]:.6g}", *(int(cv[k][t]) for k in COLUMNS[1:5]), f"{cv['frr'][t]:.6g}",
                          f"{cv['fa_per_hour'][t]:.9g}"]

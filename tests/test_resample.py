@@ -357,7 +357,7 @@ def run_cli(module, argv, capsys):
 
 
 def check_end_to_end(lib, tmp_path, capsys, monkeypatch, seconds):
-    from tcresnet_amd import deploy, runtime, scan_audio, stream_audio, sweep_audio
+    from tcresnet_amd import audio_input, deploy, runtime, scan_audio, stream_audio, streaming, sweep_audio
     Rs = resampling()
     dev = Cm.device_of(lib)
     fe, net, _, _, _ = setup(lib)
@@ -377,12 +377,20 @@ def check_end_to_end(lib, tmp_path, capsys, monkeypatch, seconds):
         scanner = model.scanner(**CLI_KW)
         step = scanner.step_samples
         rows = {}
+
+        def recordings(paths, det):
+            """(the whole recordings as the tools take them: one chunk of every step, their lengths)"""
+            rec = audio_input.Recordings(paths, det)
+            (i0, buf), = rec.chunks()
+            assert i0 == 0
+            return buf, rec.lengths
+
         for name in ("a48.wav", "b44.wav"):
             x, rate, _ = pcm[name]
             # each row of the buffer: bitwise Resampler(rate, 16000, 1).resample(pcm), cut to whole steps
             want = Rs.Resampler(rate, 16000, 1, device=dev, lib=lib).resample(dev_tensor(lib, x[None, :]))
             want = want[:, :want.shape[1] // step * step]
-            buf, lengths = scan_audio.load_signals([wavs[name]], scanner)
+            buf, lengths = recordings([wavs[name]], scanner)
             assert lengths == [want.shape[1]] and torch.equal(buf, want)
             rows[name] = want
             # scan_audio.py's stdout: exactly the lines scanner.scan of that buffer yields; time_ms in real time
@@ -401,16 +409,21 @@ def check_end_to_end(lib, tmp_path, capsys, monkeypatch, seconds):
                                           "--chunk_seconds", sec], capsys)
                 assert rc.out == r.out and rc.err == r.err
             # stream_audio.py: the same signal, the same lines
-            st = stream_audio.load_streams([wavs[name]], model.streaming(1, **CLI_KW))
-            assert np.array_equal(st[0].view(np.uint32), want[0].cpu().numpy().view(np.uint32))
-            rs_ = run_cli(stream_audio, ["--frozen", path, "--wav", wavs[name], "--labels", ",".join(labels), *CLI_DET], capsys)
+            st, _ = recordings([wavs[name]], model.streaming(1, **CLI_KW))
+            assert torch.equal(st.view(torch.int32), want.view(torch.int32))
+            fed, push = [], streaming.StreamingDetector.push
+            with monkeypatch.context() as m:                                  # what the tool pushes, step by step
+                m.setattr(streaming.StreamingDetector, "push", lambda self, x: (fed.append(x.clone()), push(self, x))[1])
+                rs_ = run_cli(stream_audio, ["--frozen", path, "--wav", wavs[name], "--labels", ",".join(labels), *CLI_DET], capsys)
             assert rs_.out == r.out
+            assert all(x.shape == (1, step) and x.is_contiguous() for x in fed)
+            assert torch.equal(torch.cat(fed, dim=1).view(torch.int32), want.view(torch.int32))
         # 16 kHz, 48 kHz and 44.1 kHz in one invocation: each row is the file's single-file row, zero-padded to the longest
         x16 = pcm["c16.wav"][0]
         row16 = dev_tensor(lib, (x16.astype(np.float32) * (1.0 / 32768.0))[None, :len(x16) // step * step])
         order = ["c16.wav", "a48.wav", "b44.wav"]
         rows["c16.wav"] = row16
-        buf, lengths = scan_audio.load_signals([wavs[n] for n in order], scanner)
+        buf, lengths = recordings([wavs[n] for n in order], scanner)
         capsys.readouterr()
         assert lengths == [rows[n].shape[1] for n in order] and buf.shape == (3, max(lengths))
         for s, n in enumerate(order):
@@ -419,7 +432,8 @@ def check_end_to_end(lib, tmp_path, capsys, monkeypatch, seconds):
         r = run_cli(scan_audio, mixed, capsys)
         rc = run_cli(scan_audio, mixed + ["--chunk_seconds", "0.3"], capsys)
         assert rc.out == r.out and rc.err == r.err and len(r.out.splitlines()) >= 3
-        chunks = torch.cat([c for _, c in scan_audio.signal_chunks([wavs[n] for n in order], scanner, 0.3)], dim=1)
+        chunks = torch.cat([c for _, c in audio_input.Recordings([wavs[n] for n in order], scanner).chunks(0.3)], dim=1)
+        capsys.readouterr()
         assert torch.equal(chunks, buf)
         # sweep_audio.py reads the same buffer: its chunked run prints what its one-call run prints
         ev = tmp_path / "events.csv"
@@ -433,9 +447,8 @@ def check_end_to_end(lib, tmp_path, capsys, monkeypatch, seconds):
         # files at the model's rate: no Resampler is built, the buffer is the host decode
         def boom(*args, **kw):
             raise AssertionError("a Resampler was constructed for files at the model's rate")
-        monkeypatch.setattr(scan_audio, "Resampler", boom)
-        monkeypatch.setattr(stream_audio, "Resampler", boom)
-        buf, lengths = scan_audio.load_signals([wavs["c16.wav"]], scanner)
+        monkeypatch.setattr(audio_input, "Resampler", boom)             # the one place the tools construct one
+        buf, lengths = recordings([wavs["c16.wav"]], scanner)
         assert torch.equal(buf, row16)
         only16 = ["--frozen", path, "--wav", wavs["c16.wav"], "--labels", ",".join(labels), *CLI_DET]
         r16 = run_cli(scan_audio, only16, capsys)

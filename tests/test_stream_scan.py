@@ -189,11 +189,12 @@ def test_push_many_refusals(emu_lib):
     assert scan(0, 640, 1 << 18) == -1 and b"number of streams must be positive" in lib.tcr_last_error()
 
 
-def test_wav_chunks_read_what_the_one_call_path_pads(tmp_path):
-    """scan_audio.py's chunked reader: whole steps of every file, zeros once a file has ended, chunks rounded down to whole steps;
-    concatenated they are the one-call path's zero-padded array, and the dropped samples are noted the same way."""
+def test_wav_chunks_read_what_the_one_call_path_pads(tmp_path, capsys):
+    """The tools' chunked reader (audio_input.Recordings): whole steps of every file, zeros once a file has ended, chunks rounded down
+    to whole steps; concatenated they are the one-call path's zero-padded array, and the dropped samples are noted the same way."""
+    from types import SimpleNamespace
+    from tcresnet_amd.audio_input import Recordings
     from tcresnet_amd.datasets.augmentation_factory import read_wav_pcm16
-    from tcresnet_amd.scan_audio import wav_chunks, whole_step_lengths
     rng = np.random.RandomState(60)
     pcm = [rng.randint(-32768, 32767, n).astype(np.int16) for n in (33333, 1000, 12800, 0)]
     wavs = [str(tmp_path / f"{i}.wav") for i in range(len(pcm))]
@@ -205,14 +206,21 @@ def test_wav_chunks_read_what_the_one_call_path_pads(tmp_path):
     want = np.zeros((len(wavs), max(len(a) for a in audio)), np.float32)
     for s, a in enumerate(audio):
         want[s, :len(a)] = a
-    assert whole_step_lengths(wavs, step) == [len(a) for a in audio]
+    # a detector's side of the reader: its step, rate and device (16 kHz files: no resampler, so no library)
+    det = SimpleNamespace(step_samples=step, frontend=SimpleNamespace(cfg=SimpleNamespace(sample_rate=16000)), device=torch.device("cpu"), lib=None)
+    rec = Recordings(wavs, det)
+    assert rec.lengths == [len(a) for a in audio] and rec.n_steps == want.shape[1] // step
+    assert capsys.readouterr().err.splitlines() == [f"{w}: dropping the last {len(x) % step} samples (not a whole step of {step})"
+                                                    for w, x in zip(wavs, pcm) if len(x) % step]
+    whole = list(rec.chunks())                                               # the one-call path: one chunk of every step
+    assert len(whole) == 1 and whole[0][0] == 0 and np.array_equal(whole[0][1].numpy(), want)
     for sec in (0.1, 0.5, 1.0, 100.0):
-        parts = list(wav_chunks(wavs, step, sec, 16000))
+        parts = list(rec.chunks(sec))
         assert [i0 for i0, _ in parts] == [i * max(1, int(sec * 16000) // step) for i in range(len(parts))]
-        assert all(h.shape[1] % step == 0 for _, h in parts)
-        assert np.array_equal(np.concatenate([h for _, h in parts], axis=1), want)
+        assert all(h.shape[1] % step == 0 and h.dtype == torch.float32 for _, h in parts)
+        assert np.array_equal(np.concatenate([h.numpy() for _, h in parts], axis=1), want)
     with pytest.raises(SystemExit, match="shorter than one step"):
-        list(wav_chunks(wavs, step, 0.01, 16000))
+        list(rec.chunks(0.01))
 
 
 # ---- MI355X ---------------------------------------------------------------------------------------------------------------------
