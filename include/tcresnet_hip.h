@@ -576,7 +576,7 @@ const char* tcr_kernel_name(int index);
 enum { TCR_TUNE_CONV_PATH = 0,   /* 0 auto: implicit-GEMM MFMA conv where the shape fits, 1: scalar-fed VALU conv, 2: as 0 */
        TCR_TUNE_FRONTEND = 1,    /* 0 / 5: packed-FP32 kernel (default); 1..4: scalar-FP32 kernel, variant (v-1): bit0 wave-local phase ordering, bit1 sample prefetch */
        TCR_TUNE_CONV_B = 2,      /* MFMA conv activations: 0 straight from global/L1 (default), 1 via an LDS image; 3: wide 1x1 convs on the register-fed kernel instead of the LDS-tiled one, DS-CNN conv_1 not fused with the first depthwise layer */
-       TCR_TUNE_NET_FUSED = 3,   /* eval forward: 0 one fused LDS-resident kernel for the whole net (default; layers of the flagship shapes run compile-time-specialised), 1 per-layer kernels, 2 fused with the features copied to LDS, 3 fused, generic layer walk only, 4 the round-2 static-shape layer, 5 the static kernel with four 16-position tiles per job in block 0's layers instead of two (round 5 experiment: bitwise, no faster), 7 fused without the bank-aligned utterance strides (A/B arm); the static kernels' nine-tap layers (round 6): 0 work dealt in 16-position units, as even over the waves as units allow, + a whole tap of weight lookahead in the layers of <= 32 input channels (TCResNet14-1.5: <= 48) (default), 8 jobs of two tiles dealt round-robin (rounds 3-5), 9 units without the lookahead (all bitwise) */
+       TCR_TUNE_NET_FUSED = 3,   /* eval forward: 0 one fused LDS-resident kernel for the whole net (default; layers of the flagship shapes run compile-time-specialised), 1 per-layer kernels, 2 fused with the features copied to LDS, 3 fused, generic layer walk only, 4 the round-2 static-shape layer, 5 the static kernel with four 16-position tiles per job in block 0's layers instead of two (round 5 experiment: bitwise, no faster), 7 fused without the bank-aligned utterance strides (A/B arm); the static kernels' nine-tap layers (round 6): 0 work dealt in 16-position units, as even over the waves as units allow, + a whole tap of weight lookahead in the layers of <= 32 input channels (TCResNet14-1.5: <= 48) (default), 8 jobs of two tiles dealt round-robin (rounds 3-5), 9 units without the lookahead; TCResNet8-1.0's kernel, conv0_1 (block 0's nine-tap layer of 24 input channels): 0 a row tile's whole weight set resident in registers across a wave's run of units, requested in front of the phase's barrier (default at 49 frames), 10 the round-6 walk (default at 98 frames, where the resident form measured no faster), 11 the resident walk at either frame count (all bitwise) */
        TCR_TUNE_FUSED_GROUP = 4, /* utterances per workgroup group of the fused kernel (0: largest that fits 64 KB of LDS) */
        TCR_TUNE_FUSED_WAVES = 5, /* fused kernel: waves per workgroup (4, 8, 16) + 100 * weight-ring depth (4, 8, 16); 0: default */
        TCR_TUNE_CONV_KSPLIT = 6, /* train-mode conv / data-gradient: waves sharing one 32-position group's reduction (0 auto, 1, 2, 4) */
@@ -609,6 +609,11 @@ enum { TCR_TUNE_CONV_PATH = 0,   /* 0 auto: implicit-GEMM MFMA conv where the sh
        TCR_TUNE_WGRAD_PIPE = 33, /* 16-byte-load filter gradients (conv_wgrad_mfma4_kernel): 0 software-pipelined -- the operands of a wave's NEXT trip (the next 16 / 8 positions, or the next utterance's first) are requested before the current trip's MFMAs, two register sets alternating (round 6; bitwise the old kernel: same trips, same order; default), 1 every trip loads, waits, multiplies (rounds 3-5) */
        TCR_TUNE_COUNT = 34 };
 int tcr_tune(int knob, int value);
+
+/* Host-side view of how the fused eval kernel's resident-weight layers deal their work (no launch): the run of wave `wave` of `nw` in a
+ * layer of `nrt` row tiles (16 output channels) x `nt16` column tiles (16 positions).  out3 = {row tile, first column, end column}: the
+ * wave's units are (row tile, c) for first <= c < end, all in ONE row tile.  0, or -1 on bad arguments (nw not a multiple of nrt). */
+int tcr_fused_deal_run(int nrt, int nt16, int nw, int wave, int* out3);
 
 /* The library's internal streams (hipStream_t), one set per device and process.  HIP multiplexes streams onto a few hardware queues
  * and streams that share a queue serialise; the set is chosen on first use -- candidates are probed -- so that streams 0, 1, 2 and

@@ -492,6 +492,115 @@ __device__ __forceinline__ void fused_layer_u(const FusedArgs& a, const FusedLay
     }
 }
 
+// Resident weights for a nine-tap layer of <= 24 input channels (TCResNet8's conv0_1, 24 -> 24).  In fused_layer_u a wave walks its 3 - 4
+// units as ~2 jobs and every job's nine taps each start with weight loads from L2 that the tap's MFMAs wait for: ~18 dependent round trips
+// per wave and phase.  All units of a wave that lie in one 16-channel row tile use the SAME K x CIN / 4 fragments (54 registers), so here
+// the wave requests that set ONCE -- in front of the barrier that precedes the phase, where it holds no job state (fused_resident_request)
+// -- and walks a run of units dealt inside one row tile (fused_deal_run, kernels.h) out of those registers; only the LDS operands (one
+// tap ahead) are read per unit.  Per output tile the MFMA sequence is the one of fused_job_s (taps outer, channel quads inner, same
+// fragments): bitwise.  The barrier in front of the phase is __syncthreads(), whose fence waits for the request (vmcnt(0)): one round
+// trip per phase, shared with the wait for the slowest wave.  Phase stamps (OPTLOG "Resident weights"): conv0_1 35.6 -> 29.6 k cycles per
+// group, what the phase takes with its weight refills removed (28.2 k); requested BEHIND the barrier the gain is gone (35.3 k).  conv0_0
+// (16 -> 24) in this form gains nothing (as its no-refill what-if said) and its request lengthens the first conv's phase: not used there.
+template <int NW, int K, int CIN, int COUT>
+__device__ __forceinline__ void fused_resident_request(const FusedArgs& a, const FusedLayer& L, const int wave, const int r_in, const int q_in,
+                                                       float (&ws)[K * (CIN / 4)]) {
+    constexpr int NRT = (COUT + 15) / 16, C4 = CIN / 4, WSTEP = 4 * COUT;
+    static_assert(NW % NRT == 0, "the waves split evenly over the row tiles");
+    const int oz = opaque_zero();          // (keeps the request inside the group loop: hoisted, the set would live through every layer)
+    const int r = r_in + oz, q = q_in + oz;
+    const int m = wave / (NW / NRT);       // this wave's row tile (fused_deal_run); requested whether or not its run is empty
+    const buf_rsrc wr = make_rsrc(a.params + L.w_off);
+    const unsigned wl = (unsigned)(q * COUT + min(m * 16 + r, COUT - 1)) * 4u;
+#pragma unroll
+    for (int i = 0; i < K * C4; ++i) ws[i] = buf_load_f32(wr, wl, (unsigned)(i * WSTEP) * 4u);      // i = tap * C4 + channel quad
+}
+
+template <int NW, int K, int S, int CIN, int COUT, int TIN, bool HAS_RES>
+__device__ __forceinline__ void fused_layer_r(const FusedArgs& a, const FusedLayer& L, const float* __restrict__ xin, const int in_sz,
+                                              float* lds, const int ng, const int wave, const int r_in, const int q_in,
+                                              const float (&ws)[K * (CIN / 4)]) {
+    const int oz = opaque_zero();
+    const int r = r_in + oz, q = q_in + oz;
+    constexpr int TOUT = (TIN + S - 1) / S;
+    constexpr int NRT = (COUT + 15) / 16;
+    constexpr bool IL = S == 1;
+    constexpr int PADT = ((TOUT - 1) * S + K - TIN) > 0 ? ((TOUT - 1) * S + K - TIN) : 0;
+    constexpr int PADLO = PADT / 2;
+    constexpr int TPI = TIN + 2 * kHalo, TPO = TOUT + 2 * kHalo;
+    constexpr int C4 = CIN / 4, XSTEP = 4 * TPI;
+    float* yout = lds + a.buf_off[L.out_buf];
+    const float* res = L.res_buf >= 0 ? lds + a.buf_off[L.res_buf] : nullptr;
+    const int out_sz = L.out_sz;
+    const int res_sz = L.res_sz;
+    const int npos = ng * TOUT;
+    const int full = npos >> 5, rem = npos & 31;
+    const int nt16 = IL ? 2 * full + (rem == 0 ? 0 : (rem <= 16 ? 1 : 2)) : (npos + 15) >> 4;          // (tiles and columns: as fused_layer_u)
+    const int il_end = (IL && rem > 0 && rem <= 16) ? 2 * full : nt16;
+    const FusedRun run = fused_deal_run(NRT, nt16, NW, wave);
+    const int m = run.m;
+    const float* scale = a.ss + L.ss_off;
+    const float* shift = scale + L.c_pad;
+    float sc[4], sh[4];
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+        const int co = min(m * 16 + q * 4 + reg, COUT - 1);
+        sc[reg] = scale[co];
+        sh[reg] = shift[co];
+    }
+    // this lane's position in column tile c -> (utterance of the group, frame); computed twice per unit, in front of the taps for the operand
+    // address and again behind them for the stores, so that nothing but the address is live across the 9 x C4 MFMAs (the 128-register budget)
+    auto place = [&](const int c, const int rr, int& g, int& t) {
+        const int cc = (IL && c < il_end) ? (c >> 1) * 32 + 2 * rr + (c & 1) : (IL ? full * 32 + rr : c * 16 + rr);
+        const int p = min(cc, npos - 1);
+        g = p / TOUT;
+        t = p - g * TOUT;
+        return cc < npos;
+    };
+    for (int c = run.c0; c < run.c1; ++c) {
+        int g, t;
+        place(c, r, g, t);
+        const float* xp = xin + g * in_sz + q * TPI + t * S + kHalo - PADLO;
+        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+        // LDS operands: one register per channel quad, refilled for the next tap as soon as its MFMA has issued (a tap = C4 MFMAs of lookahead)
+        float b[C4];
+#pragma unroll
+        for (int c4 = 0; c4 < C4; ++c4) b[c4] = xp[c4 * XSTEP];
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+#pragma unroll
+            for (int c4 = 0; c4 < C4; ++c4) {
+                acc = TCR_MFMA(ws[j * C4 + c4], b[c4], acc);
+                if (j + 1 < K) b[c4] = xp[c4 * XSTEP + (TCR_WHATIF(4) ? 0 : j + 1)];
+            }
+        }
+        // ---- epilogue: folded BN (+ shortcut) (+ ReLU) -> LDS rows (as fused_job_s) ----
+        const int oe = opaque_zero_after(acc[0]);
+        const int re = r_in + oe, qe = q_in + oe;
+        const bool pv = place(c, re, g, t);
+        const int dump = a.buf_off[2] + a.group * a.buf_sz[2] + (qe * 16 + re) - a.buf_off[L.out_buf];
+        const float lo = L.relu ? 0.f : -3.4e38f;
+        float rv[4];
+        if (HAS_RES) {
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int co = min(m * 16 + qe * 4 + reg, COUT - 1);
+                rv[reg] = res[g * res_sz + co * TPO + kHalo + t];
+            }
+        }
+        const int base = g * out_sz + kHalo + t;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int co = m * 16 + qe * 4 + reg;
+            float v = fmaf(acc[reg], sc[reg], sh[reg]);
+            if (HAS_RES) v = fmaxf(v + rv[reg], 0.f);       // tc_resnet.py:40-41
+            else v = fmaxf(v, lo);
+            const bool ok = pv && (COUT % 16 == 0 || co < COUT) && !(TCR_WHATIF(32) && v != 12345.f);
+            yout[ok ? base + co * TPO : dump] = v;
+        }
+    }
+}
+
 // First conv of the static-shape kernel (3 x 1, 40 -> 16, stride 1), activations straight from global memory.  In the generic form
 // every K-step's two operand loads were issued ONE MFMA ahead of their use (ISA: `s_waitcnt vmcnt(1)` in front of each MFMA): 30
 // exposed L1 / L2 / HBM latencies per job -- the layer took 25 us of the kernel's 125 (timing what-if, scripts/whatif_net.py) for
@@ -572,13 +681,16 @@ __device__ __forceinline__ void fused_head_s(const FusedArgs& a, float* lds, con
     // wave 0: the weight fragments are requested before the pooling phase (their latency hides behind it)
     float af[FC / 4];
     if (tid < 64) {
-        const int zero = opaque_zero();        // (keeps these loads inside the group loop: hoisted, they would live through every layer)
+        // (the lane geometry behind an opaque zero keeps these loads AND their twelve 64-bit lane addresses inside the group loop: hoisted, the
+        //  addresses lived through every layer -- they were 96 of the kernel's 116 B of scratch per lane, stored at entry, reloaded here)
+        const int zero = opaque_zero();
+        const int rz = r + zero, qz = q + zero;
 #pragma unroll
         for (int s = 0; s < FC / 4; ++s) {
-            const int c = 4 * s + q;
-            const float* src = r < NCLS ? a.params + a.fc_off + c * NCLS + r : a.params + a.fc2_off + c * 2 + min(r - NCLS, 1);
-            const float v = src[zero];
-            af[s] = r < NCLS + 2 ? v : 0.f;
+            const int c = 4 * s + qz;
+            const float* src = rz < NCLS ? a.params + a.fc_off + c * NCLS + rz : a.params + a.fc2_off + c * 2 + min(rz - NCLS, 1);
+            const float v = src[0];
+            af[s] = rz < NCLS + 2 ? v : 0.f;
         }
     }
     for (int i = tid; i < ng * FC; i += NT) {
@@ -750,7 +862,14 @@ __global__ __launch_bounds__(NW * 64) TCR_WAVES_PER_SIMD_4 void net_fused_tc8_ke
     //  so that a SIMD's two waves are not in the shortcut's load / store-bound jobs together: 96.5 vs 95.6 us at 49 frames, 173.9 vs 176.1 at 98.)
     // (tiles per job: two; NTJ0 = 4: four for block 0's layers -- 16 / 24 channels at T0 / 2 frames --, the TCR_TUNE_NET_FUSED = 5 arm)
     // (NTJ0 = 0: the nine-tap layers' work dealt in 16-position units, fused_layer_u)
-#define TCR_TC8(LI, K_, S_, CI_, CO_, T_) fused_layer_sel<NW, K_, S_, CI_, CO_, T_, WD, (LI == 3 || LI == 6 || LI == 9), (K_ != 1 && LI != 9), ((LI >= 1 && LI <= 3 && NTJ0 == 4) ? 4 : (((NTJ0 == 0 || NTJ0 == 3) && K_ == 9) ? NTJ0 : 2))>(a, a.layer[LI], lds + a.buf_off[a.layer[LI].in_buf], a.layer[LI].in_sz, lds, ng, wave, r, q)
+    // (NTJ0 = 6: conv0_1 -- block 0's nine-tap layer of 24 input channels -- in its resident-weight form, fused_layer_r; every other layer as NTJ0 = 3)
+    constexpr bool RES = WD >= 0 && NTJ0 == 6;
+    constexpr int NTJU = RES ? 3 : NTJ0;
+#define TCR_TC8(LI, K_, S_, CI_, CO_, T_) fused_layer_sel<NW, K_, S_, CI_, CO_, T_, WD, (LI == 3 || LI == 6 || LI == 9), (K_ != 1 && LI != 9), ((LI >= 1 && LI <= 3 && NTJU == 4) ? 4 : (((NTJU == 0 || NTJU == 3) && K_ == 9) ? NTJU : 2))>(a, a.layer[LI], lds + a.buf_off[a.layer[LI].in_buf], a.layer[LI].in_sz, lds, ng, wave, r, q)
+    // (resident form of layer LI: halo zeros of its output rows, then the walk out of the set WS_ requested in front of the barrier)
+#define TCR_TC8_R(LI, S_, CI_, T_, WS_) do { \
+        fused_zero_halo<NT, 24, (T_ + S_ - 1) / S_>(lds + a.buf_off[a.layer[LI].out_buf], a.layer[LI].out_sz, ng, tid); \
+        fused_layer_r<NW, 9, S_, CI_, 24, T_, (LI == 3)>(a, a.layer[LI], lds + a.buf_off[a.layer[LI].in_buf], a.layer[LI].in_sz, lds, ng, wave, r, q, WS_); } while (0)
     for (int grp = blockIdx.x; grp < (TCR_WHATIF(512) ? 0 : a.n_groups); grp += gridDim.x) {
         const int n0 = grp * a.group;
         const int ng = min(a.group, a.batch - n0);
@@ -763,12 +882,23 @@ __global__ __launch_bounds__(NW * 64) TCR_WAVES_PER_SIMD_4 void net_fused_tc8_ke
             fused_zero_halo<NT, 16, T0>(lds + a.buf_off[a.layer[0].out_buf], a.layer[0].out_sz, ng, tid);
             fused_conv0_s<NW, T0>(a, a.layer[0], a.feat + (size_t)n0 * row, row, lds, ng, wave, r, q);
         }
+        if constexpr (RES) {
+            float ws3[9 * 6];
+            TCR_TC8_BARRIER;
+            TCR_TC8(1, 1, 2, 16, 24, T0);
+            TCR_TC8(2, 9, 2, 16, 24, T0);
+            fused_resident_request<NW, 9, 24, 24>(a, a.layer[3], wave, r, q, ws3);      // (no job state is live here: the set costs no register of the budget)
+            TCR_TC8_BARRIER;
+            TCR_TC8_R(3, 1, 24, T1, ws3);
+            TCR_TC8_BARRIER;
+        } else {
         TCR_TC8_BARRIER;
         TCR_TC8(1, 1, 2, 16, 24, T0);           // block0/down (reads the same rows as conv0_0: no barrier in between)
         TCR_TC8(2, 9, 2, 16, 24, T0);
         TCR_TC8_BARRIER;
         TCR_TC8(3, 9, 1, 24, 24, T1);
         TCR_TC8_BARRIER;
+        }
         TCR_TC8(4, 1, 2, 24, 32, T1);
         TCR_TC8(5, 9, 2, 24, 32, T1);
         TCR_TC8_BARRIER;
@@ -792,6 +922,7 @@ __global__ __launch_bounds__(NW * 64) TCR_WAVES_PER_SIMD_4 void net_fused_tc8_ke
 #endif
     }
 #undef TCR_TC8
+#undef TCR_TC8_R
 #undef TCR_TC8_BARRIER
 }
 
@@ -1206,7 +1337,12 @@ int launch_net_fused(const FusedArgs& a, size_t lds_bytes, int grid, int waves, 
     const bool j2 = tune_get(TCR_TUNE_NET_FUSED) == 8;
     const bool ju = tune_get(TCR_TUNE_NET_FUSED) == 9;
     const bool j4 = tune_get(TCR_TUNE_NET_FUSED) == 5;         // 5: four 16-position tiles per job in block 0's layers (A/B arm, bitwise; measured 103.6 vs 103.2 us at 49 frames, 184.9 vs 181.2 at 98: no gain)
-#define TCR_FS(NW_, T_) if (tc8 == T_ && waves == NW_) kern = r2 ? net_fused_tc8_kernel<NW_, T_, -1> : (j4 ? net_fused_tc8_kernel<NW_, T_, 0, 4> : (ju ? net_fused_tc8_kernel<NW_, T_, 0, 0> : (j2 ? net_fused_tc8_kernel<NW_, T_, 0, 2> : net_fused_tc8_kernel<NW_, T_, 0, 3>)));
+    // conv0_1's weights resident in registers across a wave's run of units (fused_layer_r): the default at 49 frames (kernel alone 107.4 - 108.5 ->
+    // 106.0 - 106.3 us); at 98 frames it measured no faster (186.5 - 188.1 against 185.7 - 186.1 us) and the round-6 walk stays.  A/B arms (bitwise):
+    // 10 the round-6 walk (a tap of weight lookahead per job) in that layer too, 11 the resident walk at either frame count.
+    const bool jl = tune_get(TCR_TUNE_NET_FUSED) == 10;
+    const bool jr = tune_get(TCR_TUNE_NET_FUSED) == 11;
+#define TCR_FS(NW_, T_) if (tc8 == T_ && waves == NW_) kern = r2 ? net_fused_tc8_kernel<NW_, T_, -1> : (j4 ? net_fused_tc8_kernel<NW_, T_, 0, 4> : (ju ? net_fused_tc8_kernel<NW_, T_, 0, 0> : (j2 ? net_fused_tc8_kernel<NW_, T_, 0, 2> : ((jr || (T_ == 49 && !jl)) ? net_fused_tc8_kernel<NW_, T_, 0, 6> : net_fused_tc8_kernel<NW_, T_, 0, 3>))));
     TCR_FS(4, 49) TCR_FS(8, 49) TCR_FS(16, 49) TCR_FS(4, 98) TCR_FS(8, 98) TCR_FS(16, 98)
 #undef TCR_FS
     const int tc14 = (kern || tune_get(TCR_TUNE_NET_FUSED) == 3 || tune_get(TCR_TUNE_NET_FUSED) == 4) ? 0 : fused_tc14w_frames(a);
@@ -1229,3 +1365,13 @@ int launch_net_fused(const FusedArgs& a, size_t lds_bytes, int grid, int waves, 
 }
 
 }  // namespace tcr
+
+extern "C" int tcr_fused_deal_run(int nrt, int nt16, int nw, int wave, int* out3) {
+    if (!out3 || nrt < 1 || nt16 < 0 || nw < nrt || nw % nrt != 0 || wave < 0 || wave >= nw) {
+        tcr::set_error("tcr_fused_deal_run: bad arguments (%d row tiles, %d column tiles, wave %d of %d)", nrt, nt16, wave, nw);
+        return TCR_ERR_ARG;
+    }
+    const tcr::FusedRun run = tcr::fused_deal_run(nrt, nt16, nw, wave);
+    out3[0] = run.m; out3[1] = run.c0; out3[2] = run.c1;
+    return TCR_OK;
+}

@@ -201,6 +201,20 @@ struct FusedArgs {
     FusedLayer layer[kFusedMaxLayers];
 };
 
+// Deal of a layer's units (16 output channels x 16 positions; row tile m, column c, u = m * nt16 + c) for the resident-weight walk
+// (fused_layer_r): a wave keeps ONE row tile's weight fragments in registers, so its run [c0, c1) lies inside one row tile m.  The nw
+// waves are split evenly over the nrt row tiles (nw % nrt == 0) and a tile's columns go to its nw / nrt waves as evenly as they divide;
+// the waves that take one column more are rotated from tile to tile, so that the SIMDs (waves w, w + 4, ...) stay within one unit.
+struct FusedRun { int m, c0, c1; };
+__host__ __device__ inline FusedRun fused_deal_run(const int nrt, const int nt16, const int nw, const int wave) {
+    const int wpt = nw / nrt;
+    const int m = wave / wpt, l = wave - m * wpt;
+    const int per = nt16 / wpt, extra = nt16 - per * wpt;
+    const int rank = (l + wpt - (m * extra) % wpt) % wpt;
+    const int c0 = rank * per + (rank < extra ? rank : extra);
+    return FusedRun{m, c0, c0 + per + (rank < extra ? 1 : 0)};
+}
+
 constexpr int kSmallBatchMax = 64;      // batches up to this many utterances take the small-batch (latency) kernel where it exists
 // returns 1 when the launch could not be configured (caller falls back to the per-layer kernels)
 int launch_net_fused(const FusedArgs& a, size_t lds_bytes, int grid, int waves, int ring, hipStream_t s);
