@@ -531,6 +531,45 @@ int tcr_detect_sweep(int n_signals, int64_t steps, int num_classes, const int32_
                      const int32_t* event_label, int32_t* detections, int32_t* hits, int32_t* duplicates,
                      uint8_t* fired, void* stream);
 
+/* Ragged scanning: tcr_scan_m over N signals of different lengths in one call, packed one after the other.  Signal n is
+ * samples[sample_offsets[n] .. sample_offsets[n + 1]) (float32, device); sample_offsets is a HOST array [N + 1] that starts at 0
+ * and does not decrease, every length a multiple of k * hop (0 allowed: a signal without steps has no rows).  Step i of signal n is
+ * packed row sample_offsets[n] / (k * hop) + i of logits / probs / smoothed [total_steps][num_classes] and top / score / is_new
+ * [total_steps] (all positions int64).  Contract: signal n's rows are bitwise what tcr_scan_m returns for that signal alone
+ * (n_signals = 1; the same cfg, model, k and det; a fresh start from one clip of silence) -- whatever the workspace's size, the
+ * group size the call picks and the other signals of the call.  The smoothing of a signal's first steps and its suppression walk
+ * never read another signal's rows.  The model is a tcr_model_ref of any family (TC-ResNet: TCR_FAMILY_TCRESNET with aux =
+ * frozen_ss), so there is one entry.
+ * Workspace: tcr_scan_ragged_workspace_bytes = the offset tables of max_signals signals (2 (max_signals + 1) int64, rounded up to
+ * 256 bytes: step and group offsets, uploaded by the call) + tcr_scan_workspace_bytes_m(cfg, model, k, max_windows).  The call
+ * places the tables of its n_signals at the front and runs the largest chunks the rest holds, so max_signals and max_windows only
+ * size the bytes.  The tables are copied from the host on `stream` and the call waits for that copy before it launches (the stream's
+ * earlier work included): sample_offsets may be freed when it returns; the call cannot be captured into a graph.  Everything else is
+ * enqueued on `stream`.
+ * Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched): null arguments, n_signals <= 0, more signals than the workspace's
+ * tables hold, sample_offsets[0] != 0, decreasing offsets, a length that is not a multiple of k * hop, total_steps == 0,
+ * total_steps x num_classes >= 2^31, and everything tcr_scan_m refuses, with its messages.  TCR_ERR_WORKSPACE when the bytes behind
+ * the tables are below one window. */
+size_t tcr_scan_ragged_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_model_ref* model, int k, int max_windows,
+                                       int max_signals);
+int tcr_scan_ragged(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_signals,
+                    const int64_t* sample_offsets /* HOST [N + 1] */, int k, const tcr_detect_cfg* det,
+                    const float* samples /* device, packed */, void* workspace, size_t ws_bytes, float* logits, float* probs,
+                    float* smoothed /* [total_steps][C] */, int32_t* top, float* score, int32_t* is_new /* [total_steps] */,
+                    void* stream);
+
+/* tcr_detect_sweep over a ragged scan: top / score are packed [total_steps] and signal n's steps are rows step_offsets[n] ..
+ * step_offsets[n + 1] - 1 (DEVICE int64 [N + 1], from 0, non-decreasing: a precondition, the host does not read it).  The rule is
+ * tcr_detect_sweep's, walked over each signal's own rows from prev_label = -1; events stay CSR per signal, in steps relative to the
+ * signal's first step.  For every n and t the counts equal tcr_detect_sweep on the zero-padded dense layout with valid_steps[n] =
+ * the signal's steps.  fired uint8 [T][total_steps] (NULL: not written) is zeroed and set by the kernel.  Refusals: those of
+ * tcr_detect_sweep that do not need the step counts, and a null step_offsets. */
+int tcr_detect_sweep_ragged(int n_signals, const int64_t* step_offsets /* DEVICE [N + 1] */, int num_classes, const int32_t* top,
+                            const float* score, int32_t suppression_steps, int n_thresholds, const float* thresholds,
+                            const int32_t* event_offsets, const int64_t* event_first, const int64_t* event_last,
+                            const int32_t* event_label, int32_t* detections, int32_t* hits, int32_t* duplicates,
+                            uint8_t* fired /* [T][total_steps] or NULL */, void* stream);
+
 /* Sample-rate conversion: a rational-ratio polyphase FIR in front of the detectors (which take float32 at the model's rate).
  * in_rate -> out_rate, g = gcd: up = L = out_rate / g, down = M = in_rate / g; taps = P per phase (even, or 1); table float32
  * [up][taps], designed on the host (tcresnet_amd.resampling.design_table: windowed sinc, fc = rolloff / max(1, M / L), Kaiser

@@ -101,6 +101,26 @@ class Recordings:
             yield i0, buf
 
 
+    def packed(self) -> Tuple[torch.Tensor, List[int]]:
+        """(float32 1-D on det's device, lengths): the files one after the other, each at its own whole-step length -- what
+        `KeywordScanner.scan_ragged` takes.  A file's samples are the columns `chunks()` yields for it, bitwise: decoded on the host at
+        the model's rate, converted on the device by the same `Resampler` calls at another."""
+        dev = self.det.device
+        buf = torch.zeros(sum(self.lengths), dtype=torch.float32, device=dev)
+        at = 0
+        for f, keep in zip(self.files, self.lengths):
+            if keep == 0:
+                continue
+            if f.rate == self.rate:
+                buf[at:at + keep] = torch.from_numpy(f.read_pcm(0, keep).astype(np.float32) * (1.0 / 32768.0)).to(dev)
+            else:
+                rs = self.resampler(f.rate)
+                first, n = rs.span(0, keep)
+                rs.convert(torch.from_numpy(f.read_pcm(first, n)[None, :]).to(dev), first, 0, keep, out=buf[at:at + keep].unsqueeze(0))
+            at += keep
+        return buf, list(self.lengths)
+
+
 def format_time_ms(ms: float) -> str:
     return f"{round(ms, 3):g}"
 
@@ -117,6 +137,21 @@ def print_detections(rec: Recordings, out, i0: int, names: List[str], counts: Di
         name = names[top[s, i]]
         counts[name] = counts.get(name, 0) + 1
         print(f"{rec.paths[s]},{format_time_ms(1000.0 * (i0 + i + 1) * rec.step / rec.rate)},{name},{float(score[s, i]):.6f}", flush=True)
+
+
+def print_detections_ragged(rec: Recordings, out, names: List[str], counts: Dict[str, int]) -> None:
+    """`print_detections` for a scanning.RaggedScanOutput over rec's files: the same lines in the same order (step order, then file
+    order); a file has no steps past its own end, so none is printed there."""
+    fired = np.flatnonzero(out.is_new.cpu().numpy())
+    if not fired.size:
+        return
+    top, score = out.top.cpu().numpy(), out.score.cpu().numpy()
+    s = np.searchsorted(out.offsets, fired, side="right") - 1
+    i = fired - out.offsets[s]
+    for o in np.lexsort((s, i)):
+        name = names[top[fired[o]]]
+        counts[name] = counts.get(name, 0) + 1
+        print(f"{rec.paths[s[o]]},{format_time_ms(1000.0 * (int(i[o]) + 1) * rec.step / rec.rate)},{name},{float(score[fired[o]]):.6f}", flush=True)
 
 
 def summary_line(rec: Recordings, counts: Dict[str, int]) -> str:
@@ -140,6 +175,8 @@ def add_detector_flags(p, each: str = "signal", threshold: bool = True, offline:
     if offline:
         p.add_argument("--max_windows", type=int, default=None, help="windows per network launch (the workspace's size)")
         p.add_argument("--chunk_seconds", type=float, default=None, help="read and scan the files this many seconds at a time")
+        p.add_argument("--ragged", action="store_true",
+                       help="scan every file at its own length in one ragged call (KeywordScanner.scan_ragged): no padding to the longest")
 
 
 def detector_settings(args) -> dict:
@@ -151,6 +188,8 @@ def detector_settings(args) -> dict:
 def open_detector(model, args):
     """(detector, its call on one chunk): a KeywordScanner and `scan` for the one-call run, which allocates no stream state; with
     --chunk_seconds a StreamingDetector over the files and `push_many`, which carries the state from chunk to chunk."""
+    if getattr(args, "ragged", False) and args.chunk_seconds is not None:
+        raise SystemExit("--ragged scans the whole files in one call: it cannot be combined with --chunk_seconds")
     if args.chunk_seconds is None:
         det = model.scanner(**detector_settings(args))
         return det, det.scan

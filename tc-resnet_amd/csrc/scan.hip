@@ -31,14 +31,27 @@
 //                         smoothing has read the old ones), the detections in step order from the carried prev_label and
 //                         prev_step - n0, rewritten into is_new, then the five detector integers.
 //
+// Ragged (tcr_scan_ragged): N fresh signals of different lengths, packed.  The same stages, with two prefix tables in place of
+// q / groups and n steps + i: step_off [N + 1] (signal n's steps are packed rows step_off[n] ..) and, once G is chosen, group_off
+// [N + 1] (its ceil(steps_n / G) groups are flattened rows group_off[n] ..); the host builds both and uploads them to the front of
+// the workspace, and the kernels find the signal of a flattened group or a packed step by binary search (ragged_signal).  A signal's
+// groups cover its steps in order, so a chunk's live steps are one contiguous range of packed steps: the gather writes them
+// compactly (slot = p - p(q0)), the network runs at the batch of the live steps and writes their rows of the caller's logits /
+// probs itself -- no scatter, and the dead slots of a short last group cost front-end frames only.  The smoothing counts from the
+// signal's first row and the suppression walks the signal's own rows, so a signal's rows are bitwise its dense scan alone.  G is
+// the group size with the fewest front-end frames over the call (scan_ragged_chunking).  The ragged arms are compile-time instances
+// (RAGGED) or sibling kernels: the dense instances carry no test for them.
+//
 // Workspace (tcr_scan_workspace_bytes), regions 256-byte aligned:
 //   staging [R][stage_stride] | frame rows [R][n_coef][F + 8] | windows [R G][n_coef][Tp] (2-D graph: planes [R G][T n_coef + 8])
 //   | logits, probs [R G][C] | network at R G.
-// It does not depend on the signals' length; R and G are derived from the bytes the caller passes.
+// It does not depend on the signals' length; R and G are derived from the bytes the caller passes.  tcr_scan_ragged_workspace_bytes
+// puts the tables [2][max_signals + 1] int64 (rounded up to 256 bytes) in front of it.
 //
 // Compiled as part of frontend_pk3.hip's translation unit (included at its end, after stream.hip).
 #pragma once
 #include <algorithm>
+#include <vector>
 
 #include "frontend_plan.h"
 #include "frontend_args.h"
@@ -108,7 +121,25 @@ struct ScanChunkArgs {
     int64_t L, stride, q0, rows, groups, steps, n_prefix, k_hop;
     int64_t s0;                 // scan_carry_kernel: the first stream whose last group is in the chunk
     int G, k, T, tp, n_coef, ftp;
+    // ragged (tcr_scan_ragged): the prefix tables, and the packed step of the chunk's first slot
+    const int64_t* step_off;    // [N + 1]: signal n's steps are packed rows step_off[n] .. step_off[n + 1] - 1
+    const int64_t* group_off;   // [N + 1]: its groups are flattened rows group_off[n] .. group_off[n + 1] - 1
+    int64_t p0;
+    int n_sig;
 };
+
+// Ragged index mapping: the signal of packed step (or flattened group) v < off[N] is the last n with off[n] <= v -- a signal without
+// steps shares its successor's offset and is never the answer.  A binary search over the table, log2 N reads that every lane of a
+// wave shares (the table of a whole evaluation corpus stays in L2).
+__device__ __forceinline__ int ragged_signal(const int64_t* off, int n_sig, int64_t v) {
+    int lo = 0, hi = n_sig - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= v) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
 
 // Staging row r = group q0 + r: x from new frame g G k + k - T on, i.e. from sample (g G + 1) k hop of  zeros(n_prefix) ++ signal ++
 // zeros  (n_prefix = the clip's n_samples = T hop + tail_len), with the stream's tail in the last tail_len samples of the prefix.
@@ -129,16 +160,47 @@ __global__ __launch_bounds__(256) void scan_stage_kernel(const ScanChunkArgs a) 
     }
 }
 
+// The ragged staging row: bx workgroups per row, so that the row's signal is looked up once per thread and not once per sample.
+// Signal n's samples start at step_off[n] k hop of the packed buffer and it is fresh: zeros in front and behind.
+__global__ __launch_bounds__(256) void scan_stage_ragged_kernel(const ScanChunkArgs a, const int bx) {
+    const int64_t r = blockIdx.x / (unsigned)bx;
+    const int part = (int)(blockIdx.x - (unsigned)r * bx);
+    const int64_t q = a.q0 + r;
+    const int n = ragged_signal(a.group_off, a.n_sig, q);
+    const int64_t g = q - a.group_off[n];
+    const int64_t first = a.step_off[n], len = (a.step_off[n + 1] - first) * a.k_hop;
+    const float* src = a.samples + first * a.k_hop;
+    const int64_t base = (g * a.G + 1) * a.k_hop - a.n_prefix;
+    float* dst = a.stage + r * a.stride;
+    for (int64_t x = (int64_t)part * 256 + threadIdx.x; x < a.stride; x += (int64_t)bx * 256) {
+        const int64_t pos = base + x;
+        dst[x] = pos >= 0 && pos < len ? src[pos] : 0.f;
+    }
+}
+
 // One workgroup per window slot b = r G + j (step i = g G + j): column t is column j k + t of frame row r when new frame
 // (i + 1) k - T + t >= 0 or the signal is fresh, else column (i + 1) k + t of the carried window; the halo is zero.  PLANES (2-D
 // graph): the same window as its [T x n_coef] plane, written in plane order (coalesced): plane offset t n_coef + c <- window column t,
 // coefficient c (features_to_plane_kernel's map, net2d_kernels.hip).  A pure copy: bitwise the planar gather followed by
 // features_to_plane_kernel.  CARRIED: the call has a state; without one no column is carried, and the instance is the plain copy
-// (the test at run time cost tcr_scan 5 % of this kernel, profiles/scan_unify_kernel_stats.csv).
-template <bool PLANES, bool CARRIED>
+// (the test at run time cost tcr_scan 5 % of this kernel, profiles/scan_unify_kernel_stats.csv).  RAGGED: the windows are compact --
+// slot b is packed step p0 + b, whose signal, step, group and frame row come from the prefix tables -- so the chunk's slots are
+// its live steps only and the network writes their rows of the caller's outputs itself.
+template <bool PLANES, bool CARRIED, bool RAGGED = false>
 __global__ __launch_bounds__(256) void scan_gather_kernel(const ScanChunkArgs a) {
+    static_assert(!(CARRIED && RAGGED), "ragged signals are fresh");
     const int b = blockIdx.x;
-    const int r = b / a.G, j = b - r * a.G;
+    int r, j;
+    if constexpr (RAGGED) {
+        const int64_t p = a.p0 + b;
+        const int n = ragged_signal(a.step_off, a.n_sig, p);
+        const int64_t i = p - a.step_off[n], g = i / a.G;
+        j = (int)(i - g * a.G);
+        r = (int)(a.group_off[n] + g - a.q0);
+    } else {
+        r = b / a.G;
+        j = b - r * a.G;
+    }
     const float* src = a.frames + (size_t)r * a.n_coef * a.ftp + j * a.k;      // window column x <- frame-row column j k + x
     const float* old = src;                                                     // (not read while sh = T)
     int sh = a.T;                                                               // carried columns: t < T - sh
@@ -240,30 +302,42 @@ struct ScanDetectArgs {
     int64_t steps;
     int N, C, W, min_count, suppression;
     float threshold;
+    const int64_t* step_off;    // ragged: [N + 1] (the rows are packed, `steps` is their total)
 };
 
 // A lane per (signal, step, class), 256 / C steps per workgroup: the streaming detector's smoothing over the last
 // count = min(count0 + i + 1, W) probability vectors (smooth_mean, stream.hip: the same expression), those of steps before the call
 // from ring slot (head0 + j) mod W (j < 0, oldest first); the argmax from LDS by the step's first lane, top / score (-1 / 0 below
 // min_count) and the candidate flag.  Consecutive lanes read consecutive floats.  CARRIED: the call has a state; without one the
-// ring is never read, and the instance has no test for it (at run time it doubled this kernel's time for tcr_scan).
-template <bool CARRIED>
+// ring is never read, and the instance has no test for it (at run time it doubled this kernel's time for tcr_scan).  RAGGED: w is
+// a packed step; i is relative to its signal's first row, so count = min(i + 1, W) never reaches the previous signal's rows.
+template <bool CARRIED, bool RAGGED = false>
 __global__ __launch_bounds__(256) void scan_smooth_kernel(const ScanDetectArgs a) {
+    static_assert(!(CARRIED && RAGGED), "ragged signals are fresh");
     __shared__ float s_sm[256];
     const int C = a.C, W = a.W;
     const int per = 256 / C;
     const int ls = threadIdx.x / C, c = threadIdx.x - ls * C;
     const int64_t w = (int64_t)blockIdx.x * per + ls;                   // window = s steps + i
-    const bool live = ls < per && w < a.N * a.steps;
+    const bool live = ls < per && w < (RAGGED ? a.steps : a.N * a.steps);
     int count = 0;
     if (live) {
-        const int64_t s = w / a.steps, i = w - s * a.steps;
+        int64_t s, i, row0;
+        if constexpr (RAGGED) {
+            s = ragged_signal(a.step_off, a.N, w);
+            row0 = a.step_off[s];
+            i = w - row0;
+        } else {
+            s = w / a.steps;
+            i = w - s * a.steps;
+            row0 = s * a.steps;
+        }
         const bool fresh = !CARRIED || scan_fresh(a.st, s);
         const int head0 = fresh ? 0 : a.st.ist[s], count0 = fresh ? 0 : a.st.ist[a.N + s];
         count = count0 + i + 1 < W ? (int)(count0 + i + 1) : W;
         int64_t jj = i - count + 1;                                     // oldest step (< 0: before the call)
         int slot = jj < 0 ? (head0 + (int)jj < 0 ? head0 + (int)jj + W : head0 + (int)jj) : 0;
-        const float* p = a.probs + s * a.steps * C + c;
+        const float* p = a.probs + row0 * C + c;
         const size_t ring_row = (size_t)a.N * C, sc = (size_t)s * C + c;
         const float v = smooth_mean(count, [&]() {
             float x;
@@ -299,7 +373,9 @@ __global__ __launch_bounds__(256) void scan_smooth_kernel(const ScanDetectArgs a
 // suppression), so after a detection the walk jumps past the suppressed steps, and from there the first candidate whose label differs
 // from prev_label fires -- 256 steps per probe (four per lane, the lowest index by a butterfly minimum), one probe per detection or
 // per 256 steps.  A detection is marked -1 in LDS; then the candidates' flags are rewritten as 0 / 1.  Non-candidates never fire and
-// never change the state.
+// never change the state.  RAGGED: the signal's rows start at step_off[s] and there are step_off[s + 1] - step_off[s] of them; a signal
+// without steps returns at once.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void scan_suppress_kernel(const ScanDetectArgs a) {
     constexpr int PASS = 256 * kSuppressPer;
     constexpr int NONE = 0x7fffffff;
@@ -307,7 +383,9 @@ __global__ __launch_bounds__(256) void scan_suppress_kernel(const ScanDetectArgs
     __shared__ int s_any[2];
     const int s = blockIdx.x, tid = threadIdx.x;
     const int N = a.N, C = a.C, W = a.W;
-    const int64_t steps = a.steps;
+    const int64_t row0 = RAGGED ? a.step_off[s] : (int64_t)s * a.steps;
+    const int64_t steps = RAGGED ? a.step_off[s + 1] - row0 : a.steps;
+    if (RAGGED && steps == 0) return;
     int* ist = a.st.ist;
     const bool fresh = scan_fresh(a.st, s);
     const int head0 = fresh ? 0 : ist[s], count0 = fresh ? 0 : ist[N + s];
@@ -320,10 +398,10 @@ __global__ __launch_bounds__(256) void scan_suppress_kernel(const ScanDetectArgs
         for (int e = tid; e < nw * C; e += 256) {
             const int d = e / C, c = e - d * C;
             const int slot = (int)((head0 + i0 + d) % W);
-            a.st.ring[(size_t)slot * N * C + (size_t)s * C + c] = a.probs[((int64_t)s * steps + i0 + d) * C + c];
+            a.st.ring[(size_t)slot * N * C + (size_t)s * C + c] = a.probs[(row0 + i0 + d) * C + c];
         }
     }
-    int32_t* fl = a.is_new + (int64_t)s * steps;
+    int32_t* fl = a.is_new + row0;
     if (tid == 0) s_any[0] = 0;
     __syncthreads();
     int it = 0;
@@ -421,6 +499,62 @@ int scan_chunking(const tcr_frontend_cfg& cfg, const tcr_model_ref& m, const Mod
     return TCR_OK;
 }
 
+// A ragged call (tcr_scan_ragged): the host's step offsets [N + 1] and the device tables [2][N + 1] (step offsets, then group
+// offsets) at the front of the workspace.  Null in scan_run: the dense layout.
+struct ScanRagged {
+    const int64_t* step_off;    // host
+    int64_t* tables;            // device
+};
+
+size_t scan_ragged_tables_bytes(int64_t n_signals) { return (size_t)round_up64(2 * (n_signals + 1) * (int64_t)sizeof(int64_t), 256); }
+
+// Front-end frames of the call at group size G: every group is a row of G k + T - k frames, whatever its live steps.
+int64_t scan_ragged_frames(const int64_t* so, int n_signals, int k, int T, int G) {
+    int64_t rows = 0;
+    for (int n = 0; n < n_signals; ++n) rows += ceil_div64(so[n + 1] - so[n], G);
+    return rows * ((int64_t)G * k + T - k);
+}
+
+// The ragged chunking: G, at most kScanGroup, the longest signal and what one row of the workspace holds, with the fewest front-end
+// frames over the call (ties: the larger G, fewer rows) -- the results do not depend on G, so this is a cost choice only; the sum is
+// evaluated for every candidate while N x candidates stays small, for every few otherwise -- then R as scan_chunking finds it.
+int scan_ragged_chunking(const tcr_frontend_cfg& cfg, const tcr_model_ref& m, const ModelIO& io, int k, const int64_t* so, int n_signals,
+                         size_t ws_bytes, const char* what, ScanGeom& out) {
+    const auto fits = [&](int G, int64_t R) {
+        return scan_geom_ok(k, cfg.n_frames, G, R, io.max_batch) && (size_t)scan_geom(cfg, m, io, k, G, (int)R).ws_floats * sizeof(float) <= ws_bytes;
+    };
+    if (!fits(1, 1)) {
+        set_error("%s: workspace %zu bytes < one window's %zu", what, ws_bytes, (size_t)scan_geom(cfg, m, io, k, 1, 1).ws_floats * sizeof(float));
+        return TCR_ERR_WORKSPACE;
+    }
+    int64_t longest = 1;
+    for (int n = 0; n < n_signals; ++n) longest = std::max(longest, so[n + 1] - so[n]);
+    int lo = 1, hi = (int)std::min<int64_t>(kScanGroup, longest);      // the largest G one row of which fits (the size grows with G)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) / 2;
+        if (fits(mid, 1)) lo = mid;
+        else hi = mid - 1;
+    }
+    const int g_max = lo;
+    const int stride = (int)std::max<int64_t>(1, ceil_div64((int64_t)n_signals * g_max, (int64_t)1 << 22));
+    int G = g_max;
+    int64_t best = scan_ragged_frames(so, n_signals, k, cfg.n_frames, G);
+    for (int c = g_max - stride; c >= 1; c -= stride) {
+        const int64_t f = scan_ragged_frames(so, n_signals, k, cfg.n_frames, c);
+        if (f < best) { best = f; G = c; }
+    }
+    int64_t total_groups = 0;
+    for (int n = 0; n < n_signals; ++n) total_groups += ceil_div64(so[n + 1] - so[n], G);
+    int64_t rlo = 1, rhi = total_groups;
+    while (rlo < rhi) {
+        const int64_t mid = (rlo + rhi + 1) / 2;
+        if (fits(G, mid)) rlo = mid;
+        else rhi = mid - 1;
+    }
+    out = scan_geom(cfg, m, io, k, G, (int)rlo);
+    return TCR_OK;
+}
+
 size_t scan_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_model_ref* m, int k, int max_windows, const char* what) {
     ModelIO io;
     if (stream_check(cfg, m, 1, k, nullptr, what, io) != TCR_OK) return 0;
@@ -431,15 +565,77 @@ size_t scan_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_model_ref* m,
     return (size_t)scan_geom(*cfg, *m, io, k, G, R).ws_floats * sizeof(float);
 }
 
+// scan_run's ragged arm: the same stages over chunks of flattened groups, with the prefix tables in place of q / groups and
+// n steps + i.  A chunk's live steps are the packed steps p(q0) .. p(q0 + rows) - 1 (a signal's groups cover its steps in order), so
+// its windows are gathered compactly, the network runs at the batch of its live steps and writes their rows of the caller's logits
+// and probs itself: no scatter.  The slots past a signal's last step cost front-end frames only.
+int scan_run_ragged(const tcr_frontend_cfg& cfg, const void* plan_dev, const tcr_model_ref& m, const ModelIO& io, int n_signals, int k,
+                    const tcr_detect_cfg& det, const float* samples, const ScanRagged& rg, void* workspace, size_t ws_bytes, float* logits,
+                    float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, hipStream_t s, const char* what) {
+    const int64_t* so = rg.step_off;
+    ScanGeom g;
+    TCR_TRY(scan_ragged_chunking(cfg, m, io, k, so, n_signals, ws_bytes, what, g));
+    const int G = g.G;
+    std::vector<int64_t> tables(2 * ((size_t)n_signals + 1));
+    int64_t* go = tables.data() + n_signals + 1;
+    std::copy(so, so + n_signals + 1, tables.data());
+    go[0] = 0;
+    for (int n = 0; n < n_signals; ++n) go[n + 1] = go[n] + ceil_div64(so[n + 1] - so[n], G);
+    const int64_t total_groups = go[n_signals], total_steps = so[n_signals];
+    // the tables live on the host's stack frame: the copy is complete before the call returns (and before the first launch)
+    if (hipMemcpyAsync(rg.tables, tables.data(), tables.size() * sizeof(int64_t), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        set_error("%s: the upload of the offset tables failed", what);
+        return TCR_ERR_HIP;
+    }
+    float* ws = static_cast<float*>(workspace);
+    ScanChunkArgs ca{};
+    ca.samples = samples; ca.stage = ws + g.stage_off; ca.frames = ws + g.frames_off; ca.windows = ws + g.win_off; ca.st = ScanState{};
+    ca.k_hop = (int64_t)k * cfg.hop; ca.stride = g.stage_stride; ca.n_prefix = cfg.n_samples; ca.G = G; ca.k = k; ca.T = g.T; ca.tp = g.tp;
+    ca.n_coef = g.n_coef; ca.ftp = tcr_padded_len(g.F); ca.step_off = rg.tables; ca.group_off = rg.tables + n_signals + 1; ca.n_sig = n_signals;
+    const auto gather = g.planes ? scan_gather_kernel<true, false, true> : scan_gather_kernel<false, false, true>;
+    // the packed step of flattened group q's first slot
+    const auto first_step = [&](int64_t q) {
+        if (q >= total_groups) return total_steps;
+        const int64_t n = std::upper_bound(go, go + n_signals + 1, q) - go - 1;
+        return so[n] + (q - go[n]) * G;
+    };
+    const int64_t stage_blocks = ceil_div64(g.stage_stride, 256);
+    for (int64_t q0 = 0; q0 < total_groups; q0 += g.R) {
+        const int rows = (int)std::min<int64_t>(g.R, total_groups - q0);
+        ca.q0 = q0; ca.rows = rows; ca.p0 = first_step(q0);
+        const int live = (int)(first_step(q0 + rows) - ca.p0);
+        const int bx = (int)std::max<int64_t>(1, std::min(stage_blocks, ceil_div64(8 * (int64_t)device_cus(), rows)));
+        hipLaunchKernelGGL(scan_stage_ragged_kernel, dim3((unsigned)((int64_t)rows * bx)), dim3(256), 0, s, ca, bx);
+        TCR_TRY(check_launch("scan_stage_ragged_kernel"));
+        TCR_TRY(stream_frontend(cfg, plan_dev, ca.stage, g.stage_stride, rows, g.F, ca.frames, s, ca.ftp));
+        hipLaunchKernelGGL(gather, dim3(live), dim3(256), 0, s, ca);
+        TCR_TRY(check_launch("scan_gather_kernel"));
+        TCR_TRY(model_forward(m, ca.windows, live, ws + g.net_off, ws_bytes - (size_t)g.net_off * sizeof(float), logits + ca.p0 * g.classes,
+                              probs + ca.p0 * g.classes, s));
+    }
+    ScanDetectArgs da;
+    da.probs = probs; da.smoothed = smoothed; da.top = top; da.score = score; da.is_new = is_new; da.st = ScanState{}; da.steps = total_steps;
+    da.N = n_signals; da.C = g.classes; da.W = det.average_steps; da.min_count = det.min_count; da.suppression = det.suppression_steps;
+    da.threshold = det.threshold; da.step_off = rg.tables;
+    hipLaunchKernelGGL((scan_smooth_kernel<false, true>), dim3((unsigned)ceil_div64(total_steps, 256 / g.classes)), dim3(256), 0, s, da);
+    TCR_TRY(check_launch("scan_smooth_kernel"));
+    hipLaunchKernelGGL(scan_suppress_kernel<true>, dim3(n_signals), dim3(256), 0, s, da);
+    return check_launch("scan_suppress_kernel");
+}
+
 // The pipeline of the header comment over n_signals x steps checked by the caller, from and to the state st (all null: none).
 int scan_run(const tcr_frontend_cfg& cfg, const void* plan_dev, const tcr_model_ref& m, const ModelIO& io, int n_signals, int64_t steps,
              int k, const tcr_detect_cfg& det, const float* samples, const ScanState& st, void* workspace, size_t ws_bytes, float* logits,
-             float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream, const char* what) {
+             float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream, const char* what,
+             const ScanRagged* rg = nullptr) {
     ScanGeom g;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (rg) return scan_run_ragged(cfg, plan_dev, m, io, n_signals, k, det, samples, *rg, workspace, ws_bytes, logits, probs, smoothed, top,
+                                   score, is_new, s, what);
     TCR_TRY(scan_chunking(cfg, m, io, k, steps, n_signals, ws_bytes, what, g));
     const int G = g.G;
     const int64_t groups = ceil_div64(steps, G), total_groups = groups * n_signals;
-    hipStream_t s = static_cast<hipStream_t>(stream);
     float* ws = static_cast<float*>(workspace);
     ScanChunkArgs ca;
     ca.samples = samples; ca.stage = ws + g.stage_off; ca.frames = ws + g.frames_off; ca.windows = ws + g.win_off; ca.st = st;
@@ -478,11 +674,11 @@ int scan_run(const tcr_frontend_cfg& cfg, const void* plan_dev, const tcr_model_
     ScanDetectArgs da;
     da.probs = probs; da.smoothed = smoothed; da.top = top; da.score = score; da.is_new = is_new; da.st = st; da.steps = steps;
     da.N = n_signals; da.C = g.classes; da.W = det.average_steps; da.min_count = det.min_count; da.suppression = det.suppression_steps;
-    da.threshold = det.threshold;
+    da.threshold = det.threshold; da.step_off = nullptr;
     hipLaunchKernelGGL(carried ? scan_smooth_kernel<true> : scan_smooth_kernel<false>, dim3((unsigned)ceil_div64(n_signals * steps, 256 / g.classes)),
                        dim3(256), 0, s, da);
     TCR_TRY(check_launch("scan_smooth_kernel"));
-    hipLaunchKernelGGL(scan_suppress_kernel, dim3(n_signals), dim3(256), 0, s, da);
+    hipLaunchKernelGGL(scan_suppress_kernel<false>, dim3(n_signals), dim3(256), 0, s, da);
     return check_launch("scan_suppress_kernel");
 }
 
@@ -524,11 +720,58 @@ int stream_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_mod
                     score, is_new, stream, what);
 }
 
+int scan_ragged(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* m, int n_signals, const int64_t* sample_offsets,
+                int k, const tcr_detect_cfg* det, const float* samples, void* workspace, size_t ws_bytes, float* logits, float* probs,
+                float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream, const char* what) {
+    TCR_REQUIRE(plan_dev && m && m->params && m->aux && det && sample_offsets && workspace, "%s: null argument", what);
+    TCR_REQUIRE(n_signals > 0, "%s: the number of signals must be positive (got %d)", what, n_signals);
+    ModelIO io;
+    TCR_TRY(stream_check(cfg, m, n_signals, k, det, what, io, false));
+    const size_t tables_bytes = scan_ragged_tables_bytes(n_signals);
+    TCR_REQUIRE(tables_bytes <= ws_bytes, "%s: %d signals are more than the max_signals the workspace's offset tables hold (%lld)", what,
+                n_signals, (long long)(ws_bytes / (2 * sizeof(int64_t))) - 1);
+    const int64_t khop = (int64_t)k * cfg->hop;
+    TCR_REQUIRE(sample_offsets[0] == 0, "%s: sample_offsets must start at 0 (got %lld)", what, (long long)sample_offsets[0]);
+    std::vector<int64_t> so((size_t)n_signals + 1);
+    so[0] = 0;
+    for (int n = 0; n < n_signals; ++n) {
+        const int64_t len = sample_offsets[n + 1] - sample_offsets[n];
+        TCR_REQUIRE(len >= 0, "%s: sample_offsets decrease at signal %d (%lld after %lld)", what, n, (long long)sample_offsets[n + 1],
+                    (long long)sample_offsets[n]);
+        TCR_REQUIRE(len % khop == 0, "%s: the length %lld of signal %d is not a multiple of k * hop = %lld", what, (long long)len, n,
+                    (long long)khop);
+        so[n + 1] = so[n] + len / khop;
+    }
+    const int64_t total_steps = so[n_signals];
+    TCR_REQUIRE(total_steps > 0, "%s: no signal has a whole step (total_steps == 0)", what);
+    TCR_REQUIRE(total_steps * io.classes < ((int64_t)1 << 31), "%s: %lld steps in all is too large", what, (long long)total_steps);
+    TCR_REQUIRE(samples && logits && probs && smoothed && top && score && is_new, "%s: null argument", what);
+    const ScanRagged rg{so.data(), static_cast<int64_t*>(workspace)};
+    return scan_run(*cfg, plan_dev, *m, io, n_signals, 0, k, *det, samples, ScanState{}, static_cast<char*>(workspace) + tables_bytes,
+                    ws_bytes - tables_bytes, logits, probs, smoothed, top, score, is_new, stream, what, &rg);
+}
+
 }  // namespace
 
 }  // namespace tcr
 
 using namespace tcr;
+
+extern "C" size_t tcr_scan_ragged_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_model_ref* model, int k, int max_windows,
+                                                  int max_signals) {
+    const size_t chunk = scan_workspace_bytes(cfg, model, k, max_windows, "tcr_scan_ragged_workspace_bytes");
+    if (chunk == 0) return 0;
+    if (max_signals < 1) { set_error("tcr_scan_ragged_workspace_bytes: max_signals must be >= 1 (got %d)", max_signals); return 0; }
+    return scan_ragged_tables_bytes(max_signals) + chunk;
+}
+
+extern "C" int tcr_scan_ragged(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_signals,
+                               const int64_t* sample_offsets, int k, const tcr_detect_cfg* det, const float* samples, void* workspace,
+                               size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new,
+                               void* stream) {
+    return scan_ragged(cfg, plan_dev, model, n_signals, sample_offsets, k, det, samples, workspace, ws_bytes, logits, probs, smoothed, top,
+                       score, is_new, stream, "tcr_scan_ragged");
+}
 
 extern "C" size_t tcr_scan_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_net* net, int k, int max_windows) {
     const tcr_model_ref m = tcresnet_ref(net, nullptr, nullptr);

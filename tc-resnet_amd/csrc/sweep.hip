@@ -59,10 +59,13 @@ struct SweepArgs {
     uint8_t* fired;             // [T][N][steps] or null (zeroed before the launch)
     int64_t steps;
     int n_signals, n_thr, C, suppression, tblocks;
+    const int64_t* step_off;    // ragged (tcr_detect_sweep_ragged): [N + 1]; top / score are packed, fired is [T][step_off[N]]
 };
 
 // Dynamic LDS: counters [3][kSweepBlockT][C] (detections, hits, duplicates).  At most 80 VGPRs: six waves per SIMD (86 unbounded: five;
-// 72 for seven spills).
+// 72 for seven spills).  RAGGED: the signal's rows and its step count come from step_off, on the device, and the workgroup zeroes
+// its thresholds' rows of `fired` itself before it walks (the host does not know their total).
+template <bool RAGGED>
 __global__ __launch_bounds__(256, 6) void sweep_kernel(const SweepArgs a) {
     constexpr int NONE = 0x7fffffff;
     __shared__ float s_sc[kSweepPass];                  // candidate score (NaN: never fires)
@@ -77,10 +80,24 @@ __global__ __launch_bounds__(256, 6) void sweep_kernel(const SweepArgs a) {
     const int n = (int)(blockIdx.x / (unsigned)a.tblocks), t0 = (int)(blockIdx.x - (unsigned)n * a.tblocks) * kSweepBlockT;
     const int ncnt = 3 * kSweepBlockT * C;
     for (int i = tid; i < ncnt; i += 256) cnt[i] = 0;
-    int64_t vs = a.steps;
-    if (a.valid_steps) {
-        const int64_t v = a.valid_steps[n];
-        vs = v < 0 ? 0 : v < a.steps ? v : a.steps;
+    int64_t vs = a.steps, row0, total = 0;
+    if constexpr (RAGGED) {
+        row0 = a.step_off[n];
+        vs = a.step_off[n + 1] - row0;
+        if (vs < 0) vs = 0;
+        total = a.step_off[a.n_signals];
+        if (a.fired) {
+            for (int r = 0; r < kSweepBlockT && t0 + r < a.n_thr; ++r) {
+                uint8_t* f = a.fired + (int64_t)(t0 + r) * total + row0;
+                for (int64_t i = tid; i < vs; i += 256) f[i] = 0;
+            }
+        }
+    } else {
+        row0 = (int64_t)n * a.steps;
+        if (a.valid_steps) {
+            const int64_t v = a.valid_steps[n];
+            vs = v < 0 ? 0 : v < a.steps ? v : a.steps;
+        }
     }
     const bool events = a.ev_off != nullptr;
     int64_t e_lo = 0, e_hi = 0, e_base = 0;
@@ -101,8 +118,8 @@ __global__ __launch_bounds__(256, 6) void sweep_kernel(const SweepArgs a) {
         prev_step[q] = 0;
         last_hit[q] = -1;
     }
-    const int32_t* top = a.top + (int64_t)n * a.steps;
-    const float* score = a.score + (int64_t)n * a.steps;
+    const int32_t* top = a.top + row0;
+    const float* score = a.score + row0;
     __syncthreads();
     for (int64_t base = 0; base < vs; base += kSweepPass) {
         const int len = (int)(vs - base < kSweepPass ? vs - base : kSweepPass);
@@ -190,7 +207,10 @@ __global__ __launch_bounds__(256, 6) void sweep_kernel(const SweepArgs a) {
                     int* row = cnt + (wave + 4 * q) * C + lab;
                     row[0] += 1;
                     if (hit) row[(dup ? 2 : 1) * kSweepBlockT * C] += 1;
-                    if (a.fired) a.fired[((int64_t)(t0 + wave + 4 * q) * a.n_signals + n) * a.steps + base + first] = 1;
+                    if (a.fired) {
+                        if constexpr (RAGGED) a.fired[(int64_t)(t0 + wave + 4 * q) * total + row0 + base + first] = 1;
+                        else a.fired[((int64_t)(t0 + wave + 4 * q) * a.n_signals + n) * a.steps + base + first] = 1;
+                    }
                 }
                 cur = first + 1;
             }
@@ -207,6 +227,24 @@ __global__ __launch_bounds__(256, 6) void sweep_kernel(const SweepArgs a) {
         if (a.duplicates) a.duplicates[o] = cnt[2 * kSweepBlockT * C + i];
     }
 }
+
+namespace {
+
+template <bool RAGGED>
+int sweep_launch(SweepArgs& a, hipStream_t s, const char* what) {
+    a.tblocks = (a.n_thr + kSweepBlockT - 1) / kSweepBlockT;
+    const size_t lds = (size_t)3 * kSweepBlockT * a.C * sizeof(int);
+    if (lds > 24 * 1024 &&                              // (with the static arrays, past 64 KB of LDS: C > 120)
+        hipFuncSetAttribute(reinterpret_cast<const void*>(sweep_kernel<RAGGED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+            hipSuccess) {
+        set_error("%s: hipFuncSetAttribute failed", what);
+        return TCR_ERR_HIP;
+    }
+    hipLaunchKernelGGL(sweep_kernel<RAGGED>, dim3((unsigned)((int64_t)a.n_signals * a.tblocks)), dim3(256), lds, s, a);
+    return check_launch("sweep_kernel");
+}
+
+}  // namespace
 
 }  // namespace tcr
 
@@ -239,13 +277,29 @@ extern "C" int tcr_detect_sweep(int n_signals, int64_t steps, int num_classes, c
     a.ev_off = event_offsets; a.ev_first = event_first; a.ev_last = event_last; a.ev_label = event_label;
     a.detections = detections; a.hits = hits; a.duplicates = duplicates; a.fired = fired;
     a.steps = steps; a.n_signals = n_signals; a.n_thr = n_thresholds; a.C = num_classes; a.suppression = suppression_steps;
-    a.tblocks = (n_thresholds + kSweepBlockT - 1) / kSweepBlockT;
-    const size_t lds = (size_t)3 * kSweepBlockT * num_classes * sizeof(int);
-    if (lds > 24 * 1024 &&                              // (with the static arrays, past 64 KB of LDS: C > 120)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(sweep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        set_error("tcr_detect_sweep: hipFuncSetAttribute failed");
-        return TCR_ERR_HIP;
-    }
-    hipLaunchKernelGGL(sweep_kernel, dim3((unsigned)((int64_t)n_signals * a.tblocks)), dim3(256), lds, s, a);
-    return check_launch("sweep_kernel");
+    a.step_off = nullptr;
+    return sweep_launch<false>(a, s, "tcr_detect_sweep");
+}
+
+extern "C" int tcr_detect_sweep_ragged(int n_signals, const int64_t* step_offsets, int num_classes, const int32_t* top, const float* score,
+                                       int32_t suppression_steps, int n_thresholds, const float* thresholds, const int32_t* event_offsets,
+                                       const int64_t* event_first, const int64_t* event_last, const int32_t* event_label,
+                                       int32_t* detections, int32_t* hits, int32_t* duplicates, uint8_t* fired, void* stream) {
+    const char* what = "tcr_detect_sweep_ragged";
+    TCR_REQUIRE(step_offsets && top && score && thresholds && detections, "%s: null argument", what);
+    TCR_REQUIRE(n_signals > 0, "%s: the number of signals must be positive (got %d)", what, n_signals);
+    TCR_REQUIRE(n_thresholds > 0, "%s: the number of thresholds must be positive (got %d)", what, n_thresholds);
+    TCR_REQUIRE(num_classes > 0 && num_classes <= kSweepMaxClasses, "%s: num_classes %d outside 1..%d", what, num_classes, kSweepMaxClasses);
+    TCR_REQUIRE(suppression_steps >= 0, "%s: suppression_steps must be >= 0 (got %d)", what, suppression_steps);
+    TCR_REQUIRE(!event_offsets || (event_first && event_last && event_label && hits && duplicates),
+                "%s: events need event_first, event_last, event_label, hits and duplicates", what);
+    TCR_REQUIRE((int64_t)n_signals * n_thresholds * num_classes < ((int64_t)1 << 31), "%s: %d signals x %d thresholds x %d classes is too large",
+                what, n_signals, n_thresholds, num_classes);
+    SweepArgs a;
+    a.top = top; a.score = score; a.valid_steps = nullptr; a.thresholds = thresholds;
+    a.ev_off = event_offsets; a.ev_first = event_first; a.ev_last = event_last; a.ev_label = event_label;
+    a.detections = detections; a.hits = hits; a.duplicates = duplicates; a.fired = fired;
+    a.steps = 0; a.n_signals = n_signals; a.n_thr = n_thresholds; a.C = num_classes; a.suppression = suppression_steps;
+    a.step_off = step_offsets;
+    return sweep_launch<true>(a, static_cast<hipStream_t>(stream), what);
 }

@@ -2,7 +2,7 @@
 
     python scan_audio.py --frozen MODEL.npz --wav a.wav [b.wav ...] [--frames_per_step k] [--labels l0,l1,...]
                          [--average_window_ms MS] [--detection_threshold P] [--suppression_ms MS] [--min_count N]
-                         [--max_windows B] [--summary] [--chunk_seconds X]
+                         [--max_windows B] [--summary] [--chunk_seconds X | --ragged]
 
 The files (16-bit PCM) come from `audio_input.Recordings`, zero-padded to the longest, and are scanned in one
 `scanning.KeywordScanner` call; samples that do not fill a whole step are dropped (noted on stderr).  A file at another sample rate
@@ -13,7 +13,9 @@ on the host.  With --chunk_seconds, the files are read X seconds at a time (roun
 longest ends, and the output is the one-call output, byte for byte.  The output is stream_audio.py's, line for line: one line per
 detection on stdout,  file,time_ms,label,score,  in step order and, within a step, in file order -- time_ms is the end of the
 window that fired (every file starts as if it had heard one clip of silence).  --summary adds one JSON line on stderr: the hours
-of audio scanned (each file's whole steps), the detections per label and the detections per hour."""
+of audio scanned (each file's whole steps), the detections per label and the detections per hour.  With --ragged (not together with
+--chunk_seconds) every file is scanned at its own whole-step length in one `KeywordScanner.scan_ragged` call: nothing is padded, the
+lines have the same format and order, and no file has steps (or detections) past its own end."""
 from __future__ import annotations
 
 import argparse
@@ -23,10 +25,12 @@ from typing import List, Optional
 
 if __package__ in (None, ""):           # run as a script: import the package through the repository's shim
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from tcresnet_amd.audio_input import Recordings, add_detector_flags, label_names, open_detector, print_detections, summary_line
+    from tcresnet_amd.audio_input import (Recordings, add_detector_flags, label_names, open_detector, print_detections,
+                                          print_detections_ragged, summary_line)
     from tcresnet_amd.deploy import FrozenModel
 else:
-    from .audio_input import Recordings, add_detector_flags, label_names, open_detector, print_detections, summary_line
+    from .audio_input import (Recordings, add_detector_flags, label_names, open_detector, print_detections, print_detections_ragged,
+                              summary_line)
     from .deploy import FrozenModel
 
 
@@ -41,8 +45,12 @@ def main(args) -> int:
     det, run = open_detector(FrozenModel.load(args.frozen), args)
     rec = Recordings(args.wav, det)
     names, counts = label_names(args, det), {}
-    for i0, samples in rec.chunks(args.chunk_seconds):
-        print_detections(rec, run(samples), i0, names, counts)
+    if args.ragged:
+        if rec.n_steps > 0:
+            print_detections_ragged(rec, det.scan_ragged(rec.packed()), names, counts)
+    else:
+        for i0, samples in rec.chunks(args.chunk_seconds):
+            print_detections(rec, run(samples), i0, names, counts)
     if args.summary:
         print(summary_line(rec, counts), file=sys.stderr)
     return 0

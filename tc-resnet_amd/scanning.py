@@ -5,6 +5,9 @@ A `KeywordScanner` takes a batch of N signals of equal length and returns, for e
 time: logits, probs, smoothed, top, score and is_new, bitwise.  One call computes every window at the network's batch throughput;
 only the suppression rule runs in step order, over the candidate steps.
 
+`KeywordScanner.scan_ragged` takes signals of different lengths in one call (tcr_scan_ragged): packed one after the other, each
+signal's rows bitwise its own `scan`, no padding computed, stored or detected in.
+
 `KeywordScanner.sweep` (and `detection_sweep` over raw top / score tensors) then runs that rule for many thresholds at once on the
 device and scores the detections against labelled keyword events: a DET curve (false rejects against false accepts per hour) for
 the cost of one scan and a pass over its top / score.
@@ -13,7 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, NamedTuple, Optional, Sequence, Tuple
+from typing import Dict, Iterator, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -24,6 +27,7 @@ from .engine import Frontend
 from .streaming import Network, _Detection
 
 DEFAULT_MAX_WINDOWS = 4096
+DEFAULT_MAX_SIGNALS = 65536
 
 
 class ScanOutput(NamedTuple):
@@ -37,20 +41,54 @@ class ScanOutput(NamedTuple):
     is_new: torch.Tensor
 
 
+class RaggedScanOutput:
+    """Results of a ragged scan (`KeywordScanner.scan_ragged`), on the device, packed over the signals' steps: logits / probs /
+    smoothed [total_steps, classes] float32, top / score / is_new [total_steps]; `offsets` (host int64 [N + 1], in steps): signal n's
+    steps are rows offsets[n] .. offsets[n + 1] - 1.  `len()` is N; `signal(n)` is that signal's rows as a `ScanOutput` of views with
+    a leading dimension of 1, what `scan` of the signal alone returns."""
+    FIELDS = ScanOutput._fields
+
+    def __init__(self, logits, probs, smoothed, top, score, is_new, offsets: np.ndarray):
+        self.logits, self.probs, self.smoothed, self.top, self.score, self.is_new = logits, probs, smoothed, top, score, is_new
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+
+    def __len__(self) -> int:
+        return len(self.offsets) - 1
+
+    def tensors(self) -> Iterator[Optional[torch.Tensor]]:
+        return (getattr(self, f) for f in self.FIELDS)
+
+    @property
+    def steps(self) -> np.ndarray:
+        """Every signal's steps, host int64 [N]."""
+        return np.diff(self.offsets)
+
+    def signal(self, n: int) -> ScanOutput:
+        if not 0 <= n < len(self):
+            raise IndexError(f"signal {n} of {len(self)}")
+        a, b = int(self.offsets[n]), int(self.offsets[n + 1])
+        return ScanOutput(*(None if t is None else t[a:b].unsqueeze(0) for t in self.tensors()))
+
+
 class KeywordScanner(_Detection):
     """Scans signals through `frontend` and `net` (a TCResNet, DSCNN or finalized Graph2D) with the streaming detector's settings
     (see `streaming.StreamingDetector`: the same arguments, the same ms -> steps conversion, the same weight and fold rules).  Step i of a signal is its window after
     (i + 1) * k * hop samples of audio, with one clip of silence in front.
 
     max_windows bounds the windows the network runs per launch (default 4096); the workspace, allocated once here, is sized by it
-    and not by the signals' length."""
+    and not by the signals' length.  max_signals (default 65536) sizes the offset tables of `scan_ragged`'s workspace, which is
+    allocated on its first call and again when a call brings more signals."""
 
     def __init__(self, net: Network, frontend: Frontend, frames_per_step: int = 1, average_window_ms: float = 1000,
                  min_count: int = 3, detection_threshold: float = 0.5, suppression_ms: float = 1500,
-                 frozen_ss: Optional[torch.Tensor] = None, max_windows: Optional[int] = None):
+                 frozen_ss: Optional[torch.Tensor] = None, max_windows: Optional[int] = None, max_signals: Optional[int] = None):
         self._setup("KeywordScanner", "scanner", net, frontend, frames_per_step, average_window_ms, min_count, detection_threshold,
                     suppression_ms)
         self.max_windows = DEFAULT_MAX_WINDOWS if max_windows is None else int(max_windows)
+        self.max_signals = DEFAULT_MAX_SIGNALS if max_signals is None else int(max_signals)
+        if self.max_signals < 1:
+            raise TcrError(f"KeywordScanner: max_signals must be >= 1 (got {self.max_signals})")
+        self._ragged_ws: Optional[torch.Tensor] = None
         lib, cfg = self.lib, frontend.cfg
         nws = lib.tcr_scan_workspace_bytes_m(C.byref(cfg), C.byref(self._ref()), self.k, self.max_windows)
         if nws == 0:
@@ -79,13 +117,61 @@ class KeywordScanner(_Detection):
         self._after_call()
         return out
 
+    def scan_ragged(self, signals) -> RaggedScanOutput:
+        """Signals of different lengths in one call (tcr_scan_ragged): a list of 1-D float32 device tensors, or (packed, lengths) --
+        one 1-D float32 device tensor holding the signals one after the other and their lengths in samples.  Every length is a multiple
+        of k * hop; 0 is allowed (no rows).  Returns a `RaggedScanOutput` of new tensors: `signal(n)` is bitwise `scan` of signal n
+        alone, whatever max_windows and the other signals.  The weight rules are `scan`'s."""
+        if isinstance(signals, tuple) and len(signals) == 2 and isinstance(signals[0], torch.Tensor):
+            packed, lengths = signals[0], np.asarray(signals[1], dtype=np.int64).reshape(-1)
+            if packed.dim() != 1:
+                raise TcrError(f"scan_ragged expects a packed 1-D tensor, got shape {tuple(packed.shape)}")
+        else:
+            signals = list(signals)
+            for n, x in enumerate(signals):
+                if not isinstance(x, torch.Tensor) or x.dim() != 1:
+                    raise TcrError(f"scan_ragged expects 1-D tensors, signal {n} is {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+            lengths = np.array([int(x.shape[0]) for x in signals], dtype=np.int64)
+            if not signals:
+                raise TcrError("scan_ragged: no signals")
+            packed = signals[0] if len(signals) == 1 else torch.cat(signals)
+        N = int(lengths.size)
+        offsets = np.zeros(N + 1, dtype=np.int64)
+        np.cumsum(lengths, out=offsets[1:])
+        if int(offsets[-1]) != int(packed.shape[0]) and (lengths >= 0).all():
+            raise TcrError(f"scan_ragged: the lengths sum to {int(offsets[-1])} samples, the packed tensor has {int(packed.shape[0])}")
+        self.net._check_tensor(packed, "scan samples")
+        lib, fe, net, dev = self.lib, self.frontend, self.net, self.device
+        if self._ragged_ws is None or N > self.max_signals:
+            self.max_signals = max(self.max_signals, N)
+            nws = lib.tcr_scan_ragged_workspace_bytes(C.byref(fe.cfg), C.byref(self._ref()), self.k, self.max_windows, self.max_signals)
+            if nws == 0:
+                raise TcrError(f"KeywordScanner.scan_ragged: {lib.tcr_last_error().decode()}")
+            self._ragged_ws = torch.empty(nws // 4, dtype=torch.float32, device=dev)
+        ref = self._call_ref()
+        step = self.step_samples
+        ok = N > 0 and (lengths >= 0).all() and not (lengths % step).any()
+        total = int(offsets[-1]) // step if ok else 0           # (otherwise tcr_scan_ragged refuses, and the outputs are not written)
+        ncls = net.num_classes
+        f32 = dict(dtype=torch.float32, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        out = RaggedScanOutput(torch.empty((total, ncls), **f32), torch.empty((total, ncls), **f32), torch.empty((total, ncls), **f32),
+                               torch.empty(total, **i32), torch.empty(total, **f32), torch.empty(total, **i32), offsets // step)
+        ws = self._ragged_ws
+        lib.check(lib.tcr_scan_ragged(C.byref(fe.cfg), fe.plan.data_ptr(), C.byref(ref), N, offsets.ctypes.data, self.k, C.byref(self.det),
+                                      packed.data_ptr(), ws.data_ptr(), ws.numel() * 4, *(t.data_ptr() for t in out.tensors()),
+                                      net._stream()), "tcr_scan_ragged")
+        self._after_call()
+        return out
+
 
 # ---- detection sweeps ------------------------------------------------------------------------------------------------------------
 class SweepResult(NamedTuple):
     """Results of a detection sweep (tcr_detect_sweep) over N signals, T thresholds and C classes.
 
     detections / hits / duplicates [N, T, C] int32 on the device, per detection label (hits / duplicates are zero without events);
-    fired [T, N, steps] uint8 on the device or None (1 at the steps that fire at thresholds[t]); thresholds [T] float32 (host);
+    fired [T, N, steps] uint8 on the device ([T, total_steps] for a ragged scan) or None (1 at the steps that fire at thresholds[t]);
+    thresholds [T] float32 (host);
     events [N, C] int64 (host): the labelled events per signal and label; hours [N] float64 (host): each signal's valid steps in
     hours (NaN when the step length is unknown)."""
     detections: torch.Tensor
@@ -170,35 +256,55 @@ def _thresholds(thresholds) -> np.ndarray:
 
 def detection_sweep(top: torch.Tensor, score: torch.Tensor, thresholds, suppression_steps: int, num_classes: int,
                     events: Optional[Sequence[Sequence[Tuple[int, int, int]]]] = None, valid_steps=None,
-                    step_seconds: Optional[float] = None, return_fired: bool = False, lib=None) -> SweepResult:
+                    step_seconds: Optional[float] = None, return_fired: bool = False, lib=None, step_offsets=None) -> SweepResult:
     """The streaming detector's suppression rule (include/tcresnet_hip.h, tcr_detect_sweep) for every threshold at once, over top
     int32 / score float32 [N, steps] on the device (a scan's, or streaming outputs stacked over steps), scored against events.
 
     events: per signal, a list of (first_step, last_step, label) or an integer array [E, 3] of them (no conversion then): inclusive
     step ranges, disjoint within a signal (checked);
-    valid_steps: per signal, the steps that count (None: all); step_seconds: one step's duration, for SweepResult.hours."""
+    valid_steps: per signal, the steps that count (None: all); step_seconds: one step's duration, for SweepResult.hours.
+
+    step_offsets (host int64 [N + 1], from 0, non-decreasing): the ragged form (tcr_detect_sweep_ragged) -- top / score are packed
+    [total_steps], signal n's steps are rows step_offsets[n] .. step_offsets[n + 1] - 1, events are in steps relative to the signal's
+    first, fired is [T, total_steps]; valid_steps is refused (the offsets are the lengths)."""
     if lib is None:
         lib = _lib.get()
-    if top.dim() != 2 or score.shape != top.shape:
+    ragged = step_offsets is not None
+    if ragged:
+        soff = np.ascontiguousarray(np.asarray(step_offsets, dtype=np.int64).reshape(-1))
+        if valid_steps is not None:
+            raise TcrError("detection sweep: valid_steps with step_offsets (a ragged scan's offsets are its signals' lengths)")
+        if top.dim() != 1 or score.shape != top.shape:
+            raise TcrError(f"detection sweep with step_offsets expects packed top and score [total_steps], got {tuple(top.shape)} and "
+                           f"{tuple(score.shape)}")
+        if soff.size < 2 or soff[0] != 0 or (np.diff(soff) < 0).any() or int(soff[-1]) != int(top.shape[0]):
+            raise TcrError(f"detection sweep: step_offsets must run from 0 to the {int(top.shape[0])} packed steps without decreasing")
+    elif top.dim() != 2 or score.shape != top.shape:
         raise TcrError(f"detection sweep expects top and score [N, steps], got {tuple(top.shape)} and {tuple(score.shape)}")
     if top.dtype != torch.int32 or score.dtype != torch.float32 or not top.is_contiguous() or not score.is_contiguous():
         raise TcrError("detection sweep expects contiguous int32 top and float32 score")
     if top.device != score.device:
         raise TcrError("detection sweep: top and score are on different devices")
     dev = top.device
-    N, steps, ncls = int(top.shape[0]), int(top.shape[1]), int(num_classes)
+    if ragged:
+        N, steps, ncls = int(soff.size) - 1, int(top.shape[0]), int(num_classes)
+    else:
+        N, steps, ncls = int(top.shape[0]), int(top.shape[1]), int(num_classes)
     thr = _thresholds(thresholds)
     T = int(thr.size)
-    vs = np.full(N, steps, np.int64) if valid_steps is None else np.asarray(valid_steps, np.int64).reshape(-1)
+    if ragged:
+        vs = np.diff(soff)
+    else:
+        vs = np.full(N, steps, np.int64) if valid_steps is None else np.asarray(valid_steps, np.int64).reshape(-1)
     if vs.shape != (N,):
         raise TcrError(f"detection sweep: {vs.size} valid_steps for {N} signals")
-    if (vs < 0).any() or (vs > steps).any():
+    if not ragged and ((vs < 0).any() or (vs > steps).any()):
         raise TcrError(f"detection sweep: valid_steps outside 0..{steps}: {vs.tolist()}")
     i32 = dict(dtype=torch.int32, device=dev)
     detections = torch.empty((N, T, ncls), **i32)
     hits = torch.zeros((N, T, ncls), **i32)
     dups = torch.zeros((N, T, ncls), **i32)
-    fired = torch.empty((T, N, steps), dtype=torch.uint8, device=dev) if return_fired else None
+    fired = torch.empty((T, steps) if ragged else (T, N, steps), dtype=torch.uint8, device=dev) if return_fired else None
     counts = np.zeros((N, ncls), np.int64)
     ev_args = [None, None, None, None]
     keep = []
@@ -226,10 +332,16 @@ def detection_sweep(top: torch.Tensor, score: torch.Tensor, thresholds, suppress
         keep = [torch.from_numpy(x).to(dev) for x in host]
         ev_args = [t.data_ptr() for t in keep]
     thr_dev = torch.from_numpy(thr).to(dev)
-    vs_dev = torch.from_numpy(vs).to(dev)
     stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+    hours = vs * float(step_seconds) / 3600.0 if step_seconds is not None else np.full(N, np.nan)
+    if ragged:
+        off_dev = torch.from_numpy(soff).to(dev)
+        lib.check(lib.tcr_detect_sweep_ragged(N, off_dev.data_ptr(), ncls, top.data_ptr(), score.data_ptr(), int(suppression_steps), T,
+                                              thr_dev.data_ptr(), *ev_args, detections.data_ptr(), hits.data_ptr(), dups.data_ptr(),
+                                              None if fired is None else fired.data_ptr(), stream), "tcr_detect_sweep_ragged")
+        return SweepResult(detections, hits, dups, fired, thr, counts, hours)
+    vs_dev = torch.from_numpy(vs).to(dev)
     lib.check(lib.tcr_detect_sweep(N, steps, ncls, top.data_ptr(), score.data_ptr(), vs_dev.data_ptr(), int(suppression_steps), T,
                                    thr_dev.data_ptr(), *ev_args, detections.data_ptr(), hits.data_ptr(), dups.data_ptr(),
                                    None if fired is None else fired.data_ptr(), stream), "tcr_detect_sweep")
-    hours = vs * float(step_seconds) / 3600.0 if step_seconds is not None else np.full(N, np.nan)
     return SweepResult(detections, hits, dups, fired, thr, counts, hours)

@@ -130,13 +130,24 @@ class _Detection:
         the window that fired, scan_audio.py's time) and hits an event of its label when  start_ms <= t_i <= end_ms + tolerance_ms;
         each event becomes the inclusive step range of those i, computed in float64.  Refused: events that overlap once the
         tolerance is added (start of the next <= end + tolerance_ms), that end before they start or start past the signal's
-        length, unknown labels."""
-        from .scanning import _first_steps, _last_steps, detection_sweep
-        N, steps = int(out.top.shape[0]), int(out.top.shape[1])
+        length, unknown labels.
+
+        `out` may be a scanning.RaggedScanOutput (`KeywordScanner.scan_ragged`): every signal is walked over its own rows, its events
+        are relative to its own start, `fired` is [T, total_steps] and `hours` come from each signal's steps; `lengths` is refused,
+        because the scan's lengths are the lengths."""
+        from .scanning import RaggedScanOutput, _first_steps, _last_steps, detection_sweep
         step, sr = self.step_samples, self.frontend.cfg.sample_rate
-        if lengths is None:
+        ragged = isinstance(out, RaggedScanOutput)
+        if ragged:
+            if lengths is not None:
+                raise TcrError("sweep: lengths given with a ragged scan (the scan's lengths are the lengths)")
+            N, steps, valid = len(out), 0, out.steps
+            lengths = (valid * step).tolist()           # (the events below are checked against each signal's own end)
+        elif lengths is None:
+            N, steps = int(out.top.shape[0]), int(out.top.shape[1])
             valid = np.full(N, steps, np.int64)
         else:
+            N, steps = int(out.top.shape[0]), int(out.top.shape[1])
             lens = np.asarray(lengths, np.int64).reshape(-1)
             if lens.shape != (N,):
                 raise TcrError(f"sweep: {lens.size} lengths for {N} signals")
@@ -170,6 +181,9 @@ class _Detection:
                     a, b = evs[order[ov[0]]], evs[order[ov[0] + 1]]
                     raise TcrError(f"sweep: signal {n}: events {tuple(a)} and {tuple(b)} overlap with tolerance_ms = {tol:g}")
                 ev_steps.append(np.stack([_first_steps(se[:, 0], step, sr), _last_steps(se[:, 1] + tol, step, sr), cls], axis=1))
+        if ragged:
+            return detection_sweep(out.top, out.score, thresholds, self.suppression_steps, self.net.num_classes, ev_steps, None,
+                                   step / sr, return_fired, self.lib, step_offsets=out.offsets)
         return detection_sweep(out.top, out.score, thresholds, self.suppression_steps, self.net.num_classes, ev_steps, valid,
                                step / sr, return_fired, self.lib)
 

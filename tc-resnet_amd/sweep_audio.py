@@ -4,14 +4,15 @@ curve (false rejects against false accepts per hour) from one scan.
     python sweep_audio.py --frozen MODEL.npz --wav a.wav [b.wav ...] --events EVENTS.csv [--thresholds LO:HI:STEP | t0,t1,...]
                           [--tolerance_ms MS] [--keywords l0,l1,...] [--per_label] [--target_fa_per_hour F]
                           [--frames_per_step k] [--labels l0,l1,...] [--average_window_ms MS] [--suppression_ms MS]
-                          [--min_count N] [--max_windows B] [--chunk_seconds X]
+                          [--min_count N] [--max_windows B] [--chunk_seconds X | --ragged]
 
 The files are read as scan_audio.py reads them (`audio_input.Recordings`: 16-bit PCM, converted to the model's sample rate on the
 device where it differs, only whole steps), zero-padded to the longest and scanned in one call; one `KeywordScanner.sweep` then
 walks the detector's suppression rule at every threshold over each file's true length (--detection_threshold is not an input: the
 thresholds are).  With --chunk_seconds the files are read and scanned chunk by chunk (scan_audio.py's --chunk_seconds:
 `StreamingDetector.push_many`); either way the chunks' top / score are concatenated on the device and swept once: the output is the
-one-call output, byte for byte.  EVENTS.csv has a header and the columns
+one-call output, byte for byte.  With --ragged (not together with --chunk_seconds) the files are scanned at their own lengths in
+one `KeywordScanner.scan_ragged` call and swept over its packed rows: the same curve without the padding.  EVENTS.csv has a header and the columns
 file,start_ms,end_ms,label  (file as given to --wav, label one of --labels or a class index).  A detection at time t (the end of
 the window that fired, scan_audio.py's time) hits an event of its label when  start_ms <= t <= end_ms + tolerance_ms; the first
 hit of an event counts as a hit, later ones as duplicates, every other detection as a false accept.
@@ -93,13 +94,16 @@ def main(args) -> int:
     if rec.n_steps == 0:
         raise SystemExit("no whole step of audio in the files")
     events = read_events(args.events, args.wav)
-    tops, scores = [], []                               # (only what the sweep reads stays on the device)
-    for _, samples in rec.chunks(args.chunk_seconds):
-        o = run(samples)
-        tops.append(o.top)
-        scores.append(o.score)
-    out = ScanOutput(None, None, None, torch.cat(tops, dim=1), torch.cat(scores, dim=1), None)
-    res = scanner.sweep(out, thresholds, events=events, lengths=rec.lengths, tolerance_ms=args.tolerance_ms, labels=names)
+    if args.ragged:
+        res = scanner.sweep(scanner.scan_ragged(rec.packed()), thresholds, events=events, tolerance_ms=args.tolerance_ms, labels=names)
+    else:
+        tops, scores = [], []                           # (only what the sweep reads stays on the device)
+        for _, samples in rec.chunks(args.chunk_seconds):
+            o = run(samples)
+            tops.append(o.top)
+            scores.append(o.score)
+        out = ScanOutput(None, None, None, torch.cat(tops, dim=1), torch.cat(scores, dim=1), None)
+        res = scanner.sweep(out, thresholds, events=events, lengths=rec.lengths, tolerance_ms=args.tolerance_ms, labels=names)
     w = csv.writer(sys.stdout, lineterminator="\n")
     fmt = lambda cv, t: [f"{cv['threshold'][t]:.6g}", *(int(cv[k][t]) for k in COLUMNS[1:5]), f"{cv['frr'][t]:.6g}",
                          f"{cv['fa_per_hour'][t]:.9g}"]
