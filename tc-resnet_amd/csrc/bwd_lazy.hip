@@ -67,7 +67,12 @@ __global__ __launch_bounds__(kLzNW * 64) void bwd_lazy_kernel(const BwdLazyArgs 
     for (int si = 0; si < n_src; ++si) {                    // the per-channel tables (packed rows of bn_bwd_finalize: two 16-byte halves per channel)
         const LazySrc& S = a.src[si];
         float* cf = coef + (si ? 8 * a.src[0].c : 0);
-        for (int i = tid; i < S.c * 2; i += NT) reinterpret_cast<f32x4*>(cf)[i] = reinterpret_cast<const f32x4*>(S.tab)[i];
+        // (16-byte copies where the table starts on a 16-byte boundary; a workspace a C-ABI caller aligned to 4 bytes only: by element)
+        if ((reinterpret_cast<uintptr_t>(S.tab) & 15) == 0) {
+            for (int i = tid; i < S.c * 2; i += NT) reinterpret_cast<f32x4*>(cf)[i] = reinterpret_cast<const f32x4*>(S.tab)[i];
+        } else {
+            for (int i = tid; i < S.c * 8; i += NT) cf[i] = S.tab[i];
+        }
     }
     for (int i = tid; i < a.out_c; i += NT)
         for (int k = 0; k < 2; ++k) {

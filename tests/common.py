@@ -69,8 +69,29 @@ def fixture_params(fx, name, width):
     return arch, p, s
 
 
+def net_channels(name, width):
+    """The channel list of a net given by its width multiplier -- or the list itself when `width` already is one."""
+    return [int(c) for c in width] if isinstance(width, (list, tuple)) else R.tcresnet_channels(name, float(width))
+
+
+def make_arch(name, width, in_channels=40, num_classes=12):
+    """R.make_tcresnet, also for an explicit channel list (tc_resnet() takes any list: a block whose width differs from the one in
+    front of it gets the stride-2 pair and a 1x1 shortcut conv, an equal one the identity shortcut)."""
+    if not isinstance(width, (list, tuple)):
+        return R.make_tcresnet(name, float(width), in_channels=in_channels, num_classes=num_classes)
+    ch = net_channels(name, width)
+    blocks, c = [], ch[0]
+    for i, n in enumerate(ch[1:]):
+        down = R.ConvSpec(f"block{i}/down", 1, 2, c, n) if n != c else None
+        blocks.append(R.BlockSpec(i, down, R.ConvSpec(f"block{i}/conv{i}_0", 9, 2 if n != c else 1, c, n),
+                                  R.ConvSpec(f"block{i}/conv{i}_1", 9, 1, n, n, relu=False)))
+        c = n
+    return R.TCResNetArch(name, in_channels, num_classes, R.ConvSpec("conv0", 3, 1, in_channels, ch[0]), blocks,
+                          R.ConvSpec("fc", 1, 1, c, num_classes, bn=False, relu=False), R.ConvSpec("fc2", 1, 1, c, 2, bn=False, relu=False))
+
+
 def make_net(lib, name, width, t_in, p, s, in_channels=40, num_classes=12):
-    net = T.TCResNet(name, R.tcresnet_channels(name, float(width)), in_channels, t_in, num_classes, lib=lib, device=device_of(lib))
+    net = T.TCResNet(name, net_channels(name, width), in_channels, t_in, num_classes, lib=lib, device=device_of(lib))
     sd = dict(p)
     sd.update(s)
     net.load_state_dict(sd)
@@ -485,19 +506,29 @@ def check_small_batch(lib, batch, name="TCResNet8", width=1.0, tag="4020", seeds
     return worst
 
 
-def check_staged_equals_unstaged(lib, name, width, batch, tag="4020", keep_prob=0.5, handoff="level", bwd_knob=None):
+def check_staged_equals_unstaged(lib, name, width, batch, tag="4020", keep_prob=0.5, handoff="level", bwd_knob=None, in_channels=40,
+                                 num_classes=12, t_in=None):
     """One replica: forward_train / backward run stage by stage through the sync-BN hand-off API with an identity hook must be
-    BITWISE the unstaged path (logits, loss, every gradient, moving statistics)."""
+    BITWISE the unstaged path (logits, loss, every gradient, moving statistics).  `width`: a multiplier or an explicit channel list.
+    t_in = None: the `tag` front-end's features of synthetic waveforms (40 coefficients); a frame count: features drawn uniformly in
+    [-2, 2] at in_channels x t_in, no front-end."""
     cfg = R.FRONTEND_4020 if tag == "4020" else R.FRONTEND_3010
-    arch = R.make_tcresnet(name, float(width))
+    arch = make_arch(name, width, in_channels, num_classes)
     p, s = R.init_params(arch, 2)
     R.randomize_bn(arch, p, s, 3)
-    base = R.synth_waveforms(min(batch, 64), seed=21)
-    reps = max(batch // base.shape[0], 1)
-    wav = to_dev(lib, np.tile(base, (reps, 1)))
-    labels = to_dev(lib, np.tile(R.synth_labels(base.shape[0]), (reps, 1)))
-    fe = make_frontend(lib, cfg.win, cfg.hop)
-    feat = fe(wav)
+    if t_in is None:
+        assert in_channels == 40
+        base = R.synth_waveforms(min(batch, 64), seed=21)
+        reps = max(batch // base.shape[0], 1)
+        wav = to_dev(lib, np.tile(base, (reps, 1)))
+        labels = to_dev(lib, np.tile(R.synth_labels(base.shape[0], num_classes), (reps, 1)))
+        fe = make_frontend(lib, cfg.win, cfg.hop)
+        feat = fe(wav)
+        t_in = fe.n_frames
+    else:
+        x = np.random.RandomState(21).uniform(-2.0, 2.0, (batch, t_in, in_channels)).astype(np.float32)
+        feat = T.features_to_planar(torch.from_numpy(x).to(device_of(lib)), lib=lib)
+        labels = to_dev(lib, R.synth_labels(batch, num_classes))
     outs = []
     seen = []
     # The per-unit stage API keeps the per-layer backward chain (reduce -> bn_bwd_apply -> data gradient); whole passes and dependency
@@ -506,7 +537,7 @@ def check_staged_equals_unstaged(lib, name, width, batch, tag="4020", keep_prob=
     lib.tcr_tune(9, bwd_knob if bwd_knob is not None else (2 if handoff == "unit" else 0))
     try:
         for hook in (None, lambda sums: seen.append((sums.dtype, sums.numel()))):
-            net = make_net(lib, name, width, fe.n_frames, p, s)
+            net = make_net(lib, name, width, t_in, p, s, in_channels=in_channels, num_classes=num_classes)
             net.handoff = handoff
             logits, probs, loss = net.forward_train(feat, labels, keep_prob=keep_prob, seed=11, sync_hook=hook)
             g = net.backward().clone()
@@ -514,7 +545,7 @@ def check_staged_equals_unstaged(lib, name, width, batch, tag="4020", keep_prob=
     finally:
         lib.tcr_tune(9, 0)
     # one hand-off per dependency level each way: conv0, and per block (shortcut + first conv) | second conv
-    nblocks = len(R.tcresnet_channels(name, float(width))) - 1
+    nblocks = len(net_channels(name, width)) - 1
     assert lib.tcr_net_num_levels(net._h, 0) - 1 == 1 + 2 * nblocks == lib.tcr_net_num_levels(net._h, 1) - 1
     nbn = len([c for c in arch.convs() if c.bn])
     assert len(seen) == (2 * (1 + 2 * nblocks) if handoff == "level" else 2 * nbn) and all(dt == torch.float64 for dt, _ in seen)

@@ -13,6 +13,8 @@
 // without it; only tests/ load the emulator build.
 #pragma once
 #include <chrono>
+#include <cxxabi.h>
+#include <dlfcn.h>
 #include <ucontext.h>
 
 #include <algorithm>
@@ -22,6 +24,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <string>
+#include <unordered_map>
 #include <vector>
 
 #define TCR_HOST_EMULATION 1
@@ -345,8 +349,60 @@ inline f32x16_emu mfma_32x32x2(float a, float b, f32x16_emu c) {
 #define gridDim (emu::gdim())
 static const int warpSize = 64;
 
+// Launch log (tests/test_net_configs.py pins which kernel families a configuration reached: eval's fused and per-layer paths are
+// bitwise equal, so the results cannot tell).  Every hipLaunchKernelGGL since the last clear, in launch order: the stringified kernel
+// expression and, where the dynamic loader can name the function it evaluated to, " = " + the demangled instance (the launchers that
+// pick an instance into a function pointer all launch `kern`).  One list per process, at most kLaunchLogMax entries; what does not fit
+// is counted.  Test infrastructure: the product library has no such symbols.
+namespace emu {
+constexpr size_t kLaunchLogMax = 1 << 16;
+struct LaunchLog {
+    std::vector<std::string> entries;
+    std::unordered_map<const void*, std::string> names;     // function -> demangled symbol ("" when the loader has none)
+    size_t dropped = 0;
+};
+inline LaunchLog& launch_log() { static LaunchLog l; return l; }
+inline void log_launch(const char* text, const void* fn) {
+    LaunchLog& l = launch_log();
+    if (l.entries.size() >= kLaunchLogMax) { ++l.dropped; return; }
+    auto it = l.names.find(fn);
+    if (it == l.names.end()) {
+        std::string name;
+        Dl_info info;
+        if (fn && dladdr(fn, &info) && info.dli_sname) {
+            int status = 0;
+            char* d = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &status);
+            name = (status == 0 && d) ? d : info.dli_sname;
+            free(d);
+        }
+        it = l.names.emplace(fn, name).first;
+    }
+    l.entries.push_back(it->second.empty() ? std::string(text) : std::string(text) + " = " + it->second);
+}
+}  // namespace emu
+
+// Forgets the launches logged so far.
+extern "C" __attribute__((used, visibility("default"))) inline void tcr_emu_launch_log_clear() {
+    emu::launch_log().entries.clear();
+    emu::launch_log().dropped = 0;
+}
+// The log as newline-separated entries, NUL-terminated, into buf[0 .. cap); a last line "!dropped <n>" when entries did not fit the
+// list.  Returns the bytes the whole text needs (NUL included): call with cap = 0 to size the buffer.
+extern "C" __attribute__((used, visibility("default"))) inline long tcr_emu_launch_log_read(char* buf, long cap) {
+    const emu::LaunchLog& l = emu::launch_log();
+    std::string text;
+    for (const std::string& e : l.entries) { text += e; text += '\n'; }
+    if (l.dropped) text += "!dropped " + std::to_string(l.dropped) + "\n";
+    if (buf && cap > 0) {
+        const size_t n = std::min(text.size(), (size_t)cap - 1);
+        memcpy(buf, text.data(), n);
+        buf[n] = '\0';
+    }
+    return (long)text.size() + 1;
+}
+
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-    emu::launch(dim3(grid), dim3(block), [&]() { (kernel)(__VA_ARGS__); })
+    (emu::log_launch(#kernel, reinterpret_cast<const void*>(kernel)), emu::launch(dim3(grid), dim3(block), [&]() { (kernel)(__VA_ARGS__); }))
 
 static inline void __syncthreads() { emu::block_barrier(); }
 template <class T> static inline T __shfl(T v, int src, int width = 64) {
