@@ -558,6 +558,33 @@ int tcr_scan_ragged(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr
                     float* smoothed /* [total_steps][C] */, int32_t* top, float* score, int32_t* is_new /* [total_steps] */,
                     void* stream);
 
+/* Ragged many-step pushes: tcr_stream_scan_m with a step count of its own for every stream.  Stream s advances by
+ * m_s = (sample_offsets[s + 1] - sample_offsets[s]) / (k * hop) >= 0 steps; samples, sample_offsets (HOST [S + 1], from 0, not
+ * decreasing, every length a multiple of k * hop) and the six outputs are packed as tcr_scan_ragged packs them: step i of stream s
+ * is row sample_offsets[s] / (k * hop) + i.  reset [S] uint8 or NULL; state: the region tcr_stream_init_m made for (cfg, model, S, k,
+ * det); workspace: tcr_scan_ragged_workspace_bytes(cfg, model, k, max_windows, max_signals >= n_streams) bytes.
+ * Contract: stream s's rows, and the state it is left in (window, tail, the five integers and the ring slots of the last
+ * min(count, W) vectors), are bitwise what m_s calls of tcr_stream_step_m produce for that stream, the reset applied before the
+ * first of them; a call with the same m_s for every stream is bitwise tcr_stream_scan_m.  A stream with m_s == 0 is untouched: its
+ * window, tail, ring and integers are byte for byte what they were, and reset[s] != 0 is IGNORED for it (no step, no reset: pass
+ * the flag again with the call that brings the stream's next step).  Calls of tcr_stream_step, tcr_stream_scan and
+ * tcr_stream_scan_ragged may be mixed on one state in any order.  The offset tables are uploaded as tcr_scan_ragged uploads them
+ * (host copy on `stream`, then a wait), so the call cannot be captured into a graph; everything else is enqueued on `stream`.
+ * Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched and the state is untouched): everything tcr_scan_ragged refuses except
+ * that a stream without steps is allowed, everything tcr_stream_scan_m refuses, a call without any step (total_steps == 0), and
+ * more streams than the workspace's tables hold.  TCR_ERR_WORKSPACE when the bytes behind the tables are below one window.
+ * tcr_stream_scan_ragged is the entry with a TCR_FAMILY_TCRESNET reference built from (net, params, frozen_ss). */
+int tcr_stream_scan_ragged(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params,
+                           const float* frozen_ss, int n_streams, const int64_t* sample_offsets /* HOST [S + 1] */, int k,
+                           const tcr_detect_cfg* det, const float* samples /* device, packed */, const uint8_t* reset, void* state,
+                           void* workspace, size_t ws_bytes, float* logits, float* probs, float* smoothed /* [total_steps][C] */,
+                           int32_t* top, float* score, int32_t* is_new /* [total_steps] */, void* stream);
+int tcr_stream_scan_ragged_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_streams,
+                             const int64_t* sample_offsets /* HOST [S + 1] */, int k, const tcr_detect_cfg* det,
+                             const float* samples /* device, packed */, const uint8_t* reset, void* state, void* workspace,
+                             size_t ws_bytes, float* logits, float* probs, float* smoothed /* [total_steps][C] */, int32_t* top,
+                             float* score, int32_t* is_new /* [total_steps] */, void* stream);
+
 /* tcr_detect_sweep over a ragged scan: top / score are packed [total_steps] and signal n's steps are rows step_offsets[n] ..
  * step_offsets[n + 1] - 1 (DEVICE int64 [N + 1], from 0, non-decreasing: a precondition, the host does not read it).  The rule is
  * tcr_detect_sweep's, walked over each signal's own rows from prev_label = -1; events stay CSR per signal, in steps relative to the

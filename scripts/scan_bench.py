@@ -10,13 +10,23 @@ relayout into its planes, which the scan's gather writes directly).
     python scripts/scan_bench.py --trace_one         # one 1-hour scan after a warm-up (for rocprofv3 --kernel-trace --stats)
     python scripts/scan_bench.py --ragged [--out profiles/scan_ragged_bench.json]
     python scripts/scan_bench.py --ab_lib tc-resnet_amd/lib/side/libtcr_parent.so      # the dense legs against another build
+    python scripts/scan_bench.py --ragged_push [--out profiles/stream_scan_ragged_bench.json]
 
 --ragged: KeywordScanner.scan_ragged (tcr_scan_ragged) over a seeded corpus of 255 signals of 1 - 10 s (whole steps) and one of
 10 min, next to the padded dense scan of the same corpus ([256, 10 min], what a caller without it runs) and the dense scan of 256
 equal-length signals with the same total audio; the group size the call picks (the library's rule, restated here) and the ratio of
 the front-end frames it computes to the live ones (steps x k) are reported with the times.  --trace_one --ragged runs the ragged
 scan once after a warm-up.  --ab_lib: the 1 x 1 h and 64 x 1 min dense scans through this build and through the library given
-(scripts/build_ref_lib.py), alternating in one process.
+(scripts/build_ref_lib.py), alternating in one process; so do a dense push_many (256 streams x 10 s) and the ragged scan of the
+--ragged corpus.
+
+--ragged_push: StreamingDetector.push_ragged (tcr_stream_scan_ragged).  server: S = 4096 streams that advance by 0 - 3 steps each
+(seed 0) in one call, next to the lockstep prepared push and push_many of 1 and 2 steps per stream (the ragged call's mean is 1.5):
+device time and wall time per call -- the ragged call uploads its offset tables and waits, which device events alone do not
+show -- and per advanced step.  corpus: the --ragged corpus pushed in 10 s chunks, every stream its next min(10 s, what remains),
+next to the one-call scan_ragged and the lockstep push_many of the corpus zero-padded to the longest, in the same chunks.  host: the
+wall time of one call of one step per stream on an idle device, push_ragged against push_many, at S = 1 and S = 4096 (the
+difference is the table upload and its wait), next to a host-to-device copy of a table of that size followed by a stream wait.
 
 Each number is the median over --reps timed calls (device events) after a warm-up call; the legs alternate within a rep.  Weights
 and audio are random (timing does not depend on them)."""
@@ -65,8 +75,7 @@ def ragged_group(steps, k, T, cap):
 def ragged_leg(args, fe, net, dev):
     import numpy as np
     scanner = KeywordScanner(net, fe, average_window_ms=1000)
-    rng = np.random.RandomState(0)
-    steps = np.concatenate([rng.randint(SR // HOP, 10 * SR // HOP + 1, 255), [600 * SR // HOP]]).astype(np.int64)
+    steps = corpus_steps()
     total = int(steps.sum())
     g = torch.Generator(device="cuda").manual_seed(0)
     packed = ((torch.rand(total * HOP, device=dev, generator=g) - 0.5) * 0.8).contiguous()
@@ -112,6 +121,127 @@ def ragged_leg(args, fe, net, dev):
             json.dump({"device": torch.cuda.get_device_name(0), **row}, fh, indent=1)
 
 
+def corpus_steps():
+    """The --ragged corpus: 255 signals of 1 - 10 s and one of 10 min, in steps (seed 0)."""
+    import numpy as np
+    rng = np.random.RandomState(0)
+    return np.concatenate([rng.randint(SR // HOP, 10 * SR // HOP + 1, 255), [600 * SR // HOP]]).astype(np.int64)
+
+
+def wall_ms(fn, iters=1):
+    """Host time of `iters` calls on an idle device, the device's work included."""
+    import time
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return 1000.0 * (time.perf_counter() - t0) / iters
+
+
+def ragged_push_leg(args, fe, net, dev):
+    import numpy as np
+    g = torch.Generator(device="cuda").manual_seed(0)
+    noise = lambda *shape: ((torch.rand(shape, device=dev, generator=g) - 0.5) * 0.8).contiguous()      # noqa: E731
+    legs = {}
+    # (a) the server shape
+    S = 4096
+    m = np.random.RandomState(0).randint(0, 4, S).astype(np.int64)
+    advanced = int(m.sum())
+    srv = StreamingDetector(net, fe, S, average_window_ms=1000)
+    packed, lengths = noise(advanced * HOP), (m * HOP).tolist()
+    x1, x2 = noise(S, HOP), noise(S, 2 * HOP)
+    step = srv.prepared(x1)
+    ragged = lambda: srv.push_ragged((packed, lengths))          # noqa: E731
+    legs["server_ragged_ms"] = lambda: time_ms(ragged, 20)
+    legs["server_ragged_wall_ms"] = lambda: wall_ms(ragged, 20)
+    legs["server_push_ms"] = lambda: time_ms(step, 200)
+    legs["server_push_wall_ms"] = lambda: wall_ms(step, 200)
+    legs["server_push_many_1_ms"] = lambda: time_ms(lambda: srv.push_many(x1), 20)
+    legs["server_push_many_1_wall_ms"] = lambda: wall_ms(lambda: srv.push_many(x1), 20)
+    legs["server_push_many_2_ms"] = lambda: time_ms(lambda: srv.push_many(x2), 20)
+    legs["server_push_many_2_wall_ms"] = lambda: wall_ms(lambda: srv.push_many(x2), 20)
+    # (b) the corpus shape
+    steps = corpus_steps()
+    N, total, chunk = len(steps), int(steps.sum()), 10 * SR // HOP
+    corpus = noise(total * HOP)
+    first = np.concatenate([[0], np.cumsum(steps)])[:-1] * HOP
+    cor_len = (steps * HOP).tolist()
+    padded = torch.zeros((N, int(steps.max()) * HOP), device=dev)
+    for n in range(N):
+        padded[n, :cor_len[n]] = corpus[first[n]:first[n] + cor_len[n]]
+    pieces = []
+    for i0 in range(0, int(steps.max()), chunk):
+        ms_ = np.clip(steps - i0, 0, chunk)
+        pieces.append((torch.cat([corpus[first[n] + i0 * HOP:first[n] + (i0 + ms_[n]) * HOP] for n in range(N)]), (ms_ * HOP).tolist()))
+    pad_pieces = [padded[:, i0 * HOP:(i0 + chunk) * HOP].contiguous() for i0 in range(0, int(steps.max()), chunk)]
+    det = StreamingDetector(net, fe, N, average_window_ms=1000)
+    scanner = KeywordScanner(net, fe, average_window_ms=1000)
+    everyone = np.ones(N, bool)
+
+    def chunked():
+        det.reset(everyone)
+        for piece in pieces:
+            det.push_ragged(piece)
+
+    def lockstep():
+        det.reset(everyone)
+        for piece in pad_pieces:
+            det.push_many(piece)
+    legs["corpus_push_ragged_10s_ms"] = lambda: wall_ms(chunked)
+    legs["corpus_scan_ragged_ms"] = lambda: wall_ms(lambda: scanner.scan_ragged((corpus, cor_len)))
+    legs["corpus_padded_push_many_10s_ms"] = lambda: wall_ms(lockstep)
+    # (c) the host cost of a call
+    for s_ in (1, S):
+        d = srv if s_ == S else StreamingDetector(net, fe, 1, average_window_ms=1000)
+        xs, one = noise(s_, HOP), [HOP] * s_
+        table = torch.zeros(2 * (s_ + 1), dtype=torch.int64)
+        table_dev = torch.zeros(2 * (s_ + 1), dtype=torch.int64, device=dev)
+
+        def upload(table=table, table_dev=table_dev):
+            table_dev.copy_(table, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+        legs["host_s%d_push_ragged_wall_us" % s_] = lambda d=d, xs=xs, one=one: 1000.0 * wall_ms(lambda: d.push_ragged((xs.view(-1), one)), 50)
+        legs["host_s%d_push_many_wall_us" % s_] = lambda d=d, xs=xs: 1000.0 * wall_ms(lambda: d.push_many(xs), 50)
+        legs["host_s%d_table_copy_and_wait_us" % s_] = lambda upload=upload: 1000.0 * wall_ms(upload, 200)
+    for fn in legs.values():
+        fn()
+    res = {k: [] for k in legs}
+    for _ in range(args.reps):
+        for k, fn in legs.items():
+            res[k].append(fn())
+    med = {k: statistics.median(v) for k, v in res.items()}
+    rnd = lambda v: round(v, 4)                                      # noqa: E731
+    row = {
+        "workload": "TCResNet8-1.0, 4020, k = 1, W = 50, max_windows = %d" % DEFAULT_MAX_WINDOWS,
+        "server": {"streams": S, "steps_per_stream": "0 - 3 (seed 0)", "advanced_steps": advanced,
+                   "streams_without_steps": int((m == 0).sum()),
+                   "push_ragged_ms": rnd(med["server_ragged_ms"]), "push_ragged_wall_ms": rnd(med["server_ragged_wall_ms"]),
+                   "push_ragged_wall_us_per_step": rnd(1000.0 * med["server_ragged_wall_ms"] / advanced),
+                   "push_ms": rnd(med["server_push_ms"]), "push_wall_ms": rnd(med["server_push_wall_ms"]),
+                   "push_wall_us_per_step": rnd(1000.0 * med["server_push_wall_ms"] / S),
+                   "push_many_1_ms": rnd(med["server_push_many_1_ms"]), "push_many_1_wall_ms": rnd(med["server_push_many_1_wall_ms"]),
+                   "push_many_1_wall_us_per_step": rnd(1000.0 * med["server_push_many_1_wall_ms"] / S),
+                   "push_many_2_ms": rnd(med["server_push_many_2_ms"]), "push_many_2_wall_ms": rnd(med["server_push_many_2_wall_ms"]),
+                   "push_many_2_wall_us_per_step": rnd(1000.0 * med["server_push_many_2_wall_ms"] / (2 * S))},
+        "corpus": {"signals": N, "total_steps": total, "chunk_steps": chunk, "chunks": len(pieces),
+                   "padded_steps": N * int(steps.max()),
+                   "push_ragged_10s_chunks_ms": rnd(med["corpus_push_ragged_10s_ms"]),
+                   "scan_ragged_one_call_ms": rnd(med["corpus_scan_ragged_ms"]),
+                   "padded_push_many_10s_chunks_ms": rnd(med["corpus_padded_push_many_10s_ms"])},
+        "host": {("s%d" % s_): {"push_ragged_wall_us": rnd(med["host_s%d_push_ragged_wall_us" % s_]),
+                                "push_many_wall_us": rnd(med["host_s%d_push_many_wall_us" % s_]),
+                                "difference_us": rnd(med["host_s%d_push_ragged_wall_us" % s_] - med["host_s%d_push_many_wall_us" % s_]),
+                                "table_copy_and_wait_us": rnd(med["host_s%d_table_copy_and_wait_us" % s_])} for s_ in (1, S)},
+        "reps": args.reps, "raw": {k: [rnd(x) for x in v] for k, v in res.items()},
+    }
+    print(json.dumps(row), flush=True)
+    if args.out:
+        with open(args.out, "w") as fh:
+            json.dump({"device": torch.cuda.get_device_name(0), "command": "python scripts/scan_bench.py --ragged_push --reps %d" % args.reps,
+                       **row}, fh, indent=1)
+
+
 def ab_leg(args, dev):
     """The dense scans through this build and through --ab_lib, alternating: medians and ranges of both."""
     import tcresnet_amd as T
@@ -123,6 +253,10 @@ def ab_leg(args, dev):
     g = torch.Generator(device="cuda").manual_seed(0)
     hour = ((torch.rand((1, HOUR), device=dev, generator=g) - 0.5) * 0.8).contiguous()
     minutes = ((torch.rand((64, 60 * SR), device=dev, generator=g) - 0.5) * 0.8).contiguous()
+    ten = ((torch.rand((256, 10 * SR), device=dev, generator=g) - 0.5) * 0.8).contiguous()
+    steps = corpus_steps()
+    corpus = ((torch.rand(int(steps.sum()) * HOP, device=dev, generator=g) - 0.5) * 0.8).contiguous()
+    cor_len = (steps * HOP).tolist()
     legs = {}
     for name, lib in libs.items():
         fe = T.Frontend(window_size_samples=640, window_stride_samples=HOP, device=dev, lib=lib)
@@ -131,6 +265,9 @@ def ab_leg(args, dev):
         sc = KeywordScanner(net, fe, average_window_ms=1000)
         legs[name + "_scan_1x1h_ms"] = lambda sc=sc: time_ms(lambda: sc.scan(hour))
         legs[name + "_scan_64x1min_ms"] = lambda sc=sc: time_ms(lambda: sc.scan(minutes))
+        st = StreamingDetector(net, fe, 256, average_window_ms=1000)
+        legs[name + "_push_many_256x10s_ms"] = lambda st=st: time_ms(lambda: st.push_many(ten))
+        legs[name + "_scan_ragged_corpus_ms"] = lambda sc=sc: time_ms(lambda: sc.scan_ragged((corpus, cor_len)))
     for fn in legs.values():
         fn()
     res = {k: [] for k in legs}
@@ -155,10 +292,13 @@ def main():
     ap.add_argument("--model", default="TCResNet8", choices=MODELS)
     ap.add_argument("--ragged", action="store_true")
     ap.add_argument("--ab_lib", default=None)
+    ap.add_argument("--ragged_push", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda")
     if args.ab_lib:
         return ab_leg(args, dev)
+    if args.ragged_push:
+        return ragged_push_leg(args, *build(640, HOP, "TCResNet8", 1.0, dev), dev)
     if args.ragged:
         return ragged_leg(args, *build(640, HOP, "TCResNet8", 1.0, dev), dev)
     if args.model == "TCResNet8":

@@ -191,6 +191,10 @@ _PROTOTYPES = {
     "tcr_scan_ragged_workspace_bytes": (C.c_size_t, [C.POINTER(FrontendCfg), C.POINTER(ModelRef), C.c_int, C.c_int, C.c_int]),
     "tcr_scan_ragged": (C.c_int, [C.POINTER(FrontendCfg), _P, C.POINTER(ModelRef), C.c_int, _P, C.c_int, C.POINTER(DetectCfg), _P, _P,
                                   C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
+    "tcr_stream_scan_ragged": (C.c_int, [C.POINTER(FrontendCfg), _P, _P, _P, _P, C.c_int, _P, C.c_int, C.POINTER(DetectCfg), _P, _P, _P, _P,
+                                         C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
+    "tcr_stream_scan_ragged_m": (C.c_int, [C.POINTER(FrontendCfg), _P, C.POINTER(ModelRef), C.c_int, _P, C.c_int, C.POINTER(DetectCfg), _P, _P,
+                                           _P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
     "tcr_detect_sweep_ragged": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, C.c_int32, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "tcr_resample": (C.c_int, [C.POINTER(ResampleCfg), _P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64,
                                _P]),

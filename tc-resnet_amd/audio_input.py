@@ -100,6 +100,32 @@ class Recordings:
                     rs.convert(torch.from_numpy(f.read_pcm(first, n)[None, :]).to(dev), first, at, keep, out=buf[s:s + 1, :keep])
             yield i0, buf
 
+    def ragged_chunks(self, chunk_seconds: float) -> Iterator[Tuple[int, torch.Tensor, List[int]]]:
+        """(first step, float32 1-D on det's device, lengths) chunk_seconds (rounded down to whole steps) at a time, up to the longest
+        file's last whole step: every file contributes its next min(chunk, what remains) whole steps, possibly none, one after the
+        other -- what `StreamingDetector.push_ragged` takes.  Every chunk covers the same step range of every file that still has
+        steps, and a file's samples are the bytes `packed()` holds for them: the same host decode, the same `Resampler.convert` calls
+        by global position."""
+        chunk_steps = int(chunk_seconds * self.rate) // self.step
+        if chunk_steps < 1:
+            raise SystemExit(f"--ragged_chunk_seconds {chunk_seconds:g} is shorter than one step ({self.step} samples)")
+        dev = self.det.device
+        for i0 in range(0, self.n_steps, chunk_steps):
+            at = i0 * self.step
+            lengths = [max(0, min(chunk_steps * self.step, n - at)) for n in self.lengths]
+            buf = torch.zeros(sum(lengths), dtype=torch.float32, device=dev)
+            pos = 0
+            for f, keep in zip(self.files, lengths):
+                if keep == 0:
+                    continue
+                if f.rate == self.rate:
+                    buf[pos:pos + keep] = torch.from_numpy(f.read_pcm(at, keep).astype(np.float32) * (1.0 / 32768.0)).to(dev)
+                else:
+                    rs = self.resampler(f.rate)
+                    first, n = rs.span(at, keep)
+                    rs.convert(torch.from_numpy(f.read_pcm(first, n)[None, :]).to(dev), first, at, keep, out=buf[pos:pos + keep].unsqueeze(0))
+                pos += keep
+            yield i0, buf, lengths
 
     def packed(self) -> Tuple[torch.Tensor, List[int]]:
         """(float32 1-D on det's device, lengths): the files one after the other, each at its own whole-step length -- what
@@ -139,9 +165,10 @@ def print_detections(rec: Recordings, out, i0: int, names: List[str], counts: Di
         print(f"{rec.paths[s]},{format_time_ms(1000.0 * (i0 + i + 1) * rec.step / rec.rate)},{name},{float(score[s, i]):.6f}", flush=True)
 
 
-def print_detections_ragged(rec: Recordings, out, names: List[str], counts: Dict[str, int]) -> None:
+def print_detections_ragged(rec: Recordings, out, names: List[str], counts: Dict[str, int], i0: int = 0) -> None:
     """`print_detections` for a scanning.RaggedScanOutput over rec's files: the same lines in the same order (step order, then file
-    order); a file has no steps past its own end, so none is printed there."""
+    order); a file has no steps past its own end, so none is printed there.  `i0`: the step of every file that out's rows start at
+    (a chunk of `Recordings.ragged_chunks`)."""
     fired = np.flatnonzero(out.is_new.cpu().numpy())
     if not fired.size:
         return
@@ -151,7 +178,7 @@ def print_detections_ragged(rec: Recordings, out, names: List[str], counts: Dict
     for o in np.lexsort((s, i)):
         name = names[top[fired[o]]]
         counts[name] = counts.get(name, 0) + 1
-        print(f"{rec.paths[s[o]]},{format_time_ms(1000.0 * (int(i[o]) + 1) * rec.step / rec.rate)},{name},{float(score[fired[o]]):.6f}", flush=True)
+        print(f"{rec.paths[s[o]]},{format_time_ms(1000.0 * (i0 + int(i[o]) + 1) * rec.step / rec.rate)},{name},{float(score[fired[o]]):.6f}", flush=True)
 
 
 def summary_line(rec: Recordings, counts: Dict[str, int]) -> str:
@@ -177,6 +204,9 @@ def add_detector_flags(p, each: str = "signal", threshold: bool = True, offline:
         p.add_argument("--chunk_seconds", type=float, default=None, help="read and scan the files this many seconds at a time")
         p.add_argument("--ragged", action="store_true",
                        help="scan every file at its own length in one ragged call (KeywordScanner.scan_ragged): no padding to the longest")
+        p.add_argument("--ragged_chunk_seconds", type=float, default=None,
+                       help="read the files this many seconds at a time, each at its own length (StreamingDetector.push_ragged): --ragged's "
+                            "output with one chunk of every file in host memory")
 
 
 def detector_settings(args) -> dict:
@@ -187,9 +217,17 @@ def detector_settings(args) -> dict:
 
 def open_detector(model, args):
     """(detector, its call on one chunk): a KeywordScanner and `scan` for the one-call run, which allocates no stream state; with
-    --chunk_seconds a StreamingDetector over the files and `push_many`, which carries the state from chunk to chunk."""
+    --chunk_seconds a StreamingDetector over the files and `push_many`, which carries the state from chunk to chunk; with
+    --ragged_chunk_seconds the same detector and `push_ragged`, every file advancing by what it has left."""
     if getattr(args, "ragged", False) and args.chunk_seconds is not None:
         raise SystemExit("--ragged scans the whole files in one call: it cannot be combined with --chunk_seconds")
+    if getattr(args, "ragged_chunk_seconds", None) is not None:
+        if args.chunk_seconds is not None:
+            raise SystemExit("--ragged_chunk_seconds reads every file at its own length: it cannot be combined with --chunk_seconds")
+        if getattr(args, "ragged", False):
+            raise SystemExit("--ragged_chunk_seconds is the chunked form of --ragged: give one of the two")
+        det = model.streaming(len(args.wav), **detector_settings(args))
+        return det, det.push_ragged
     if args.chunk_seconds is None:
         det = model.scanner(**detector_settings(args))
         return det, det.scan

@@ -42,6 +42,18 @@
 // the group size with the fewest front-end frames over the call (scan_ragged_chunking).  The ragged arms are compile-time instances
 // (RAGGED) or sibling kernels: the dense instances carry no test for them.
 //
+// Ragged with a state (tcr_stream_scan_ragged): stream s advances by m_s >= 0 steps of its own, samples and rows packed as above.  The
+// ragged stages with the carried arms: the staging row reads the stream's tail in front of its samples (scan_stage_ragged_tail_kernel;
+// with a small G several groups of a stream reach into the prefix), the gather takes the first T - (i + 1) k columns of a stream's
+// early steps from its carried window (CARRIED && RAGGED), the smoothing counts from the stream's count0 and reads its ring, the
+// suppression is the ragged instance run with the state, and scan_carry_ragged_kernel writes window and tail back.  State ordering:
+// the flattened groups are ordered by stream (group_off), so a stream's groups are consecutive rows here too and the dense argument
+// holds -- a stream's window and tail are written only in the chunk that holds its last group, group_off[s + 1] - 1, after that
+// chunk's stage and gather, and no later chunk has a group of that stream; ring and integers are written by the suppression, after
+// the smoothing of every stream has read them.  A stream without steps (m_s == 0) has no group, no row and no carry, and its
+// suppression workgroup returns before it reads or writes anything: its window, tail, ring and five integers are byte for byte what
+// they were -- and so reset[s] != 0 with m_s == 0 is ignored (the caller keeps it for the call that brings the stream's next step).
+//
 // Workspace (tcr_scan_workspace_bytes), regions 256-byte aligned:
 //   staging [R][stage_stride] | frame rows [R][n_coef][F + 8] | windows [R G][n_coef][Tp] (2-D graph: planes [R G][T n_coef + 8])
 //   | logits, probs [R G][C] | network at R G.
@@ -178,6 +190,32 @@ __global__ __launch_bounds__(256) void scan_stage_ragged_kernel(const ScanChunkA
     }
 }
 
+// The ragged staging row of a call with a state: positions before the call come from the last tail_len samples of the prefix, the
+// stream's tail (zeros when it is fresh); everything else is scan_stage_ragged_kernel.
+__global__ __launch_bounds__(256) void scan_stage_ragged_tail_kernel(const ScanChunkArgs a, const int bx) {
+    const int64_t r = blockIdx.x / (unsigned)bx;
+    const int part = (int)(blockIdx.x - (unsigned)r * bx);
+    const int64_t q = a.q0 + r;
+    const int n = ragged_signal(a.group_off, a.n_sig, q);
+    const int64_t g = q - a.group_off[n];
+    const int64_t first = a.step_off[n], len = (a.step_off[n + 1] - first) * a.k_hop;
+    const float* src = a.samples + first * a.k_hop;
+    const int tail_len = a.st.tail_len;
+    const float* tail = scan_fresh(a.st, n) ? nullptr : a.st.tail + (size_t)n * tail_len + tail_len;      // (indexed by pos < 0)
+    const int64_t base = (g * a.G + 1) * a.k_hop - a.n_prefix;
+    float* dst = a.stage + r * a.stride;
+    for (int64_t x = (int64_t)part * 256 + threadIdx.x; x < a.stride; x += (int64_t)bx * 256) {
+        const int64_t pos = base + x;
+        float v = 0.f;
+        if (pos >= 0) {
+            if (pos < len) v = src[pos];
+        } else if (tail && pos + tail_len >= 0) {
+            v = tail[pos];
+        }
+        dst[x] = v;
+    }
+}
+
 // One workgroup per window slot b = r G + j (step i = g G + j): column t is column j k + t of frame row r when new frame
 // (i + 1) k - T + t >= 0 or the signal is fresh, else column (i + 1) k + t of the carried window; the halo is zero.  PLANES (2-D
 // graph): the same window as its [T x n_coef] plane, written in plane order (coalesced): plane offset t n_coef + c <- window column t,
@@ -185,18 +223,21 @@ __global__ __launch_bounds__(256) void scan_stage_ragged_kernel(const ScanChunkA
 // features_to_plane_kernel.  CARRIED: the call has a state; without one no column is carried, and the instance is the plain copy
 // (the test at run time cost tcr_scan 5 % of this kernel, profiles/scan_unify_kernel_stats.csv).  RAGGED: the windows are compact --
 // slot b is packed step p0 + b, whose signal, step, group and frame row come from the prefix tables -- so the chunk's slots are
-// its live steps only and the network writes their rows of the caller's outputs itself.
+// its live steps only and the network writes their rows of the caller's outputs itself.  CARRIED && RAGGED: the slot's signal is a
+// stream of the state and i its step within the call, so the carried columns are those of the dense arm.
 template <bool PLANES, bool CARRIED, bool RAGGED = false>
 __global__ __launch_bounds__(256) void scan_gather_kernel(const ScanChunkArgs a) {
-    static_assert(!(CARRIED && RAGGED), "ragged signals are fresh");
     const int b = blockIdx.x;
     int r, j;
+    int64_t rs = 0, ri1 = 0;                                                    // RAGGED: the slot's stream and (i + 1) k
     if constexpr (RAGGED) {
         const int64_t p = a.p0 + b;
         const int n = ragged_signal(a.step_off, a.n_sig, p);
         const int64_t i = p - a.step_off[n], g = i / a.G;
         j = (int)(i - g * a.G);
         r = (int)(a.group_off[n] + g - a.q0);
+        rs = n;
+        ri1 = (i + 1) * a.k;
     } else {
         r = b / a.G;
         j = b - r * a.G;
@@ -204,7 +245,10 @@ __global__ __launch_bounds__(256) void scan_gather_kernel(const ScanChunkArgs a)
     const float* src = a.frames + (size_t)r * a.n_coef * a.ftp + j * a.k;      // window column x <- frame-row column j k + x
     const float* old = src;                                                     // (not read while sh = T)
     int sh = a.T;                                                               // carried columns: t < T - sh
-    if constexpr (CARRIED) {
+    if constexpr (CARRIED && RAGGED) {
+        if (ri1 < a.T && !scan_fresh(a.st, rs)) sh = (int)ri1;
+        old = a.st.window + (size_t)rs * a.n_coef * a.tp + sh;
+    } else if constexpr (CARRIED) {
         const int64_t q = a.q0 + r, s = q / a.groups, g = q - s * a.groups;
         const int64_t i1 = (g * a.G + j + 1) * a.k;                             // (i + 1) k
         if (i1 < a.T && !scan_fresh(a.st, s)) sh = (int)i1;
@@ -269,6 +313,40 @@ __global__ __launch_bounds__(256) void scan_carry_kernel(const ScanChunkArgs a) 
     for (int i = tid; i < tail_len; i += 256) tail[i] = i < keep ? s_tail[i] : src[a.L - tail_len + i];
 }
 
+// scan_carry_kernel of a ragged call: one workgroup per stream s0 + blockIdx.x of a range whose streams with steps all have their
+// last group in the chunk; a stream without steps in between returns at once.  The window is that of the stream's last live slot,
+// step_off[s + 1] - 1 - p0 (the slots are compact); the tail comes from the stream's own packed samples.
+template <bool PLANES>
+__global__ __launch_bounds__(256) void scan_carry_ragged_kernel(const ScanChunkArgs a) {
+    __shared__ float s_tail[kMaxTail];
+    const int64_t s = a.s0 + blockIdx.x;
+    const int tid = threadIdx.x;
+    const int64_t first = a.step_off[s], m = a.step_off[s + 1] - first;
+    if (m == 0) return;
+    const int64_t b = first + m - 1 - a.p0;
+    const int64_t L = m * a.k_hop;
+    const int win_elems = a.n_coef * a.tp;
+    float* wdst = a.st.window + s * win_elems;
+    if constexpr (PLANES) {
+        const float* wsrc = a.windows + b * (a.T * a.n_coef + 2 * kHalo) + kHalo;
+        for (int i = tid; i < win_elems; i += 256) {
+            const int c = i / a.tp, t = i - c * a.tp - kHalo;
+            wdst[i] = t >= 0 && t < a.T ? wsrc[t * a.n_coef + c] : 0.f;
+        }
+    } else {
+        const float* wsrc = a.windows + b * win_elems;
+        for (int i = tid; i < win_elems; i += 256) wdst[i] = wsrc[i];
+    }
+    const int tail_len = a.st.tail_len;
+    const bool rst = scan_fresh(a.st, s);
+    float* tail = a.st.tail + s * tail_len;
+    const float* src = a.samples + first * a.k_hop;
+    const int keep = L < tail_len ? (int)(tail_len - L) : 0;                   // old tail samples L .. tail_len - 1 stay
+    for (int i = tid; i < keep; i += 256) s_tail[i] = rst ? 0.f : tail[L + i];
+    __syncthreads();
+    for (int i = tid; i < tail_len; i += 256) tail[i] = i < keep ? s_tail[i] : src[L - tail_len + i];
+}
+
 struct ScanScatterArgs {
     const float* logits_in;     // [R G][C]
     const float* probs_in;
@@ -311,9 +389,9 @@ struct ScanDetectArgs {
 // min_count) and the candidate flag.  Consecutive lanes read consecutive floats.  CARRIED: the call has a state; without one the
 // ring is never read, and the instance has no test for it (at run time it doubled this kernel's time for tcr_scan).  RAGGED: w is
 // a packed step; i is relative to its signal's first row, so count = min(i + 1, W) never reaches the previous signal's rows.
+// CARRIED && RAGGED: the stream's own head0 and count0, the steps before the call from its ring slots.
 template <bool CARRIED, bool RAGGED = false>
 __global__ __launch_bounds__(256) void scan_smooth_kernel(const ScanDetectArgs a) {
-    static_assert(!(CARRIED && RAGGED), "ragged signals are fresh");
     __shared__ float s_sm[256];
     const int C = a.C, W = a.W;
     const int per = 256 / C;
@@ -568,10 +646,13 @@ size_t scan_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_model_ref* m,
 // scan_run's ragged arm: the same stages over chunks of flattened groups, with the prefix tables in place of q / groups and
 // n steps + i.  A chunk's live steps are the packed steps p(q0) .. p(q0 + rows) - 1 (a signal's groups cover its steps in order), so
 // its windows are gathered compactly, the network runs at the batch of its live steps and writes their rows of the caller's logits
-// and probs itself: no scatter.  The slots past a signal's last step cost front-end frames only.
+// and probs itself: no scatter.  The slots past a signal's last step cost front-end frames only.  With a state st
+// (tcr_stream_scan_ragged) the signals are its streams: the carried forms of the stages, and after a chunk's gather the write-back
+// of the streams whose last group is one of its rows (the header's state ordering).
 int scan_run_ragged(const tcr_frontend_cfg& cfg, const void* plan_dev, const tcr_model_ref& m, const ModelIO& io, int n_signals, int k,
-                    const tcr_detect_cfg& det, const float* samples, const ScanRagged& rg, void* workspace, size_t ws_bytes, float* logits,
-                    float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, hipStream_t s, const char* what) {
+                    const tcr_detect_cfg& det, const float* samples, const ScanState& st, const ScanRagged& rg, void* workspace,
+                    size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, hipStream_t s,
+                    const char* what) {
     const int64_t* so = rg.step_off;
     ScanGeom g;
     TCR_TRY(scan_ragged_chunking(cfg, m, io, k, so, n_signals, ws_bytes, what, g));
@@ -590,10 +671,13 @@ int scan_run_ragged(const tcr_frontend_cfg& cfg, const void* plan_dev, const tcr
     }
     float* ws = static_cast<float*>(workspace);
     ScanChunkArgs ca{};
-    ca.samples = samples; ca.stage = ws + g.stage_off; ca.frames = ws + g.frames_off; ca.windows = ws + g.win_off; ca.st = ScanState{};
+    ca.samples = samples; ca.stage = ws + g.stage_off; ca.frames = ws + g.frames_off; ca.windows = ws + g.win_off; ca.st = st;
     ca.k_hop = (int64_t)k * cfg.hop; ca.stride = g.stage_stride; ca.n_prefix = cfg.n_samples; ca.G = G; ca.k = k; ca.T = g.T; ca.tp = g.tp;
     ca.n_coef = g.n_coef; ca.ftp = tcr_padded_len(g.F); ca.step_off = rg.tables; ca.group_off = rg.tables + n_signals + 1; ca.n_sig = n_signals;
-    const auto gather = g.planes ? scan_gather_kernel<true, false, true> : scan_gather_kernel<false, false, true>;
+    const bool carried = st.window != nullptr;
+    const auto gather = g.planes ? (carried ? scan_gather_kernel<true, true, true> : scan_gather_kernel<true, false, true>)
+                                 : (carried ? scan_gather_kernel<false, true, true> : scan_gather_kernel<false, false, true>);
+    int next = 0;                                       // carried: the first stream whose write-back is still to come
     // the packed step of flattened group q's first slot
     const auto first_step = [&](int64_t q) {
         if (q >= total_groups) return total_steps;
@@ -606,19 +690,41 @@ int scan_run_ragged(const tcr_frontend_cfg& cfg, const void* plan_dev, const tcr
         ca.q0 = q0; ca.rows = rows; ca.p0 = first_step(q0);
         const int live = (int)(first_step(q0 + rows) - ca.p0);
         const int bx = (int)std::max<int64_t>(1, std::min(stage_blocks, ceil_div64(8 * (int64_t)device_cus(), rows)));
-        hipLaunchKernelGGL(scan_stage_ragged_kernel, dim3((unsigned)((int64_t)rows * bx)), dim3(256), 0, s, ca, bx);
-        TCR_TRY(check_launch("scan_stage_ragged_kernel"));
+        if (carried) {
+            hipLaunchKernelGGL(scan_stage_ragged_tail_kernel, dim3((unsigned)((int64_t)rows * bx)), dim3(256), 0, s, ca, bx);
+            TCR_TRY(check_launch("scan_stage_ragged_tail_kernel"));
+        } else {
+            hipLaunchKernelGGL(scan_stage_ragged_kernel, dim3((unsigned)((int64_t)rows * bx)), dim3(256), 0, s, ca, bx);
+            TCR_TRY(check_launch("scan_stage_ragged_kernel"));
+        }
         TCR_TRY(stream_frontend(cfg, plan_dev, ca.stage, g.stage_stride, rows, g.F, ca.frames, s, ca.ftp));
         hipLaunchKernelGGL(gather, dim3(live), dim3(256), 0, s, ca);
         TCR_TRY(check_launch("scan_gather_kernel"));
+        if (carried) {
+            // the streams with steps whose last group (go[n + 1] - 1, increasing over them) is one of this chunk's rows: next .. the
+            // last such one, streams without steps in between included (their workgroups return at once)
+            int s_lo = -1, s_hi = -1;
+            for (; next < n_signals && (so[next + 1] == so[next] || go[next + 1] - 1 < q0 + rows); ++next) {
+                if (so[next + 1] == so[next]) continue;
+                if (s_lo < 0) s_lo = next;
+                s_hi = next;
+            }
+            if (s_lo >= 0) {
+                ca.s0 = s_lo;
+                if (g.planes) hipLaunchKernelGGL(scan_carry_ragged_kernel<true>, dim3((unsigned)(s_hi - s_lo + 1)), dim3(256), 0, s, ca);
+                else hipLaunchKernelGGL(scan_carry_ragged_kernel<false>, dim3((unsigned)(s_hi - s_lo + 1)), dim3(256), 0, s, ca);
+                TCR_TRY(check_launch("scan_carry_ragged_kernel"));
+            }
+        }
         TCR_TRY(model_forward(m, ca.windows, live, ws + g.net_off, ws_bytes - (size_t)g.net_off * sizeof(float), logits + ca.p0 * g.classes,
                               probs + ca.p0 * g.classes, s));
     }
     ScanDetectArgs da;
-    da.probs = probs; da.smoothed = smoothed; da.top = top; da.score = score; da.is_new = is_new; da.st = ScanState{}; da.steps = total_steps;
+    da.probs = probs; da.smoothed = smoothed; da.top = top; da.score = score; da.is_new = is_new; da.st = st; da.steps = total_steps;
     da.N = n_signals; da.C = g.classes; da.W = det.average_steps; da.min_count = det.min_count; da.suppression = det.suppression_steps;
     da.threshold = det.threshold; da.step_off = rg.tables;
-    hipLaunchKernelGGL((scan_smooth_kernel<false, true>), dim3((unsigned)ceil_div64(total_steps, 256 / g.classes)), dim3(256), 0, s, da);
+    if (carried) hipLaunchKernelGGL((scan_smooth_kernel<true, true>), dim3((unsigned)ceil_div64(total_steps, 256 / g.classes)), dim3(256), 0, s, da);
+    else hipLaunchKernelGGL((scan_smooth_kernel<false, true>), dim3((unsigned)ceil_div64(total_steps, 256 / g.classes)), dim3(256), 0, s, da);
     TCR_TRY(check_launch("scan_smooth_kernel"));
     hipLaunchKernelGGL(scan_suppress_kernel<true>, dim3(n_signals), dim3(256), 0, s, da);
     return check_launch("scan_suppress_kernel");
@@ -631,8 +737,8 @@ int scan_run(const tcr_frontend_cfg& cfg, const void* plan_dev, const tcr_model_
              const ScanRagged* rg = nullptr) {
     ScanGeom g;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (rg) return scan_run_ragged(cfg, plan_dev, m, io, n_signals, k, det, samples, *rg, workspace, ws_bytes, logits, probs, smoothed, top,
-                                   score, is_new, s, what);
+    if (rg) return scan_run_ragged(cfg, plan_dev, m, io, n_signals, k, det, samples, st, *rg, workspace, ws_bytes, logits, probs, smoothed,
+                                   top, score, is_new, s, what);
     TCR_TRY(scan_chunking(cfg, m, io, k, steps, n_signals, ws_bytes, what, g));
     const int G = g.G;
     const int64_t groups = ceil_div64(steps, G), total_groups = groups * n_signals;
@@ -751,11 +857,65 @@ int scan_ragged(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_mod
                     ws_bytes - tables_bytes, logits, probs, smoothed, top, score, is_new, stream, what, &rg);
 }
 
+// tcr_stream_scan_ragged: scan_ragged's checks with the streams of a state in place of fresh signals (a stream without steps is
+// allowed, a call without any step is not), then the ragged pipeline from and to the state.
+int stream_scan_ragged(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* m, int n_streams, const int64_t* sample_offsets,
+                       int k, const tcr_detect_cfg* det, const float* samples, const uint8_t* reset, void* state, void* workspace,
+                       size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream,
+                       const char* what) {
+    TCR_REQUIRE(plan_dev && m && m->params && m->aux && det && sample_offsets && state && workspace, "%s: null argument", what);
+    ModelIO io;
+    TCR_TRY(stream_check(cfg, m, n_streams, k, det, what, io));
+    const size_t tables_bytes = scan_ragged_tables_bytes(n_streams);
+    TCR_REQUIRE(tables_bytes <= ws_bytes, "%s: %d streams are more than the max_signals the workspace's offset tables hold (%lld)", what,
+                n_streams, (long long)(ws_bytes / (2 * sizeof(int64_t))) - 1);
+    const int64_t khop = (int64_t)k * cfg->hop;
+    TCR_REQUIRE(sample_offsets[0] == 0, "%s: sample_offsets must start at 0 (got %lld)", what, (long long)sample_offsets[0]);
+    std::vector<int64_t> so((size_t)n_streams + 1);
+    so[0] = 0;
+    for (int n = 0; n < n_streams; ++n) {
+        const int64_t len = sample_offsets[n + 1] - sample_offsets[n];
+        TCR_REQUIRE(len >= 0, "%s: sample_offsets decrease at stream %d (%lld after %lld)", what, n, (long long)sample_offsets[n + 1],
+                    (long long)sample_offsets[n]);
+        TCR_REQUIRE(len % khop == 0, "%s: the length %lld of stream %d is not a multiple of k * hop = %lld", what, (long long)len, n,
+                    (long long)khop);
+        so[n + 1] = so[n] + len / khop;
+    }
+    const int64_t total_steps = so[n_streams];
+    TCR_REQUIRE(total_steps > 0, "%s: no stream has a whole step (total_steps == 0)", what);
+    TCR_REQUIRE(total_steps * io.classes < ((int64_t)1 << 31), "%s: %lld steps in all is too large", what, (long long)total_steps);
+    TCR_REQUIRE(samples && logits && probs && smoothed && top && score && is_new, "%s: null argument", what);
+    const StreamGeom sg = stream_geom(*cfg, *m, io, n_streams, k, det->average_steps);
+    float* st = static_cast<float*>(state);
+    const ScanState carried{st + sg.win_off, st + sg.tail_off, st + sg.ring_off, reinterpret_cast<int*>(st + sg.ist_off), reset, sg.tail_len};
+    const ScanRagged rg{so.data(), static_cast<int64_t*>(workspace)};
+    return scan_run(*cfg, plan_dev, *m, io, n_streams, 0, k, *det, samples, carried, static_cast<char*>(workspace) + tables_bytes,
+                    ws_bytes - tables_bytes, logits, probs, smoothed, top, score, is_new, stream, what, &rg);
+}
+
 }  // namespace
 
 }  // namespace tcr
 
 using namespace tcr;
+
+extern "C" int tcr_stream_scan_ragged(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params,
+                                      const float* frozen_ss, int n_streams, const int64_t* sample_offsets, int k, const tcr_detect_cfg* det,
+                                      const float* samples, const uint8_t* reset, void* state, void* workspace, size_t ws_bytes,
+                                      float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new,
+                                      void* stream) {
+    const tcr_model_ref m = tcresnet_ref(net, params, frozen_ss);
+    return stream_scan_ragged(cfg, plan_dev, &m, n_streams, sample_offsets, k, det, samples, reset, state, workspace, ws_bytes, logits, probs,
+                              smoothed, top, score, is_new, stream, "tcr_stream_scan_ragged");
+}
+
+extern "C" int tcr_stream_scan_ragged_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_streams,
+                                        const int64_t* sample_offsets, int k, const tcr_detect_cfg* det, const float* samples,
+                                        const uint8_t* reset, void* state, void* workspace, size_t ws_bytes, float* logits, float* probs,
+                                        float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream) {
+    return stream_scan_ragged(cfg, plan_dev, model, n_streams, sample_offsets, k, det, samples, reset, state, workspace, ws_bytes, logits,
+                              probs, smoothed, top, score, is_new, stream, "tcr_stream_scan_ragged_m");
+}
 
 extern "C" size_t tcr_scan_ragged_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_model_ref* model, int k, int max_windows,
                                                   int max_signals) {

@@ -2,7 +2,7 @@
 
     python scan_audio.py --frozen MODEL.npz --wav a.wav [b.wav ...] [--frames_per_step k] [--labels l0,l1,...]
                          [--average_window_ms MS] [--detection_threshold P] [--suppression_ms MS] [--min_count N]
-                         [--max_windows B] [--summary] [--chunk_seconds X | --ragged]
+                         [--max_windows B] [--summary] [--chunk_seconds X | --ragged | --ragged_chunk_seconds X]
 
 The files (16-bit PCM) come from `audio_input.Recordings`, zero-padded to the longest, and are scanned in one
 `scanning.KeywordScanner` call; samples that do not fill a whole step are dropped (noted on stderr).  A file at another sample rate
@@ -15,7 +15,10 @@ detection on stdout,  file,time_ms,label,score,  in step order and, within a ste
 window that fired (every file starts as if it had heard one clip of silence).  --summary adds one JSON line on stderr: the hours
 of audio scanned (each file's whole steps), the detections per label and the detections per hour.  With --ragged (not together with
 --chunk_seconds) every file is scanned at its own whole-step length in one `KeywordScanner.scan_ragged` call: nothing is padded, the
-lines have the same format and order, and no file has steps (or detections) past its own end."""
+lines have the same format and order, and no file has steps (or detections) past its own end.  --ragged_chunk_seconds X (on its own:
+not with --chunk_seconds or --ragged) is that run in bounded host memory: every file is read X seconds at a time at its own length --
+its next whole steps, none once it has ended -- and the chunks go to one `StreamingDetector.push_ragged`; stdout and the --summary
+line are those of --ragged, byte for byte."""
 from __future__ import annotations
 
 import argparse
@@ -45,7 +48,10 @@ def main(args) -> int:
     det, run = open_detector(FrozenModel.load(args.frozen), args)
     rec = Recordings(args.wav, det)
     names, counts = label_names(args, det), {}
-    if args.ragged:
+    if args.ragged_chunk_seconds is not None:
+        for i0, packed, lengths in rec.ragged_chunks(args.ragged_chunk_seconds):
+            print_detections_ragged(rec, run((packed, lengths)), names, counts, i0)
+    elif args.ragged:
         if rec.n_steps > 0:
             print_detections_ragged(rec, det.scan_ragged(rec.packed()), names, counts)
     else:

@@ -6,7 +6,8 @@ one-second window kept on the device and smooths the posteriors into detections 
 rule, stated in steps: see tcr_stream_step).  After a push, `window()` is bitwise the ordinary `Frontend` of each stream's last
 n_samples samples, and the logits / probs are bitwise the network's eval forward of those windows at batch S
 (`TCResNet.forward_frozen`, `DSCNN.forward_infer`, `Graph2D.forward_infer`).  `push_many` (tcr_stream_scan) appends many steps at
-once at the offline scan's throughput, bitwise the same pushes.  Every model family runs: TC-ResNet, DS-CNN and the 2-D graphs
+once at the offline scan's throughput, bitwise the same pushes; `push_ragged` (tcr_stream_scan_ragged) does so with a step count of
+its own for every stream, none included.  Every model family runs: TC-ResNet, DS-CNN and the 2-D graphs
 (tcr_model_ref of include/tcresnet_hip.h).
 """
 from __future__ import annotations
@@ -206,7 +207,8 @@ class StreamingDetector(_Detection):
 
     `push_many` advances every stream by many steps in one call at the offline scan's throughput (tcr_stream_scan), bitwise the
     same pushes; max_windows (default scanning.DEFAULT_MAX_WINDOWS) bounds its windows per network launch and sizes the scan
-    workspace it allocates on first use."""
+    workspace it allocates on first use.  `push_ragged` advances every stream by its own number of steps (tcr_stream_scan_ragged):
+    a stream without steps in a call stays exactly where it is."""
 
     def __init__(self, net: Network, frontend: Frontend, n_streams: int, frames_per_step: int = 1, average_window_ms: float = 1000,
                  min_count: int = 3, detection_threshold: float = 0.5, suppression_ms: float = 1500,
@@ -219,6 +221,7 @@ class StreamingDetector(_Detection):
             max_windows = DEFAULT_MAX_WINDOWS
         self.max_windows = int(max_windows)
         self._scan_ws: Optional[torch.Tensor] = None
+        self._ragged_ws: Optional[torch.Tensor] = None
         cfg = frontend.cfg
         S, lib = self.n_streams, self.lib
         if S <= 0:
@@ -325,6 +328,65 @@ class StreamingDetector(_Detection):
         lib.check(lib.tcr_stream_scan_m(C.byref(fe.cfg), fe.plan.data_ptr(), C.byref(ref), S, L, self.k, C.byref(self.det),
                                         samples.data_ptr(), self._take_reset(), self.state.data_ptr(), ws.data_ptr(), ws.numel() * 4,
                                         *(t.data_ptr() for t in out), net._stream()), "tcr_stream_scan")
+        self._after_call()
+        return out
+
+    def push_ragged(self, signals):
+        """Every stream advances by its own number of steps in one call (tcr_stream_scan_ragged): `signals` is a list of S 1-D float32
+        device tensors, stream s's m_s * k * hop new samples (m_s = 0: an empty tensor, the stream stays where it is), or (packed,
+        lengths) -- one 1-D float32 device tensor holding them one after the other and their lengths in samples: the two forms
+        `KeywordScanner.scan_ragged` takes.  Returns a scanning.RaggedScanOutput of new tensors (`offsets` in steps, `signal(s)` views
+        of stream s's rows): stream s's rows are bitwise what m_s `push` calls return for it, and it is left as they leave it, so
+        `push`, `push_many` and `push_ragged` mix freely.  A pending `reset` applies to a stream at the first call in which it has
+        steps and stays pending for a stream without steps in this call; `out` is not touched.  The weight / fold rules are `push`'s.
+        The ragged workspace (sized by max_windows and n_streams) is allocated on the first call.  At least one stream must have a
+        step."""
+        from .scanning import RaggedScanOutput
+        S, step = self.n_streams, self.step_samples
+        if isinstance(signals, tuple) and len(signals) == 2 and isinstance(signals[0], torch.Tensor):
+            packed, lengths = signals[0], np.asarray(signals[1], dtype=np.int64).reshape(-1)
+            if packed.dim() != 1:
+                raise TcrError(f"push_ragged expects a packed 1-D tensor, got shape {tuple(packed.shape)}")
+        else:
+            signals = list(signals)
+            for n, x in enumerate(signals):
+                if not isinstance(x, torch.Tensor) or x.dim() != 1:
+                    raise TcrError(f"push_ragged expects 1-D tensors, stream {n} is {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+            lengths = np.array([int(x.shape[0]) for x in signals], dtype=np.int64)
+            packed = signals[0] if len(signals) == 1 else (torch.cat(signals) if signals else None)
+        if int(lengths.size) != S:
+            raise TcrError(f"push_ragged expects {S} signals (one per stream, empty for a stream without steps), got {int(lengths.size)}")
+        offsets = np.zeros(S + 1, dtype=np.int64)
+        np.cumsum(lengths, out=offsets[1:])
+        if int(offsets[-1]) != int(packed.shape[0]) and (lengths >= 0).all():
+            raise TcrError(f"push_ragged: the lengths sum to {int(offsets[-1])} samples, the packed tensor has {int(packed.shape[0])}")
+        self.net._check_tensor(packed, "stream samples")
+        lib, fe, net, dev = self.lib, self.frontend, self.net, self.device
+        if self._ragged_ws is None:
+            nws = lib.tcr_scan_ragged_workspace_bytes(C.byref(fe.cfg), C.byref(self._ref()), self.k, self.max_windows, S)
+            if nws == 0:
+                raise TcrError(f"StreamingDetector.push_ragged: {lib.tcr_last_error().decode()}")
+            self._ragged_ws = torch.empty(nws // 4, dtype=torch.float32, device=dev)
+        ref = self._call_ref()
+        ok = bool((lengths >= 0).all()) and not (lengths % step).any()
+        total = int(offsets[-1]) // step if ok else 0           # (otherwise the call refuses, and the outputs are not written)
+        ncls = net.num_classes
+        f32 = dict(dtype=torch.float32, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        out = RaggedScanOutput(torch.empty((total, ncls), **f32), torch.empty((total, ncls), **f32), torch.empty((total, ncls), **f32),
+                               torch.empty(total, **i32), torch.empty(total, **f32), torch.empty(total, **i32), offsets // step)
+        reset_ptr = None
+        if self._pending is not None:                           # (the call ignores the flag of a stream without steps)
+            self._reset_dev.copy_(torch.from_numpy(self._pending.astype(np.uint8)))
+            reset_ptr = self._reset_dev.data_ptr()
+        ws = self._ragged_ws
+        lib.check(lib.tcr_stream_scan_ragged_m(C.byref(fe.cfg), fe.plan.data_ptr(), C.byref(ref), S, offsets.ctypes.data, self.k,
+                                               C.byref(self.det), packed.data_ptr(), reset_ptr, self.state.data_ptr(), ws.data_ptr(),
+                                               ws.numel() * 4, *(t.data_ptr() for t in out.tensors()), net._stream()),
+                  "tcr_stream_scan_ragged")
+        if self._pending is not None:
+            left = self._pending & (lengths == 0)
+            self._pending = left if left.any() else None
         self._after_call()
         return out
 

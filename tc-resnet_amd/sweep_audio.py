@@ -4,7 +4,7 @@ curve (false rejects against false accepts per hour) from one scan.
     python sweep_audio.py --frozen MODEL.npz --wav a.wav [b.wav ...] --events EVENTS.csv [--thresholds LO:HI:STEP | t0,t1,...]
                           [--tolerance_ms MS] [--keywords l0,l1,...] [--per_label] [--target_fa_per_hour F]
                           [--frames_per_step k] [--labels l0,l1,...] [--average_window_ms MS] [--suppression_ms MS]
-                          [--min_count N] [--max_windows B] [--chunk_seconds X | --ragged]
+                          [--min_count N] [--max_windows B] [--chunk_seconds X | --ragged | --ragged_chunk_seconds X]
 
 The files are read as scan_audio.py reads them (`audio_input.Recordings`: 16-bit PCM, converted to the model's sample rate on the
 device where it differs, only whole steps), zero-padded to the longest and scanned in one call; one `KeywordScanner.sweep` then
@@ -12,7 +12,9 @@ walks the detector's suppression rule at every threshold over each file's true l
 thresholds are).  With --chunk_seconds the files are read and scanned chunk by chunk (scan_audio.py's --chunk_seconds:
 `StreamingDetector.push_many`); either way the chunks' top / score are concatenated on the device and swept once: the output is the
 one-call output, byte for byte.  With --ragged (not together with --chunk_seconds) the files are scanned at their own lengths in
-one `KeywordScanner.scan_ragged` call and swept over its packed rows: the same curve without the padding.  EVENTS.csv has a header and the columns
+one `KeywordScanner.scan_ragged` call and swept over its packed rows: the same curve without the padding; --ragged_chunk_seconds X
+(on its own) reads the files X seconds at a time at their own lengths (`StreamingDetector.push_ragged`), keeps every file's top /
+score rows on the device, puts them back into the packed layout and sweeps once: --ragged's output, byte for byte.  EVENTS.csv has a header and the columns
 file,start_ms,end_ms,label  (file as given to --wav, label one of --labels or a class index).  A detection at time t (the end of
 the window that fired, scan_audio.py's time) hits an event of its label when  start_ms <= t <= end_ms + tolerance_ms; the first
 hit of an event counts as a hit, later ones as duplicates, every other detection as a false accept.
@@ -36,11 +38,11 @@ if __package__ in (None, ""):           # run as a script: import the package th
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from tcresnet_amd.audio_input import Recordings, add_detector_flags, label_names, open_detector
     from tcresnet_amd.deploy import FrozenModel
-    from tcresnet_amd.scanning import ScanOutput
+    from tcresnet_amd.scanning import RaggedScanOutput, ScanOutput
 else:
     from .audio_input import Recordings, add_detector_flags, label_names, open_detector
     from .deploy import FrozenModel
-    from .scanning import ScanOutput
+    from .scanning import RaggedScanOutput, ScanOutput
 
 COLUMNS = ("threshold", "hits", "events", "false_accepts", "duplicates", "frr", "fa_per_hour")
 
@@ -94,7 +96,20 @@ def main(args) -> int:
     if rec.n_steps == 0:
         raise SystemExit("no whole step of audio in the files")
     events = read_events(args.events, args.wav)
-    if args.ragged:
+    if args.ragged_chunk_seconds is not None:
+        tops, scores = [[] for _ in args.wav], [[] for _ in args.wav]      # per file, its rows chunk by chunk
+        for _, packed, lengths in rec.ragged_chunks(args.ragged_chunk_seconds):
+            o = run((packed, lengths))
+            for n in range(len(args.wav)):
+                a, b = int(o.offsets[n]), int(o.offsets[n + 1])
+                if b > a:
+                    tops[n].append(o.top[a:b])
+                    scores[n].append(o.score[a:b])
+        offsets = np.concatenate([[0], np.cumsum([x // rec.step for x in rec.lengths])])
+        out = RaggedScanOutput(None, None, None, torch.cat([t for f in tops for t in f]), torch.cat([t for f in scores for t in f]), None,
+                               offsets)
+        res = scanner.sweep(out, thresholds, events=events, tolerance_ms=args.tolerance_ms, labels=names)
+    elif args.ragged:
         res = scanner.sweep(scanner.scan_ragged(rec.packed()), thresholds, events=events, tolerance_ms=args.tolerance_ms, labels=names)
     else:
         tops, scores = [], []                           # (only what the sweep reads stays on the device)
