@@ -17,8 +17,8 @@ relayout into its planes, which the scan's gather writes directly).
 equal-length signals with the same total audio; the group size the call picks (the library's rule, restated here) and the ratio of
 the front-end frames it computes to the live ones (steps x k) are reported with the times.  --trace_one --ragged runs the ragged
 scan once after a warm-up.  --ab_lib: the 1 x 1 h and 64 x 1 min dense scans through this build and through the library given
-(scripts/build_ref_lib.py), alternating in one process; so do a dense push_many (256 streams x 10 s) and the ragged scan of the
---ragged corpus.
+(scripts/build_ref_lib.py), alternating in one process; so do a dense push_many (256 streams x 10 s), the ragged scan of the
+--ragged corpus and that corpus as one push_ragged of 256 streams: the four scan entries.
 
 --ragged_push: StreamingDetector.push_ragged (tcr_stream_scan_ragged).  server: S = 4096 streams that advance by 0 - 3 steps each
 (seed 0) in one call, next to the lockstep prepared push and push_many of 1 and 2 steps per stream (the ragged call's mean is 1.5):
@@ -243,7 +243,7 @@ def ragged_push_leg(args, fe, net, dev):
 
 
 def ab_leg(args, dev):
-    """The dense scans through this build and through --ab_lib, alternating: medians and ranges of both."""
+    """The four scan entries through this build and through --ab_lib, alternating: medians and ranges of both."""
     import tcresnet_amd as T
     from oracle import numpy_ref as R
     libs = {"this": T._lib.get(), "other": T._lib.load_from(args.ab_lib, "hip", allow_missing=True)}
@@ -268,6 +268,7 @@ def ab_leg(args, dev):
         st = StreamingDetector(net, fe, 256, average_window_ms=1000)
         legs[name + "_push_many_256x10s_ms"] = lambda st=st: time_ms(lambda: st.push_many(ten))
         legs[name + "_scan_ragged_corpus_ms"] = lambda sc=sc: time_ms(lambda: sc.scan_ragged((corpus, cor_len)))
+        legs[name + "_push_ragged_corpus_ms"] = lambda st=st: time_ms(lambda: st.push_ragged((corpus, cor_len)))
     for fn in legs.values():
         fn()
     res = {k: [] for k in legs}

@@ -1,7 +1,11 @@
-// Many detector steps in one call: tcr_stream_scan advances S streams by m steps from their stream state (stream.hip) and writes the
-// state back, bitwise m calls of tcr_stream_step -- outputs and state; tcr_scan is the same call from a fresh state without the
-// write-back: every step of N recordings, bitwise what a fresh streaming detector returns push by push.  One pipeline runs both; the
-// state (ScanState) is its variable part, and "fresh" is what reset[s] != 0 means as well.
+// Many detector steps in one call, over one chunk pipeline with three compile-time axes:
+//   CARRIED  the call starts from the stream state of stream.hip and writes it back (tcr_stream_scan, tcr_stream_scan_ragged: bitwise
+//            that many calls of tcr_stream_step, outputs and state) or starts fresh and writes nothing back (tcr_scan, tcr_scan_ragged:
+//            every step of N recordings, bitwise what a fresh streaming detector returns push by push).  The state (ScanState) is the
+//            pipeline's variable part, and "fresh" is what reset[s] != 0 means as well;
+//   RAGGED   every signal (stream) brings its own number of steps, packed one after the other (the _ragged entries), or all bring the
+//            same number (dense);
+//   PLANES   the windows are the 2-D graph's [T x n_coef] planes or planar [n_coef][T + 2 TCR_HALO].
 //
 // In frames of  x = tail ++ samples  (the stream's tail, zeros when fresh, then the call's L = m k hop samples), new frame j covers
 // x[j hop, j hop + win): the samples tcr_stream_step's staging rows hold for the same frame, and a frame is a pure function of its
@@ -12,47 +16,45 @@
 // suppression state changes only at candidate steps (count >= min_count && score > threshold).  So the windows are computed at the
 // network's batch throughput and only the suppression is sequential.
 //
-// Steps are cut into groups of G consecutive steps of one signal; group g of signal n is one front-end row of F = G k + T - k frames
-// from new frame g G k + k - T on.  A chunk is R consecutive groups (flattened over signals) = R G window slots:
-//   scan_stage_kernel     the R staging rows (tail ++ samples, zeros outside);
+// Steps are cut into groups of G consecutive steps of one signal; a group is one front-end row of F = G k + T - k frames from new frame
+// g G k + k - T on.  The groups are flattened over the signals in order (dense: signal q / groups, group q % groups; ragged: the prefix
+// table group_off), and a chunk is R consecutive groups:
+//   staging               the R rows (tail ++ samples, zeros outside): scan_stage_kernel, a thread per sample, or
+//                         scan_stage_ragged_kernel<CARRIED>, whose workgroups look their row's signal up once;
 //   frontend_pk3_kernel   <.., STREAM = true> over R rows of F frames into frame rows [R][n_coef][F + 2 TCR_HALO] (column 0 on);
-//   scan_gather_kernel    the windows from the frame rows, or from carried columns for negative frames: planar
-//                         [R G][n_coef][T + 2 TCR_HALO] (zero halo), or the 2-D graph's planes [R G][1][T n_coef + 2 TCR_HALO];
-//   scan_carry_kernel     with a state: window and tail write-back of the streams whose last group is in this chunk (their last
-//                         step's window, gathered just before; the last tail_len samples of x, the old tail read before it is
-//                         written); a stream's groups are consecutive, so no later chunk reads its window or tail;
-//   the network at batch R G (detect_model.h: tcr_net_forward_frozen, tcr_dscnn_forward_infer or tcr_g2d_forward_infer, unchanged);
-//   scan_scatter_kernel   logits / probs of the slots that are steps (g G + j < steps) into the caller's [N][steps][C].
-// Slots past a signal's last step (the last group of a signal may be short) are computed and dropped.  Then, once per call:
-//   scan_smooth_kernel    a lane per (signal, step, class): smoothed over count_i = min(count0 + i + 1, W) vectors, those of steps
-//                         before the call from ring slots (head0 - d) mod W, oldest first; top, score and the candidate flag
-//                         (is_new = top + 1 or 0);
-//   scan_suppress_kernel  a workgroup per signal: the ring write-back (the last min(W, m) vectors at slots (head0 + i) mod W: the
-//                         smoothing has read the old ones), the detections in step order from the carried prev_label and
+//   scan_gather_kernel    <PLANES, CARRIED, RAGGED>: the windows from the frame rows, or from carried columns for negative frames,
+//                         [slots][n_coef][T + 2 TCR_HALO] (zero halo) or the planes [slots][1][T n_coef + 2 TCR_HALO];
+//   scan_carry_kernel     <PLANES, RAGGED>, with a state: window and tail write-back of the streams whose last group is in this chunk;
+//   the network at the batch of the slots (detect_model.h: tcr_net_forward_frozen, tcr_dscnn_forward_infer or tcr_g2d_forward_infer);
+//   scan_scatter_kernel   dense only: logits / probs of the slots that are steps (g G + j < steps) into the caller's [N][steps][C].
+// Dense, a chunk has R G slots; those past a signal's last step (the last group of a signal may be short) are computed and dropped.
+// Ragged, a signal's groups cover its steps in order, so a chunk's live steps are one contiguous range of packed steps: the gather
+// writes them compactly (slot = p - p(q0)), the network runs at the batch of the live steps and writes their rows of the caller's
+// logits / probs itself -- no scatter, and the dead slots of a short last group cost front-end frames only.  Then, once per call:
+//   scan_smooth_kernel    <CARRIED, RAGGED>, a lane per (signal, step, class): smoothed over count_i = min(count0 + i + 1, W) vectors,
+//                         those of steps before the call from ring slots (head0 - d) mod W, oldest first; top, score and the candidate
+//                         flag (is_new = top + 1 or 0);
+//   scan_suppress_kernel  <RAGGED>, a workgroup per signal: the ring write-back (the last min(W, m) vectors at slots (head0 + i) mod W:
+//                         the smoothing has read the old ones), the detections in step order from the carried prev_label and
 //                         prev_step - n0, rewritten into is_new, then the five detector integers.
 //
-// Ragged (tcr_scan_ragged): N fresh signals of different lengths, packed.  The same stages, with two prefix tables in place of
-// q / groups and n steps + i: step_off [N + 1] (signal n's steps are packed rows step_off[n] ..) and, once G is chosen, group_off
-// [N + 1] (its ceil(steps_n / G) groups are flattened rows group_off[n] ..); the host builds both and uploads them to the front of
-// the workspace, and the kernels find the signal of a flattened group or a packed step by binary search (ragged_signal).  A signal's
-// groups cover its steps in order, so a chunk's live steps are one contiguous range of packed steps: the gather writes them
-// compactly (slot = p - p(q0)), the network runs at the batch of the live steps and writes their rows of the caller's logits /
-// probs itself -- no scatter, and the dead slots of a short last group cost front-end frames only.  The smoothing counts from the
-// signal's first row and the suppression walks the signal's own rows, so a signal's rows are bitwise its dense scan alone.  G is
-// the group size with the fewest front-end frames over the call (scan_ragged_chunking).  The ragged arms are compile-time instances
-// (RAGGED) or sibling kernels: the dense instances carry no test for them.
+// The ragged tables: step_off [N + 1] (signal n's steps are packed rows step_off[n] ..) and, once G is chosen, group_off [N + 1] (its
+// ceil(steps_n / G) groups are flattened rows group_off[n] ..); the host builds both and uploads them to the front of the workspace, and
+// the kernels find the signal of a flattened group or a packed step by binary search (ragged_signal).  The smoothing counts from the
+// signal's first row and the suppression walks the signal's own rows, so a signal's rows are bitwise its dense scan alone.  The results
+// do not depend on G: dense takes balanced groups, ragged the group size with the fewest front-end frames over the call (scan_chunking).
 //
-// Ragged with a state (tcr_stream_scan_ragged): stream s advances by m_s >= 0 steps of its own, samples and rows packed as above.  The
-// ragged stages with the carried arms: the staging row reads the stream's tail in front of its samples (scan_stage_ragged_tail_kernel;
-// with a small G several groups of a stream reach into the prefix), the gather takes the first T - (i + 1) k columns of a stream's
-// early steps from its carried window (CARRIED && RAGGED), the smoothing counts from the stream's count0 and reads its ring, the
-// suppression is the ragged instance run with the state, and scan_carry_ragged_kernel writes window and tail back.  State ordering:
-// the flattened groups are ordered by stream (group_off), so a stream's groups are consecutive rows here too and the dense argument
-// holds -- a stream's window and tail are written only in the chunk that holds its last group, group_off[s + 1] - 1, after that
-// chunk's stage and gather, and no later chunk has a group of that stream; ring and integers are written by the suppression, after
-// the smoothing of every stream has read them.  A stream without steps (m_s == 0) has no group, no row and no carry, and its
-// suppression workgroup returns before it reads or writes anything: its window, tail, ring and five integers are byte for byte what
-// they were -- and so reset[s] != 0 with m_s == 0 is ignored (the caller keeps it for the call that brings the stream's next step).
+// State ordering.  A stream's groups are consecutive flattened rows (dense and ragged), so its window and tail are written only in the
+// chunk that holds its last group, after that chunk's stage and gather (the window is its last step's, gathered just before; the tail
+// the last tail_len samples of x, the old samples that survive a short call read before it is written), and no later chunk has a group
+// of that stream to read them; ring and integers are written by the suppression, after the smoothing of every stream has read them.  A
+// stream without steps (m_s == 0, ragged) has no group, no row and no carry, and its suppression workgroup returns before it reads or
+// writes anything: its window, tail, ring and five integers are byte for byte what they were -- and so reset[s] != 0 with m_s == 0 is
+// ignored (the caller keeps it for the call that brings the stream's next step).
+//
+// The axes are compile-time instances and not tests at run time because the dense fresh scan pays for such tests: the state test cost
+// tcr_scan 5 % of the gather and doubled its smoothing (profiles/scan_unify_kernel_stats.csv), and the dense instances carry no table
+// lookup.  The dense staging keeps its thread-per-sample form.
 //
 // Workspace (tcr_scan_workspace_bytes), regions 256-byte aligned:
 //   staging [R][stage_stride] | frame rows [R][n_coef][F + 8] | windows [R G][n_coef][Tp] (2-D graph: planes [R G][T n_coef + 8])
@@ -173,7 +175,10 @@ __global__ __launch_bounds__(256) void scan_stage_kernel(const ScanChunkArgs a) 
 }
 
 // The ragged staging row: bx workgroups per row, so that the row's signal is looked up once per thread and not once per sample.
-// Signal n's samples start at step_off[n] k hop of the packed buffer and it is fresh: zeros in front and behind.
+// Signal n's samples start at step_off[n] k hop of the packed buffer, with zeros in front and behind.  CARRIED: positions before the
+// call come from the last tail_len samples of the prefix, the stream's tail (zeros when it is fresh; with a small G several groups of
+// a stream reach into the prefix).
+template <bool CARRIED>
 __global__ __launch_bounds__(256) void scan_stage_ragged_kernel(const ScanChunkArgs a, const int bx) {
     const int64_t r = blockIdx.x / (unsigned)bx;
     const int part = (int)(blockIdx.x - (unsigned)r * bx);
@@ -182,26 +187,9 @@ __global__ __launch_bounds__(256) void scan_stage_ragged_kernel(const ScanChunkA
     const int64_t g = q - a.group_off[n];
     const int64_t first = a.step_off[n], len = (a.step_off[n + 1] - first) * a.k_hop;
     const float* src = a.samples + first * a.k_hop;
-    const int64_t base = (g * a.G + 1) * a.k_hop - a.n_prefix;
-    float* dst = a.stage + r * a.stride;
-    for (int64_t x = (int64_t)part * 256 + threadIdx.x; x < a.stride; x += (int64_t)bx * 256) {
-        const int64_t pos = base + x;
-        dst[x] = pos >= 0 && pos < len ? src[pos] : 0.f;
-    }
-}
-
-// The ragged staging row of a call with a state: positions before the call come from the last tail_len samples of the prefix, the
-// stream's tail (zeros when it is fresh); everything else is scan_stage_ragged_kernel.
-__global__ __launch_bounds__(256) void scan_stage_ragged_tail_kernel(const ScanChunkArgs a, const int bx) {
-    const int64_t r = blockIdx.x / (unsigned)bx;
-    const int part = (int)(blockIdx.x - (unsigned)r * bx);
-    const int64_t q = a.q0 + r;
-    const int n = ragged_signal(a.group_off, a.n_sig, q);
-    const int64_t g = q - a.group_off[n];
-    const int64_t first = a.step_off[n], len = (a.step_off[n + 1] - first) * a.k_hop;
-    const float* src = a.samples + first * a.k_hop;
     const int tail_len = a.st.tail_len;
-    const float* tail = scan_fresh(a.st, n) ? nullptr : a.st.tail + (size_t)n * tail_len + tail_len;      // (indexed by pos < 0)
+    const float* tail = nullptr;                                                // (indexed by pos < 0)
+    if constexpr (CARRIED) tail = scan_fresh(a.st, n) ? nullptr : a.st.tail + (size_t)n * tail_len + tail_len;
     const int64_t base = (g * a.G + 1) * a.k_hop - a.n_prefix;
     float* dst = a.stage + r * a.stride;
     for (int64_t x = (int64_t)part * 256 + threadIdx.x; x < a.stride; x += (int64_t)bx * 256) {
@@ -209,50 +197,60 @@ __global__ __launch_bounds__(256) void scan_stage_ragged_tail_kernel(const ScanC
         float v = 0.f;
         if (pos >= 0) {
             if (pos < len) v = src[pos];
-        } else if (tail && pos + tail_len >= 0) {
-            v = tail[pos];
+        } else if constexpr (CARRIED) {
+            if (tail && pos + tail_len >= 0) v = tail[pos];
         }
         dst[x] = v;
     }
 }
 
-// One workgroup per window slot b = r G + j (step i = g G + j): column t is column j k + t of frame row r when new frame
-// (i + 1) k - T + t >= 0 or the signal is fresh, else column (i + 1) k + t of the carried window; the halo is zero.  PLANES (2-D
-// graph): the same window as its [T x n_coef] plane, written in plane order (coalesced): plane offset t n_coef + c <- window column t,
-// coefficient c (features_to_plane_kernel's map, net2d_kernels.hip).  A pure copy: bitwise the planar gather followed by
-// features_to_plane_kernel.  CARRIED: the call has a state; without one no column is carried, and the instance is the plain copy
-// (the test at run time cost tcr_scan 5 % of this kernel, profiles/scan_unify_kernel_stats.csv).  RAGGED: the windows are compact --
-// slot b is packed step p0 + b, whose signal, step, group and frame row come from the prefix tables -- so the chunk's slots are
-// its live steps only and the network writes their rows of the caller's outputs itself.  CARRIED && RAGGED: the slot's signal is a
-// stream of the state and i its step within the call, so the carried columns are those of the dense arm.
-template <bool PLANES, bool CARRIED, bool RAGGED = false>
-__global__ __launch_bounds__(256) void scan_gather_kernel(const ScanChunkArgs a) {
-    const int b = blockIdx.x;
+// Window slot b of a chunk: its frame row r and step j within the row's group, its signal (stream) s and (i + 1) k of its step i = g G +
+// j.  Dense: slot b = r G + j of flattened group q0 + r.  RAGGED: the slots are compact, slot b is packed step p0 + b, and signal, step
+// and group come from the prefix tables.
+struct ScanSlot {
     int r, j;
-    int64_t rs = 0, ri1 = 0;                                                    // RAGGED: the slot's stream and (i + 1) k
+    int64_t s, i1;
+};
+
+template <bool RAGGED>
+__device__ __forceinline__ ScanSlot scan_slot(const ScanChunkArgs& a, int b) {
+    ScanSlot o;
     if constexpr (RAGGED) {
         const int64_t p = a.p0 + b;
         const int n = ragged_signal(a.step_off, a.n_sig, p);
         const int64_t i = p - a.step_off[n], g = i / a.G;
-        j = (int)(i - g * a.G);
-        r = (int)(a.group_off[n] + g - a.q0);
-        rs = n;
-        ri1 = (i + 1) * a.k;
+        o.j = (int)(i - g * a.G);
+        o.r = (int)(a.group_off[n] + g - a.q0);
+        o.s = n;
+        o.i1 = (i + 1) * a.k;
     } else {
-        r = b / a.G;
-        j = b - r * a.G;
+        o.r = b / a.G;
+        o.j = b - o.r * a.G;
+        const int64_t q = a.q0 + o.r;
+        o.s = q / a.groups;
+        const int64_t g = q - o.s * a.groups;
+        o.i1 = (g * a.G + o.j + 1) * a.k;
     }
-    const float* src = a.frames + (size_t)r * a.n_coef * a.ftp + j * a.k;      // window column x <- frame-row column j k + x
+    return o;
+}
+
+// One workgroup per window slot b (scan_slot): column t is column j k + t of frame row r when new frame (i + 1) k - T + t >= 0 or the
+// signal is fresh, else column (i + 1) k + t of the carried window; the halo is zero.  PLANES (2-D graph): the same window as its
+// [T x n_coef] plane, written in plane order (coalesced): plane offset t n_coef + c <- window column t, coefficient c
+// (features_to_plane_kernel's map, net2d_kernels.hip).  A pure copy: bitwise the planar gather followed by features_to_plane_kernel.
+// CARRIED: the call has a state; without one no column is carried, and the instance is the plain copy (the test at run time cost
+// tcr_scan 5 % of this kernel, profiles/scan_unify_kernel_stats.csv).  sh is set by a select and the carried pointer unconditionally:
+// a nested-if form was compiled wrongly for reset[s] == 0 under a non-null reset array (profiles/scan_unify_kernel_regs.txt).
+template <bool PLANES, bool CARRIED, bool RAGGED>
+__global__ __launch_bounds__(256) void scan_gather_kernel(const ScanChunkArgs a) {
+    const int b = blockIdx.x;
+    const ScanSlot sl = scan_slot<RAGGED>(a, b);
+    const float* src = a.frames + (size_t)sl.r * a.n_coef * a.ftp + sl.j * a.k;        // window column x <- frame-row column j k + x
     const float* old = src;                                                     // (not read while sh = T)
     int sh = a.T;                                                               // carried columns: t < T - sh
-    if constexpr (CARRIED && RAGGED) {
-        if (ri1 < a.T && !scan_fresh(a.st, rs)) sh = (int)ri1;
-        old = a.st.window + (size_t)rs * a.n_coef * a.tp + sh;
-    } else if constexpr (CARRIED) {
-        const int64_t q = a.q0 + r, s = q / a.groups, g = q - s * a.groups;
-        const int64_t i1 = (g * a.G + j + 1) * a.k;                             // (i + 1) k
-        if (i1 < a.T && !scan_fresh(a.st, s)) sh = (int)i1;
-        old = a.st.window + (size_t)s * a.n_coef * a.tp + sh;
+    if constexpr (CARRIED) {
+        if (sl.i1 < a.T && !scan_fresh(a.st, sl.s)) sh = (int)sl.i1;
+        old = a.st.window + (size_t)sl.s * a.n_coef * a.tp + sh;
     }
     if constexpr (PLANES) {
         const int n = a.T * a.n_coef, pp = n + 2 * kHalo;
@@ -281,16 +279,30 @@ __global__ __launch_bounds__(256) void scan_gather_kernel(const ScanChunkArgs a)
     }
 }
 
-// One workgroup per stream s0 + blockIdx.x whose last group is in the chunk: window = its last step's gathered window (planar, zero
-// halo: the state's layout; PLANES: read back from the last step's plane, column t, coefficient c <- plane offset t n_coef + c);
-// tail = the last tail_len samples of  tail ++ samples  (old samples that survive a short call are read into LDS before the tail is
-// written).
-template <bool PLANES>
+// The state write-back, one workgroup per stream s = s0 + blockIdx.x of a range whose streams (RAGGED: those with steps; one without
+// returns at once) all have their last group in the chunk.  Its last slot b, the call's length L for it and its samples: dense from
+// groups / steps, RAGGED from the tables (the slots are compact: packed step step_off[s + 1] - 1 - p0; the stream's own packed samples).
+// window = the last step's gathered window (planar, zero halo: the state's layout; PLANES: read back from the last step's plane,
+// column t, coefficient c <- plane offset t n_coef + c); tail = the last tail_len samples of  tail ++ samples  (old samples that
+// survive a short call are read into LDS before the tail is written).
+template <bool PLANES, bool RAGGED>
 __global__ __launch_bounds__(256) void scan_carry_kernel(const ScanChunkArgs a) {
     __shared__ float s_tail[kMaxTail];
     const int64_t s = a.s0 + blockIdx.x;
     const int tid = threadIdx.x;
-    const int64_t b = (s * a.groups + a.groups - 1 - a.q0) * a.G + a.steps - 1 - (a.groups - 1) * a.G;
+    int64_t b, L;
+    const float* src;
+    if constexpr (RAGGED) {
+        const int64_t first = a.step_off[s], m = a.step_off[s + 1] - first;
+        if (m == 0) return;
+        b = first + m - 1 - a.p0;
+        L = m * a.k_hop;
+        src = a.samples + first * a.k_hop;
+    } else {
+        b = (s * a.groups + a.groups - 1 - a.q0) * a.G + a.steps - 1 - (a.groups - 1) * a.G;
+        L = a.L;
+        src = a.samples + s * a.L;
+    }
     const int win_elems = a.n_coef * a.tp;
     float* wdst = a.st.window + s * win_elems;
     if constexpr (PLANES) {
@@ -306,41 +318,6 @@ __global__ __launch_bounds__(256) void scan_carry_kernel(const ScanChunkArgs a) 
     const int tail_len = a.st.tail_len;
     const bool rst = scan_fresh(a.st, s);
     float* tail = a.st.tail + s * tail_len;
-    const float* src = a.samples + s * a.L;
-    const int keep = a.L < tail_len ? (int)(tail_len - a.L) : 0;               // old tail samples L .. tail_len - 1 stay
-    for (int i = tid; i < keep; i += 256) s_tail[i] = rst ? 0.f : tail[a.L + i];
-    __syncthreads();
-    for (int i = tid; i < tail_len; i += 256) tail[i] = i < keep ? s_tail[i] : src[a.L - tail_len + i];
-}
-
-// scan_carry_kernel of a ragged call: one workgroup per stream s0 + blockIdx.x of a range whose streams with steps all have their
-// last group in the chunk; a stream without steps in between returns at once.  The window is that of the stream's last live slot,
-// step_off[s + 1] - 1 - p0 (the slots are compact); the tail comes from the stream's own packed samples.
-template <bool PLANES>
-__global__ __launch_bounds__(256) void scan_carry_ragged_kernel(const ScanChunkArgs a) {
-    __shared__ float s_tail[kMaxTail];
-    const int64_t s = a.s0 + blockIdx.x;
-    const int tid = threadIdx.x;
-    const int64_t first = a.step_off[s], m = a.step_off[s + 1] - first;
-    if (m == 0) return;
-    const int64_t b = first + m - 1 - a.p0;
-    const int64_t L = m * a.k_hop;
-    const int win_elems = a.n_coef * a.tp;
-    float* wdst = a.st.window + s * win_elems;
-    if constexpr (PLANES) {
-        const float* wsrc = a.windows + b * (a.T * a.n_coef + 2 * kHalo) + kHalo;
-        for (int i = tid; i < win_elems; i += 256) {
-            const int c = i / a.tp, t = i - c * a.tp - kHalo;
-            wdst[i] = t >= 0 && t < a.T ? wsrc[t * a.n_coef + c] : 0.f;
-        }
-    } else {
-        const float* wsrc = a.windows + b * win_elems;
-        for (int i = tid; i < win_elems; i += 256) wdst[i] = wsrc[i];
-    }
-    const int tail_len = a.st.tail_len;
-    const bool rst = scan_fresh(a.st, s);
-    float* tail = a.st.tail + s * tail_len;
-    const float* src = a.samples + first * a.k_hop;
     const int keep = L < tail_len ? (int)(tail_len - L) : 0;                   // old tail samples L .. tail_len - 1 stay
     for (int i = tid; i < keep; i += 256) s_tail[i] = rst ? 0.f : tail[L + i];
     __syncthreads();
@@ -544,6 +521,33 @@ __global__ __launch_bounds__(256) void scan_suppress_kernel(const ScanDetectArgs
 
 namespace {
 
+struct ScanOutputs {
+    float *logits, *probs, *smoothed;   // [N][steps][C] (ragged: [total_steps][C])
+    int32_t* top;                       // [N][steps]
+    float* score;
+    int32_t* is_new;
+};
+
+// One call of the four entries, as the extern "C" functions fill it; scan_entry checks it and completes io, tables and the workspace.
+struct ScanCall {
+    const tcr_frontend_cfg* cfg;
+    const void* plan_dev;
+    const tcr_model_ref* m;
+    ModelIO io;
+    int n, k;                           // signals (streams), frames per step
+    const tcr_detect_cfg* det;
+    const float* samples;
+    const uint8_t* reset;               // [n] or null
+    void* state;                        // the stream state (stream.hip); read only when `carried`
+    bool carried;                       // the call starts from `state` and writes it back: the n signals are its streams
+    void* workspace;
+    size_t ws_bytes;
+    int64_t* tables;                    // ragged: the device tables [2][n + 1] (step offsets, then group offsets), the workspace's front
+    ScanOutputs out;
+    void* stream;
+    const char* what;
+};
+
 // the front-end row length for `steps` steps: at most kScanGroup (and max_windows) steps, balanced so the groups of a signal differ
 // by at most one step from each other in size
 int scan_group(int64_t steps, int cap) {
@@ -552,84 +556,60 @@ int scan_group(int64_t steps, int cap) {
     return (int)ceil_div64(steps, groups);
 }
 
-// The largest chunk the workspace holds for n_signals x steps: G = the balanced group (smaller when even one row of it does not fit),
-// R rows (TCR_ERR_WORKSPACE below one window).  R G also stays within io.max_batch (scan_geom_ok; G <= kScanGroup is far below
-// every family's bound), so that every window of a DS-CNN scan runs on the kernel path a stream step of up to kDscnnMaxBatch
-// streams runs: the result does not depend on the chunking.
-int scan_chunking(const tcr_frontend_cfg& cfg, const tcr_model_ref& m, const ModelIO& io, int k, int64_t steps, int n_signals,
-                  size_t ws_bytes, const char* what, ScanGeom& out) {
-    int G = scan_group(steps, kScanGroup);
-    while (G > 1 && (size_t)scan_geom(cfg, m, io, k, G, 1).ws_floats * sizeof(float) > ws_bytes) G = scan_group(steps, G / 2);
-    if ((size_t)scan_geom(cfg, m, io, k, G, 1).ws_floats * sizeof(float) > ws_bytes) {
-        set_error("%s: workspace %zu bytes < one window's %zu", what, ws_bytes,
-                  (size_t)scan_geom(cfg, m, io, k, 1, 1).ws_floats * sizeof(float));
-        return TCR_ERR_WORKSPACE;
-    }
-    const int64_t total_groups = ceil_div64(steps, G) * n_signals;
-    int64_t lo = 1, hi = total_groups;                  // R: the largest that fits (binary search; the size grows with R)
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) / 2;
-        if (scan_geom_ok(k, cfg.n_frames, G, mid, io.max_batch) &&
-            (size_t)scan_geom(cfg, m, io, k, G, (int)mid).ws_floats * sizeof(float) <= ws_bytes) lo = mid;
-        else hi = mid - 1;
-    }
-    out = scan_geom(cfg, m, io, k, G, (int)lo);
-    return TCR_OK;
-}
-
-// A ragged call (tcr_scan_ragged): the host's step offsets [N + 1] and the device tables [2][N + 1] (step offsets, then group
-// offsets) at the front of the workspace.  Null in scan_run: the dense layout.
-struct ScanRagged {
-    const int64_t* step_off;    // host
-    int64_t* tables;            // device
-};
-
 size_t scan_ragged_tables_bytes(int64_t n_signals) { return (size_t)round_up64(2 * (n_signals + 1) * (int64_t)sizeof(int64_t), 256); }
 
-// Front-end frames of the call at group size G: every group is a row of G k + T - k frames, whatever its live steps.
-int64_t scan_ragged_frames(const int64_t* so, int n_signals, int k, int T, int G) {
+// Front-end rows of a ragged call at group size G (every group is a row of G k + T - k frames, whatever its live steps)
+int64_t scan_ragged_groups(const int64_t* so, int n_signals, int G) {
     int64_t rows = 0;
     for (int n = 0; n < n_signals; ++n) rows += ceil_div64(so[n + 1] - so[n], G);
-    return rows * ((int64_t)G * k + T - k);
+    return rows;
 }
 
-// The ragged chunking: G, at most kScanGroup, the longest signal and what one row of the workspace holds, with the fewest front-end
-// frames over the call (ties: the larger G, fewer rows) -- the results do not depend on G, so this is a cost choice only; the sum is
-// evaluated for every candidate while N x candidates stays small, for every few otherwise -- then R as scan_chunking finds it.
-int scan_ragged_chunking(const tcr_frontend_cfg& cfg, const tcr_model_ref& m, const ModelIO& io, int k, const int64_t* so, int n_signals,
-                         size_t ws_bytes, const char* what, ScanGeom& out) {
-    const auto fits = [&](int G, int64_t R) {
-        return scan_geom_ok(k, cfg.n_frames, G, R, io.max_batch) && (size_t)scan_geom(cfg, m, io, k, G, (int)R).ws_floats * sizeof(float) <= ws_bytes;
+// The largest chunk the workspace holds: G by the call's policy, then R rows (TCR_ERR_WORKSPACE below one window).  R G also stays
+// within io.max_batch (scan_geom_ok; G <= kScanGroup is far below every family's bound), so that every window of a DS-CNN scan runs on
+// the kernel path a stream step of up to kDscnnMaxBatch streams runs.  The results do not depend on the chunking, so G is a cost
+// choice only.  Dense (so == null, n x steps): the balanced group, smaller when even one row of it does not fit.  Ragged (so: the
+// step offsets [n + 1]): G, at most kScanGroup, the longest signal and what one row of the workspace holds, with the fewest front-end
+// frames over the call (ties: the larger G, fewer rows); the sum is evaluated for every candidate while n x candidates stays small,
+// for every few otherwise.
+int scan_chunking(const ScanCall& c, int64_t steps, const int64_t* so, ScanGeom& out) {
+    const int k = c.k, T = c.cfg->n_frames;
+    const auto bytes = [&](int G, int64_t R) { return (size_t)scan_geom(*c.cfg, *c.m, c.io, k, G, (int)R).ws_floats * sizeof(float); };
+    const auto fits = [&](int G, int64_t R) { return scan_geom_ok(k, T, G, R, c.io.max_batch) && bytes(G, R) <= c.ws_bytes; };
+    // the largest v of lo .. hi with ok(v), lo when there is none (binary search; the size grows with R and with G)
+    const auto largest = [](int64_t lo, int64_t hi, const auto& ok) {
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) / 2;
+            if (ok(mid)) lo = mid;
+            else hi = mid - 1;
+        }
+        return lo;
     };
     if (!fits(1, 1)) {
-        set_error("%s: workspace %zu bytes < one window's %zu", what, ws_bytes, (size_t)scan_geom(cfg, m, io, k, 1, 1).ws_floats * sizeof(float));
+        set_error("%s: workspace %zu bytes < one window's %zu", c.what, c.ws_bytes, bytes(1, 1));
         return TCR_ERR_WORKSPACE;
     }
-    int64_t longest = 1;
-    for (int n = 0; n < n_signals; ++n) longest = std::max(longest, so[n + 1] - so[n]);
-    int lo = 1, hi = (int)std::min<int64_t>(kScanGroup, longest);      // the largest G one row of which fits (the size grows with G)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) / 2;
-        if (fits(mid, 1)) lo = mid;
-        else hi = mid - 1;
+    int G;
+    int64_t total_groups;
+    if (!so) {
+        G = scan_group(steps, kScanGroup);
+        while (G > 1 && bytes(G, 1) > c.ws_bytes) G = scan_group(steps, G / 2);
+        total_groups = ceil_div64(steps, G) * c.n;
+    } else {
+        int64_t longest = 1;
+        for (int n = 0; n < c.n; ++n) longest = std::max(longest, so[n + 1] - so[n]);
+        const int g_max = (int)largest(1, std::min<int64_t>(kScanGroup, longest), [&](int64_t g) { return fits((int)g, 1); });
+        const auto frames = [&](int g) { return scan_ragged_groups(so, c.n, g) * ((int64_t)g * k + T - k); };
+        const int stride = (int)std::max<int64_t>(1, ceil_div64((int64_t)c.n * g_max, (int64_t)1 << 22));
+        G = g_max;
+        int64_t best = frames(G);
+        for (int g = g_max - stride; g >= 1; g -= stride) {
+            const int64_t f = frames(g);
+            if (f < best) { best = f; G = g; }
+        }
+        total_groups = scan_ragged_groups(so, c.n, G);
     }
-    const int g_max = lo;
-    const int stride = (int)std::max<int64_t>(1, ceil_div64((int64_t)n_signals * g_max, (int64_t)1 << 22));
-    int G = g_max;
-    int64_t best = scan_ragged_frames(so, n_signals, k, cfg.n_frames, G);
-    for (int c = g_max - stride; c >= 1; c -= stride) {
-        const int64_t f = scan_ragged_frames(so, n_signals, k, cfg.n_frames, c);
-        if (f < best) { best = f; G = c; }
-    }
-    int64_t total_groups = 0;
-    for (int n = 0; n < n_signals; ++n) total_groups += ceil_div64(so[n + 1] - so[n], G);
-    int64_t rlo = 1, rhi = total_groups;
-    while (rlo < rhi) {
-        const int64_t mid = (rlo + rhi + 1) / 2;
-        if (fits(G, mid)) rlo = mid;
-        else rhi = mid - 1;
-    }
-    out = scan_geom(cfg, m, io, k, G, (int)rlo);
+    out = scan_geom(*c.cfg, *c.m, c.io, k, G, (int)largest(1, total_groups, [&](int64_t R) { return fits(G, R); }));
     return TCR_OK;
 }
 
@@ -643,254 +623,181 @@ size_t scan_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_model_ref* m,
     return (size_t)scan_geom(*cfg, *m, io, k, G, R).ws_floats * sizeof(float);
 }
 
-// scan_run's ragged arm: the same stages over chunks of flattened groups, with the prefix tables in place of q / groups and
-// n steps + i.  A chunk's live steps are the packed steps p(q0) .. p(q0 + rows) - 1 (a signal's groups cover its steps in order), so
-// its windows are gathered compactly, the network runs at the batch of its live steps and writes their rows of the caller's logits
-// and probs itself: no scatter.  The slots past a signal's last step cost front-end frames only.  With a state st
-// (tcr_stream_scan_ragged) the signals are its streams: the carried forms of the stages, and after a chunk's gather the write-back
-// of the streams whose last group is one of its rows (the header's state ordering).
-int scan_run_ragged(const tcr_frontend_cfg& cfg, const void* plan_dev, const tcr_model_ref& m, const ModelIO& io, int n_signals, int k,
-                    const tcr_detect_cfg& det, const float* samples, const ScanState& st, const ScanRagged& rg, void* workspace,
-                    size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, hipStream_t s,
-                    const char* what) {
-    const int64_t* so = rg.step_off;
+// The pipeline of the header comment over a checked call: n x steps (dense, so empty) or the step offsets so [n + 1] (ragged), from
+// and to the state st (all null: none).  The dense and the ragged form differ at the five places marked (1) .. (5).
+int scan_run(const ScanCall& c, const ScanState& st, int64_t steps, const std::vector<int64_t>& so) {
+    const tcr_frontend_cfg& cfg = *c.cfg;
+    const bool ragged = !so.empty(), carried = st.window != nullptr;
+    const int N = c.n, k = c.k;
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
     ScanGeom g;
-    TCR_TRY(scan_ragged_chunking(cfg, m, io, k, so, n_signals, ws_bytes, what, g));
+    TCR_TRY(scan_chunking(c, steps, ragged ? so.data() : nullptr, g));
     const int G = g.G;
-    std::vector<int64_t> tables(2 * ((size_t)n_signals + 1));
-    int64_t* go = tables.data() + n_signals + 1;
-    std::copy(so, so + n_signals + 1, tables.data());
-    go[0] = 0;
-    for (int n = 0; n < n_signals; ++n) go[n + 1] = go[n] + ceil_div64(so[n + 1] - so[n], G);
-    const int64_t total_groups = go[n_signals], total_steps = so[n_signals];
-    // the tables live on the host's stack frame: the copy is complete before the call returns (and before the first launch)
-    if (hipMemcpyAsync(rg.tables, tables.data(), tables.size() * sizeof(int64_t), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        set_error("%s: the upload of the offset tables failed", what);
-        return TCR_ERR_HIP;
-    }
-    float* ws = static_cast<float*>(workspace);
+    float* ws = static_cast<float*>(c.workspace);
     ScanChunkArgs ca{};
-    ca.samples = samples; ca.stage = ws + g.stage_off; ca.frames = ws + g.frames_off; ca.windows = ws + g.win_off; ca.st = st;
+    ca.samples = c.samples; ca.stage = ws + g.stage_off; ca.frames = ws + g.frames_off; ca.windows = ws + g.win_off; ca.st = st;
     ca.k_hop = (int64_t)k * cfg.hop; ca.stride = g.stage_stride; ca.n_prefix = cfg.n_samples; ca.G = G; ca.k = k; ca.T = g.T; ca.tp = g.tp;
-    ca.n_coef = g.n_coef; ca.ftp = tcr_padded_len(g.F); ca.step_off = rg.tables; ca.group_off = rg.tables + n_signals + 1; ca.n_sig = n_signals;
-    const bool carried = st.window != nullptr;
-    const auto gather = g.planes ? (carried ? scan_gather_kernel<true, true, true> : scan_gather_kernel<true, false, true>)
-                                 : (carried ? scan_gather_kernel<false, true, true> : scan_gather_kernel<false, false, true>);
-    int next = 0;                                       // carried: the first stream whose write-back is still to come
-    // the packed step of flattened group q's first slot
+    ca.n_coef = g.n_coef; ca.ftp = tcr_padded_len(g.F);
+    // the flattened groups: dense, `groups` per signal; ragged, the table go [N + 1] next to so, both uploaded
+    std::vector<int64_t> tables;
+    const int64_t* go = nullptr;
+    int64_t groups = 0, total_groups, total_steps;
+    if (ragged) {
+        tables.resize(2 * ((size_t)N + 1));
+        std::copy(so.begin(), so.end(), tables.begin());
+        int64_t* t = tables.data() + N + 1;
+        t[0] = 0;
+        for (int n = 0; n < N; ++n) t[n + 1] = t[n] + ceil_div64(so[n + 1] - so[n], G);
+        go = t;
+        total_groups = go[N]; total_steps = so[N];
+        // the tables live on the host's stack frame: the copy is complete before the call returns (and before the first launch)
+        if (hipMemcpyAsync(c.tables, tables.data(), tables.size() * sizeof(int64_t), hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) {
+            set_error("%s: the upload of the offset tables failed", c.what);
+            return TCR_ERR_HIP;
+        }
+        ca.step_off = c.tables; ca.group_off = c.tables + N + 1; ca.n_sig = N;
+    } else {
+        groups = ceil_div64(steps, G);
+        total_groups = groups * N; total_steps = N * steps;
+        ca.L = steps * ca.k_hop; ca.groups = groups; ca.steps = steps;
+    }
+    // ragged: the packed step of flattened group q's first slot
     const auto first_step = [&](int64_t q) {
         if (q >= total_groups) return total_steps;
-        const int64_t n = std::upper_bound(go, go + n_signals + 1, q) - go - 1;
+        const int64_t n = std::upper_bound(go, go + N + 1, q) - go - 1;
         return so[n] + (q - go[n]) * G;
     };
+    const auto stage_ragged = carried ? scan_stage_ragged_kernel<true> : scan_stage_ragged_kernel<false>;
+    const auto gather = g.planes ? (carried ? (ragged ? scan_gather_kernel<true, true, true> : scan_gather_kernel<true, true, false>)
+                                            : (ragged ? scan_gather_kernel<true, false, true> : scan_gather_kernel<true, false, false>))
+                                 : (carried ? (ragged ? scan_gather_kernel<false, true, true> : scan_gather_kernel<false, true, false>)
+                                            : (ragged ? scan_gather_kernel<false, false, true> : scan_gather_kernel<false, false, false>));
+    const auto carry = g.planes ? (ragged ? scan_carry_kernel<true, true> : scan_carry_kernel<true, false>)
+                                : (ragged ? scan_carry_kernel<false, true> : scan_carry_kernel<false, false>);
     const int64_t stage_blocks = ceil_div64(g.stage_stride, 256);
+    int next = 0;                                       // ragged, carried: the first stream whose write-back is still to come
     for (int64_t q0 = 0; q0 < total_groups; q0 += g.R) {
         const int rows = (int)std::min<int64_t>(g.R, total_groups - q0);
-        ca.q0 = q0; ca.rows = rows; ca.p0 = first_step(q0);
-        const int live = (int)(first_step(q0 + rows) - ca.p0);
-        const int bx = (int)std::max<int64_t>(1, std::min(stage_blocks, ceil_div64(8 * (int64_t)device_cus(), rows)));
-        if (carried) {
-            hipLaunchKernelGGL(scan_stage_ragged_tail_kernel, dim3((unsigned)((int64_t)rows * bx)), dim3(256), 0, s, ca, bx);
-            TCR_TRY(check_launch("scan_stage_ragged_tail_kernel"));
-        } else {
-            hipLaunchKernelGGL(scan_stage_ragged_kernel, dim3((unsigned)((int64_t)rows * bx)), dim3(256), 0, s, ca, bx);
-            TCR_TRY(check_launch("scan_stage_ragged_kernel"));
-        }
-        TCR_TRY(stream_frontend(cfg, plan_dev, ca.stage, g.stage_stride, rows, g.F, ca.frames, s, ca.ftp));
-        hipLaunchKernelGGL(gather, dim3(live), dim3(256), 0, s, ca);
-        TCR_TRY(check_launch("scan_gather_kernel"));
-        if (carried) {
-            // the streams with steps whose last group (go[n + 1] - 1, increasing over them) is one of this chunk's rows: next .. the
-            // last such one, streams without steps in between included (their workgroups return at once)
-            int s_lo = -1, s_hi = -1;
-            for (; next < n_signals && (so[next + 1] == so[next] || go[next + 1] - 1 < q0 + rows); ++next) {
-                if (so[next + 1] == so[next]) continue;
-                if (s_lo < 0) s_lo = next;
-                s_hi = next;
-            }
-            if (s_lo >= 0) {
-                ca.s0 = s_lo;
-                if (g.planes) hipLaunchKernelGGL(scan_carry_ragged_kernel<true>, dim3((unsigned)(s_hi - s_lo + 1)), dim3(256), 0, s, ca);
-                else hipLaunchKernelGGL(scan_carry_ragged_kernel<false>, dim3((unsigned)(s_hi - s_lo + 1)), dim3(256), 0, s, ca);
-                TCR_TRY(check_launch("scan_carry_ragged_kernel"));
-            }
-        }
-        TCR_TRY(model_forward(m, ca.windows, live, ws + g.net_off, ws_bytes - (size_t)g.net_off * sizeof(float), logits + ca.p0 * g.classes,
-                              probs + ca.p0 * g.classes, s));
-    }
-    ScanDetectArgs da;
-    da.probs = probs; da.smoothed = smoothed; da.top = top; da.score = score; da.is_new = is_new; da.st = st; da.steps = total_steps;
-    da.N = n_signals; da.C = g.classes; da.W = det.average_steps; da.min_count = det.min_count; da.suppression = det.suppression_steps;
-    da.threshold = det.threshold; da.step_off = rg.tables;
-    if (carried) hipLaunchKernelGGL((scan_smooth_kernel<true, true>), dim3((unsigned)ceil_div64(total_steps, 256 / g.classes)), dim3(256), 0, s, da);
-    else hipLaunchKernelGGL((scan_smooth_kernel<false, true>), dim3((unsigned)ceil_div64(total_steps, 256 / g.classes)), dim3(256), 0, s, da);
-    TCR_TRY(check_launch("scan_smooth_kernel"));
-    hipLaunchKernelGGL(scan_suppress_kernel<true>, dim3(n_signals), dim3(256), 0, s, da);
-    return check_launch("scan_suppress_kernel");
-}
-
-// The pipeline of the header comment over n_signals x steps checked by the caller, from and to the state st (all null: none).
-int scan_run(const tcr_frontend_cfg& cfg, const void* plan_dev, const tcr_model_ref& m, const ModelIO& io, int n_signals, int64_t steps,
-             int k, const tcr_detect_cfg& det, const float* samples, const ScanState& st, void* workspace, size_t ws_bytes, float* logits,
-             float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream, const char* what,
-             const ScanRagged* rg = nullptr) {
-    ScanGeom g;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (rg) return scan_run_ragged(cfg, plan_dev, m, io, n_signals, k, det, samples, st, *rg, workspace, ws_bytes, logits, probs, smoothed,
-                                   top, score, is_new, s, what);
-    TCR_TRY(scan_chunking(cfg, m, io, k, steps, n_signals, ws_bytes, what, g));
-    const int G = g.G;
-    const int64_t groups = ceil_div64(steps, G), total_groups = groups * n_signals;
-    float* ws = static_cast<float*>(workspace);
-    ScanChunkArgs ca;
-    ca.samples = samples; ca.stage = ws + g.stage_off; ca.frames = ws + g.frames_off; ca.windows = ws + g.win_off; ca.st = st;
-    ca.k_hop = (int64_t)k * cfg.hop; ca.L = steps * ca.k_hop; ca.stride = g.stage_stride; ca.groups = groups; ca.steps = steps;
-    ca.n_prefix = cfg.n_samples; ca.G = G; ca.k = k; ca.T = g.T; ca.tp = g.tp; ca.n_coef = g.n_coef; ca.ftp = tcr_padded_len(g.F);
-    const bool carried = st.window != nullptr;
-    const auto gather = g.planes ? (carried ? scan_gather_kernel<true, true> : scan_gather_kernel<true, false>)
-                                 : (carried ? scan_gather_kernel<false, true> : scan_gather_kernel<false, false>);
-    for (int64_t q0 = 0; q0 < total_groups; q0 += g.R) {
-        const int rows = (int)std::min<int64_t>(g.R, total_groups - q0);
-        const int slots = rows * G;
         ca.q0 = q0; ca.rows = rows;
-        // the streams whose last group (s groups + groups - 1) is one of this chunk's rows
-        const int64_t s_lo = (q0 + 1 + groups - 1) / groups - 1, s_hi = (q0 + rows) / groups - 1;
-        ca.s0 = s_lo;
-        const int64_t staged = (int64_t)rows * g.stage_stride;
-        hipLaunchKernelGGL(scan_stage_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(staged, 256), 8 * (int64_t)device_cus())), dim3(256), 0,
-                           s, ca);
-        TCR_TRY(check_launch("scan_stage_kernel"));
-        TCR_TRY(stream_frontend(cfg, plan_dev, ca.stage, g.stage_stride, rows, g.F, ca.frames, s, ca.ftp));
+        // (1) the staging launch
+        if (ragged) {
+            const int bx = (int)std::max<int64_t>(1, std::min(stage_blocks, ceil_div64(8 * (int64_t)device_cus(), rows)));
+            hipLaunchKernelGGL(stage_ragged, dim3((unsigned)((int64_t)rows * bx)), dim3(256), 0, s, ca, bx);
+        } else {
+            const int64_t staged = (int64_t)rows * g.stage_stride;
+            hipLaunchKernelGGL(scan_stage_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(staged, 256), 8 * (int64_t)device_cus())), dim3(256), 0,
+                               s, ca);
+        }
+        TCR_TRY(check_launch(ragged ? "scan_stage_ragged_kernel" : "scan_stage_kernel"));
+        TCR_TRY(stream_frontend(cfg, c.plan_dev, ca.stage, g.stage_stride, rows, g.F, ca.frames, s, ca.ftp));
+        // (2) the slots: every step of the rows, or (a signal's groups cover its steps in order) the live steps p0 .. p(q0 + rows) - 1
+        int slots = rows * G;
+        if (ragged) {
+            ca.p0 = first_step(q0);
+            slots = (int)(first_step(q0 + rows) - ca.p0);
+        }
         hipLaunchKernelGGL(gather, dim3(slots), dim3(256), 0, s, ca);
         TCR_TRY(check_launch("scan_gather_kernel"));
-        if (carried && s_hi >= s_lo) {
-            if (g.planes) hipLaunchKernelGGL(scan_carry_kernel<true>, dim3((unsigned)(s_hi - s_lo + 1)), dim3(256), 0, s, ca);
-            else hipLaunchKernelGGL(scan_carry_kernel<false>, dim3((unsigned)(s_hi - s_lo + 1)), dim3(256), 0, s, ca);
-            TCR_TRY(check_launch("scan_carry_kernel"));
+        // (3) the write-back range: the streams whose last group is one of this chunk's rows.  Dense: group s groups + groups - 1.
+        // Ragged: go[n + 1] - 1, increasing over the streams with steps; next .. the last such one, streams without steps in between
+        // included (their workgroups return at once)
+        if (carried) {
+            int64_t s_lo = N, s_hi = -1;
+            if (ragged) {
+                for (; next < N && (so[next + 1] == so[next] || go[next + 1] - 1 < q0 + rows); ++next) {
+                    if (so[next + 1] == so[next]) continue;
+                    s_lo = std::min<int64_t>(s_lo, next);
+                    s_hi = next;
+                }
+            } else {
+                s_lo = (q0 + 1 + groups - 1) / groups - 1;
+                s_hi = (q0 + rows) / groups - 1;
+            }
+            if (s_hi >= s_lo) {
+                ca.s0 = s_lo;
+                hipLaunchKernelGGL(carry, dim3((unsigned)(s_hi - s_lo + 1)), dim3(256), 0, s, ca);
+                TCR_TRY(check_launch("scan_carry_kernel"));
+            }
         }
-        TCR_TRY(model_forward(m, ca.windows, slots, ws + g.net_off, ws_bytes - (size_t)g.net_off * sizeof(float), ws + g.logits_off,
-                              ws + g.probs_off, stream));
-        ScanScatterArgs xa;
-        xa.logits_in = ws + g.logits_off; xa.probs_in = ws + g.probs_off; xa.logits = logits; xa.probs = probs; xa.q0 = q0;
-        xa.groups = groups; xa.steps = steps; xa.G = G; xa.C = g.classes; xa.slots = slots;
-        hipLaunchKernelGGL(scan_scatter_kernel, dim3(ceil_div(slots * g.classes, 256)), dim3(256), 0, s, xa);
-        TCR_TRY(check_launch("scan_scatter_kernel"));
+        // (4) the network's outputs: the chunk's slots in the workspace, or the live steps' rows of the caller's
+        float* logits = ragged ? c.out.logits + ca.p0 * g.classes : ws + g.logits_off;
+        float* probs = ragged ? c.out.probs + ca.p0 * g.classes : ws + g.probs_off;
+        TCR_TRY(model_forward(*c.m, ca.windows, slots, ws + g.net_off, c.ws_bytes - (size_t)g.net_off * sizeof(float), logits, probs, c.stream));
+        // (5) the scatter of the slots that are steps
+        if (!ragged) {
+            ScanScatterArgs xa;
+            xa.logits_in = logits; xa.probs_in = probs; xa.logits = c.out.logits; xa.probs = c.out.probs; xa.q0 = q0;
+            xa.groups = groups; xa.steps = steps; xa.G = G; xa.C = g.classes; xa.slots = slots;
+            hipLaunchKernelGGL(scan_scatter_kernel, dim3(ceil_div(slots * g.classes, 256)), dim3(256), 0, s, xa);
+            TCR_TRY(check_launch("scan_scatter_kernel"));
+        }
     }
+    // the detector tail, once per call
     ScanDetectArgs da;
-    da.probs = probs; da.smoothed = smoothed; da.top = top; da.score = score; da.is_new = is_new; da.st = st; da.steps = steps;
-    da.N = n_signals; da.C = g.classes; da.W = det.average_steps; da.min_count = det.min_count; da.suppression = det.suppression_steps;
-    da.threshold = det.threshold; da.step_off = nullptr;
-    hipLaunchKernelGGL(carried ? scan_smooth_kernel<true> : scan_smooth_kernel<false>, dim3((unsigned)ceil_div64(n_signals * steps, 256 / g.classes)),
-                       dim3(256), 0, s, da);
+    da.probs = c.out.probs; da.smoothed = c.out.smoothed; da.top = c.out.top; da.score = c.out.score; da.is_new = c.out.is_new; da.st = st;
+    da.steps = ragged ? total_steps : steps; da.N = N; da.C = g.classes; da.W = c.det->average_steps; da.min_count = c.det->min_count;
+    da.suppression = c.det->suppression_steps; da.threshold = c.det->threshold; da.step_off = ragged ? c.tables : nullptr;
+    const auto smooth = carried ? (ragged ? scan_smooth_kernel<true, true> : scan_smooth_kernel<true, false>)
+                                : (ragged ? scan_smooth_kernel<false, true> : scan_smooth_kernel<false, false>);
+    hipLaunchKernelGGL(smooth, dim3((unsigned)ceil_div64(total_steps, 256 / g.classes)), dim3(256), 0, s, da);
     TCR_TRY(check_launch("scan_smooth_kernel"));
-    hipLaunchKernelGGL(scan_suppress_kernel<false>, dim3(n_signals), dim3(256), 0, s, da);
+    const auto suppress = ragged ? scan_suppress_kernel<true> : scan_suppress_kernel<false>;
+    hipLaunchKernelGGL(suppress, dim3(N), dim3(256), 0, s, da);
     return check_launch("scan_suppress_kernel");
 }
 
-int scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* m, int n_signals, int64_t n_samples, int k,
-         const tcr_detect_cfg* det, const float* samples, void* workspace, size_t ws_bytes, float* logits, float* probs, float* smoothed,
-         int32_t* top, float* score, int32_t* is_new, void* stream, const char* what) {
-    TCR_REQUIRE(plan_dev && m && m->params && m->aux && det && samples && workspace && logits && probs && smoothed && top && score && is_new,
-                "%s: null argument", what);
-    TCR_REQUIRE(n_signals > 0, "%s: the number of signals must be positive (got %d)", what, n_signals);
-    ModelIO io;
-    TCR_TRY(stream_check(cfg, m, n_signals, k, det, what, io, false));
-    const int64_t khop = (int64_t)k * cfg->hop;
-    TCR_REQUIRE(n_samples > 0 && n_samples % khop == 0, "%s: the signal length %lld is not a positive multiple of k * hop = %lld", what,
-                (long long)n_samples, (long long)khop);
-    const int64_t steps = n_samples / khop;
-    TCR_REQUIRE((int64_t)n_signals * steps * io.classes < ((int64_t)1 << 31), "%s: %d signals x %lld steps is too large", what, n_signals,
-                (long long)steps);
-    return scan_run(*cfg, plan_dev, *m, io, n_signals, steps, k, *det, samples, ScanState{}, workspace, ws_bytes, logits, probs, smoothed,
-                    top, score, is_new, stream, what);
-}
-
-int stream_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* m, int n_streams, int64_t n_samples, int k,
-                const tcr_detect_cfg* det, const float* samples, const uint8_t* reset, void* state, void* workspace, size_t ws_bytes,
-                float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream, const char* what) {
-    TCR_REQUIRE(plan_dev && m && m->params && m->aux && det && samples && state && workspace && logits && probs && smoothed && top && score &&
-                is_new, "%s: null argument", what);
-    ModelIO io;
-    TCR_TRY(stream_check(cfg, m, n_streams, k, det, what, io));
-    const int64_t khop = (int64_t)k * cfg->hop;
-    TCR_REQUIRE(n_samples > 0 && n_samples % khop == 0, "%s: the signal length %lld is not a positive multiple of k * hop = %lld", what,
-                (long long)n_samples, (long long)khop);
-    const int64_t steps = n_samples / khop;
-    TCR_REQUIRE((int64_t)n_streams * steps * io.classes < ((int64_t)1 << 31), "%s: %d streams x %lld steps is too large", what, n_streams,
-                (long long)steps);
-    const StreamGeom sg = stream_geom(*cfg, *m, io, n_streams, k, det->average_steps);
-    float* st = static_cast<float*>(state);
-    const ScanState carried{st + sg.win_off, st + sg.tail_off, st + sg.ring_off, reinterpret_cast<int*>(st + sg.ist_off), reset, sg.tail_len};
-    return scan_run(*cfg, plan_dev, *m, io, n_streams, steps, k, *det, samples, carried, workspace, ws_bytes, logits, probs, smoothed, top,
-                    score, is_new, stream, what);
-}
-
-int scan_ragged(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* m, int n_signals, const int64_t* sample_offsets,
-                int k, const tcr_detect_cfg* det, const float* samples, void* workspace, size_t ws_bytes, float* logits, float* probs,
-                float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream, const char* what) {
-    TCR_REQUIRE(plan_dev && m && m->params && m->aux && det && sample_offsets && workspace, "%s: null argument", what);
-    TCR_REQUIRE(n_signals > 0, "%s: the number of signals must be positive (got %d)", what, n_signals);
-    ModelIO io;
-    TCR_TRY(stream_check(cfg, m, n_signals, k, det, what, io, false));
-    const size_t tables_bytes = scan_ragged_tables_bytes(n_signals);
-    TCR_REQUIRE(tables_bytes <= ws_bytes, "%s: %d signals are more than the max_signals the workspace's offset tables hold (%lld)", what,
-                n_signals, (long long)(ws_bytes / (2 * sizeof(int64_t))) - 1);
-    const int64_t khop = (int64_t)k * cfg->hop;
-    TCR_REQUIRE(sample_offsets[0] == 0, "%s: sample_offsets must start at 0 (got %lld)", what, (long long)sample_offsets[0]);
-    std::vector<int64_t> so((size_t)n_signals + 1);
-    so[0] = 0;
-    for (int n = 0; n < n_signals; ++n) {
-        const int64_t len = sample_offsets[n + 1] - sample_offsets[n];
-        TCR_REQUIRE(len >= 0, "%s: sample_offsets decrease at signal %d (%lld after %lld)", what, n, (long long)sample_offsets[n + 1],
-                    (long long)sample_offsets[n]);
-        TCR_REQUIRE(len % khop == 0, "%s: the length %lld of signal %d is not a multiple of k * hop = %lld", what, (long long)len, n,
-                    (long long)khop);
-        so[n + 1] = so[n] + len / khop;
+// The checks of the four entries, in one order; then the state's regions and the pipeline.  Dense (sample_offsets == null): n_samples
+// per signal become `steps`.  Ragged: sample_offsets [n + 1] become step offsets, the tables take the workspace's front, and samples
+// and outputs may be null up to the late check (a caller sizes its outputs by what the offsets yield).  With a state the n signals are
+// its streams (a stream without steps is allowed, a call without any step is not), and the messages say so.
+int scan_entry(ScanCall& c, bool ragged, int64_t n_samples, const int64_t* sample_offsets) {
+    const char* what = c.what;
+    const char* noun = c.carried ? "stream" : "signal";
+    const ScanOutputs& o = c.out;
+    const bool io_ptrs = c.samples && o.logits && o.probs && o.smoothed && o.top && o.score && o.is_new;
+    TCR_REQUIRE(c.plan_dev && c.m && c.m->params && c.m->aux && c.det && c.workspace && (!c.carried || c.state) &&
+                (ragged ? sample_offsets != nullptr : io_ptrs), "%s: null argument", what);
+    if (!c.carried) TCR_REQUIRE(c.n > 0, "%s: the number of signals must be positive (got %d)", what, c.n);
+    TCR_TRY(stream_check(c.cfg, c.m, c.n, c.k, c.det, what, c.io, c.carried));
+    const int64_t khop = (int64_t)c.k * c.cfg->hop;
+    int64_t steps = 0;
+    std::vector<int64_t> so;
+    if (!ragged) {
+        TCR_REQUIRE(n_samples > 0 && n_samples % khop == 0, "%s: the signal length %lld is not a positive multiple of k * hop = %lld", what,
+                    (long long)n_samples, (long long)khop);
+        steps = n_samples / khop;
+        TCR_REQUIRE((int64_t)c.n * steps * c.io.classes < ((int64_t)1 << 31), "%s: %d %ss x %lld steps is too large", what, c.n, noun,
+                    (long long)steps);
+    } else {
+        const size_t tables_bytes = scan_ragged_tables_bytes(c.n);
+        TCR_REQUIRE(tables_bytes <= c.ws_bytes, "%s: %d %ss are more than the max_signals the workspace's offset tables hold (%lld)", what,
+                    c.n, noun, (long long)(c.ws_bytes / (2 * sizeof(int64_t))) - 1);
+        TCR_REQUIRE(sample_offsets[0] == 0, "%s: sample_offsets must start at 0 (got %lld)", what, (long long)sample_offsets[0]);
+        so.resize((size_t)c.n + 1);
+        so[0] = 0;
+        for (int n = 0; n < c.n; ++n) {
+            const int64_t len = sample_offsets[n + 1] - sample_offsets[n];
+            TCR_REQUIRE(len >= 0, "%s: sample_offsets decrease at %s %d (%lld after %lld)", what, noun, n, (long long)sample_offsets[n + 1],
+                        (long long)sample_offsets[n]);
+            TCR_REQUIRE(len % khop == 0, "%s: the length %lld of %s %d is not a multiple of k * hop = %lld", what, (long long)len, noun, n,
+                        (long long)khop);
+            so[n + 1] = so[n] + len / khop;
+        }
+        TCR_REQUIRE(so[c.n] > 0, "%s: no %s has a whole step (total_steps == 0)", what, noun);
+        TCR_REQUIRE(so[c.n] * c.io.classes < ((int64_t)1 << 31), "%s: %lld steps in all is too large", what, (long long)so[c.n]);
+        TCR_REQUIRE(io_ptrs, "%s: null argument", what);
+        c.tables = static_cast<int64_t*>(c.workspace);
+        c.workspace = static_cast<char*>(c.workspace) + tables_bytes;
+        c.ws_bytes -= tables_bytes;
     }
-    const int64_t total_steps = so[n_signals];
-    TCR_REQUIRE(total_steps > 0, "%s: no signal has a whole step (total_steps == 0)", what);
-    TCR_REQUIRE(total_steps * io.classes < ((int64_t)1 << 31), "%s: %lld steps in all is too large", what, (long long)total_steps);
-    TCR_REQUIRE(samples && logits && probs && smoothed && top && score && is_new, "%s: null argument", what);
-    const ScanRagged rg{so.data(), static_cast<int64_t*>(workspace)};
-    return scan_run(*cfg, plan_dev, *m, io, n_signals, 0, k, *det, samples, ScanState{}, static_cast<char*>(workspace) + tables_bytes,
-                    ws_bytes - tables_bytes, logits, probs, smoothed, top, score, is_new, stream, what, &rg);
-}
-
-// tcr_stream_scan_ragged: scan_ragged's checks with the streams of a state in place of fresh signals (a stream without steps is
-// allowed, a call without any step is not), then the ragged pipeline from and to the state.
-int stream_scan_ragged(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* m, int n_streams, const int64_t* sample_offsets,
-                       int k, const tcr_detect_cfg* det, const float* samples, const uint8_t* reset, void* state, void* workspace,
-                       size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream,
-                       const char* what) {
-    TCR_REQUIRE(plan_dev && m && m->params && m->aux && det && sample_offsets && state && workspace, "%s: null argument", what);
-    ModelIO io;
-    TCR_TRY(stream_check(cfg, m, n_streams, k, det, what, io));
-    const size_t tables_bytes = scan_ragged_tables_bytes(n_streams);
-    TCR_REQUIRE(tables_bytes <= ws_bytes, "%s: %d streams are more than the max_signals the workspace's offset tables hold (%lld)", what,
-                n_streams, (long long)(ws_bytes / (2 * sizeof(int64_t))) - 1);
-    const int64_t khop = (int64_t)k * cfg->hop;
-    TCR_REQUIRE(sample_offsets[0] == 0, "%s: sample_offsets must start at 0 (got %lld)", what, (long long)sample_offsets[0]);
-    std::vector<int64_t> so((size_t)n_streams + 1);
-    so[0] = 0;
-    for (int n = 0; n < n_streams; ++n) {
-        const int64_t len = sample_offsets[n + 1] - sample_offsets[n];
-        TCR_REQUIRE(len >= 0, "%s: sample_offsets decrease at stream %d (%lld after %lld)", what, n, (long long)sample_offsets[n + 1],
-                    (long long)sample_offsets[n]);
-        TCR_REQUIRE(len % khop == 0, "%s: the length %lld of stream %d is not a multiple of k * hop = %lld", what, (long long)len, n,
-                    (long long)khop);
-        so[n + 1] = so[n] + len / khop;
+    ScanState st{};
+    if (c.carried) {
+        const StreamGeom sg = stream_geom(*c.cfg, *c.m, c.io, c.n, c.k, c.det->average_steps);
+        float* f = static_cast<float*>(c.state);
+        st = ScanState{f + sg.win_off, f + sg.tail_off, f + sg.ring_off, reinterpret_cast<int*>(f + sg.ist_off), c.reset, sg.tail_len};
     }
-    const int64_t total_steps = so[n_streams];
-    TCR_REQUIRE(total_steps > 0, "%s: no stream has a whole step (total_steps == 0)", what);
-    TCR_REQUIRE(total_steps * io.classes < ((int64_t)1 << 31), "%s: %lld steps in all is too large", what, (long long)total_steps);
-    TCR_REQUIRE(samples && logits && probs && smoothed && top && score && is_new, "%s: null argument", what);
-    const StreamGeom sg = stream_geom(*cfg, *m, io, n_streams, k, det->average_steps);
-    float* st = static_cast<float*>(state);
-    const ScanState carried{st + sg.win_off, st + sg.tail_off, st + sg.ring_off, reinterpret_cast<int*>(st + sg.ist_off), reset, sg.tail_len};
-    const ScanRagged rg{so.data(), static_cast<int64_t*>(workspace)};
-    return scan_run(*cfg, plan_dev, *m, io, n_streams, 0, k, *det, samples, carried, static_cast<char*>(workspace) + tables_bytes,
-                    ws_bytes - tables_bytes, logits, probs, smoothed, top, score, is_new, stream, what, &rg);
+    return scan_run(c, st, steps, so);
 }
 
 }  // namespace
@@ -898,40 +805,6 @@ int stream_scan_ragged(const tcr_frontend_cfg* cfg, const void* plan_dev, const 
 }  // namespace tcr
 
 using namespace tcr;
-
-extern "C" int tcr_stream_scan_ragged(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params,
-                                      const float* frozen_ss, int n_streams, const int64_t* sample_offsets, int k, const tcr_detect_cfg* det,
-                                      const float* samples, const uint8_t* reset, void* state, void* workspace, size_t ws_bytes,
-                                      float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new,
-                                      void* stream) {
-    const tcr_model_ref m = tcresnet_ref(net, params, frozen_ss);
-    return stream_scan_ragged(cfg, plan_dev, &m, n_streams, sample_offsets, k, det, samples, reset, state, workspace, ws_bytes, logits, probs,
-                              smoothed, top, score, is_new, stream, "tcr_stream_scan_ragged");
-}
-
-extern "C" int tcr_stream_scan_ragged_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_streams,
-                                        const int64_t* sample_offsets, int k, const tcr_detect_cfg* det, const float* samples,
-                                        const uint8_t* reset, void* state, void* workspace, size_t ws_bytes, float* logits, float* probs,
-                                        float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream) {
-    return stream_scan_ragged(cfg, plan_dev, model, n_streams, sample_offsets, k, det, samples, reset, state, workspace, ws_bytes, logits,
-                              probs, smoothed, top, score, is_new, stream, "tcr_stream_scan_ragged_m");
-}
-
-extern "C" size_t tcr_scan_ragged_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_model_ref* model, int k, int max_windows,
-                                                  int max_signals) {
-    const size_t chunk = scan_workspace_bytes(cfg, model, k, max_windows, "tcr_scan_ragged_workspace_bytes");
-    if (chunk == 0) return 0;
-    if (max_signals < 1) { set_error("tcr_scan_ragged_workspace_bytes: max_signals must be >= 1 (got %d)", max_signals); return 0; }
-    return scan_ragged_tables_bytes(max_signals) + chunk;
-}
-
-extern "C" int tcr_scan_ragged(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_signals,
-                               const int64_t* sample_offsets, int k, const tcr_detect_cfg* det, const float* samples, void* workspace,
-                               size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new,
-                               void* stream) {
-    return scan_ragged(cfg, plan_dev, model, n_signals, sample_offsets, k, det, samples, workspace, ws_bytes, logits, probs, smoothed, top,
-                       score, is_new, stream, "tcr_scan_ragged");
-}
 
 extern "C" size_t tcr_scan_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_net* net, int k, int max_windows) {
     const tcr_model_ref m = tcresnet_ref(net, nullptr, nullptr);
@@ -942,20 +815,39 @@ extern "C" size_t tcr_scan_workspace_bytes_m(const tcr_frontend_cfg* cfg, const 
     return scan_workspace_bytes(cfg, model, k, max_windows, "tcr_scan_workspace_bytes_m");
 }
 
-extern "C" int tcr_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params, const float* frozen_ss,
-                        int n_signals, int64_t n_samples, int k, const tcr_detect_cfg* det, const float* samples, void* workspace,
-                        size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new,
-                        void* stream) {
-    const tcr_model_ref m = tcresnet_ref(net, params, frozen_ss);
-    return scan(cfg, plan_dev, &m, n_signals, n_samples, k, det, samples, workspace, ws_bytes, logits, probs, smoothed, top, score, is_new,
-                stream, "tcr_scan");
+extern "C" size_t tcr_scan_ragged_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_model_ref* model, int k, int max_windows,
+                                                  int max_signals) {
+    const size_t chunk = scan_workspace_bytes(cfg, model, k, max_windows, "tcr_scan_ragged_workspace_bytes");
+    if (chunk == 0) return 0;
+    if (max_signals < 1) { set_error("tcr_scan_ragged_workspace_bytes: max_signals must be >= 1 (got %d)", max_signals); return 0; }
+    return scan_ragged_tables_bytes(max_signals) + chunk;
 }
 
 extern "C" int tcr_scan_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_signals, int64_t n_samples,
                           int k, const tcr_detect_cfg* det, const float* samples, void* workspace, size_t ws_bytes, float* logits,
                           float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream) {
-    return scan(cfg, plan_dev, model, n_signals, n_samples, k, det, samples, workspace, ws_bytes, logits, probs, smoothed, top, score, is_new,
-                stream, "tcr_scan_m");
+    ScanCall c{cfg, plan_dev, model, {}, n_signals, k, det, samples, nullptr, nullptr, false, workspace, ws_bytes, nullptr,
+               {logits, probs, smoothed, top, score, is_new}, stream, "tcr_scan_m"};
+    return scan_entry(c, false, n_samples, nullptr);
+}
+
+extern "C" int tcr_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params, const float* frozen_ss,
+                        int n_signals, int64_t n_samples, int k, const tcr_detect_cfg* det, const float* samples, void* workspace,
+                        size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new,
+                        void* stream) {
+    const tcr_model_ref m = tcresnet_ref(net, params, frozen_ss);
+    ScanCall c{cfg, plan_dev, &m, {}, n_signals, k, det, samples, nullptr, nullptr, false, workspace, ws_bytes, nullptr,
+               {logits, probs, smoothed, top, score, is_new}, stream, "tcr_scan"};
+    return scan_entry(c, false, n_samples, nullptr);
+}
+
+extern "C" int tcr_stream_scan_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_streams,
+                                 int64_t n_samples, int k, const tcr_detect_cfg* det, const float* samples, const uint8_t* reset, void* state,
+                                 void* workspace, size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score,
+                                 int32_t* is_new, void* stream) {
+    ScanCall c{cfg, plan_dev, model, {}, n_streams, k, det, samples, reset, state, true, workspace, ws_bytes, nullptr,
+               {logits, probs, smoothed, top, score, is_new}, stream, "tcr_stream_scan_m"};
+    return scan_entry(c, false, n_samples, nullptr);
 }
 
 extern "C" int tcr_stream_scan(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params,
@@ -963,14 +855,36 @@ extern "C" int tcr_stream_scan(const tcr_frontend_cfg* cfg, const void* plan_dev
                                const float* samples, const uint8_t* reset, void* state, void* workspace, size_t ws_bytes, float* logits,
                                float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream) {
     const tcr_model_ref m = tcresnet_ref(net, params, frozen_ss);
-    return stream_scan(cfg, plan_dev, &m, n_streams, n_samples, k, det, samples, reset, state, workspace, ws_bytes, logits, probs, smoothed,
-                       top, score, is_new, stream, "tcr_stream_scan");
+    ScanCall c{cfg, plan_dev, &m, {}, n_streams, k, det, samples, reset, state, true, workspace, ws_bytes, nullptr,
+               {logits, probs, smoothed, top, score, is_new}, stream, "tcr_stream_scan"};
+    return scan_entry(c, false, n_samples, nullptr);
 }
 
-extern "C" int tcr_stream_scan_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_streams,
-                                 int64_t n_samples, int k, const tcr_detect_cfg* det, const float* samples, const uint8_t* reset, void* state,
-                                 void* workspace, size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score,
-                                 int32_t* is_new, void* stream) {
-    return stream_scan(cfg, plan_dev, model, n_streams, n_samples, k, det, samples, reset, state, workspace, ws_bytes, logits, probs,
-                       smoothed, top, score, is_new, stream, "tcr_stream_scan_m");
+extern "C" int tcr_scan_ragged(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_signals,
+                               const int64_t* sample_offsets, int k, const tcr_detect_cfg* det, const float* samples, void* workspace,
+                               size_t ws_bytes, float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new,
+                               void* stream) {
+    ScanCall c{cfg, plan_dev, model, {}, n_signals, k, det, samples, nullptr, nullptr, false, workspace, ws_bytes, nullptr,
+               {logits, probs, smoothed, top, score, is_new}, stream, "tcr_scan_ragged"};
+    return scan_entry(c, true, 0, sample_offsets);
+}
+
+extern "C" int tcr_stream_scan_ragged_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_streams,
+                                        const int64_t* sample_offsets, int k, const tcr_detect_cfg* det, const float* samples,
+                                        const uint8_t* reset, void* state, void* workspace, size_t ws_bytes, float* logits, float* probs,
+                                        float* smoothed, int32_t* top, float* score, int32_t* is_new, void* stream) {
+    ScanCall c{cfg, plan_dev, model, {}, n_streams, k, det, samples, reset, state, true, workspace, ws_bytes, nullptr,
+               {logits, probs, smoothed, top, score, is_new}, stream, "tcr_stream_scan_ragged_m"};
+    return scan_entry(c, true, 0, sample_offsets);
+}
+
+extern "C" int tcr_stream_scan_ragged(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params,
+                                      const float* frozen_ss, int n_streams, const int64_t* sample_offsets, int k, const tcr_detect_cfg* det,
+                                      const float* samples, const uint8_t* reset, void* state, void* workspace, size_t ws_bytes,
+                                      float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new,
+                                      void* stream) {
+    const tcr_model_ref m = tcresnet_ref(net, params, frozen_ss);
+    ScanCall c{cfg, plan_dev, &m, {}, n_streams, k, det, samples, reset, state, true, workspace, ws_bytes, nullptr,
+               {logits, probs, smoothed, top, score, is_new}, stream, "tcr_stream_scan_ragged"};
+    return scan_entry(c, true, 0, sample_offsets);
 }

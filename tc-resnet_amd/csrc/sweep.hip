@@ -244,6 +244,42 @@ int sweep_launch(SweepArgs& a, hipStream_t s, const char* what) {
     return check_launch("sweep_kernel");
 }
 
+// What the two entries share: the checks in their order, the argument fill and the launch.  Dense: `steps` per signal (checked, and
+// `fired` is cleared here); ragged (step_offsets non-null where the entry requires it): the packed rows of step_offsets.
+int sweep(const char* what, bool ragged, int n_signals, int64_t steps, const int64_t* step_offsets, int num_classes, const int32_t* top,
+          const float* score, const int64_t* valid_steps, int32_t suppression_steps, int n_thresholds, const float* thresholds,
+          const int32_t* event_offsets, const int64_t* event_first, const int64_t* event_last, const int32_t* event_label,
+          int32_t* detections, int32_t* hits, int32_t* duplicates, uint8_t* fired, void* stream) {
+    TCR_REQUIRE((!ragged || step_offsets) && top && score && thresholds && detections, "%s: null argument", what);
+    TCR_REQUIRE(n_signals > 0, "%s: the number of signals must be positive (got %d)", what, n_signals);
+    TCR_REQUIRE(ragged || steps > 0, "%s: the number of steps must be positive (got %lld)", what, (long long)steps);
+    TCR_REQUIRE(n_thresholds > 0, "%s: the number of thresholds must be positive (got %d)", what, n_thresholds);
+    TCR_REQUIRE(num_classes > 0 && num_classes <= kSweepMaxClasses, "%s: num_classes %d outside 1..%d", what, num_classes, kSweepMaxClasses);
+    TCR_REQUIRE(suppression_steps >= 0, "%s: suppression_steps must be >= 0 (got %d)", what, suppression_steps);
+    TCR_REQUIRE(!event_offsets || (event_first && event_last && event_label && hits && duplicates),
+                "%s: events need event_first, event_last, event_label, hits and duplicates", what);
+    const bool results_fit = (int64_t)n_signals * n_thresholds * num_classes < ((int64_t)1 << 31);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ragged) {
+        TCR_REQUIRE(results_fit, "%s: %d signals x %d thresholds x %d classes is too large", what, n_signals, n_thresholds, num_classes);
+    } else {
+        TCR_REQUIRE((int64_t)n_signals * steps < ((int64_t)1 << 31) && results_fit,
+                    "%s: %d signals x %lld steps x %d thresholds x %d classes is too large", what, n_signals, (long long)steps, n_thresholds,
+                    num_classes);
+        if (fired && hipMemsetAsync(fired, 0, (size_t)n_thresholds * n_signals * steps, s) != hipSuccess) {
+            set_error("%s: hipMemsetAsync of fired failed", what);
+            return TCR_ERR_HIP;
+        }
+    }
+    SweepArgs a;
+    a.top = top; a.score = score; a.valid_steps = valid_steps; a.thresholds = thresholds;
+    a.ev_off = event_offsets; a.ev_first = event_first; a.ev_last = event_last; a.ev_label = event_label;
+    a.detections = detections; a.hits = hits; a.duplicates = duplicates; a.fired = fired;
+    a.steps = steps; a.n_signals = n_signals; a.n_thr = n_thresholds; a.C = num_classes; a.suppression = suppression_steps;
+    a.step_off = step_offsets;
+    return ragged ? sweep_launch<true>(a, s, what) : sweep_launch<false>(a, s, what);
+}
+
 }  // namespace
 
 }  // namespace tcr
@@ -255,51 +291,14 @@ extern "C" int tcr_detect_sweep(int n_signals, int64_t steps, int num_classes, c
                                 const int32_t* event_offsets, const int64_t* event_first, const int64_t* event_last,
                                 const int32_t* event_label, int32_t* detections, int32_t* hits, int32_t* duplicates, uint8_t* fired,
                                 void* stream) {
-    TCR_REQUIRE(top && score && thresholds && detections, "tcr_detect_sweep: null argument");
-    TCR_REQUIRE(n_signals > 0, "tcr_detect_sweep: the number of signals must be positive (got %d)", n_signals);
-    TCR_REQUIRE(steps > 0, "tcr_detect_sweep: the number of steps must be positive (got %lld)", (long long)steps);
-    TCR_REQUIRE(n_thresholds > 0, "tcr_detect_sweep: the number of thresholds must be positive (got %d)", n_thresholds);
-    TCR_REQUIRE(num_classes > 0 && num_classes <= kSweepMaxClasses, "tcr_detect_sweep: num_classes %d outside 1..%d", num_classes,
-                kSweepMaxClasses);
-    TCR_REQUIRE(suppression_steps >= 0, "tcr_detect_sweep: suppression_steps must be >= 0 (got %d)", suppression_steps);
-    TCR_REQUIRE(!event_offsets || (event_first && event_last && event_label && hits && duplicates),
-                "tcr_detect_sweep: events need event_first, event_last, event_label, hits and duplicates");
-    TCR_REQUIRE((int64_t)n_signals * steps < ((int64_t)1 << 31) && (int64_t)n_signals * n_thresholds * num_classes < ((int64_t)1 << 31),
-                "tcr_detect_sweep: %d signals x %lld steps x %d thresholds x %d classes is too large", n_signals, (long long)steps,
-                n_thresholds, num_classes);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (fired && hipMemsetAsync(fired, 0, (size_t)n_thresholds * n_signals * steps, s) != hipSuccess) {
-        set_error("tcr_detect_sweep: hipMemsetAsync of fired failed");
-        return TCR_ERR_HIP;
-    }
-    SweepArgs a;
-    a.top = top; a.score = score; a.valid_steps = valid_steps; a.thresholds = thresholds;
-    a.ev_off = event_offsets; a.ev_first = event_first; a.ev_last = event_last; a.ev_label = event_label;
-    a.detections = detections; a.hits = hits; a.duplicates = duplicates; a.fired = fired;
-    a.steps = steps; a.n_signals = n_signals; a.n_thr = n_thresholds; a.C = num_classes; a.suppression = suppression_steps;
-    a.step_off = nullptr;
-    return sweep_launch<false>(a, s, "tcr_detect_sweep");
+    return sweep("tcr_detect_sweep", false, n_signals, steps, nullptr, num_classes, top, score, valid_steps, suppression_steps, n_thresholds,
+                 thresholds, event_offsets, event_first, event_last, event_label, detections, hits, duplicates, fired, stream);
 }
 
 extern "C" int tcr_detect_sweep_ragged(int n_signals, const int64_t* step_offsets, int num_classes, const int32_t* top, const float* score,
                                        int32_t suppression_steps, int n_thresholds, const float* thresholds, const int32_t* event_offsets,
                                        const int64_t* event_first, const int64_t* event_last, const int32_t* event_label,
                                        int32_t* detections, int32_t* hits, int32_t* duplicates, uint8_t* fired, void* stream) {
-    const char* what = "tcr_detect_sweep_ragged";
-    TCR_REQUIRE(step_offsets && top && score && thresholds && detections, "%s: null argument", what);
-    TCR_REQUIRE(n_signals > 0, "%s: the number of signals must be positive (got %d)", what, n_signals);
-    TCR_REQUIRE(n_thresholds > 0, "%s: the number of thresholds must be positive (got %d)", what, n_thresholds);
-    TCR_REQUIRE(num_classes > 0 && num_classes <= kSweepMaxClasses, "%s: num_classes %d outside 1..%d", what, num_classes, kSweepMaxClasses);
-    TCR_REQUIRE(suppression_steps >= 0, "%s: suppression_steps must be >= 0 (got %d)", what, suppression_steps);
-    TCR_REQUIRE(!event_offsets || (event_first && event_last && event_label && hits && duplicates),
-                "%s: events need event_first, event_last, event_label, hits and duplicates", what);
-    TCR_REQUIRE((int64_t)n_signals * n_thresholds * num_classes < ((int64_t)1 << 31), "%s: %d signals x %d thresholds x %d classes is too large",
-                what, n_signals, n_thresholds, num_classes);
-    SweepArgs a;
-    a.top = top; a.score = score; a.valid_steps = nullptr; a.thresholds = thresholds;
-    a.ev_off = event_offsets; a.ev_first = event_first; a.ev_last = event_last; a.ev_label = event_label;
-    a.detections = detections; a.hits = hits; a.duplicates = duplicates; a.fired = fired;
-    a.steps = 0; a.n_signals = n_signals; a.n_thr = n_thresholds; a.C = num_classes; a.suppression = suppression_steps;
-    a.step_off = step_offsets;
-    return sweep_launch<true>(a, static_cast<hipStream_t>(stream), what);
+    return sweep("tcr_detect_sweep_ragged", true, n_signals, 0, step_offsets, num_classes, top, score, nullptr, suppression_steps, n_thresholds,
+                 thresholds, event_offsets, event_first, event_last, event_label, detections, hits, duplicates, fired, stream);
 }

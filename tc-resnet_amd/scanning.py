@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from ._lib import TcrError
 from .engine import Frontend
-from .streaming import Network, _Detection
+from .streaming import Network, _Detection, _ragged_scan_output, _ragged_signals, _scan_output
 
 DEFAULT_MAX_WINDOWS = 4096
 DEFAULT_MAX_SIGNALS = 65536
@@ -105,11 +105,7 @@ class KeywordScanner(_Detection):
         self.net._check_tensor(samples, "scan samples")
         N, L = int(samples.shape[0]), int(samples.shape[1])        # (tcr_scan refuses N <= 0 and L not a multiple of k * hop)
         ref = self._call_ref()
-        steps, ncls, dev = max(L // self.step_samples, 0), self.net.num_classes, self.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        out = ScanOutput(torch.empty((N, steps, ncls), **f32), torch.empty((N, steps, ncls), **f32), torch.empty((N, steps, ncls), **f32),
-                         torch.empty((N, steps), **i32), torch.empty((N, steps), **f32), torch.empty((N, steps), **i32))
+        out = _scan_output(N, max(L // self.step_samples, 0), self.net.num_classes, self.device)
         fe, net = self.frontend, self.net
         self.lib.check(self.lib.tcr_scan_m(C.byref(fe.cfg), fe.plan.data_ptr(), C.byref(ref), N, L, self.k, C.byref(self.det),
                                            samples.data_ptr(), self.workspace.data_ptr(), self.workspace.numel() * 4,
@@ -122,42 +118,13 @@ class KeywordScanner(_Detection):
         one 1-D float32 device tensor holding the signals one after the other and their lengths in samples.  Every length is a multiple
         of k * hop; 0 is allowed (no rows).  Returns a `RaggedScanOutput` of new tensors: `signal(n)` is bitwise `scan` of signal n
         alone, whatever max_windows and the other signals.  The weight rules are `scan`'s."""
-        if isinstance(signals, tuple) and len(signals) == 2 and isinstance(signals[0], torch.Tensor):
-            packed, lengths = signals[0], np.asarray(signals[1], dtype=np.int64).reshape(-1)
-            if packed.dim() != 1:
-                raise TcrError(f"scan_ragged expects a packed 1-D tensor, got shape {tuple(packed.shape)}")
-        else:
-            signals = list(signals)
-            for n, x in enumerate(signals):
-                if not isinstance(x, torch.Tensor) or x.dim() != 1:
-                    raise TcrError(f"scan_ragged expects 1-D tensors, signal {n} is {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
-            lengths = np.array([int(x.shape[0]) for x in signals], dtype=np.int64)
-            if not signals:
-                raise TcrError("scan_ragged: no signals")
-            packed = signals[0] if len(signals) == 1 else torch.cat(signals)
+        packed, lengths, offsets = _ragged_signals("scan_ragged", "signal", signals)
         N = int(lengths.size)
-        offsets = np.zeros(N + 1, dtype=np.int64)
-        np.cumsum(lengths, out=offsets[1:])
-        if int(offsets[-1]) != int(packed.shape[0]) and (lengths >= 0).all():
-            raise TcrError(f"scan_ragged: the lengths sum to {int(offsets[-1])} samples, the packed tensor has {int(packed.shape[0])}")
         self.net._check_tensor(packed, "scan samples")
-        lib, fe, net, dev = self.lib, self.frontend, self.net, self.device
-        if self._ragged_ws is None or N > self.max_signals:
-            self.max_signals = max(self.max_signals, N)
-            nws = lib.tcr_scan_ragged_workspace_bytes(C.byref(fe.cfg), C.byref(self._ref()), self.k, self.max_windows, self.max_signals)
-            if nws == 0:
-                raise TcrError(f"KeywordScanner.scan_ragged: {lib.tcr_last_error().decode()}")
-            self._ragged_ws = torch.empty(nws // 4, dtype=torch.float32, device=dev)
+        lib, fe, net = self.lib, self.frontend, self.net
+        ws = self._ragged_workspace("scan_ragged", N)
         ref = self._call_ref()
-        step = self.step_samples
-        ok = N > 0 and (lengths >= 0).all() and not (lengths % step).any()
-        total = int(offsets[-1]) // step if ok else 0           # (otherwise tcr_scan_ragged refuses, and the outputs are not written)
-        ncls = net.num_classes
-        f32 = dict(dtype=torch.float32, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        out = RaggedScanOutput(torch.empty((total, ncls), **f32), torch.empty((total, ncls), **f32), torch.empty((total, ncls), **f32),
-                               torch.empty(total, **i32), torch.empty(total, **f32), torch.empty(total, **i32), offsets // step)
-        ws = self._ragged_ws
+        out = _ragged_scan_output(lengths, offsets, self.step_samples, net.num_classes, self.device)
         lib.check(lib.tcr_scan_ragged(C.byref(fe.cfg), fe.plan.data_ptr(), C.byref(ref), N, offsets.ctypes.data, self.k, C.byref(self.det),
                                       packed.data_ptr(), ws.data_ptr(), ws.numel() * 4, *(t.data_ptr() for t in out.tensors()),
                                       net._stream()), "tcr_scan_ragged")

@@ -40,6 +40,52 @@ def ms_to_steps(ms: float, step_ms: float) -> int:
     return int(round(float(ms) / step_ms))
 
 
+def _ragged_signals(what: str, noun: str, signals, count: Optional[int] = None):
+    """The `signals` argument of `what` (scan_ragged, push_ragged) -> (packed, lengths, offsets in samples [N + 1]): a list of 1-D
+    tensors, one per `noun`, or (packed, lengths).  count: the signals the caller expects (None: any number, a list not empty)."""
+    if isinstance(signals, tuple) and len(signals) == 2 and isinstance(signals[0], torch.Tensor):
+        packed, lengths = signals[0], np.asarray(signals[1], dtype=np.int64).reshape(-1)
+        if packed.dim() != 1:
+            raise TcrError(f"{what} expects a packed 1-D tensor, got shape {tuple(packed.shape)}")
+    else:
+        signals = list(signals)
+        for n, x in enumerate(signals):
+            if not isinstance(x, torch.Tensor) or x.dim() != 1:
+                raise TcrError(f"{what} expects 1-D tensors, {noun} {n} is {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+        lengths = np.array([int(x.shape[0]) for x in signals], dtype=np.int64)
+        if count is None and not signals:
+            raise TcrError(f"{what}: no signals")
+        packed = signals[0] if len(signals) == 1 else (torch.cat(signals) if signals else None)
+    if count is not None and int(lengths.size) != count:
+        raise TcrError(f"{what} expects {count} signals (one per stream, empty for a stream without steps), got {int(lengths.size)}")
+    offsets = np.zeros(int(lengths.size) + 1, dtype=np.int64)
+    np.cumsum(lengths, out=offsets[1:])
+    if int(offsets[-1]) != int(packed.shape[0]) and (lengths >= 0).all():
+        raise TcrError(f"{what}: the lengths sum to {int(offsets[-1])} samples, the packed tensor has {int(packed.shape[0])}")
+    return packed, lengths, offsets
+
+
+def _scan_output(n: int, steps: int, ncls: int, dev):
+    """A scanning.ScanOutput of new tensors for n signals x steps."""
+    from .scanning import ScanOutput
+    f32 = dict(dtype=torch.float32, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    return ScanOutput(torch.empty((n, steps, ncls), **f32), torch.empty((n, steps, ncls), **f32), torch.empty((n, steps, ncls), **f32),
+                      torch.empty((n, steps), **i32), torch.empty((n, steps), **f32), torch.empty((n, steps), **i32))
+
+
+def _ragged_scan_output(lengths: np.ndarray, offsets: np.ndarray, step: int, ncls: int, dev):
+    """A scanning.RaggedScanOutput of new tensors for signals of `lengths` samples (`offsets`: their running sum) at `step` samples a
+    step; without rows when a length is no whole number of steps (the call refuses then, and the outputs are not written)."""
+    from .scanning import RaggedScanOutput
+    ok = lengths.size > 0 and bool((lengths >= 0).all()) and not (lengths % step).any()
+    total = int(offsets[-1]) // step if ok else 0
+    f32 = dict(dtype=torch.float32, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    return RaggedScanOutput(torch.empty((total, ncls), **f32), torch.empty((total, ncls), **f32), torch.empty((total, ncls), **f32),
+                            torch.empty(total, **i32), torch.empty(total, **f32), torch.empty(total, **i32), offsets // step)
+
+
 class _Detection:
     """What `StreamingDetector` and `scanning.KeywordScanner` share: the argument checks, the detector settings in steps, the model
     reference of the C calls and the weight / fold rules (see `StreamingDetector`)."""
@@ -98,6 +144,18 @@ class _Detection:
     def _after_call(self) -> None:
         if self._family == FAMILY_TCRESNET:
             self.net._note_fold_reader()
+
+    def _ragged_workspace(self, what: str, n: int) -> torch.Tensor:
+        """The workspace of the ragged calls (sized by max_windows and max_signals), allocated on the first call and again when a call
+        brings more than max_signals signals."""
+        if self._ragged_ws is None or n > self.max_signals:
+            self.max_signals = max(self.max_signals, n)
+            lib = self.lib
+            nws = lib.tcr_scan_ragged_workspace_bytes(C.byref(self.frontend.cfg), C.byref(self._ref()), self.k, self.max_windows, self.max_signals)
+            if nws == 0:
+                raise TcrError(f"{self._what}.{what}: {lib.tcr_last_error().decode()}")
+            self._ragged_ws = torch.empty(nws // 4, dtype=torch.float32, device=self.device)
+        return self._ragged_ws
 
     # ---- detector settings in steps ------------------------------------------------------------------------------------
     @property
@@ -219,7 +277,7 @@ class StreamingDetector(_Detection):
         if max_windows is None:
             from .scanning import DEFAULT_MAX_WINDOWS
             max_windows = DEFAULT_MAX_WINDOWS
-        self.max_windows = int(max_windows)
+        self.max_windows, self.max_signals = int(max_windows), self.n_streams
         self._scan_ws: Optional[torch.Tensor] = None
         self._ragged_ws: Optional[torch.Tensor] = None
         cfg = frontend.cfg
@@ -306,7 +364,6 @@ class StreamingDetector(_Detection):
         of m `push` calls returns, and the detector is left as those pushes leave it, so `push` and `push_many` mix freely.  Pending
         `reset`s apply at the first step; `out` is not touched.  The weight / fold rules are `push`'s.  The scan workspace (sized
         by max_windows) is allocated on the first call."""
-        from .scanning import ScanOutput
         S, step = self.n_streams, self.step_samples
         if samples.dim() != 2 or int(samples.shape[0]) != S:
             raise TcrError(f"push_many expects samples [{S}, m * {step}] (m steps of k * hop per stream), got {tuple(samples.shape)}")
@@ -319,11 +376,7 @@ class StreamingDetector(_Detection):
             self._scan_ws = torch.empty(nws // 4, dtype=torch.float32, device=self.device)
         ref = self._call_ref()
         L = int(samples.shape[1])
-        steps, ncls = max(L // step, 0), net.num_classes
-        f32 = dict(dtype=torch.float32, device=self.device)
-        i32 = dict(dtype=torch.int32, device=self.device)
-        out = ScanOutput(torch.empty((S, steps, ncls), **f32), torch.empty((S, steps, ncls), **f32), torch.empty((S, steps, ncls), **f32),
-                         torch.empty((S, steps), **i32), torch.empty((S, steps), **f32), torch.empty((S, steps), **i32))
+        out = _scan_output(S, max(L // step, 0), net.num_classes, self.device)
         ws = self._scan_ws
         lib.check(lib.tcr_stream_scan_m(C.byref(fe.cfg), fe.plan.data_ptr(), C.byref(ref), S, L, self.k, C.byref(self.det),
                                         samples.data_ptr(), self._take_reset(), self.state.data_ptr(), ws.data_ptr(), ws.numel() * 4,
@@ -341,51 +394,21 @@ class StreamingDetector(_Detection):
         steps and stays pending for a stream without steps in this call; `out` is not touched.  The weight / fold rules are `push`'s.
         The ragged workspace (sized by max_windows and n_streams) is allocated on the first call.  At least one stream must have a
         step."""
-        from .scanning import RaggedScanOutput
-        S, step = self.n_streams, self.step_samples
-        if isinstance(signals, tuple) and len(signals) == 2 and isinstance(signals[0], torch.Tensor):
-            packed, lengths = signals[0], np.asarray(signals[1], dtype=np.int64).reshape(-1)
-            if packed.dim() != 1:
-                raise TcrError(f"push_ragged expects a packed 1-D tensor, got shape {tuple(packed.shape)}")
-        else:
-            signals = list(signals)
-            for n, x in enumerate(signals):
-                if not isinstance(x, torch.Tensor) or x.dim() != 1:
-                    raise TcrError(f"push_ragged expects 1-D tensors, stream {n} is {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
-            lengths = np.array([int(x.shape[0]) for x in signals], dtype=np.int64)
-            packed = signals[0] if len(signals) == 1 else (torch.cat(signals) if signals else None)
-        if int(lengths.size) != S:
-            raise TcrError(f"push_ragged expects {S} signals (one per stream, empty for a stream without steps), got {int(lengths.size)}")
-        offsets = np.zeros(S + 1, dtype=np.int64)
-        np.cumsum(lengths, out=offsets[1:])
-        if int(offsets[-1]) != int(packed.shape[0]) and (lengths >= 0).all():
-            raise TcrError(f"push_ragged: the lengths sum to {int(offsets[-1])} samples, the packed tensor has {int(packed.shape[0])}")
+        S = self.n_streams
+        packed, lengths, offsets = _ragged_signals("push_ragged", "stream", signals, S)
         self.net._check_tensor(packed, "stream samples")
-        lib, fe, net, dev = self.lib, self.frontend, self.net, self.device
-        if self._ragged_ws is None:
-            nws = lib.tcr_scan_ragged_workspace_bytes(C.byref(fe.cfg), C.byref(self._ref()), self.k, self.max_windows, S)
-            if nws == 0:
-                raise TcrError(f"StreamingDetector.push_ragged: {lib.tcr_last_error().decode()}")
-            self._ragged_ws = torch.empty(nws // 4, dtype=torch.float32, device=dev)
+        lib, fe, net = self.lib, self.frontend, self.net
+        ws = self._ragged_workspace("push_ragged", S)
         ref = self._call_ref()
-        ok = bool((lengths >= 0).all()) and not (lengths % step).any()
-        total = int(offsets[-1]) // step if ok else 0           # (otherwise the call refuses, and the outputs are not written)
-        ncls = net.num_classes
-        f32 = dict(dtype=torch.float32, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        out = RaggedScanOutput(torch.empty((total, ncls), **f32), torch.empty((total, ncls), **f32), torch.empty((total, ncls), **f32),
-                               torch.empty(total, **i32), torch.empty(total, **f32), torch.empty(total, **i32), offsets // step)
-        reset_ptr = None
-        if self._pending is not None:                           # (the call ignores the flag of a stream without steps)
-            self._reset_dev.copy_(torch.from_numpy(self._pending.astype(np.uint8)))
-            reset_ptr = self._reset_dev.data_ptr()
-        ws = self._ragged_ws
+        out = _ragged_scan_output(lengths, offsets, self.step_samples, net.num_classes, self.device)
+        pending, reset_ptr = self._pending, self._take_reset()
+        self._pending = pending                                 # (until the call has run; it ignores the flag of a stream without steps)
         lib.check(lib.tcr_stream_scan_ragged_m(C.byref(fe.cfg), fe.plan.data_ptr(), C.byref(ref), S, offsets.ctypes.data, self.k,
                                                C.byref(self.det), packed.data_ptr(), reset_ptr, self.state.data_ptr(), ws.data_ptr(),
                                                ws.numel() * 4, *(t.data_ptr() for t in out.tensors()), net._stream()),
                   "tcr_stream_scan_ragged")
-        if self._pending is not None:
-            left = self._pending & (lengths == 0)
+        if pending is not None:
+            left = pending & (lengths == 0)
             self._pending = left if left.any() else None
         self._after_call()
         return out

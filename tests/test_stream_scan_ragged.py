@@ -238,6 +238,32 @@ def test_push_ragged_short_call_against_the_tail_3010(emu_lib):
     rig.ragged([1, 0, 2, 3])
 
 
+def planes_write_back_with_surviving_tail(lib):
+    """The planes form of the write-back with old tail samples surviving a call, through the ragged and the dense caller: a 2-D graph at
+    win 480 / hop 160, k = 1, so that a step of 160 samples leaves 160 of the tail's 320.  Outputs and every state part are the
+    one-stream oracles' after every call, a pending reset waits for its stream's next step, and a stream without steps keeps every
+    byte (Rig.ragged)."""
+    from tests.test_detect_families import kws_graph
+    fe, net = kws_graph(lib, "tiny_conv", win=480, hop=160)
+    cfg = fe.cfg
+    tail_len = cfg.win - cfg.hop + (cfg.n_samples - cfg.win) % cfg.hop
+    assert tail_len == 320 and 0 < tail_len - 1 * cfg.hop == 160
+    rig = Rig(lib, fe, net, 3, 5, 83, det=dict(DET, average_window_ms=50, suppression_ms=30), max_windows=2)
+    assert rig.step == 160
+    rig.ragged([1, 0, 2])
+    rig.reset([0, 1])
+    rig.ragged([1, 0, 1])
+    assert rig.dut._pending.tolist() == [False, True, False]
+    rig.lockstep(1, many=True)
+    assert rig.dut._pending is None
+    rig.ragged([0, 1, 1])
+    assert state_parts(rig.dut)[3].cpu().numpy()[4].tolist() == [2, 2, 5]
+
+
+def test_push_ragged_planes_write_back_with_surviving_tail(emu_lib):
+    planes_write_back_with_surviving_tail(emu_lib)
+
+
 @pytest.mark.parametrize("case", ["4020_k3", "4020_k49", "3010_log_mel_k2"])
 def test_push_ragged_other_k(emu_lib, case):
     if case == "3010_log_mel_k2":
@@ -296,29 +322,34 @@ def test_push_ragged_launch_log(emu_lib):
     det = St.StreamingDetector(net, fe, 2, max_windows=16, **DET)
     with Log(emu_lib) as g:
         det.push_ragged([x[0], x[1, :320]])
-    for name in ("scan_stage_ragged_tail_kernel", "scan_gather_kernel<false, true, true>", "scan_carry_ragged_kernel<false>",
+    for name in ("scan_stage_ragged_kernel<true>", "scan_gather_kernel<false, true, true>", "scan_carry_kernel<false, true>",
                  "scan_smooth_kernel<true, true>", "scan_suppress_kernel<true>"):
         assert g.has(name), (name, g.entries)
-    for name in ("scan_stage_kernel", "scan_stage_ragged_kernel", "scan_carry_kernel", "scan_scatter_kernel"):
+    for name in ("scan_stage_kernel", "scan_stage_ragged_kernel<false>", "scan_carry_kernel<false, false>", "scan_carry_kernel<true",
+                 "scan_scatter_kernel", "scan_gather_kernel<false, true, false>", "scan_smooth_kernel<true, false>",
+                 "scan_suppress_kernel<false>"):
         assert not g.has(name), (name, g.entries)
     with Log(emu_lib) as g:
         det.push_many(x)
-    for name in ("scan_stage_kernel", "scan_gather_kernel<false, true, false>", "scan_carry_kernel<false>", "scan_scatter_kernel",
-                 "scan_smooth_kernel<true", "scan_suppress_kernel<false>"):
+    for name in ("scan_stage_kernel", "scan_gather_kernel<false, true, false>", "scan_carry_kernel<false, false>", "scan_scatter_kernel",
+                 "scan_smooth_kernel<true, false>", "scan_suppress_kernel<false>"):
         assert g.has(name), (name, g.entries)
     assert not g.has("ragged") and not g.has("scan_smooth_kernel<true, true>"), g.entries
+    for name in ("scan_carry_kernel<false, true>", "scan_carry_kernel<true", "scan_gather_kernel<false, true, true>", "scan_suppress_kernel<true>"):
+        assert not g.has(name), (name, g.entries)
     with Log(emu_lib) as g:
         Sc.KeywordScanner(net, fe, max_windows=16, **DET).scan_ragged([x[0], x[1, :320]])
-    for name in ("scan_stage_ragged_kernel", "scan_gather_kernel<false, false, true>", "scan_smooth_kernel<false, true>",
+    for name in ("scan_stage_ragged_kernel<false>", "scan_gather_kernel<false, false, true>", "scan_smooth_kernel<false, true>",
                  "scan_suppress_kernel<true>"):
         assert g.has(name), (name, g.entries)
-    assert not g.has("scan_stage_ragged_tail_kernel") and not g.has("carry"), g.entries
+    assert not g.has("scan_stage_ragged_kernel<true>") and not g.has("carry") and not g.has("scan_stage_kernel"), g.entries
     from tests.test_detect_families import MODELS
     fe2, net2 = MODELS["tiny_conv"](emu_lib)
     x2 = Cm.to_dev(emu_lib, segment_audio(2, 2 * fe2.cfg.hop, 80))
     with Log(emu_lib) as g:
         St.StreamingDetector(net2, fe2, 2, max_windows=4, **DET).push_ragged([x2[0], x2[1, :0]])
-    assert g.has("scan_gather_kernel<true, true, true>") and g.has("scan_carry_ragged_kernel<true>"), g.entries
+    assert g.has("scan_gather_kernel<true, true, true>") and g.has("scan_carry_kernel<true, true>"), g.entries
+    assert not g.has("scan_carry_kernel<true, false>") and not g.has("scan_carry_kernel<false"), g.entries
 
 
 def test_push_ragged_argument_errors(emu_lib):
@@ -472,6 +503,11 @@ def test_gpu_push_ragged_families(hip_lib, model):
     from tests.test_detect_families import MODELS
     fe, net = MODELS[model](hip_lib)
     run_gpu_plan(hip_lib, fe, net, gpu_plan(94, 8, 60, 3), 95, det=dict(GPU_DET, average_window_ms=300, suppression_ms=400))
+
+
+@pytest.mark.gpu
+def test_gpu_push_ragged_planes_write_back_with_surviving_tail(hip_lib):
+    planes_write_back_with_surviving_tail(hip_lib)
 
 
 @pytest.mark.gpu
