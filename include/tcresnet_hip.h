@@ -597,6 +597,57 @@ int tcr_detect_sweep_ragged(int n_signals, const int64_t* step_offsets /* DEVICE
                             const int32_t* event_label, int32_t* detections, int32_t* hits, int32_t* duplicates,
                             uint8_t* fired /* [T][total_steps] or NULL */, void* stream);
 
+/* Detector tuning from one scan.  logits / probs of a scan do not depend on det, so the detector tail can be run again on the probs a
+ * scan wrote, with any other det, without the front-end and the network.
+ *
+ * tcr_detect_redetect: probs [N][steps][num_classes] (what tcr_scan / tcr_scan_m wrote, with any det) -> smoothed [N][steps][C] (NULL:
+ * not written), top / score / is_new [N][steps]: for every signal bitwise what tcr_scan_m writes for it with this det (the rule of
+ * tcr_stream_step above, from a fresh detector).  tcr_detect_redetect_ragged: the same over packed probs [total_steps][C] with signal
+ * n's steps in rows step_offsets[n] .. step_offsets[n + 1] - 1 (DEVICE int64 [N + 1], from 0, non-decreasing, step_offsets[N] ==
+ * total_steps: preconditions, the host does not read the table): bitwise tcr_scan_ragged's outputs; a signal's first steps never read
+ * the signal before it.  Both only enqueue kernels on `stream` -- no copy, no wait -- so, unlike tcr_scan_ragged, they can be captured
+ * into a graph.  Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched): null probs / det / top / score / is_new (ragged:
+ * step_offsets), N, steps (ragged: total_steps) or num_classes <= 0, num_classes > 256, average_steps < 1, min_count outside
+ * 1..average_steps, suppression_steps < 0, N x steps x num_classes >= 2^31. */
+int tcr_detect_redetect(int n_signals, int64_t steps, int num_classes, const float* probs /* [N][steps][C] */,
+                        const tcr_detect_cfg* det, float* smoothed /* [N][steps][C] or NULL */, int32_t* top, float* score,
+                        int32_t* is_new, void* stream);
+int tcr_detect_redetect_ragged(int n_signals, const int64_t* step_offsets /* DEVICE [N + 1] */, int64_t total_steps, int num_classes,
+                               const float* probs /* packed [total_steps][C] */, const tcr_detect_cfg* det, float* smoothed,
+                               int32_t* top, float* score, int32_t* is_new, void* stream);
+
+/* The detector grid: J points (average_steps, min_count, suppression_steps) x T thresholds from one scan's probs, in one call.  For
+ * point j the slice [j] of detections / hits / duplicates int32 [J][N][T][num_classes] equals tcr_detect_sweep (step_offsets != NULL:
+ * tcr_detect_sweep_ragged) over the top / score of a scan of the same audio with det = {points[j], any threshold} -- the same
+ * thresholds, events (in steps: they do not depend on the point) and valid_steps.  Dense: probs [N][steps][C], total_steps = N x
+ * steps, valid_steps [N] or NULL.  Ragged: probs packed [total_steps][C], step_offsets a DEVICE table as above, `steps` ignored,
+ * valid_steps NULL.  `points` is a HOST array, read before the call returns; every other pointer is device memory.  There is no
+ * `fired` output (J x T x steps bytes): the detections of one point are tcr_detect_redetect plus tcr_detect_sweep.
+ * How: the points are reduced to their distinct (average_steps, min_count) pairs.  One kernel stages tiles of TCR_GRID_TILE steps (and
+ * the average_steps - 1 rows in front of them) in LDS and writes top / score for every pair into workspace rows, smoothing once per
+ * distinct average_steps; then tcr_detect_sweep's kernel runs once per point over its pair's rows.  The staged tile holds
+ * (TCR_GRID_TILE + W - 1) x num_classes floats in 63 KB of LDS, so it takes average_steps up to  W_max = 16128 / num_classes - 255
+ * (num_classes 12: 1089; 3: 5121; 36: 193; none from 63 classes on); pairs above W_max are smoothed by tcr_detect_redetect's kernel,
+ * one launch each, into the same rows (the same results, each row read average_steps times from memory instead).
+ * Workspace: tcr_detect_grid_workspace_bytes(total_steps, n_points) holds the rows of n_points pairs (0: invalid arguments), which
+ * is enough for any grid of n_points points; with fewer bytes the pairs run in batches that fit, the counts are the same, and below
+ * tcr_detect_grid_workspace_bytes(total_steps, 1) the call returns TCR_ERR_WORKSPACE.  Everything is enqueued on `stream`.
+ * Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched): everything tcr_detect_sweep refuses (ragged: tcr_detect_sweep_ragged),
+ * everything tcr_detect_redetect refuses, for every point; null points or workspace, n_points <= 0, J x N x T x num_classes >= 2^31,
+ * valid_steps together with step_offsets, and (dense) total_steps != N x steps. */
+#define TCR_GRID_TILE 256
+typedef struct tcr_detect_point {
+    int32_t average_steps, min_count, suppression_steps;
+} tcr_detect_point;
+size_t tcr_detect_grid_workspace_bytes(int64_t total_steps, int n_points);
+int tcr_detect_grid(int n_signals, int64_t steps /* dense; ignored when step_offsets != NULL */,
+                    const int64_t* step_offsets /* DEVICE [N + 1] or NULL */, int64_t total_steps, int num_classes,
+                    const float* probs, const int64_t* valid_steps /* dense only, or NULL */, int n_points,
+                    const tcr_detect_point* points /* HOST */, int n_thresholds, const float* thresholds,
+                    const int32_t* event_offsets, const int64_t* event_first, const int64_t* event_last,
+                    const int32_t* event_label, int32_t* detections, int32_t* hits,
+                    int32_t* duplicates /* [J][N][T][C] */, void* workspace, size_t ws_bytes, void* stream);
+
 /* Sample-rate conversion: a rational-ratio polyphase FIR in front of the detectors (which take float32 at the model's rate).
  * in_rate -> out_rate, g = gcd: up = L = out_rate / g, down = M = in_rate / g; taps = P per phase (even, or 1); table float32
  * [up][taps], designed on the host (tcresnet_amd.resampling.design_table: windowed sinc, fc = rolloff / max(1, M / L), Kaiser

@@ -13,6 +13,7 @@ from typing import Optional
 
 HALO = 4
 MAX_BLOCKS = 16
+GRID_TILE = 256            # == TCR_GRID_TILE: steps per tile of tcr_detect_grid's smoothing kernel
 ABI_VERSION = 3            # == TCR_ABI_VERSION of include/tcresnet_hip.h these prototypes were written against
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_HERE, "lib", "libtcresnet_hip.so")
@@ -43,6 +44,11 @@ class DSCNNCfg(C.Structure):
 
 class DetectCfg(C.Structure):
     _fields_ = [("average_steps", C.c_int32), ("min_count", C.c_int32), ("suppression_steps", C.c_int32), ("threshold", C.c_float)]
+
+
+class DetectPoint(C.Structure):
+    """tcr_detect_point: one point of tcr_detect_grid's grid."""
+    _fields_ = [("average_steps", C.c_int32), ("min_count", C.c_int32), ("suppression_steps", C.c_int32)]
 
 
 class ResampleCfg(C.Structure):
@@ -196,6 +202,11 @@ _PROTOTYPES = {
     "tcr_stream_scan_ragged_m": (C.c_int, [C.POINTER(FrontendCfg), _P, C.POINTER(ModelRef), C.c_int, _P, C.c_int, C.POINTER(DetectCfg), _P, _P,
                                            _P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
     "tcr_detect_sweep_ragged": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, C.c_int32, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "tcr_detect_redetect": (C.c_int, [C.c_int, C.c_int64, C.c_int, _P, C.POINTER(DetectCfg), _P, _P, _P, _P, _P]),
+    "tcr_detect_redetect_ragged": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, C.POINTER(DetectCfg), _P, _P, _P, _P, _P]),
+    "tcr_detect_grid_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "tcr_detect_grid": (C.c_int, [C.c_int, C.c_int64, _P, C.c_int64, C.c_int, _P, _P, C.c_int, C.POINTER(DetectPoint), C.c_int, _P, _P, _P, _P, _P,
+                                  _P, _P, _P, _P, C.c_size_t, _P]),
     "tcr_resample": (C.c_int, [C.POINTER(ResampleCfg), _P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64,
                                _P]),
     "tcr_resample_span": (C.c_int, [C.POINTER(ResampleCfg), C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -497,4 +497,5 @@ int launch_frontend_pk3_stream(int nc, const FrontendArgs& a, int n_items, hipSt
 #include "stream.hip"
 #include "scan.hip"
 #include "sweep.hip"
+#include "detect_grid.hip"
 #include "resample.hip"

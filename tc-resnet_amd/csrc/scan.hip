@@ -367,8 +367,12 @@ struct ScanDetectArgs {
 // ring is never read, and the instance has no test for it (at run time it doubled this kernel's time for tcr_scan).  RAGGED: w is
 // a packed step; i is relative to its signal's first row, so count = min(i + 1, W) never reaches the previous signal's rows.
 // CARRIED && RAGGED: the stream's own head0 and count0, the steps before the call from its ring slots.
-template <bool CARRIED, bool RAGGED = false>
-__global__ __launch_bounds__(256) void scan_smooth_kernel(const ScanDetectArgs a) {
+// The kernel's body is scan_smooth, with one more compile-time axis, OUTS: what is written.  The scans' kernels are kSmoothAll and
+// carry no test; kSmoothNoVector leaves `smoothed` out (tcr_detect_redetect with smoothed == NULL), kSmoothTopScore the candidate
+// flag as well (tcr_detect_grid's per-pair path writes top / score rows only): detect_smooth_kernel, detect_grid.hip.
+constexpr int kSmoothAll = 0, kSmoothNoVector = 1, kSmoothTopScore = 2;
+template <bool CARRIED, bool RAGGED, int OUTS>
+__device__ __forceinline__ void scan_smooth(const ScanDetectArgs& a) {
     __shared__ float s_sm[256];
     const int C = a.C, W = a.W;
     const int per = 256 / C;
@@ -405,7 +409,7 @@ __global__ __launch_bounds__(256) void scan_smooth_kernel(const ScanDetectArgs a
             ++jj;
             return x;
         });
-        a.smoothed[w * C + c] = v;
+        if constexpr (OUTS == kSmoothAll) a.smoothed[w * C + c] = v;
         s_sm[threadIdx.x] = v;
     }
     __syncthreads();
@@ -419,7 +423,12 @@ __global__ __launch_bounds__(256) void scan_smooth_kernel(const ScanDetectArgs a
     const bool warm = count >= a.min_count;
     a.top[w] = warm ? best : -1;
     a.score[w] = warm ? best_v : 0.f;
-    a.is_new[w] = warm && best_v > a.threshold ? best + 1 : 0;
+    if constexpr (OUTS != kSmoothTopScore) a.is_new[w] = warm && best_v > a.threshold ? best + 1 : 0;
+}
+
+template <bool CARRIED, bool RAGGED = false>
+__global__ __launch_bounds__(256) void scan_smooth_kernel(const ScanDetectArgs a) {
+    scan_smooth<CARRIED, RAGGED, kSmoothAll>(a);
 }
 
 // One workgroup per signal: the ring write-back, the suppression walk from the carried detector, the detector integers.  The walk goes

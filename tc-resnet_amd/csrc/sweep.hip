@@ -244,12 +244,11 @@ int sweep_launch(SweepArgs& a, hipStream_t s, const char* what) {
     return check_launch("sweep_kernel");
 }
 
-// What the two entries share: the checks in their order, the argument fill and the launch.  Dense: `steps` per signal (checked, and
-// `fired` is cleared here); ragged (step_offsets non-null where the entry requires it): the packed rows of step_offsets.
-int sweep(const char* what, bool ragged, int n_signals, int64_t steps, const int64_t* step_offsets, int num_classes, const int32_t* top,
-          const float* score, const int64_t* valid_steps, int32_t suppression_steps, int n_thresholds, const float* thresholds,
-          const int32_t* event_offsets, const int64_t* event_first, const int64_t* event_last, const int32_t* event_label,
-          int32_t* detections, int32_t* hits, int32_t* duplicates, uint8_t* fired, void* stream) {
+// The refusals of the two entries, in their order (tcr_detect_grid, detect_grid.hip, applies them to its own arguments too).
+int sweep_check(const char* what, bool ragged, int n_signals, int64_t steps, const int64_t* step_offsets, int num_classes, const int32_t* top,
+                const float* score, int32_t suppression_steps, int n_thresholds, const float* thresholds, const int32_t* event_offsets,
+                const int64_t* event_first, const int64_t* event_last, const int32_t* event_label, const int32_t* detections,
+                const int32_t* hits, const int32_t* duplicates) {
     TCR_REQUIRE((!ragged || step_offsets) && top && score && thresholds && detections, "%s: null argument", what);
     TCR_REQUIRE(n_signals > 0, "%s: the number of signals must be positive (got %d)", what, n_signals);
     TCR_REQUIRE(ragged || steps > 0, "%s: the number of steps must be positive (got %lld)", what, (long long)steps);
@@ -259,17 +258,28 @@ int sweep(const char* what, bool ragged, int n_signals, int64_t steps, const int
     TCR_REQUIRE(!event_offsets || (event_first && event_last && event_label && hits && duplicates),
                 "%s: events need event_first, event_last, event_label, hits and duplicates", what);
     const bool results_fit = (int64_t)n_signals * n_thresholds * num_classes < ((int64_t)1 << 31);
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (ragged) {
         TCR_REQUIRE(results_fit, "%s: %d signals x %d thresholds x %d classes is too large", what, n_signals, n_thresholds, num_classes);
     } else {
         TCR_REQUIRE((int64_t)n_signals * steps < ((int64_t)1 << 31) && results_fit,
                     "%s: %d signals x %lld steps x %d thresholds x %d classes is too large", what, n_signals, (long long)steps, n_thresholds,
                     num_classes);
-        if (fired && hipMemsetAsync(fired, 0, (size_t)n_thresholds * n_signals * steps, s) != hipSuccess) {
-            set_error("%s: hipMemsetAsync of fired failed", what);
-            return TCR_ERR_HIP;
-        }
+    }
+    return TCR_OK;
+}
+
+// What the two entries share: the checks, the argument fill and the launch.  Dense: `steps` per signal (checked, and `fired` is
+// cleared here); ragged (step_offsets non-null where the entry requires it): the packed rows of step_offsets.
+int sweep(const char* what, bool ragged, int n_signals, int64_t steps, const int64_t* step_offsets, int num_classes, const int32_t* top,
+          const float* score, const int64_t* valid_steps, int32_t suppression_steps, int n_thresholds, const float* thresholds,
+          const int32_t* event_offsets, const int64_t* event_first, const int64_t* event_last, const int32_t* event_label,
+          int32_t* detections, int32_t* hits, int32_t* duplicates, uint8_t* fired, void* stream) {
+    TCR_TRY(sweep_check(what, ragged, n_signals, steps, step_offsets, num_classes, top, score, suppression_steps, n_thresholds, thresholds,
+                        event_offsets, event_first, event_last, event_label, detections, hits, duplicates));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!ragged && fired && hipMemsetAsync(fired, 0, (size_t)n_thresholds * n_signals * steps, s) != hipSuccess) {
+        set_error("%s: hipMemsetAsync of fired failed", what);
+        return TCR_ERR_HIP;
     }
     SweepArgs a;
     a.top = top; a.score = score; a.valid_steps = valid_steps; a.thresholds = thresholds;

@@ -132,6 +132,72 @@ class KeywordScanner(_Detection):
         return out
 
 
+    # ---- detector tuning from one scan ---------------------------------------------------------------------------------------
+    def redetect(self, out, average_window_ms: Optional[float] = None, min_count: Optional[int] = None,
+                 detection_threshold: Optional[float] = None, suppression_ms: Optional[float] = None):
+        """The detector tail of `out` (a `ScanOutput` or `RaggedScanOutput` of this scanner's net and front-end) with other settings
+        (None: the scanner's own; ms become steps as in the constructor): the same kind of output, logits / probs `out`'s own
+        tensors, smoothed / top / score / is_new new tensors, bitwise what a scanner built with those settings returns for the same
+        audio (tcr_detect_redetect).  Neither the front-end nor the network runs."""
+        own = self.det
+        det = self._detect_cfg(0.0 if average_window_ms is None else average_window_ms, own.min_count if min_count is None else min_count,
+                               own.threshold if detection_threshold is None else detection_threshold,
+                               0.0 if suppression_ms is None else suppression_ms)
+        if average_window_ms is None:
+            det.average_steps = own.average_steps
+        if suppression_ms is None:
+            det.suppression_steps = own.suppression_steps
+        lib, ncls, dev = self.lib, self.net.num_classes, self.device
+        probs = out.probs
+        self.net._check_tensor(probs, "redetect probs")
+        stream = self.net._stream()
+        if isinstance(out, RaggedScanOutput):
+            total = int(probs.shape[0])
+            new = RaggedScanOutput(out.logits, probs, torch.empty_like(probs), torch.empty(total, dtype=torch.int32, device=dev),
+                                   torch.empty(total, dtype=torch.float32, device=dev), torch.empty(total, dtype=torch.int32, device=dev),
+                                   out.offsets)
+            off = torch.from_numpy(out.offsets).to(dev)
+            lib.check(lib.tcr_detect_redetect_ragged(len(out), off.data_ptr(), total, ncls, probs.data_ptr(), C.byref(det),
+                                                     new.smoothed.data_ptr(), new.top.data_ptr(), new.score.data_ptr(),
+                                                     new.is_new.data_ptr(), stream), "tcr_detect_redetect_ragged")
+            return new
+        if probs.dim() != 3:
+            raise TcrError(f"redetect expects probs [N, steps, classes], got shape {tuple(probs.shape)}")
+        N, steps = int(probs.shape[0]), int(probs.shape[1])
+        new = ScanOutput(out.logits, probs, torch.empty_like(probs), torch.empty((N, steps), dtype=torch.int32, device=dev),
+                         torch.empty((N, steps), dtype=torch.float32, device=dev), torch.empty((N, steps), dtype=torch.int32, device=dev))
+        lib.check(lib.tcr_detect_redetect(N, steps, ncls, probs.data_ptr(), C.byref(det), new.smoothed.data_ptr(), new.top.data_ptr(),
+                                          new.score.data_ptr(), new.is_new.data_ptr(), stream), "tcr_detect_redetect")
+        return new
+
+    def tune(self, out, thresholds, average_window_ms: Sequence[float] = (), min_count: Sequence[int] = (),
+             suppression_ms: Sequence[float] = (), events=None, lengths=None, tolerance_ms: float = 1000.0,
+             labels: Optional[Sequence[str]] = None) -> "GridResult":
+        """Every detector setting from one scan (tcr_detect_grid): the Cartesian grid average_window_ms x min_count x suppression_ms
+        (in this nesting order; an empty axis: the scanner's own setting) x thresholds over `out`'s probs.  Point j's
+        `GridResult.result(j)` equals `sweep(redetect(out, *point), thresholds, ...)`; events, lengths, tolerance_ms and labels are
+        `sweep`'s (lengths is refused for a ragged output).  Combinations with min_count above the window's steps are dropped and
+        listed in `GridResult.dropped`."""
+        own = self.det
+        ws = [(float(w), self._detect_cfg(w, 1, 0.0, 0).average_steps) for w in average_window_ms] or [(None, own.average_steps)]
+        mcs = [int(m) for m in min_count] or [own.min_count]
+        sps = [(float(x), self._detect_cfg(self.step_ms, 1, 0.0, x).suppression_steps) for x in suppression_ms] or \
+            [(None, own.suppression_steps)]
+        points, dropped = [], []
+        for w_ms, w in ws:
+            for mc in mcs:
+                for s_ms, sp in sps:
+                    (points if 1 <= mc <= w else dropped).append(GridPoint(w_ms, mc, s_ms, w, sp))
+        if not points:
+            raise TcrError(f"tune: every point of the grid has min_count above its window's steps: {[tuple(p) for p in dropped]}")
+        ragged, valid, ev_steps = self._sweep_inputs(out, events, lengths, tolerance_ms, labels)
+        self.net._check_tensor(out.probs, "tune probs")
+        step_s = self.step_samples / self.frontend.cfg.sample_rate
+        res = detection_grid(out.probs, points, thresholds, self.net.num_classes, ev_steps, out.offsets if ragged else None,
+                             None if ragged else valid, step_s, self.lib)
+        return GridResult(points, dropped, *res)
+
+
 # ---- detection sweeps ------------------------------------------------------------------------------------------------------------
 class SweepResult(NamedTuple):
     """Results of a detection sweep (tcr_detect_sweep) over N signals, T thresholds and C classes.
@@ -221,6 +287,36 @@ def _thresholds(thresholds) -> np.ndarray:
     return thr
 
 
+def _pack_events(events, N: int, ncls: int, dev):
+    """events (per signal, inclusive step ranges (first, last, label)) -> (the events per signal and label [N, ncls] int64, the four
+    CSR device pointers of the C calls (None without events), the tensors that own them)."""
+    counts = np.zeros((N, ncls), np.int64)
+    if events is None:
+        return counts, [None, None, None, None], []
+    if len(events) != N:
+        raise TcrError(f"detection sweep: events for {len(events)} signals, the scan has {N}")
+    off, rows = np.zeros(N + 1, np.int32), []
+    for n, evs in enumerate(events):
+        a = np.asarray(evs, dtype=np.int64).reshape(-1, 3)
+        a = a[np.lexsort((a[:, 1], a[:, 0]))]
+        bad = np.flatnonzero((a[:, 2] < 0) | (a[:, 2] >= ncls))
+        if bad.size:
+            raise TcrError(f"detection sweep: signal {n}: event {tuple(a[bad[0]].tolist())} has an unknown label "
+                           f"(classes 0..{ncls - 1})")
+        ov = np.flatnonzero(a[1:, 0] <= a[:-1, 1])
+        if ov.size:
+            raise TcrError(f"detection sweep: signal {n}: events {tuple(a[ov[0]].tolist())} and {tuple(a[ov[0] + 1].tolist())} overlap")
+        counts[n] = np.bincount(a[:, 2], minlength=ncls)
+        rows.append(a)
+        off[n + 1] = off[n] + len(a)
+    a = np.concatenate(rows) if rows else np.zeros((0, 3), np.int64)
+    if len(a) == 0:
+        a = np.zeros((1, 3), np.int64)              # (never read: every signal's range is empty)
+    host = [off, np.ascontiguousarray(a[:, 0]), np.ascontiguousarray(a[:, 1]), np.ascontiguousarray(a[:, 2].astype(np.int32))]
+    keep = [torch.from_numpy(x).to(dev) for x in host]
+    return counts, [t.data_ptr() for t in keep], keep
+
+
 def detection_sweep(top: torch.Tensor, score: torch.Tensor, thresholds, suppression_steps: int, num_classes: int,
                     events: Optional[Sequence[Sequence[Tuple[int, int, int]]]] = None, valid_steps=None,
                     step_seconds: Optional[float] = None, return_fired: bool = False, lib=None, step_offsets=None) -> SweepResult:
@@ -272,32 +368,7 @@ def detection_sweep(top: torch.Tensor, score: torch.Tensor, thresholds, suppress
     hits = torch.zeros((N, T, ncls), **i32)
     dups = torch.zeros((N, T, ncls), **i32)
     fired = torch.empty((T, steps) if ragged else (T, N, steps), dtype=torch.uint8, device=dev) if return_fired else None
-    counts = np.zeros((N, ncls), np.int64)
-    ev_args = [None, None, None, None]
-    keep = []
-    if events is not None:
-        if len(events) != N:
-            raise TcrError(f"detection sweep: events for {len(events)} signals, the scan has {N}")
-        off, rows = np.zeros(N + 1, np.int32), []
-        for n, evs in enumerate(events):
-            a = np.asarray(evs, dtype=np.int64).reshape(-1, 3)
-            a = a[np.lexsort((a[:, 1], a[:, 0]))]
-            bad = np.flatnonzero((a[:, 2] < 0) | (a[:, 2] >= ncls))
-            if bad.size:
-                raise TcrError(f"detection sweep: signal {n}: event {tuple(a[bad[0]].tolist())} has an unknown label "
-                               f"(classes 0..{ncls - 1})")
-            ov = np.flatnonzero(a[1:, 0] <= a[:-1, 1])
-            if ov.size:
-                raise TcrError(f"detection sweep: signal {n}: events {tuple(a[ov[0]].tolist())} and {tuple(a[ov[0] + 1].tolist())} overlap")
-            counts[n] = np.bincount(a[:, 2], minlength=ncls)
-            rows.append(a)
-            off[n + 1] = off[n] + len(a)
-        a = np.concatenate(rows) if rows else np.zeros((0, 3), np.int64)
-        if len(a) == 0:
-            a = np.zeros((1, 3), np.int64)              # (never read: every signal's range is empty)
-        host = [off, np.ascontiguousarray(a[:, 0]), np.ascontiguousarray(a[:, 1]), np.ascontiguousarray(a[:, 2].astype(np.int32))]
-        keep = [torch.from_numpy(x).to(dev) for x in host]
-        ev_args = [t.data_ptr() for t in keep]
+    counts, ev_args, keep = _pack_events(events, N, ncls, dev)
     thr_dev = torch.from_numpy(thr).to(dev)
     stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
     hours = vs * float(step_seconds) / 3600.0 if step_seconds is not None else np.full(N, np.nan)
@@ -312,3 +383,111 @@ def detection_sweep(top: torch.Tensor, score: torch.Tensor, thresholds, suppress
                                    thr_dev.data_ptr(), *ev_args, detections.data_ptr(), hits.data_ptr(), dups.data_ptr(),
                                    None if fired is None else fired.data_ptr(), stream), "tcr_detect_sweep")
     return SweepResult(detections, hits, dups, fired, thr, counts, hours)
+
+
+# ---- detector tuning -------------------------------------------------------------------------------------------------------------
+class GridPoint(NamedTuple):
+    """One point of a detector grid: the settings as given and in steps."""
+    average_window_ms: Optional[float]
+    min_count: int
+    suppression_ms: Optional[float]
+    average_steps: int
+    suppression_steps: int
+
+    @property
+    def steps(self) -> Tuple[int, int, int]:
+        """(average_steps, min_count, suppression_steps): tcr_detect_point."""
+        return self.average_steps, self.min_count, self.suppression_steps
+
+
+class GridResult:
+    """Results of a detector grid (tcr_detect_grid) over J points, N signals, T thresholds and C classes.
+
+    points: the J `GridPoint`s in grid order; dropped: the combinations left out (min_count > average_steps), as `GridPoint`s;
+    detections / hits / duplicates [J, N, T, C] int32 on the device; thresholds, events, hours: `SweepResult`'s.
+    `result(j)` is point j's `SweepResult` (views; fired is None), so `curve` and `operating_point` apply to it unchanged."""
+
+    def __init__(self, points, dropped, detections, hits, duplicates, thresholds, events, hours):
+        self.points, self.dropped = list(points), list(dropped)
+        self.detections, self.hits, self.duplicates = detections, hits, duplicates
+        self.thresholds, self.events, self.hours = thresholds, events, hours
+
+    def __len__(self) -> int:
+        return len(self.points)
+
+    def result(self, j: int) -> SweepResult:
+        if not 0 <= j < len(self):
+            raise IndexError(f"point {j} of {len(self)}")
+        return SweepResult(self.detections[j], self.hits[j], self.duplicates[j], None, self.thresholds, self.events, self.hours)
+
+    def best(self, max_fa_per_hour: float, classes: Optional[Sequence[int]] = None) -> Optional[Dict]:
+        """The point and threshold of the lowest FRR with fa_per_hour <= max_fa_per_hour (ties: fewer false accepts per hour, then
+        grid order; within a point, `SweepResult.operating_point`'s rule): {"index": j, "point": points[j], **operating point}, or
+        None when no point has a threshold in budget."""
+        best = None
+        for j in range(len(self)):
+            op = self.result(j).operating_point(max_fa_per_hour, classes)
+            if op is None:
+                continue
+            key = (0.0 if np.isnan(op["frr"]) else op["frr"], op["fa_per_hour"])
+            if best is None or key < best[0]:
+                best = (key, j, op)
+        if best is None:
+            return None
+        return {"index": best[1], "point": self.points[best[1]], **best[2]}
+
+
+def detection_grid(probs: torch.Tensor, points, thresholds, num_classes: int,
+                   events: Optional[Sequence[Sequence[Tuple[int, int, int]]]] = None, step_offsets=None, valid_steps=None,
+                   step_seconds: Optional[float] = None, lib=None, workspace_bytes: Optional[int] = None):
+    """tcr_detect_grid over a scan's probs (float32 on the device, [N, steps, C]; with step_offsets (host int64 [N + 1]) packed
+    [total_steps, C]): for every point (average_steps, min_count, suppression_steps) the counts of `detection_sweep` over the top /
+    score a scan with those settings returns.  thresholds, events (in steps), valid_steps, step_seconds: `detection_sweep`'s.
+    workspace_bytes: the bytes to run in (None: enough for every pair at once; fewer run the pairs in batches).
+    Returns (detections, hits, duplicates [J, N, T, C] int32 on the device, thresholds, events [N, C], hours [N])."""
+    if lib is None:
+        lib = _lib.get()
+    ragged = step_offsets is not None
+    ncls = int(num_classes)
+    if probs.dtype != torch.float32 or not probs.is_contiguous():
+        raise TcrError("detection grid expects contiguous float32 probs")
+    if ragged:
+        soff = np.ascontiguousarray(np.asarray(step_offsets, dtype=np.int64).reshape(-1))
+        if valid_steps is not None:
+            raise TcrError("detection grid: valid_steps with step_offsets (a ragged scan's offsets are its signals' lengths)")
+        if probs.dim() != 2 or int(probs.shape[1]) != ncls:
+            raise TcrError(f"detection grid with step_offsets expects packed probs [total_steps, {ncls}], got {tuple(probs.shape)}")
+        if soff.size < 2 or soff[0] != 0 or (np.diff(soff) < 0).any() or int(soff[-1]) != int(probs.shape[0]):
+            raise TcrError(f"detection grid: step_offsets must run from 0 to the {int(probs.shape[0])} packed steps without decreasing")
+        N, steps, total = int(soff.size) - 1, 0, int(probs.shape[0])
+        vs = np.diff(soff)
+    else:
+        if probs.dim() != 3 or int(probs.shape[2]) != ncls:
+            raise TcrError(f"detection grid expects probs [N, steps, {ncls}], got {tuple(probs.shape)}")
+        N, steps = int(probs.shape[0]), int(probs.shape[1])
+        total = N * steps
+        vs = np.full(N, steps, np.int64) if valid_steps is None else np.asarray(valid_steps, np.int64).reshape(-1)
+        if vs.shape != (N,):
+            raise TcrError(f"detection grid: {vs.size} valid_steps for {N} signals")
+        if (vs < 0).any() or (vs > steps).any():
+            raise TcrError(f"detection grid: valid_steps outside 0..{steps}: {vs.tolist()}")
+    pts = [tuple(int(v) for v in (p.steps if isinstance(p, GridPoint) else p)) for p in points]
+    J = len(pts)
+    arr = (_lib.DetectPoint * max(J, 1))(*(_lib.DetectPoint(*p) for p in pts))
+    thr = _thresholds(thresholds)
+    T = int(thr.size)
+    dev = probs.device
+    counts, ev_args, keep = _pack_events(events, N, ncls, dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    detections, hits, dups = (torch.zeros((J, N, T, ncls), **i32) for _ in range(3))
+    nws = lib.tcr_detect_grid_workspace_bytes(total, max(J, 1)) if workspace_bytes is None else int(workspace_bytes)
+    ws = torch.empty(max(nws, 4) // 4 + 1, dtype=torch.int32, device=dev)
+    thr_dev = torch.from_numpy(thr).to(dev)
+    off_dev = torch.from_numpy(soff).to(dev) if ragged else None
+    vs_dev = None if ragged else torch.from_numpy(vs).to(dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+    lib.check(lib.tcr_detect_grid(N, steps, None if off_dev is None else off_dev.data_ptr(), total, ncls, probs.data_ptr(),
+                                  None if vs_dev is None else vs_dev.data_ptr(), J, arr, T, thr_dev.data_ptr(), *ev_args,
+                                  detections.data_ptr(), hits.data_ptr(), dups.data_ptr(), ws.data_ptr(), nws, stream), "tcr_detect_grid")
+    hours = vs * float(step_seconds) / 3600.0 if step_seconds is not None else np.full(N, np.nan)
+    return detections, hits, dups, thr, counts, hours

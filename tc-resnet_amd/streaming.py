@@ -111,9 +111,13 @@ class _Detection:
             raise TcrError(f"{what}: frames per step k = {self.k} outside 1..T = {cfg.n_frames}")
         self.step_samples = self.k * cfg.hop
         self.step_ms = 1000.0 * self.step_samples / cfg.sample_rate
-        self.det = DetectCfg(max(1, ms_to_steps(average_window_ms, self.step_ms)), int(min_count),
-                             max(0, ms_to_steps(suppression_ms, self.step_ms)), float(detection_threshold))
+        self.det = self._detect_cfg(average_window_ms, min_count, detection_threshold, suppression_ms)
         self._what, self._noun = what, noun
+
+    def _detect_cfg(self, average_window_ms: float, min_count: int, detection_threshold: float, suppression_ms: float) -> DetectCfg:
+        """The detector settings in steps (the nearest whole number; the averaging ring holds at least one vector)."""
+        return DetectCfg(max(1, ms_to_steps(average_window_ms, self.step_ms)), int(min_count),
+                         max(0, ms_to_steps(suppression_ms, self.step_ms)), float(detection_threshold))
 
     def _bind_frozen(self, frozen_ss: Optional[torch.Tensor]) -> None:
         net = self.net
@@ -194,8 +198,21 @@ class _Detection:
         `out` may be a scanning.RaggedScanOutput (`KeywordScanner.scan_ragged`): every signal is walked over its own rows, its events
         are relative to its own start, `fired` is [T, total_steps] and `hours` come from each signal's steps; `lengths` is refused,
         because the scan's lengths are the lengths."""
-        from .scanning import RaggedScanOutput, _first_steps, _last_steps, detection_sweep
+        from .scanning import detection_sweep
+        ragged, valid, ev_steps = self._sweep_inputs(out, events, lengths, tolerance_ms, labels)
         step, sr = self.step_samples, self.frontend.cfg.sample_rate
+        if ragged:
+            return detection_sweep(out.top, out.score, thresholds, self.suppression_steps, self.net.num_classes, ev_steps, None,
+                                   step / sr, return_fired, self.lib, step_offsets=out.offsets)
+        return detection_sweep(out.top, out.score, thresholds, self.suppression_steps, self.net.num_classes, ev_steps, valid,
+                               step / sr, return_fired, self.lib)
+
+    def _sweep_inputs(self, out, events, lengths, tolerance_ms: float, labels: Optional[Sequence[str]]):
+        """`sweep`'s (and `KeywordScanner.tune`'s) arguments in steps: (out is ragged, every signal's valid steps, the events as
+        inclusive step ranges per signal or None); the shapes come from out.probs where out.top is None."""
+        from .scanning import RaggedScanOutput, _first_steps, _last_steps
+        step, sr = self.step_samples, self.frontend.cfg.sample_rate
+        shape = out.top.shape if out.top is not None else out.probs.shape
         ragged = isinstance(out, RaggedScanOutput)
         if ragged:
             if lengths is not None:
@@ -203,10 +220,10 @@ class _Detection:
             N, steps, valid = len(out), 0, out.steps
             lengths = (valid * step).tolist()           # (the events below are checked against each signal's own end)
         elif lengths is None:
-            N, steps = int(out.top.shape[0]), int(out.top.shape[1])
+            N, steps = int(shape[0]), int(shape[1])
             valid = np.full(N, steps, np.int64)
         else:
-            N, steps = int(out.top.shape[0]), int(out.top.shape[1])
+            N, steps = int(shape[0]), int(shape[1])
             lens = np.asarray(lengths, np.int64).reshape(-1)
             if lens.shape != (N,):
                 raise TcrError(f"sweep: {lens.size} lengths for {N} signals")
@@ -240,11 +257,7 @@ class _Detection:
                     a, b = evs[order[ov[0]]], evs[order[ov[0] + 1]]
                     raise TcrError(f"sweep: signal {n}: events {tuple(a)} and {tuple(b)} overlap with tolerance_ms = {tol:g}")
                 ev_steps.append(np.stack([_first_steps(se[:, 0], step, sr), _last_steps(se[:, 1] + tol, step, sr), cls], axis=1))
-        if ragged:
-            return detection_sweep(out.top, out.score, thresholds, self.suppression_steps, self.net.num_classes, ev_steps, None,
-                                   step / sr, return_fired, self.lib, step_offsets=out.offsets)
-        return detection_sweep(out.top, out.score, thresholds, self.suppression_steps, self.net.num_classes, ev_steps, valid,
-                               step / sr, return_fired, self.lib)
+        return ragged, valid, ev_steps
 
 
 class StreamingDetector(_Detection):

@@ -69,6 +69,11 @@ def parse_arguments(arguments: Optional[List[str]] = None):
     return p.parse_args(arguments)
 
 
+def format_row(cv, t: int) -> list:
+    """Row t of a `SweepResult.curve` as the CSV's fields (COLUMNS)."""
+    return [f"{cv['threshold'][t]:.6g}", *(int(cv[k][t]) for k in COLUMNS[1:5]), f"{cv['frr'][t]:.6g}", f"{cv['fa_per_hour'][t]:.9g}"]
+
+
 def read_events(path: str, wavs: List[str]):
     out = [[] for _ in wavs]
     index = {w: n for n, w in enumerate(wavs)}
@@ -120,8 +125,7 @@ def main(args) -> int:
         out = ScanOutput(None, None, None, torch.cat(tops, dim=1), torch.cat(scores, dim=1), None)
         res = scanner.sweep(out, thresholds, events=events, lengths=rec.lengths, tolerance_ms=args.tolerance_ms, labels=names)
     w = csv.writer(sys.stdout, lineterminator="\n")
-    fmt = lambda cv, t: [f"{cv['threshold'][t]:.6g}", *(int(cv[k][t]) for k in COLUMNS[1:5]), f"{cv['frr'][t]:.6g}",
-                         f"{cv['fa_per_hour'][t]:.9g}"]
+    fmt = format_row
     if args.per_label:
         w.writerow(("label",) + COLUMNS)
         for k, c in zip(keywords, classes):
