@@ -226,15 +226,23 @@ int tcr_net_backward_level(const tcr_net* net, const float* params, const float*
 /* ------------------------------------------------------------------------------------------ */
 /* Network: DS-CNN S / M / L (audio_nets/ds_cnn.py:19-118), the depthwise-separable baseline     */
 /* ------------------------------------------------------------------------------------------ */
+/* Limits.  tcr_dscnn_create refuses (TCR_ERR_ARG, tcr_last_error names the limit): h_in, w_in < 1; num_classes outside 1 .. 46
+ * (the head's num_classes + 2 <= 48); depth not a positive multiple of 4; n_separable outside 1 .. 8; conv1_kh outside 1 .. 16;
+ * conv1_kw != 4; a stride outside {1, 2}.  Everything create accepts runs eval (tcr_dscnn_forward_infer) at any batch.
+ * TRAINING has two further limits, both of conv_1's filter gradient: conv1_kh <= 12 (kh x 4 taps in a 48-tap tile) and
+ * w_in * (h_in + 8) <= 3072 floats (four copies of an utterance's padded feature map in 48 KB of LDS: 98 frames x 40 coefficients
+ * do not train, 98 x 28 and 49 x 40 do).  A net beyond them is refused by the first training call -- tcr_dscnn_train_workspace_bytes
+ * returns 0, tcr_dscnn_forward_train[_stage] returns TCR_ERR_ARG -- with the limit in tcr_last_error and nothing launched or
+ * written; tcr_dscnn_backward is never the first to object. */
 typedef struct tcr_dscnn_cfg {
     int32_t h_in;                   /* frames (49 for 40/20 ms) */
     int32_t w_in;                   /* MFCC coefficients (--num_mfccs 10) */
-    int32_t num_classes;
-    int32_t depth;                  /* 64 / 172 / 276 (ds_cnn.py:20,29,37) */
-    int32_t n_separable;            /* 4 / 4 / 5 separable blocks */
-    int32_t conv1_kh, conv1_kw;     /* 10 x 4 */
-    int32_t conv1_sh, conv1_sw;     /* (2,2) S; (2,1) M, L */
-    int32_t ds1_sh, ds1_sw;         /* stride of conv_ds_1: (1,1) S; (2,2) M, L */
+    int32_t num_classes;            /* 1 .. 46 */
+    int32_t depth;                  /* 64 / 172 / 276 (ds_cnn.py:20,29,37); any positive multiple of 4 */
+    int32_t n_separable;            /* 4 / 4 / 5 separable blocks; 1 .. 8 */
+    int32_t conv1_kh, conv1_kw;     /* 10 x 4; kh 1 .. 16 (training: <= 12), kw 4 */
+    int32_t conv1_sh, conv1_sw;     /* (2,2) S; (2,1) M, L; each 1 or 2 */
+    int32_t ds1_sh, ds1_sw;         /* stride of conv_ds_1: (1,1) S; (2,2) M, L; each 1 or 2 */
     float bn_decay;                 /* 0.96 (ds_cnn.py:107) */
     float bn_eps;                   /* 0.001 */
 } tcr_dscnn_cfg;
@@ -256,7 +264,7 @@ int tcr_dscnn_forward_infer(const tcr_dscnn* net, const float* params, const flo
 /* Train-mode forward of DSCNN() (is_training=True: batch statistics, moving averages updated with decay 0.96 --
  * DSCNN_arg_scope, ds_cnn.py:104-118) + softmax cross-entropy (factory/audio_nets.py:161-173); no dropout is applied
  * in the graph (ds_cnn.py:89-101).  Arguments as tcr_net_forward_train; the workspace keeps what backward needs. */
-size_t tcr_dscnn_train_workspace_bytes(const tcr_dscnn* net, int batch);
+size_t tcr_dscnn_train_workspace_bytes(const tcr_dscnn* net, int batch);      /* 0: bad argument, or a net past the training limits above */
 int tcr_dscnn_forward_train(const tcr_dscnn* net, const float* params, float* stats, const float* feat, const float* labels,
                             int batch, int global_batch, float label_smoothing, void* workspace, size_t workspace_bytes,
                             float* logits, float* probs, float* loss_out, void* stream);
@@ -278,6 +286,9 @@ int tcr_dscnn_unit_output(const tcr_dscnn* net, int unit, int batch, int64_t* of
  * TCR_TUNE_DS_TRAIN): this call computes it from the raw output and the batch statistics the last training forward left in the workspace,
  * into the slot tcr_dscnn_unit_output() names.  Replaces nothing in the reference (test / inspection hook for `endpoints`). */
 int tcr_dscnn_materialize_unit(const tcr_dscnn* net, int unit, int batch, void* workspace, size_t workspace_bytes, void* stream);
+/* Test hook, host arithmetic only: how the depthwise filter gradient splits `batch` utterances of `positions` output positions into
+ * chunks, and whether its plain kernel may split a chunk's flattened index with the float reciprocal (exact below 2^22) or divides. */
+int tcr_dscnn_dw_wgrad_plan(int batch, int positions, int* chunks, int* utt_per_block, int* fast_divide);
 int tcr_dscnn_num_stages(const tcr_dscnn* net);
 int tcr_dscnn_stage_sums(const tcr_dscnn* net, int backward, int stage, void* workspace, int batch, double** sums_dev, int64_t* n_doubles);
 int tcr_dscnn_forward_train_stage(const tcr_dscnn* net, const float* params, float* stats, const float* feat, const float* labels,

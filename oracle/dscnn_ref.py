@@ -29,16 +29,21 @@ class DsBlock:
     scope: str
 
 
+def blocks_from_def(depth: int, n_separable: int, conv1_stride=(2, 2), ds1_stride=(1, 1), conv1_kh: int = 10) -> List[DsBlock]:
+    """The block list of a DS-CNN-shaped net: conv_1 (conv1_kh x 4) and n_separable 3 x 3 separable blocks of one depth, the first of
+    them strided (the definition tcr_dscnn_cfg / engine.DSCNN(net_def=) take)."""
+    out = [DsBlock("conv", depth, (conv1_kh, 4), tuple(conv1_stride), "conv_1")]
+    for i in range(1, n_separable + 1):
+        out.append(DsBlock("separable", depth, (3, 3), tuple(ds1_stride) if i == 1 else (1, 1), f"conv_ds_{i}"))
+    return out
+
+
+SIZE_DEFS = {"S": (64, 4, (2, 2), (1, 1)), "M": (172, 4, (2, 1), (2, 2)), "L": (276, 5, (2, 1), (2, 2))}
+
+
 def net_def(size: str) -> List[DsBlock]:
     """S_NET_DEF / M_NET_DEF / L_NET_DEF (audio_nets/ds_cnn.py:19-43)."""
-    depth = {"S": 64, "M": 172, "L": 276}[size]
-    first = (2, 2) if size == "S" else (2, 1)
-    ds1 = (1, 1) if size == "S" else (2, 2)
-    n_ds = 4 if size in ("S", "M") else 5
-    out = [DsBlock("conv", depth, (10, 4), first, "conv_1")]
-    for i in range(1, n_ds + 1):
-        out.append(DsBlock("separable", depth, (3, 3), ds1 if i == 1 else (1, 1), f"conv_ds_{i}"))
-    return out
+    return blocks_from_def(*SIZE_DEFS[size])
 
 
 def init_params(blocks: List[DsBlock], num_classes: int = 12, in_channels: int = 1, seed: int = 0, dtype=np.float64,

@@ -1136,8 +1136,12 @@ extern "C" int tcr_dscnn_create(const tcr_dscnn_cfg* cfg, tcr_dscnn** out) {
     TCR_REQUIRE(cfg && out, "tcr_dscnn_create: null argument");
     TCR_REQUIRE(cfg->depth > 0 && cfg->depth % 4 == 0, "tcr_dscnn_create: depth %d must be a positive multiple of 4", cfg->depth);
     TCR_REQUIRE(cfg->n_separable >= 1 && cfg->n_separable <= 8, "tcr_dscnn_create: n_separable %d out of range", cfg->n_separable);
-    TCR_REQUIRE(cfg->h_in > 0 && cfg->w_in > 0 && cfg->num_classes > 0 && cfg->num_classes + 2 <= 48, "tcr_dscnn_create: bad shape");
+    TCR_REQUIRE(cfg->h_in > 0 && cfg->w_in > 0, "tcr_dscnn_create: h_in %d / w_in %d must be positive", cfg->h_in, cfg->w_in);
+    TCR_REQUIRE(cfg->num_classes > 0 && cfg->num_classes + 2 <= 48, "tcr_dscnn_create: num_classes %d outside 1 .. 46 (the head holds num_classes + 2 <= 48 rows)", cfg->num_classes);
     TCR_REQUIRE(cfg->conv1_kh >= 1 && cfg->conv1_kh <= 16 && cfg->conv1_kw == 4, "tcr_dscnn_create: conv_1 kernel must be kh x 4 (got %d x %d)", cfg->conv1_kh, cfg->conv1_kw);
+    TCR_REQUIRE(cfg->conv1_sh >= 1 && cfg->conv1_sh <= 2 && cfg->conv1_sw >= 1 && cfg->conv1_sw <= 2 && cfg->ds1_sh >= 1 && cfg->ds1_sh <= 2 &&
+                cfg->ds1_sw >= 1 && cfg->ds1_sw <= 2, "tcr_dscnn_create: strides must be 1 or 2 (conv_1 %d x %d, conv_ds_1 %d x %d)",
+                cfg->conv1_sh, cfg->conv1_sw, cfg->ds1_sh, cfg->ds1_sw);
     tcr_dscnn* net = new tcr_dscnn();
     net->cfg = *cfg;
     net->c_pad = (int)ds_align(cfg->depth);
@@ -1413,8 +1417,23 @@ static DsTrainWs ds_carve(const tcr_dscnn& net, int batch) {
 
 }  // namespace tcr
 
+// What the training kernels cannot run (eval of the same net can): conv_1's filter gradient holds the kh x 4 taps in three 16-tap tiles
+// and four wave-private LDS copies of an utterance's feature map in 48 KB (dscnn_bwd.hip, launch_dscnn_conv1_wgrad).  Known from the
+// configuration alone, so the first training call refuses -- not the backward, after other kernels have written gradients.
+static int ds_train_limits(const tcr_dscnn& net) {
+    const tcr_dscnn_cfg& c = net.cfg;
+    if (c.conv1_kh > 12) { set_error("tcr_dscnn training: conv1_kh %d > 12 (the conv_1 filter gradient's 48-tap tile); eval only", c.conv1_kh); return TCR_ERR_ARG; }
+    if ((int64_t)c.w_in * tcr_padded_len(c.h_in) > 3072) {
+        set_error("tcr_dscnn training: w_in * (h_in + 8) = %d x %d > 3072 floats (the conv_1 filter gradient's LDS copies of a feature map); eval only",
+                  c.w_in, tcr_padded_len(c.h_in));
+        return TCR_ERR_ARG;
+    }
+    return TCR_OK;
+}
+
 extern "C" size_t tcr_dscnn_train_workspace_bytes(const tcr_dscnn* net, int batch) {
     if (!net || batch <= 0) return 0;
+    if (ds_train_limits(*net) != TCR_OK) return 0;
     return (size_t)ds_carve(*net, batch).total * sizeof(float);
 }
 
@@ -1426,6 +1445,7 @@ static int ds_forward_train_stages(const tcr_dscnn* net, const float* params, fl
                                    float* logits, float* probs, float* loss_out, int stage_begin, int stage_end, void* stream) {
     TCR_REQUIRE(net && params && stats && feat && labels && workspace && logits && probs && loss_out, "tcr_dscnn_forward_train: null argument");
     TCR_REQUIRE(batch > 0 && global_batch >= batch, "tcr_dscnn_forward_train: batch %d / global_batch %d", batch, global_batch);
+    TCR_TRY(ds_train_limits(*net));
     const DsTrainWs w = ds_carve(*net, batch);
     if ((size_t)w.total * sizeof(float) > workspace_bytes) {
         set_error("tcr_dscnn_forward_train: workspace %zu bytes < required %zu", workspace_bytes, (size_t)w.total * sizeof(float));

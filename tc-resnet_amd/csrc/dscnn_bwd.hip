@@ -387,6 +387,9 @@ int launch_dscnn_dw_dgrad(const DsDwBwdArgs& a, hipStream_t s) {
     return check_launch("dscnn_dw_dgrad_kernel");
 }
 
+// The flattened (utterance, position) index of a chunk stays inside fast_div's exact range (tcr_common.h); beyond it the kernel divides.
+__host__ __device__ inline bool dw_wgrad_fast_div_ok(int utterances, int positions) { return (int64_t)utterances * positions < (1 << 22); }
+
 // partial[chunk][tap][c] = sum_{n in chunk, oh, ow} x[n][c][oh*sh + di - pad_t][ow*sw + dj - pad_l] * dz[n][c][oh][ow]
 // One wavefront per (chunk of utterances, channel); lanes walk the flattened (utterance, position) index.
 __global__ __launch_bounds__(256) void dscnn_dw_wgrad_kernel(const DsDwWgradArgs a) {
@@ -406,8 +409,9 @@ __global__ __launch_bounds__(256) void dscnn_dw_wgrad_kernel(const DsDwWgradArgs
     const float* gsrc = fly ? a.fly.da : a.dz;
     const float f_k1 = fly ? a.fly.k1[c] : 0.f, f_k2 = fly ? a.fly.k2[c] : 0.f, f_k3 = fly ? a.fly.k3[c] : 0.f, f_mu = fly ? a.fly.mean[c] : 0.f;
     const float f_sc = fly ? a.fly.self_scale[c] : 0.f, f_sh = fly ? a.fly.self_shift[c] : 0.f;
+    const bool small = dw_wgrad_fast_div_ok(cnt, P);   // (cnt grows with batch / 128, dw_wgrad_chunks: a chunk can pass fast_div's range)
     for (int idx = lane; idx < cnt * P; idx += 64) {
-        const int dn = fast_div(idx, P, inv_p), pos = idx - dn * P;
+        const int dn = small ? fast_div(idx, P, inv_p) : idx / P, pos = idx - dn * P;
         const int oh = fast_div(pos, a.ow, inv_ow), ow = pos - oh * a.ow;
         const size_t plane = (size_t)(n0 + dn) * a.c + c;
         float g = gsrc[plane * a.ppo + kHalo + pos];
@@ -628,8 +632,10 @@ static int dw_wgrad_chunks(int batch) {
 
 size_t dscnn_dw_wgrad_partial_floats(int batch, int c) { return (size_t)dw_wgrad_chunks(batch) * 9 * c; }
 
+static int dw_wgrad_utt_per_block(int batch) { return ceil_div(batch, dw_wgrad_chunks(batch)); }
+
 int launch_dscnn_dw_wgrad(DsDwWgradArgs a, float* dw, hipStream_t s) {
-    a.utt_per_block = ceil_div(a.batch, dw_wgrad_chunks(a.batch));
+    a.utt_per_block = dw_wgrad_utt_per_block(a.batch);
     dim3 grid(ceil_div(a.batch, a.utt_per_block), ceil_div(a.c, 4));
     if (dscnn_dw_wgrad_rows_covers(a)) {
         grid.y = ceil_div(a.c, 16);
@@ -804,3 +810,13 @@ int launch_dscnn_conv1_wgrad(DsConv1WgradArgs a, float* dw, hipStream_t s) {
 }
 
 }  // namespace tcr
+
+// Test hook (host arithmetic only, nothing is launched): how launch_dscnn_dw_wgrad splits `batch` utterances of `positions` output
+// positions into chunks, and whether dscnn_dw_wgrad_kernel's index split of one chunk may use the float reciprocal.
+extern "C" int tcr_dscnn_dw_wgrad_plan(int batch, int positions, int* chunks, int* utt_per_block, int* fast_divide) {
+    TCR_REQUIRE(batch > 0 && positions > 0 && chunks && utt_per_block && fast_divide, "tcr_dscnn_dw_wgrad_plan: bad argument");
+    *utt_per_block = tcr::dw_wgrad_utt_per_block(batch);
+    *chunks = tcr::ceil_div(batch, *utt_per_block);
+    *fast_divide = tcr::dw_wgrad_fast_div_ok(*utt_per_block, positions) ? 1 : 0;
+    return TCR_OK;
+}

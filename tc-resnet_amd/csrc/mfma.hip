@@ -15,6 +15,7 @@
 namespace tcr {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef f32x4 f32x4_a4 __attribute__((aligned(4)));          // the same four floats at any float address
 
 // D[row = co][col = position] = sum_ci W[ci][co] * x[b][ci][t * stride]
 template <int MT, int EPI>
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(128 * NWN, MINW) void conv1x1_lds_kernel(const Conv
 #pragma unroll
         for (int j = 0; j < WPT; ++j) {
             const float* src = a.w + (size_t)min(c0 + wrow[j], a.cin - 1) * a.cout + min(wcol[j], a.cout - 4);
-            const f32x4 v = *reinterpret_cast<const f32x4*>(src);
+            const f32x4 v = *reinterpret_cast<const f32x4_a4*>(src);       // (a C-ABI caller's parameters are 4-byte aligned: one 16-byte load all the same)
             wr[j] = wval[j] ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
         }
     };
@@ -1698,22 +1699,22 @@ __global__ __launch_bounds__(256) void pw_wgrad_lds_kernel(const PwWgradArgs a) 
     // The next utterance's rows travel global -> registers while the current one is multiplied out of LDS.
     // (Every lane always loads from a valid address -- clamped past the end; 14 named registers rather than an array,
     // which the compiler kept in scratch memory.)
-    float4 p0, p1, p2, p3, p4, p5, p6, p7, p8, p9, p10, p11, p12, p13;
-    const float4 *xg4, *dg4;
+    f32x4 p0, p1, p2, p3, p4, p5, p6, p7, p8, p9, p10, p11, p12, p13;
+    const f32x4_a4 *xg4, *dg4;                                  // (a workspace 4-byte aligned: C-ABI callers)
 #define TCR_PW_LD(I_, P_) { const int v = tid + (I_) * 256; P_ = *(v < xv ? xg4 + v : dg4 + min(v - xv, dv - 1)); }
 #define TCR_PW_ST(I_, P_) { const int v = tid + (I_) * 256; if (v < xv) xs4[v] = P_; else if (v - xv < dv) ds4[v - xv] = P_; }
 #define TCR_PW_ALL(OP_) OP_(0, p0) OP_(1, p1) OP_(2, p2) OP_(3, p3) OP_(4, p4) OP_(5, p5) OP_(6, p6) OP_(7, p7) OP_(8, p8) OP_(9, p9) \
                         OP_(10, p10) OP_(11, p11) OP_(12, p12) OP_(13, p13)
 #define TCR_PW_PREFETCH(N_)                                                                         \
     {                                                                                               \
-        xg4 = reinterpret_cast<const float4*>(a.x + ((size_t)(N_) * a.cin + ci0) * a.pp);           \
-        dg4 = reinterpret_cast<const float4*>(a.dz + ((size_t)(N_) * a.cout + co0) * a.pp);         \
+        xg4 = reinterpret_cast<const f32x4_a4*>(a.x + ((size_t)(N_) * a.cin + ci0) * a.pp);         \
+        dg4 = reinterpret_cast<const f32x4_a4*>(a.dz + ((size_t)(N_) * a.cout + co0) * a.pp);       \
         TCR_PW_ALL(TCR_PW_LD)                                                                       \
     }
     static_assert(NV == 14, "TCR_PW_ALL lists 14 registers");
     if (n_begin < n_end) TCR_PW_PREFETCH(n_begin)
-    float4* xs4 = reinterpret_cast<float4*>(xs);
-    float4* ds4 = reinterpret_cast<float4*>(ds);
+    f32x4* xs4 = reinterpret_cast<f32x4*>(xs);
+    f32x4* ds4 = reinterpret_cast<f32x4*>(ds);
     for (int n = n_begin; n < n_end; ++n) {
         __syncthreads();
         TCR_PW_ALL(TCR_PW_ST)
@@ -1808,8 +1809,8 @@ __global__ __launch_bounds__(256) void pw_wgrad_lds_p_kernel(const PwWgradArgs a
     const int n_end = min(n_begin + a.utt_per_block, a.batch);
     f4 px[NI], pd[NI];
     auto prefetch = [&](int n) {
-        const f4* xg4 = reinterpret_cast<const f4*>(a.x + ((size_t)n * a.cin + ci0) * PP);
-        const f4* dg4 = reinterpret_cast<const f4*>(a.dz + ((size_t)n * a.cout + co0) * PP);
+        const f32x4_a4* xg4 = reinterpret_cast<const f32x4_a4*>(a.x + ((size_t)n * a.cin + ci0) * PP);      // (a workspace 4-byte aligned: C-ABI callers)
+        const f32x4_a4* dg4 = reinterpret_cast<const f32x4_a4*>(a.dz + ((size_t)n * a.cout + co0) * PP);
 #pragma unroll
         for (int i = 0; i < NI; ++i) { px[i] = xg4[xo[i]]; pd[i] = dg4[dof[i]]; }
     };

@@ -574,11 +574,16 @@ class DSCNN(_Base):
         "L": (276, 5, (2, 1), (2, 2)),
     }
 
-    def __init__(self, size: str, h_in: int, w_in: int, num_classes: int, bn_decay: float = 0.96, bn_eps: float = 0.001,
-                 lib: Optional[_lib.Library] = None, device=None):
+    def __init__(self, size: Optional[str], h_in: int, w_in: int, num_classes: int, bn_decay: float = 0.96, bn_eps: float = 0.001,
+                 lib: Optional[_lib.Library] = None, device=None, net_def=None):
+        """`size` "S" / "M" / "L", or `net_def` = (depth, separable blocks, conv_1 stride, conv_ds_1 stride[, conv_1 kernel height = 10]):
+        any net tcr_dscnn_cfg describes (the three sizes are NET_DEFS' entries)."""
         self.lib, self.device = _resolve(lib, device)
-        depth, nsep, s1, sds = self.NET_DEFS[size]
-        cfg = DSCNNCfg(int(h_in), int(w_in), int(num_classes), depth, nsep, 10, 4, s1[0], s1[1], sds[0], sds[1],
+        if net_def is None:
+            net_def = self.NET_DEFS[size]
+        depth, nsep, s1, sds = net_def[:4]
+        kh = int(net_def[4]) if len(net_def) > 4 else 10
+        cfg = DSCNNCfg(int(h_in), int(w_in), int(num_classes), int(depth), int(nsep), kh, 4, int(s1[0]), int(s1[1]), int(sds[0]), int(sds[1]),
                        float(bn_decay), float(bn_eps))
         handle = C.c_void_p()
         self.lib.check(self.lib.tcr_dscnn_create(C.byref(cfg), C.byref(handle)), "tcr_dscnn_create")
@@ -602,6 +607,11 @@ class DSCNN(_Base):
         for n, ti in self.tensors.items():
             if ti.kind == 4:
                 self._view(n).fill_(1.0)
+
+    @classmethod
+    def from_def(cls, depth: int, n_separable: int, conv1_stride, ds1_stride, h_in: int, w_in: int, num_classes: int, conv1_kh: int = 10, **kw):
+        """A DS-CNN given by its definition instead of a size name."""
+        return cls(None, h_in, w_in, num_classes, net_def=(depth, n_separable, tuple(conv1_stride), tuple(ds1_stride), conv1_kh), **kw)
 
     def __del__(self):
         try:
@@ -651,6 +661,9 @@ class DSCNN(_Base):
         ws = self._train_ws.get(batch)
         if ws is None:
             nbytes = self.lib.tcr_dscnn_train_workspace_bytes(self._h, batch)
+            if nbytes == 0:         # a configuration the training kernels cannot run (tcr_dscnn_cfg's limits): eval only
+                msg = self.lib.tcr_last_error()
+                raise TcrError(f"tcr_dscnn_train_workspace_bytes: {msg.decode() if msg else 'bad argument'}")
             ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
             self._train_ws[batch] = ws
         return ws
