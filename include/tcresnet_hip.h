@@ -659,6 +659,59 @@ int tcr_detect_grid(int n_signals, int64_t steps /* dense; ignored when step_off
                     const int32_t* event_label, int32_t* detections, int32_t* hits,
                     int32_t* duplicates /* [J][N][T][C] */, void* workspace, size_t ws_bytes, void* stream);
 
+/* Sparse scans: tcr_scan_ragged's logits / probs for a chosen subset of its packed steps, at the cost of that subset -- the second
+ * stage of a cascade, or a new checkpoint rescored only around labelled events.  cfg, plan_dev, model, n_signals, sample_offsets (HOST
+ * [N + 1]), k and samples are tcr_scan_ragged's; selected is a HOST array of n_selected packed step indices (row numbers of
+ * tcr_scan_ragged's outputs), strictly increasing.  Contract: row b of logits / probs [n_selected][num_classes] (compact, in
+ * `selected`'s order) is bitwise row selected[b] of tcr_scan_ragged's logits / probs for the same arguments -- a fresh signal with one
+ * clip of silence in front, for every model family, whatever max_windows, the group size the call picks and the other selected
+ * steps.  No detector runs: there is no det and no smoothed / top / score / is_new (merge the rows into a full scan's probs and run
+ * tcr_detect_redetect_ragged).
+ * Cost: the steps are cut into groups of G steps exactly as tcr_scan_ragged cuts them, but only the groups that hold a selected step
+ * are staged and run through the front-end (a group is one row of G k + T - k frames; G: the fewest frames summed over those groups),
+ * and the network runs at the batch of the selected steps only and writes the caller's rows itself.
+ * Workspace: tcr_scan_steps_workspace_bytes = the tables of max_signals signals and max_selected steps ((max_signals + 1 + 3
+ * max_selected) int64, rounded up to 256 bytes: the step offsets, selected, every selected step's front-end row and every row's
+ * first step) + tcr_scan_workspace_bytes_m(cfg, model, k, max_windows); it does not depend on the signals' length.  The host builds
+ * the tables, copies them on `stream` and waits for that copy before it launches, as tcr_scan_ragged does: sample_offsets and selected
+ * may be freed when the call returns, and the call cannot be captured into a graph.  Everything else is enqueued on `stream`.
+ * n_selected == 0 returns TCR_OK and launches nothing (samples / logits / probs may then be NULL).
+ * Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched): everything tcr_scan_ragged refuses (except what concerns det and its
+ * four detector outputs), n_selected < 0, more signals and selected steps than the workspace's tables hold, null selected with
+ * n_selected > 0, a selected step outside 0 .. total_steps - 1 or not above the one before it.  TCR_ERR_WORKSPACE when the bytes behind
+ * the tables are below one window.
+ * tcr_scan_steps_plan: what a call with these arguments and ws_bytes would run, from the host alone (the same refusals; nothing is
+ * launched): plan[0] = G, plan[1] = the front-end rows staged, plan[2] = the frames of a row, plan[3] = the rows of a chunk (all 0
+ * when n_selected == 0). */
+size_t tcr_scan_steps_workspace_bytes(const tcr_frontend_cfg* cfg, const tcr_model_ref* model, int k, int max_windows,
+                                      int max_signals, int64_t max_selected);
+int tcr_scan_steps(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_signals,
+                   const int64_t* sample_offsets /* HOST [N + 1] */, int k, const int64_t* selected /* HOST [n_selected] */,
+                   int64_t n_selected, const float* samples /* device, packed */, void* workspace, size_t ws_bytes,
+                   float* logits, float* probs /* [n_selected][C] */, void* stream);
+int tcr_scan_steps_plan(const tcr_frontend_cfg* cfg, const tcr_model_ref* model, int n_signals,
+                        const int64_t* sample_offsets /* HOST [N + 1] */, int k, const int64_t* selected /* HOST */,
+                        int64_t n_selected, size_t ws_bytes, int64_t* plan /* HOST [4] */);
+
+/* Step selection: which steps of a scan a second stage should look at.  values [total_steps][num_classes] are a ragged scan's probs
+ * or smoothed (a dense scan's with step_offsets[n] = n x steps), step_offsets a DEVICE table as tcr_detect_redetect_ragged takes it
+ * (from 0, non-decreasing, step_offsets[N] == total_steps: preconditions).  Step p is FLAGGED when some class c with class_mask[c] !=
+ * 0 has values[p][c] >= enter (a float32 compare: a NaN value never flags), and SELECTED when a flagged step p' of the same signal
+ * has  p - pad_after <= p' <= p + pad_before  -- pad_before steps in front of every flag and pad_after behind it, never across a
+ * signal's ends.  selected (DEVICE int64, room for total_steps) receives the selected packed steps in increasing order, n_selected
+ * (DEVICE [1]) their number, mask (DEVICE [total_steps] or NULL) 1 at the selected steps and 0 elsewhere.  enter = -inf selects every
+ * step (whose masked values are not all NaN), +inf none: n_selected = 0 is a valid result.  No floating-point arithmetic: the output
+ * is exact.  Prefix sums over the packed steps in kernels of their own (no workgroup waits for another); the cost is linear in
+ * total_steps and independent of the pads.  Everything is enqueued on `stream` -- no copy, no wait.
+ * Workspace: tcr_scan_select_workspace_bytes(total_steps) (0: total_steps outside 1 .. 2^31 - 1); TCR_ERR_WORKSPACE below it.
+ * Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched): null step_offsets / values / class_mask / workspace / selected /
+ * n_selected, N or total_steps <= 0, num_classes outside 1 .. 256, total_steps x num_classes >= 2^31, NaN enter, a negative pad. */
+size_t tcr_scan_select_workspace_bytes(int64_t total_steps);
+int tcr_scan_select(int n_signals, const int64_t* step_offsets /* DEVICE [N + 1] */, int64_t total_steps, int num_classes,
+                    const float* values /* [total_steps][C] */, const uint8_t* class_mask /* DEVICE [C] */, float enter,
+                    int pad_before, int pad_after, void* workspace, size_t ws_bytes, int64_t* selected /* DEVICE */,
+                    int64_t* n_selected /* DEVICE [1] */, uint8_t* mask /* [total_steps] or NULL */, void* stream);
+
 /* Sample-rate conversion: a rational-ratio polyphase FIR in front of the detectors (which take float32 at the model's rate).
  * in_rate -> out_rate, g = gcd: up = L = out_rate / g, down = M = in_rate / g; taps = P per phase (even, or 1); table float32
  * [up][taps], designed on the host (tcresnet_amd.resampling.design_table: windowed sinc, fc = rolloff / max(1, M / L), Kaiser

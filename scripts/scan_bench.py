@@ -11,6 +11,7 @@ relayout into its planes, which the scan's gather writes directly).
     python scripts/scan_bench.py --ragged [--out profiles/scan_ragged_bench.json]
     python scripts/scan_bench.py --ab_lib tc-resnet_amd/lib/side/libtcr_parent.so      # the dense legs against another build
     python scripts/scan_bench.py --ragged_push [--out profiles/stream_scan_ragged_bench.json]
+    python scripts/scan_bench.py --cascade [--out profiles/scan_cascade_bench.json]
 
 --ragged: KeywordScanner.scan_ragged (tcr_scan_ragged) over a seeded corpus of 255 signals of 1 - 10 s (whole steps) and one of
 10 min, next to the padded dense scan of the same corpus ([256, 10 min], what a caller without it runs) and the dense scan of 256
@@ -28,6 +29,13 @@ next to the one-call scan_ragged and the lockstep push_many of the corpus zero-p
 wall time of one call of one step per stream on an idle device, push_ragged against push_many, at S = 1 and S = 4096 (the
 difference is the table upload and its wait), next to a host-to-device copy of a table of that size followed by a stream wait.
 
+--cascade: a two-stage scan (scanning.CascadeScanner) of 64 recordings of one minute: TCResNet8-1.0 first, DS-CNN-L second, both 4020
+at k = 1, W = 50.  The selected share is set directly: runs of 2 x 49 + 1 steps (the default pads around one flag) at seeded places,
+1 %, 5 %, 25 % and 100 % of the steps.  Timed: the first scan, the second model's full scan_ragged (what a caller without the
+cascade runs), KeywordScanner.scan_steps of the second model at each share, and the whole CascadeScanner.scan_ragged at each share
+(its first stage is the real scan followed by a copy that plants the flags of that share in its probs); with each share the
+front-end rows staged and the windows run (KeywordScanner.steps_plan).  This arm reports the minimum over --reps.
+
 Each number is the median over --reps timed calls (device events) after a warm-up call; the legs alternate within a rep.  Weights
 and audio are random (timing does not depend on them)."""
 from __future__ import annotations
@@ -43,7 +51,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from tcresnet_amd.scanning import DEFAULT_MAX_WINDOWS, KeywordScanner     # noqa: E402
+from tcresnet_amd.scanning import DEFAULT_MAX_WINDOWS, CascadeScanner, KeywordScanner     # noqa: E402
 from tcresnet_amd.streaming import StreamingDetector                       # noqa: E402
 from scripts.stream_bench import MODELS, build, build_model                # noqa: E402
 
@@ -242,6 +250,87 @@ def ragged_push_leg(args, fe, net, dev):
                        **row}, fh, indent=1)
 
 
+class PlantedFlags:
+    """A first-stage scanner whose scan_ragged is the real scan followed by a copy of `probs` over its probs: the flags of a
+    chosen share (--cascade).  Everything else is the scanner's own."""
+
+    def __init__(self, scanner, probs):
+        self._scanner, self._probs = scanner, probs
+
+    def __getattr__(self, name):
+        return getattr(self._scanner, name)
+
+    def scan_ragged(self, signals):
+        out = self._scanner.scan_ragged(signals)
+        out.probs.copy_(self._probs)
+        return out
+
+
+def cascade_leg(args, dev):
+    import numpy as np
+    fe1, net1 = build(640, HOP, "TCResNet8", 1.0, dev)
+    _, fe2, net2 = build_model("DSCNN-L", dev)
+    first = KeywordScanner(net1, fe1, average_window_ms=1000)
+    second = KeywordScanner(net2, fe2, average_window_ms=1000)
+    N, steps = 64, 60 * SR // HOP
+    total, pad = N * steps, second.average_steps - 1
+    run = 2 * pad + 1
+    g = torch.Generator(device="cuda").manual_seed(0)
+    packed = ((torch.rand(total * HOP, device=dev, generator=g) - 0.5) * 0.8).contiguous()
+    signals = (packed, [steps * HOP] * N)
+    # the places a run may take: `run` steps apart within a signal, so that the pads never leave it
+    slots = np.array([n * steps + j * run + pad for n in range(N) for j in range(steps // run)], np.int64)
+    rng = np.random.RandomState(0)
+    shares, legs, plans = (0.01, 0.05, 0.25, 1.0), {}, {}
+    legs["first_scan_ms"] = lambda: time_ms(lambda: first.scan_ragged(signals))
+    legs["second_full_scan_ms"] = lambda: time_ms(lambda: second.scan_ragged(signals))
+    full = second.scan_ragged(signals)
+    for share in shares:
+        probs = torch.zeros((total, 12), device=dev)
+        if share == 1.0:
+            probs[:, 2] = 1.0
+            selected = np.arange(total, dtype=np.int64)
+        else:
+            centres = np.sort(rng.choice(slots, int(round(share * total / run)), replace=False))
+            probs[torch.from_numpy(centres).to(dev), 2] = 1.0
+            selected = np.unique((centres[:, None] + np.arange(-pad, pad + 1)[None, :]).reshape(-1))
+        cascade = CascadeScanner(PlantedFlags(first, probs), second, 0.5)
+        out = cascade.scan_ragged(signals)
+        assert np.array_equal(out.selected.cpu().numpy(), selected), share
+        logits, _ = second.scan_steps(signals, selected)
+        assert torch.equal(logits, full.logits[out.selected]), share          # the rows of the full scan, bitwise
+        tag = "%g" % (100 * share)
+        plans[tag] = {"selected_steps": int(selected.size), "share": round(selected.size / total, 5), **second.steps_plan(signals, selected)}
+        legs["scan_steps_%s_ms" % tag] = lambda selected=selected: time_ms(lambda: second.scan_steps(signals, selected))
+        legs["cascade_%s_ms" % tag] = lambda cascade=cascade: time_ms(lambda: cascade.scan_ragged(signals))
+    for fn in legs.values():
+        fn()
+    res = {k: [] for k in legs}
+    for _ in range(args.reps):
+        for k, fn in legs.items():
+            res[k].append(fn())
+    low = {k: min(v) for k, v in res.items()}
+    G, frames = ragged_group(np.full(N, steps), 1, fe2.n_frames, min(1024, DEFAULT_MAX_WINDOWS))
+    hours = total * HOP / HOUR
+    row = {
+        "workload": "TCResNet8-1.0 then DS-CNN-L, 4020, k = 1, W = 50, max_windows = %d; 64 recordings of 60 s; runs of %d steps" % (
+            DEFAULT_MAX_WINDOWS, run),
+        "signals": N, "total_steps": total, "audio_hours": round(hours, 5),
+        "first_scan_ms": round(low["first_scan_ms"], 3), "second_full_scan_ms": round(low["second_full_scan_ms"], 3),
+        "second_full_scan": {"group_steps": G, "rows": frames // (G + fe2.n_frames - 1), "row_frames": G + fe2.n_frames - 1, "windows": total},
+        "shares": {tag: {**plans[tag], "scan_steps_ms": round(low["scan_steps_%s_ms" % tag], 3),
+                         "cascade_ms": round(low["cascade_%s_ms" % tag], 3),
+                         "scan_steps_over_full_scan": round(low["scan_steps_%s_ms" % tag] / low["second_full_scan_ms"], 4),
+                         "cascade_over_full_scan": round(low["cascade_%s_ms" % tag] / low["second_full_scan_ms"], 4)} for tag in plans},
+        "reps": args.reps, "statistic": "min", "raw": {k: [round(x, 4) for x in v] for k, v in res.items()},
+    }
+    print(json.dumps(row), flush=True)
+    if args.out:
+        with open(args.out, "w") as fh:
+            json.dump({"device": torch.cuda.get_device_name(0), "command": "python scripts/scan_bench.py --cascade --reps %d" % args.reps,
+                       **row}, fh, indent=1)
+
+
 def ab_leg(args, dev):
     """The four scan entries through this build and through --ab_lib, alternating: medians and ranges of both."""
     import tcresnet_amd as T
@@ -294,8 +383,11 @@ def main():
     ap.add_argument("--ragged", action="store_true")
     ap.add_argument("--ab_lib", default=None)
     ap.add_argument("--ragged_push", action="store_true")
+    ap.add_argument("--cascade", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda")
+    if args.cascade:
+        return cascade_leg(args, dev)
     if args.ab_lib:
         return ab_leg(args, dev)
     if args.ragged_push:

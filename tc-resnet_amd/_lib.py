@@ -208,6 +208,12 @@ _PROTOTYPES = {
     "tcr_detect_grid_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "tcr_detect_grid": (C.c_int, [C.c_int, C.c_int64, _P, C.c_int64, C.c_int, _P, _P, C.c_int, C.POINTER(DetectPoint), C.c_int, _P, _P, _P, _P, _P,
                                   _P, _P, _P, _P, C.c_size_t, _P]),
+    "tcr_scan_steps_workspace_bytes": (C.c_size_t, [C.POINTER(FrontendCfg), C.POINTER(ModelRef), C.c_int, C.c_int, C.c_int, C.c_int64]),
+    "tcr_scan_steps": (C.c_int, [C.POINTER(FrontendCfg), _P, C.POINTER(ModelRef), C.c_int, _P, C.c_int, _P, C.c_int64, _P, _P, C.c_size_t, _P, _P,
+                                 _P]),
+    "tcr_scan_steps_plan": (C.c_int, [C.POINTER(FrontendCfg), C.POINTER(ModelRef), C.c_int, _P, C.c_int, _P, C.c_int64, C.c_size_t, _P]),
+    "tcr_scan_select_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "tcr_scan_select": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, _P, C.c_float, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, _P, _P]),
     "tcr_resample": (C.c_int, [C.POINTER(ResampleCfg), _P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64,
                                _P]),
     "tcr_resample_span": (C.c_int, [C.POINTER(ResampleCfg), C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -181,11 +181,12 @@ def print_detections_ragged(rec: Recordings, out, names: List[str], counts: Dict
         print(f"{rec.paths[s[o]]},{format_time_ms(1000.0 * (i0 + int(i[o]) + 1) * rec.step / rec.rate)},{name},{float(score[fired[o]]):.6f}", flush=True)
 
 
-def summary_line(rec: Recordings, counts: Dict[str, int]) -> str:
-    """--summary's JSON: the hours of audio (each file's whole steps), the detections per label and per hour."""
+def summary_line(rec: Recordings, counts: Dict[str, int], extra: Optional[Dict[str, int]] = None) -> str:
+    """--summary's JSON: the hours of audio (each file's whole steps), the detections per label and per hour; `extra`: more entries
+    (a cascade run's selected_steps and total_steps)."""
     hours, total = sum(rec.lengths) / rec.rate / 3600.0, sum(counts.values())
     return json.dumps({"hours": hours, "detections": total, "detections_per_label": counts,
-                       "detections_per_hour": total / hours if hours > 0 else None})
+                       "detections_per_hour": total / hours if hours > 0 else None, **(extra or {})})
 
 
 def add_detector_flags(p, each: str = "signal", threshold: bool = True, offline: bool = True) -> None:
@@ -207,6 +208,14 @@ def add_detector_flags(p, each: str = "signal", threshold: bool = True, offline:
         p.add_argument("--ragged_chunk_seconds", type=float, default=None,
                        help="read the files this many seconds at a time, each at its own length (StreamingDetector.push_ragged): --ragged's "
                             "output with one chunk of every file in host memory")
+        p.add_argument("--second_frozen", default=None,
+                       help="cascade (with --ragged): --frozen flags steps, this artifact rescores only those (CascadeScanner); the "
+                            "detector flags configure the final detector, which is this model's")
+        p.add_argument("--enter_threshold", type=float, default=None,
+                       help="cascade: a step is flagged when a keyword class (every class from 2 on) of --frozen reaches this probability")
+        p.add_argument("--cascade_pad_ms", type=float, default=None,
+                       help="cascade: audio selected in front of and behind every flag (default: --average_window_ms minus one step)")
+        p.add_argument("--second_frames_per_step", type=int, default=1, help="cascade: --second_frozen's frames per step")
 
 
 def detector_settings(args) -> dict:
@@ -233,6 +242,37 @@ def open_detector(model, args):
         return det, det.scan
     det = model.streaming(len(args.wav), **detector_settings(args))
     return det, det.push_many
+
+
+def cascade_argv(argv: Optional[List[str]]) -> List[str]:
+    """The command line with `--enter_threshold -inf` (which argparse reads as an option) joined into one word."""
+    argv = list(sys.argv[1:] if argv is None else argv)
+    for i in range(len(argv) - 1):
+        if argv[i] == "--enter_threshold" and argv[i + 1].lower() in ("-inf", "-infinity"):
+            argv[i:i + 2] = [f"--enter_threshold={argv[i + 1]}"]
+            break
+    return argv
+
+
+def open_cascade(args):
+    """The `scanning.CascadeScanner` of --second_frozen / --enter_threshold (None without them): --frozen at --frames_per_step is the
+    first stage, --second_frozen at --second_frames_per_step the second, and the detector flags are the second's.  Accepted with
+    --ragged only: a cascade carries no state from chunk to chunk."""
+    if getattr(args, "second_frozen", None) is None:
+        if getattr(args, "enter_threshold", None) is not None or getattr(args, "cascade_pad_ms", None) is not None:
+            raise SystemExit("--enter_threshold and --cascade_pad_ms belong to a cascade: give --second_frozen")
+        return None
+    if args.enter_threshold is None:
+        raise SystemExit("--second_frozen needs --enter_threshold")
+    if args.chunk_seconds is not None or args.ragged_chunk_seconds is not None or not args.ragged:
+        raise SystemExit("--second_frozen (a cascade) runs with --ragged only: not with the padded one-call run, --chunk_seconds or "
+                         "--ragged_chunk_seconds, because no state is carried")
+    from .deploy import FrozenModel
+    from .scanning import CascadeScanner
+    settings = detector_settings(args)
+    first = FrozenModel.load(args.frozen).scanner(**settings)
+    second = FrozenModel.load(args.second_frozen).scanner(**dict(settings, frames_per_step=args.second_frames_per_step))
+    return CascadeScanner(first, second, args.enter_threshold, pad_before_ms=args.cascade_pad_ms, pad_after_ms=args.cascade_pad_ms)
 
 
 def label_names(args, det) -> List[str]:

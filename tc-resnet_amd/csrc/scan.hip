@@ -756,6 +756,25 @@ int scan_run(const ScanCall& c, const ScanState& st, int64_t steps, const std::v
     return check_launch("scan_suppress_kernel");
 }
 
+// The step offsets so [n + 1] of a ragged call's sample_offsets (HOST [n + 1]), with every refusal about them.
+int scan_step_offsets(const char* what, const char* noun, int n_signals, int64_t khop, int classes, const int64_t* sample_offsets,
+                      std::vector<int64_t>& so) {
+    TCR_REQUIRE(sample_offsets[0] == 0, "%s: sample_offsets must start at 0 (got %lld)", what, (long long)sample_offsets[0]);
+    so.resize((size_t)n_signals + 1);
+    so[0] = 0;
+    for (int n = 0; n < n_signals; ++n) {
+        const int64_t len = sample_offsets[n + 1] - sample_offsets[n];
+        TCR_REQUIRE(len >= 0, "%s: sample_offsets decrease at %s %d (%lld after %lld)", what, noun, n, (long long)sample_offsets[n + 1],
+                    (long long)sample_offsets[n]);
+        TCR_REQUIRE(len % khop == 0, "%s: the length %lld of %s %d is not a multiple of k * hop = %lld", what, (long long)len, noun, n,
+                    (long long)khop);
+        so[n + 1] = so[n] + len / khop;
+    }
+    TCR_REQUIRE(so[n_signals] > 0, "%s: no %s has a whole step (total_steps == 0)", what, noun);
+    TCR_REQUIRE(so[n_signals] * classes < ((int64_t)1 << 31), "%s: %lld steps in all is too large", what, (long long)so[n_signals]);
+    return TCR_OK;
+}
+
 // The checks of the four entries, in one order; then the state's regions and the pipeline.  Dense (sample_offsets == null): n_samples
 // per signal become `steps`.  Ragged: sample_offsets [n + 1] become step offsets, the tables take the workspace's front, and samples
 // and outputs may be null up to the late check (a caller sizes its outputs by what the offsets yield).  With a state the n signals are
@@ -782,19 +801,7 @@ int scan_entry(ScanCall& c, bool ragged, int64_t n_samples, const int64_t* sampl
         const size_t tables_bytes = scan_ragged_tables_bytes(c.n);
         TCR_REQUIRE(tables_bytes <= c.ws_bytes, "%s: %d %ss are more than the max_signals the workspace's offset tables hold (%lld)", what,
                     c.n, noun, (long long)(c.ws_bytes / (2 * sizeof(int64_t))) - 1);
-        TCR_REQUIRE(sample_offsets[0] == 0, "%s: sample_offsets must start at 0 (got %lld)", what, (long long)sample_offsets[0]);
-        so.resize((size_t)c.n + 1);
-        so[0] = 0;
-        for (int n = 0; n < c.n; ++n) {
-            const int64_t len = sample_offsets[n + 1] - sample_offsets[n];
-            TCR_REQUIRE(len >= 0, "%s: sample_offsets decrease at %s %d (%lld after %lld)", what, noun, n, (long long)sample_offsets[n + 1],
-                        (long long)sample_offsets[n]);
-            TCR_REQUIRE(len % khop == 0, "%s: the length %lld of %s %d is not a multiple of k * hop = %lld", what, (long long)len, noun, n,
-                        (long long)khop);
-            so[n + 1] = so[n] + len / khop;
-        }
-        TCR_REQUIRE(so[c.n] > 0, "%s: no %s has a whole step (total_steps == 0)", what, noun);
-        TCR_REQUIRE(so[c.n] * c.io.classes < ((int64_t)1 << 31), "%s: %lld steps in all is too large", what, (long long)so[c.n]);
+        TCR_TRY(scan_step_offsets(what, noun, c.n, khop, c.io.classes, sample_offsets, so));
         TCR_REQUIRE(io_ptrs, "%s: null argument", what);
         c.tables = static_cast<int64_t*>(c.workspace);
         c.workspace = static_cast<char*>(c.workspace) + tables_bytes;

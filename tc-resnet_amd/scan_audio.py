@@ -3,6 +3,7 @@
     python scan_audio.py --frozen MODEL.npz --wav a.wav [b.wav ...] [--frames_per_step k] [--labels l0,l1,...]
                          [--average_window_ms MS] [--detection_threshold P] [--suppression_ms MS] [--min_count N]
                          [--max_windows B] [--summary] [--chunk_seconds X | --ragged | --ragged_chunk_seconds X]
+                         [--second_frozen MODEL2.npz --enter_threshold P [--cascade_pad_ms MS] [--second_frames_per_step K]]
 
 The files (16-bit PCM) come from `audio_input.Recordings`, zero-padded to the longest, and are scanned in one
 `scanning.KeywordScanner` call; samples that do not fill a whole step are dropped (noted on stderr).  A file at another sample rate
@@ -18,7 +19,12 @@ of audio scanned (each file's whole steps), the detections per label and the det
 lines have the same format and order, and no file has steps (or detections) past its own end.  --ragged_chunk_seconds X (on its own:
 not with --chunk_seconds or --ragged) is that run in bounded host memory: every file is read X seconds at a time at its own length --
 its next whole steps, none once it has ended -- and the chunks go to one `StreamingDetector.push_ragged`; stdout and the --summary
-line are those of --ragged, byte for byte."""
+line are those of --ragged, byte for byte.  A cascade (--ragged with --second_frozen MODEL2.npz and --enter_threshold P): --frozen scans
+every step, the steps where one of its keyword classes (every class from 2 on) reaches P, and --cascade_pad_ms of audio on both sides
+of them (default: the averaging window minus one step), are computed again by MODEL2 at --second_frames_per_step, and the detector
+-- the detector flags are the second stage's -- runs on the merged posteriors (`scanning.CascadeScanner`); both models must have the
+same sample rate, classes and step (frames per step x hop).  --summary then gains selected_steps and total_steps.  With
+--enter_threshold -inf every step is MODEL2's and stdout is MODEL2's own --ragged run, byte for byte."""
 from __future__ import annotations
 
 import argparse
@@ -28,12 +34,12 @@ from typing import List, Optional
 
 if __package__ in (None, ""):           # run as a script: import the package through the repository's shim
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from tcresnet_amd.audio_input import (Recordings, add_detector_flags, label_names, open_detector, print_detections,
-                                          print_detections_ragged, summary_line)
+    from tcresnet_amd.audio_input import (Recordings, add_detector_flags, cascade_argv, label_names, open_cascade, open_detector,
+                                          print_detections, print_detections_ragged, summary_line)
     from tcresnet_amd.deploy import FrozenModel
 else:
-    from .audio_input import (Recordings, add_detector_flags, label_names, open_detector, print_detections, print_detections_ragged,
-                              summary_line)
+    from .audio_input import (Recordings, add_detector_flags, cascade_argv, label_names, open_cascade, open_detector, print_detections,
+                              print_detections_ragged, summary_line)
     from .deploy import FrozenModel
 
 
@@ -41,10 +47,25 @@ def parse_arguments(arguments: Optional[List[str]] = None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     add_detector_flags(p)
     p.add_argument("--summary", action="store_true", help="one JSON line of totals on stderr")
-    return p.parse_args(arguments)
+    return p.parse_args(cascade_argv(arguments))
+
+
+def main_cascade(args, cascade) -> int:
+    rec = Recordings(args.wav, cascade.second)
+    names, counts, extra = label_names(args, cascade.second), {}, {"selected_steps": 0, "total_steps": 0}
+    if rec.n_steps > 0:
+        out = cascade.scan_ragged(rec.packed())
+        print_detections_ragged(rec, out, names, counts)
+        extra = {"selected_steps": int(out.selected.numel()), "total_steps": int(out.top.shape[0])}
+    if args.summary:
+        print(summary_line(rec, counts, extra), file=sys.stderr)
+    return 0
 
 
 def main(args) -> int:
+    cascade = open_cascade(args)
+    if cascade is not None:
+        return main_cascade(args, cascade)
     det, run = open_detector(FrozenModel.load(args.frozen), args)
     rec = Recordings(args.wav, det)
     names, counts = label_names(args, det), {}

@@ -11,6 +11,10 @@ signal's rows bitwise its own `scan`, no padding computed, stored or detected in
 `KeywordScanner.sweep` (and `detection_sweep` over raw top / score tensors) then runs that rule for many thresholds at once on the
 device and scores the detections against labelled keyword events: a DET curve (false rejects against false accepts per hour) for
 the cost of one scan and a pass over its top / score.
+
+`KeywordScanner.scan_steps` computes a chosen subset of a ragged scan's steps at the cost of that subset (tcr_scan_steps),
+`select_steps` picks the steps around a first model's flags (tcr_scan_select), and a `CascadeScanner` puts the two together: a cheap
+scanner looks at everything, an expensive one only where the cheap one flagged, and the detector runs on the merged posteriors.
 """
 from __future__ import annotations
 
@@ -24,7 +28,7 @@ import torch
 from . import _lib
 from ._lib import TcrError
 from .engine import Frontend
-from .streaming import Network, _Detection, _ragged_scan_output, _ragged_signals, _scan_output
+from .streaming import Network, _Detection, _ragged_scan_output, _ragged_signals, _scan_output, ms_to_steps
 
 DEFAULT_MAX_WINDOWS = 4096
 DEFAULT_MAX_SIGNALS = 65536
@@ -77,7 +81,8 @@ class KeywordScanner(_Detection):
 
     max_windows bounds the windows the network runs per launch (default 4096); the workspace, allocated once here, is sized by it
     and not by the signals' length.  max_signals (default 65536) sizes the offset tables of `scan_ragged`'s workspace, which is
-    allocated on its first call and again when a call brings more signals."""
+    allocated on its first call and again when a call brings more signals; `scan_steps` has a workspace of its own, sized by the
+    signals and selected steps of the largest call so far."""
 
     def __init__(self, net: Network, frontend: Frontend, frames_per_step: int = 1, average_window_ms: float = 1000,
                  min_count: int = 3, detection_threshold: float = 0.5, suppression_ms: float = 1500,
@@ -89,6 +94,8 @@ class KeywordScanner(_Detection):
         if self.max_signals < 1:
             raise TcrError(f"KeywordScanner: max_signals must be >= 1 (got {self.max_signals})")
         self._ragged_ws: Optional[torch.Tensor] = None
+        self._steps_ws: Optional[torch.Tensor] = None
+        self._steps_ws_size = (0, 0)            # the signals and selected steps `_steps_ws` holds tables for
         lib, cfg = self.lib, frontend.cfg
         nws = lib.tcr_scan_workspace_bytes_m(C.byref(cfg), C.byref(self._ref()), self.k, self.max_windows)
         if nws == 0:
@@ -131,6 +138,64 @@ class KeywordScanner(_Detection):
         self._after_call()
         return out
 
+    def _steps_workspace(self, n: int, n_selected: int) -> torch.Tensor:
+        """The workspace of `scan_steps` (sized by max_windows, the signals and the selected steps), allocated on the first call and
+        again when a call brings more signals or more selected steps than it holds tables for."""
+        have_n, have_sel = self._steps_ws_size
+        if self._steps_ws is None or n > have_n or n_selected > have_sel:
+            lib = self.lib
+            size = (max(have_n, n, 1), max(have_sel, n_selected, self.max_windows))
+            nws = lib.tcr_scan_steps_workspace_bytes(C.byref(self.frontend.cfg), C.byref(self._ref()), self.k, self.max_windows, *size)
+            if nws == 0:
+                raise TcrError(f"KeywordScanner.scan_steps: {lib.tcr_last_error().decode()}")
+            self._steps_ws = torch.empty(nws // 4, dtype=torch.float32, device=self.device)
+            self._steps_ws_size = size
+        return self._steps_ws
+
+    def _steps_args(self, signals, selected):
+        packed, lengths, offsets = _ragged_signals("scan_steps", "signal", signals)
+        self.net._check_tensor(packed, "scan samples")
+        if isinstance(selected, torch.Tensor):
+            if selected.dtype != torch.int64:
+                raise TcrError(f"scan_steps expects int64 selected steps, got {selected.dtype}")
+            selected = selected.detach().cpu().numpy()
+        sel = np.ascontiguousarray(np.asarray(selected, dtype=np.int64))
+        if sel.ndim != 1:
+            raise TcrError(f"scan_steps expects 1-D selected steps, got shape {sel.shape}")
+        return packed, lengths, offsets, sel
+
+    def scan_steps(self, signals, selected) -> Tuple[torch.Tensor, torch.Tensor]:
+        """A chosen subset of `scan_ragged`'s steps, at the cost of that subset (tcr_scan_steps).  `signals`: the forms `scan_ragged`
+        takes; `selected`: packed step indices (rows of `scan_ragged`'s outputs), strictly increasing -- a 1-D int64 tensor on either
+        side, or an array.  Returns (logits, probs) [n_selected, classes] (new tensors): row b is bitwise row selected[b] of
+        `scan_ragged(signals)`, whatever max_windows and the other selected steps.  Only the front-end rows that hold a selected step
+        and the selected windows are computed; no detector runs (merge the rows into a scan's probs and `redetect`).  The weight
+        rules are `scan`'s.  The workspace is allocated on the first call and again when a call brings more signals or more
+        selected steps."""
+        packed, lengths, offsets, sel = self._steps_args(signals, selected)
+        N, n_sel = int(lengths.size), int(sel.size)
+        lib, fe, net = self.lib, self.frontend, self.net
+        ws = self._steps_workspace(N, n_sel)
+        ref = self._call_ref()
+        logits = torch.empty((n_sel, net.num_classes), dtype=torch.float32, device=self.device)
+        probs = torch.empty_like(logits)
+        lib.check(lib.tcr_scan_steps(C.byref(fe.cfg), fe.plan.data_ptr(), C.byref(ref), N, offsets.ctypes.data, self.k, sel.ctypes.data,
+                                     n_sel, packed.data_ptr(), ws.data_ptr(), ws.numel() * 4, logits.data_ptr(), probs.data_ptr(),
+                                     net._stream()), "tcr_scan_steps")
+        self._after_call()
+        return logits, probs
+
+    def steps_plan(self, signals, selected) -> Dict[str, int]:
+        """What `scan_steps(signals, selected)` would run, from the host alone (tcr_scan_steps_plan): group_steps (G), rows (front-end
+        rows staged), row_frames (frames of a row), chunk_rows (rows per network launch) and windows (= the selected steps)."""
+        packed, lengths, offsets, sel = self._steps_args(signals, selected)
+        N, n_sel = int(lengths.size), int(sel.size)
+        ws = self._steps_workspace(N, n_sel)
+        plan = np.zeros(4, np.int64)
+        lib = self.lib
+        lib.check(lib.tcr_scan_steps_plan(C.byref(self.frontend.cfg), C.byref(self._ref()), N, offsets.ctypes.data, self.k, sel.ctypes.data,
+                                          n_sel, ws.numel() * 4, plan.ctypes.data), "tcr_scan_steps_plan")
+        return {"group_steps": int(plan[0]), "rows": int(plan[1]), "row_frames": int(plan[2]), "chunk_rows": int(plan[3]), "windows": n_sel}
 
     # ---- detector tuning from one scan ---------------------------------------------------------------------------------------
     def redetect(self, out, average_window_ms: Optional[float] = None, min_count: Optional[int] = None,
@@ -491,3 +556,122 @@ def detection_grid(probs: torch.Tensor, points, thresholds, num_classes: int,
                                   detections.data_ptr(), hits.data_ptr(), dups.data_ptr(), ws.data_ptr(), nws, stream), "tcr_detect_grid")
     hours = vs * float(step_seconds) / 3600.0 if step_seconds is not None else np.full(N, np.nan)
     return detections, hits, dups, thr, counts, hours
+
+
+# ---- cascades --------------------------------------------------------------------------------------------------------------------
+def select_steps(values: torch.Tensor, offsets, enter: float, classes: Sequence[int], pad_before: int = 0, pad_after: int = 0,
+                 lib=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The raw form of tcr_scan_select: the steps around the flags of `values`.  values [total_steps, C] float32 on the device (a
+    ragged scan's probs or smoothed), offsets host int64 [N + 1] in steps (`RaggedScanOutput.offsets`), classes: the class indices
+    that can flag.  Step p is flagged when one of those classes has values[p, c] >= enter (float32; NaN never flags) and selected
+    when a flagged step of its signal lies in p - pad_after .. p + pad_before.  Returns (selected, mask) on the device: the selected
+    packed steps, int64, increasing, and uint8 [total_steps] membership.  Reads one integer back (the number of selected steps), so
+    the call waits for the device."""
+    if lib is None:
+        lib = _lib.get()
+    soff = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+    if values.dim() != 2 or values.dtype != torch.float32 or not values.is_contiguous():
+        raise TcrError(f"select_steps expects contiguous float32 values [total_steps, classes], got {values.dtype} {tuple(values.shape)}")
+    total, ncls = int(values.shape[0]), int(values.shape[1])
+    if soff.size < 2 or soff[0] != 0 or (np.diff(soff) < 0).any() or int(soff[-1]) != total:
+        raise TcrError(f"select_steps: offsets must run from 0 to the {total} packed steps without decreasing")
+    cls = np.asarray(list(classes), dtype=np.int64).reshape(-1)
+    if cls.size and (cls.min() < 0 or cls.max() >= ncls):
+        raise TcrError(f"select_steps: classes outside 0..{ncls - 1}: {cls.tolist()}")
+    dev = values.device
+    cmask = np.zeros(max(ncls, 1), np.uint8)
+    cmask[cls] = 1
+    mask = torch.empty(total, dtype=torch.uint8, device=dev)
+    selected = torch.empty(total, dtype=torch.int64, device=dev)
+    if total == 0:
+        return selected, mask
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    cmask_dev, off_dev = torch.from_numpy(cmask).to(dev), torch.from_numpy(soff).to(dev)
+    nws = lib.tcr_scan_select_workspace_bytes(total)
+    if nws == 0:
+        raise TcrError(f"select_steps: {lib.tcr_last_error().decode()}")
+    ws = torch.empty(nws // 4, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+    lib.check(lib.tcr_scan_select(int(soff.size) - 1, off_dev.data_ptr(), total, ncls, values.data_ptr(), cmask_dev.data_ptr(), float(enter),
+                                  int(pad_before), int(pad_after), ws.data_ptr(), nws, selected.data_ptr(), count.data_ptr(),
+                                  mask.data_ptr(), stream), "tcr_scan_select")
+    return selected[:int(count.item())], mask
+
+
+class CascadeOutput(RaggedScanOutput):
+    """Results of a cascade scan: a `RaggedScanOutput` of the merged posteriors and the final (second-stage) detector over them, so
+    `sweep` and `tune` of the second scanner take it unchanged.  `selected` (device int64): the packed steps the second model
+    computed; `first`: the first stage's own `RaggedScanOutput`."""
+
+    def __init__(self, logits, probs, smoothed, top, score, is_new, offsets, selected: torch.Tensor, first: RaggedScanOutput):
+        super().__init__(logits, probs, smoothed, top, score, is_new, offsets)
+        self.selected, self.first = selected, first
+
+
+class CascadeScanner:
+    """A two-stage scan: `first` (a cheap `KeywordScanner`) scans every step, the steps around its flags are selected, `second` (an
+    expensive one) computes only those (`scan_steps`), and `second`'s detector runs over the merged posteriors.
+
+    A step is flagged when a class of keyword_classes (default: every class from 2 on, after _silence_ and _unknown_) reaches
+    enter_threshold in the first stage's `on` ("probs" or "smoothed"); pad_before_ms / pad_after_ms of audio in front of and behind
+    every flag are selected with it (default: the second scanner's averaging window minus one step on both sides, so every vector the
+    detector smooths at a flagged step, and for a window after it, is the second model's).  The scanners must share library, device,
+    sample rate, num_classes and the step: k1 * hop1 == k2 * hop2 samples (a 30 / 10 ms first stage at k = 2 pairs with a 40 / 20 ms
+    second stage at k = 1).  No state is carried between calls."""
+
+    def __init__(self, first: KeywordScanner, second: KeywordScanner, enter_threshold: float,
+                 keyword_classes: Optional[Sequence[int]] = None, pad_before_ms: Optional[float] = None,
+                 pad_after_ms: Optional[float] = None, on: str = "probs"):
+        if first.lib is not second.lib or first.device != second.device:
+            raise TcrError("CascadeScanner: the two scanners must use the same library and device")
+        r1, r2 = first.frontend.cfg.sample_rate, second.frontend.cfg.sample_rate
+        if r1 != r2:
+            raise TcrError(f"CascadeScanner: the scanners run at different sample rates ({r1} and {r2} Hz)")
+        if first.step_samples != second.step_samples:
+            raise TcrError(f"CascadeScanner: the scanners' steps differ ({first.step_samples} and {second.step_samples} samples): "
+                           "k1 * hop1 must equal k2 * hop2")
+        if first.net.num_classes != second.net.num_classes:
+            raise TcrError(f"CascadeScanner: the scanners' models have {first.net.num_classes} and {second.net.num_classes} classes")
+        if on not in ("probs", "smoothed"):
+            raise TcrError(f"CascadeScanner: on must be 'probs' or 'smoothed', got {on!r}")
+        if math.isnan(float(enter_threshold)):
+            raise TcrError("CascadeScanner: enter_threshold is NaN")
+        ncls = second.net.num_classes
+        self.keyword_classes = list(range(2, ncls)) if keyword_classes is None else [int(c) for c in keyword_classes]
+        if any(not 0 <= c < ncls for c in self.keyword_classes):
+            raise TcrError(f"CascadeScanner: keyword_classes outside 0..{ncls - 1}: {self.keyword_classes}")
+        self.first, self.second, self.lib, self.device = first, second, second.lib, second.device
+        self.enter_threshold, self.on = float(enter_threshold), on
+        default = second.average_steps - 1
+        self.pad_before = default if pad_before_ms is None else ms_to_steps(pad_before_ms, second.step_ms)
+        self.pad_after = default if pad_after_ms is None else ms_to_steps(pad_after_ms, second.step_ms)
+        if self.pad_before < 0 or self.pad_after < 0:
+            raise TcrError(f"CascadeScanner: negative pads ({pad_before_ms} ms before, {pad_after_ms} ms after)")
+
+    def scan_ragged(self, signals) -> CascadeOutput:
+        """`signals` as `KeywordScanner.scan_ragged` takes them -> `CascadeOutput`.  first.scan_ragged, `select_steps`, the read-back
+        of the selected steps (their number, then the steps: the host builds the sparse scan's tables from them, the wait a ragged
+        scan's tables already cost), second.scan_steps; logits / probs are the first stage's rows with the selected rows replaced
+        by the second stage's, and smoothed / top / score / is_new are second.redetect of that merge.  Nothing selected: neither
+        the second front-end nor the second network runs."""
+        packed, lengths, _ = _ragged_signals("CascadeScanner.scan_ragged", "signal", signals)
+        first = self.first.scan_ragged((packed, lengths))
+        selected, _ = select_steps(getattr(first, self.on), first.offsets, self.enter_threshold, self.keyword_classes, self.pad_before,
+                                   self.pad_after, self.lib)
+        logits, probs = first.logits.clone(), first.probs.clone()
+        if selected.numel():
+            l2, p2 = self.second.scan_steps((packed, lengths), selected.cpu())
+            logits.index_copy_(0, selected, l2)
+            probs.index_copy_(0, selected, p2)
+        det = self.second.redetect(RaggedScanOutput(logits, probs, None, None, None, None, first.offsets))
+        return CascadeOutput(*det.tensors(), first.offsets, selected, first)
+
+    def scan(self, samples: torch.Tensor) -> ScanOutput:
+        """samples [N, L] float32 on the device, L a multiple of the step -> the cascade over N signals of equal length, as `ScanOutput`
+        views [N, steps, ...] of `scan_ragged`'s tensors."""
+        if samples.dim() != 2:
+            raise TcrError(f"scan expects samples [N, L], got shape {tuple(samples.shape)}")
+        N, L = int(samples.shape[0]), int(samples.shape[1])
+        out = self.scan_ragged((samples.reshape(-1), [L] * N))
+        steps = L // self.second.step_samples
+        return ScanOutput(*(t.view(N, steps, *t.shape[1:]) for t in out.tensors()))

@@ -5,6 +5,7 @@ curve (false rejects against false accepts per hour) from one scan.
                           [--tolerance_ms MS] [--keywords l0,l1,...] [--per_label] [--target_fa_per_hour F]
                           [--frames_per_step k] [--labels l0,l1,...] [--average_window_ms MS] [--suppression_ms MS]
                           [--min_count N] [--max_windows B] [--chunk_seconds X | --ragged | --ragged_chunk_seconds X]
+                          [--second_frozen MODEL2.npz --enter_threshold P [--cascade_pad_ms MS] [--second_frames_per_step K]]
 
 The files are read as scan_audio.py reads them (`audio_input.Recordings`: 16-bit PCM, converted to the model's sample rate on the
 device where it differs, only whole steps), zero-padded to the longest and scanned in one call; one `KeywordScanner.sweep` then
@@ -14,7 +15,9 @@ thresholds are).  With --chunk_seconds the files are read and scanned chunk by c
 one-call output, byte for byte.  With --ragged (not together with --chunk_seconds) the files are scanned at their own lengths in
 one `KeywordScanner.scan_ragged` call and swept over its packed rows: the same curve without the padding; --ragged_chunk_seconds X
 (on its own) reads the files X seconds at a time at their own lengths (`StreamingDetector.push_ragged`), keeps every file's top /
-score rows on the device, puts them back into the packed layout and sweeps once: --ragged's output, byte for byte.  EVENTS.csv has a header and the columns
+score rows on the device, puts them back into the packed layout and sweeps once: --ragged's output, byte for byte.  A cascade
+(--ragged with --second_frozen and --enter_threshold, scan_audio.py's flags: `scanning.CascadeScanner`) sweeps the second stage's
+detector over the merged posteriors; the JSON line then gains selected_steps and total_steps.  EVENTS.csv has a header and the columns
 file,start_ms,end_ms,label  (file as given to --wav, label one of --labels or a class index).  A detection at time t (the end of
 the window that fired, scan_audio.py's time) hits an event of its label when  start_ms <= t <= end_ms + tolerance_ms; the first
 hit of an event counts as a hit, later ones as duplicates, every other detection as a false accept.
@@ -36,11 +39,11 @@ import numpy as np
 
 if __package__ in (None, ""):           # run as a script: import the package through the repository's shim
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from tcresnet_amd.audio_input import Recordings, add_detector_flags, label_names, open_detector
+    from tcresnet_amd.audio_input import Recordings, add_detector_flags, cascade_argv, label_names, open_cascade, open_detector
     from tcresnet_amd.deploy import FrozenModel
     from tcresnet_amd.scanning import RaggedScanOutput, ScanOutput
 else:
-    from .audio_input import Recordings, add_detector_flags, label_names, open_detector
+    from .audio_input import Recordings, add_detector_flags, cascade_argv, label_names, open_cascade, open_detector
     from .deploy import FrozenModel
     from .scanning import RaggedScanOutput, ScanOutput
 
@@ -66,7 +69,7 @@ def parse_arguments(arguments: Optional[List[str]] = None):
     p.add_argument("--keywords", default=None, help="comma-separated labels scored (default: labels not starting with '_')")
     p.add_argument("--per_label", action="store_true", help="one row per keyword and threshold")
     p.add_argument("--target_fa_per_hour", type=float, default=0.5, help="false-accept budget of the operating point")
-    return p.parse_args(arguments)
+    return p.parse_args(cascade_argv(arguments))
 
 
 def format_row(cv, t: int) -> list:
@@ -89,7 +92,11 @@ def read_events(path: str, wavs: List[str]):
 
 def main(args) -> int:
     import torch
-    scanner, run = open_detector(FrozenModel.load(args.frozen), args)
+    cascade, extra = open_cascade(args), {}
+    if cascade is not None:
+        scanner, run = cascade.second, None
+    else:
+        scanner, run = open_detector(FrozenModel.load(args.frozen), args)
     names = label_names(args, scanner)
     keywords = args.keywords.split(",") if args.keywords else [x for x in names if not x.startswith("_")]
     unknown = [k for k in keywords if k not in names]
@@ -101,7 +108,11 @@ def main(args) -> int:
     if rec.n_steps == 0:
         raise SystemExit("no whole step of audio in the files")
     events = read_events(args.events, args.wav)
-    if args.ragged_chunk_seconds is not None:
+    if cascade is not None:
+        out = cascade.scan_ragged(rec.packed())
+        extra = {"selected_steps": int(out.selected.numel()), "total_steps": int(out.top.shape[0])}
+        res = scanner.sweep(out, thresholds, events=events, tolerance_ms=args.tolerance_ms, labels=names)
+    elif args.ragged_chunk_seconds is not None:
         tops, scores = [[] for _ in args.wav], [[] for _ in args.wav]      # per file, its rows chunk by chunk
         for _, packed, lengths in rec.ragged_chunks(args.ragged_chunk_seconds):
             o = run((packed, lengths))
@@ -139,7 +150,7 @@ def main(args) -> int:
             w.writerow(fmt(cv, t))
     sys.stdout.flush()
     print(json.dumps({"hours": float(res.hours.sum()), "keywords": keywords, "target_fa_per_hour": args.target_fa_per_hour,
-                      "operating_point": res.operating_point(args.target_fa_per_hour, classes)}), file=sys.stderr)
+                      "operating_point": res.operating_point(args.target_fa_per_hour, classes), **extra}), file=sys.stderr)
     return 0
 
 
