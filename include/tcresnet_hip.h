@@ -712,6 +712,86 @@ int tcr_scan_select(int n_signals, const int64_t* step_offsets /* DEVICE [N + 1]
                     int pad_before, int pad_after, void* workspace, size_t ws_bytes, int64_t* selected /* DEVICE */,
                     int64_t* n_selected /* DEVICE [1] */, uint8_t* mask /* [total_steps] or NULL */, void* stream);
 
+/* Hard-example mining: the windows a scan got wrong, the best of them, and their audio.  All layouts are the ragged ones: step_offsets
+ * is a DEVICE table as tcr_detect_redetect_ragged takes it (a dense scan: step_offsets[n] = n x steps); every pointer is device memory
+ * unless marked HOST; everything is enqueued on `stream` -- no copy, no wait -- and every result is deterministic: the tables are
+ * written by prefix sums in kernels of their own (no workgroup waits for another, no position comes from an atomic).
+ * Workspace of the first three: tcr_mine_workspace_bytes(n_items, ranked) with n_items = total_steps (tcr_mine_detections),
+ * total_steps x num_classes (tcr_mine_peaks), both with ranked = 0 (a byte per item and the tiles' sums), or n_cand with ranked = 1
+ * (tcr_mine_select: four more bytes per candidate, the ranks of the ties); 0 when n_items is outside 1 .. 2^31 - 1;
+ * TCR_ERR_WORKSPACE below it.
+ *
+ * tcr_mine_detections: a scan's detections classified against events.  top / score / is_new [total_steps] are a scan's or a
+ * redetect's; the events are tcr_detect_sweep_ragged's CSR (event_offsets int32 [N + 1], inclusive step ranges relative to the
+ * signal's first step, sorted and disjoint within a signal: preconditions) and n_events their number, event_offsets[N].  A CANDIDATE
+ * is a step with is_new != 0 and 0 <= top < num_classes.  The candidates are written in increasing packed step: cand_step int64,
+ * cand_label int32 (top), cand_value float32 (score), cand_kind uint8 (0 false accept, 1 hit, 2 duplicate), cand_event int32 (the CSR
+ * index of the event whose range covers the step, whatever its label; -1: none), each with room for total_steps; n_cand (int64 [1])
+ * their number.  event_hit int64 [n_events]: the packed step of the detection that hit the event, -1 for a miss.  The rule is
+ * tcr_detect_sweep's: a detection is a hit when an event of its label covers it and no earlier detection hit that event, a
+ * duplicate when one did, a false accept otherwise -- evaluated without the walk: the hit of event e is the first candidate in e's
+ * range whose label is e's.  Per signal and label the kinds' counts equal tcr_detect_sweep_ragged's detections - hits - duplicates,
+ * hits and duplicates at the threshold that produced is_new.  event_offsets NULL: every candidate is kind 0 with cand_event -1 and
+ * event_hit is not written.  No floating-point arithmetic.
+ * Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched): a null step_offsets / top / score / is_new / workspace / candidate table
+ * / n_cand, N or total_steps <= 0, num_classes outside 1 .. 256, total_steps x num_classes >= 2^31, event_offsets without event_first
+ * / event_last / event_label, n_events < 0, n_events > 0 with a null event_hit. */
+size_t tcr_mine_workspace_bytes(int64_t n_items, int ranked);
+int tcr_mine_detections(int n_signals, const int64_t* step_offsets /* DEVICE [N + 1] */, int64_t total_steps, int num_classes,
+                        const int32_t* top, const float* score, const int32_t* is_new, const int32_t* event_offsets /* or NULL */,
+                        const int64_t* event_first, const int64_t* event_last, const int32_t* event_label, int n_events,
+                        void* workspace, size_t ws_bytes, int64_t* cand_step, int32_t* cand_label, float* cand_value,
+                        uint8_t* cand_kind, int32_t* cand_event, int64_t* n_cand /* DEVICE [1] */,
+                        int64_t* event_hit /* [n_events] */, void* stream);
+
+/* tcr_mine_peaks: near misses, independent of any threshold.  values [total_steps][num_classes] are a scan's probs or smoothed.
+ * The pair (p, c) with class_mask[c] != 0 is a candidate when  values[p][c] >= floor  (float32 compares: a NaN never is), p lies in no
+ * exclusion range of its signal (exclude_offsets int32 [N + 1] / exclude_first / exclude_last int64: CSR per signal of inclusive step
+ * ranges relative to the signal's first step, sorted and disjoint, whatever label; NULL: none),  values[p][c] > values[q][c]  for
+ * every q in [p - R, p) and  values[p][c] >= values[q][c]  for every q in (p, p + R], q over the steps of p's own signal only and NaN
+ * neighbours ignored: on a plateau the lowest step wins.  The candidates go to cand_step / cand_label / cand_value in (packed step,
+ * class) order, the first `capacity` of them; n_cand is their true number whatever the capacity, so a caller can retry with room.
+ * How: a workgroup stages a tile of TCR_MINE_TILE steps and R steps on each side in LDS and takes every window's maximum from
+ * running maxima over blocks of R steps, at a cost per element that does not depend on R.  The staged steps take 8 bytes per class
+ * of a chunk and 4 more in 63 KB of LDS, the classes going through in chunks when they do not fit at once, so the radius is bounded
+ * by one class a chunk:  R <= TCR_MINE_RADIUS_MAX = (64512 / 12 - TCR_MINE_TILE) / 2 = 2560  whatever num_classes (all 12 classes at
+ * once up to R = 194).
+ * Refused (TCR_ERR_ARG): a null step_offsets / values / class_mask / workspace / n_cand, N or total_steps <= 0, num_classes outside
+ * 1 .. 256, total_steps x num_classes >= 2^31, a NaN floor, radius outside 1 .. TCR_MINE_RADIUS_MAX, capacity < 0, capacity > 0 with a
+ * null table, exclude_offsets without exclude_first / exclude_last. */
+#define TCR_MINE_TILE 256
+#define TCR_MINE_RADIUS_MAX 2560
+int tcr_mine_peaks(int n_signals, const int64_t* step_offsets /* DEVICE [N + 1] */, int64_t total_steps, int num_classes,
+                   const float* values /* [total_steps][C] */, const uint8_t* class_mask /* [C] */, float floor, int radius,
+                   const int32_t* exclude_offsets /* [N + 1] or NULL */, const int64_t* exclude_first, const int64_t* exclude_last,
+                   void* workspace, size_t ws_bytes, int64_t capacity, int64_t* cand_step, int32_t* cand_label, float* cand_value,
+                   int64_t* n_cand /* DEVICE [1] */, void* stream);
+
+/* tcr_mine_select: the k best of n_cand candidates, exact.  A candidate is eligible when cand_kind is NULL or bit cand_kind[j] of
+ * kind_mask is set.  Order: the larger cand_value first (a float32 compare, -0 equal to +0; NaNs by their bit image, positive ones
+ * above +inf, negative ones below -inf), then the lower index.  picked (int64, room for min(k, n_cand)) receives the indices of the
+ * first min(k, eligible) candidates of that order, in INCREASING index order; n_picked (int64 [1]) their number.  A radix select
+ * over the order-preserving integer image of the values (four histogram passes find the k-th key), then one compaction of
+ * everything above that key and the lowest-index ties at it: no sort, no floating-point arithmetic.  k == 0, n_cand == 0 or nothing
+ * eligible: n_picked = 0 (with k == 0 or n_cand == 0 only n_picked is touched, and value / workspace / picked may be NULL).
+ * Refused (TCR_ERR_ARG): a null n_picked, n_cand outside 0 .. 2^31 - 1, k < 0, a null cand_value / workspace / picked. */
+int tcr_mine_select(int64_t n_cand, const float* cand_value, const uint8_t* cand_kind /* [n_cand] or NULL */, uint32_t kind_mask,
+                    int64_t k, void* workspace, size_t ws_bytes, int64_t* picked, int64_t* n_picked /* DEVICE [1] */, void* stream);
+
+/* tcr_mine_gather: the clips.  samples: packed float32, signal n's samples at sample_offsets[n] .. sample_offsets[n + 1] - 1 (DEVICE
+ * int64 [N + 1]).  Clip i is n_samples samples of signal clip_signal[i] (int32 [n_clips]) from its sample clip_first[i] (int64,
+ * relative to the signal's start; it may be negative or run past the signal's end).  out float32 [n_clips][n_samples] (or NULL):
+ * bitwise the signal's samples, zeros outside the signal -- a neighbouring signal is never read; a clip_signal outside 0 .. N - 1
+ * gives a clip of zeros.  out_pcm int16 [n_clips][n_samples] (or NULL):  clamp(rint(x * 32768), -32768, 32767)  with ties to even and
+ * NaN -> 0, which inverts the int16 decode v / 32768 exactly.  16-byte stores (int16: 8-byte) at the row's aligned elements, fed by
+ * aligned 16-byte loads whatever clip_first; single elements at a row's unaligned ends and next to a signal's ends.  n_clips == 0: a
+ * successful no-op.
+ * Refused (TCR_ERR_ARG): out and out_pcm both NULL, N or n_samples <= 0, n_clips < 0, a null sample_offsets / samples / clip_signal /
+ * clip_first, more than 2^31 workgroups' worth of clips. */
+int tcr_mine_gather(int n_signals, const int64_t* sample_offsets /* DEVICE [N + 1] */, const float* samples, int64_t n_clips,
+                    const int32_t* clip_signal, const int64_t* clip_first, int n_samples, float* out /* or NULL */,
+                    int16_t* out_pcm /* or NULL */, void* stream);
+
 /* Sample-rate conversion: a rational-ratio polyphase FIR in front of the detectors (which take float32 at the model's rate).
  * in_rate -> out_rate, g = gcd: up = L = out_rate / g, down = M = in_rate / g; taps = P per phase (even, or 1); table float32
  * [up][taps], designed on the host (tcresnet_amd.resampling.design_table: windowed sinc, fc = rolloff / max(1, M / L), Kaiser

@@ -14,6 +14,8 @@ from typing import Optional
 HALO = 4
 MAX_BLOCKS = 16
 GRID_TILE = 256            # == TCR_GRID_TILE: steps per tile of tcr_detect_grid's smoothing kernel
+MINE_TILE = 256            # == TCR_MINE_TILE: steps per tile of tcr_mine_peaks
+MINE_RADIUS_MAX = 2560     # == TCR_MINE_RADIUS_MAX: the largest radius tcr_mine_peaks takes
 ABI_VERSION = 3            # == TCR_ABI_VERSION of include/tcresnet_hip.h these prototypes were written against
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_HERE, "lib", "libtcresnet_hip.so")
@@ -214,6 +216,13 @@ _PROTOTYPES = {
     "tcr_scan_steps_plan": (C.c_int, [C.POINTER(FrontendCfg), C.POINTER(ModelRef), C.c_int, _P, C.c_int, _P, C.c_int64, C.c_size_t, _P]),
     "tcr_scan_select_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "tcr_scan_select": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, _P, C.c_float, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, _P, _P]),
+    "tcr_mine_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "tcr_mine_detections": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, C.c_size_t, _P, _P, _P, _P, _P,
+                                      _P, _P, _P]),
+    "tcr_mine_peaks": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, _P, C.c_float, C.c_int, _P, _P, _P, _P, C.c_size_t, C.c_int64, _P, _P, _P,
+                                 _P, _P]),
+    "tcr_mine_select": (C.c_int, [C.c_int64, _P, _P, C.c_uint32, C.c_int64, _P, C.c_size_t, _P, _P, _P]),
+    "tcr_mine_gather": (C.c_int, [C.c_int, _P, _P, C.c_int64, _P, _P, C.c_int, _P, _P, _P]),
     "tcr_resample": (C.c_int, [C.POINTER(ResampleCfg), _P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64,
                                _P]),
     "tcr_resample_span": (C.c_int, [C.POINTER(ResampleCfg), C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -1,4 +1,5 @@
-"""What scan_audio.py, stream_audio.py and sweep_audio.py share: the WAV parser (`WavFile`, the package's only one), the files as the
+"""What scan_audio.py, stream_audio.py, sweep_audio.py and mine_audio.py share: the WAV parser (`WavFile`, the package's only one) and
+writer (`write_wav`), the files as the
 detector takes them (`Recordings`: whole steps at the model's rate, on its device, chunk by chunk or whole), the detection lines and
 the --summary line, and the flags the tools have in common."""
 from __future__ import annotations
@@ -49,6 +50,16 @@ class WavFile:
                 fh.seek(self.start + lo * 2 * self.channels)
                 out[lo - first:hi - first] = np.frombuffer(fh.read((hi - lo) * 2 * self.channels), dtype="<i2").reshape(-1, self.channels)[:, 0]
         return out
+
+
+def write_wav(path: str, pcm: np.ndarray, rate: int) -> None:
+    """int16 samples as a 16-bit mono PCM RIFF/WAVE file at `rate` Hz: what `WavFile` (and the dataset loader through it) reads back
+    sample for sample."""
+    data = np.ascontiguousarray(np.asarray(pcm).reshape(-1), dtype="<i2").tobytes()
+    with open(path, "wb") as fh:
+        fh.write(b"RIFF" + struct.pack("<I", 36 + len(data)) + b"WAVE")
+        fh.write(b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, int(rate), 2 * int(rate), 2, 16))
+        fh.write(b"data" + struct.pack("<I", len(data)) + data)
 
 
 class Recordings:

@@ -499,4 +499,5 @@ int launch_frontend_pk3_stream(int nc, const FrontendArgs& a, int n_items, hipSt
 #include "sweep.hip"
 #include "detect_grid.hip"
 #include "scan_select.hip"
+#include "mine.hip"
 #include "resample.hip"

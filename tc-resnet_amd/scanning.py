@@ -15,6 +15,10 @@ the cost of one scan and a pass over its top / score.
 `KeywordScanner.scan_steps` computes a chosen subset of a ragged scan's steps at the cost of that subset (tcr_scan_steps),
 `select_steps` picks the steps around a first model's flags (tcr_scan_select), and a `CascadeScanner` puts the two together: a cheap
 scanner looks at everything, an expensive one only where the cheap one flagged, and the detector runs on the merged posteriors.
+
+`KeywordScanner.mine` collects the audio a scan got wrong, for retraining: the windows that fired outside any event, the events never
+hit, the windows that came close (`mine_detections`, `mine_peaks`, `select_top`, `gather_clips` over raw tensors: tcr_mine_*), as
+`MinedClips` whose `to_pool()` is the int16 clip pool the training input stage takes.
 """
 from __future__ import annotations
 
@@ -262,6 +266,133 @@ class KeywordScanner(_Detection):
                              None if ragged else valid, step_s, self.lib)
         return GridResult(points, dropped, *res)
 
+
+    # ---- mining hard examples ---------------------------------------------------------------------------------------------
+    def _mine_workspace(self, n: int, ranked: bool) -> Optional[torch.Tensor]:
+        """The workspace of `mine`'s calls, kept between calls and replaced when one needs more."""
+        if n <= 0:
+            return None
+        ws = _mine_workspace("mine", self.lib, n, ranked, self.device, getattr(self, "_mine_ws", None))
+        self._mine_ws = ws
+        return ws
+
+    def mine(self, out, signals, events=None, k: int = 1000, source: str = "detections", kinds: Sequence[str] = ("false_accept",),
+              classes: Optional[Sequence[int]] = None, on: str = "probs", floor: float = 0.0, radius_ms: Optional[float] = None,
+              tolerance_ms: float = 1000.0, labels: Optional[Sequence[str]] = None, lead_ms: float = 0.0, pcm: bool = False) -> MinedClips:
+        """The audio `out` got wrong, for retraining.  out: a `ScanOutput` or `RaggedScanOutput` of this scanner (or a `redetect` /
+        cascade of it); signals: the audio it scanned, in the forms `scan` / `scan_ragged` take; events, tolerance_ms, labels: `sweep`'s
+        (the same conversion to step ranges).
+
+        source="detections": out's detections (is_new) classified by the sweep's rule (tcr_mine_detections); `kinds` chooses among
+        "false_accept", "hit" and "duplicate" (and `classes` among their labels; None: all), the k with the highest score are kept
+        (tcr_mine_select), and "miss" adds one clip per event no detection hit, ending at the event's last step before the tolerance.
+        source="peaks": the k highest local maxima of out's `on` ("probs" or "smoothed") over `classes` (None: every class from 2 on)
+        that reach `floor`, within radius_ms on both sides (None: the suppression time; at least one step), outside every step whose
+        window overlaps an event (tcr_mine_peaks): the near misses, whatever the threshold.
+
+        The clip of step i of a signal is  signal[(i + 1) * step_samples + lead - n_samples : (i + 1) * step_samples + lead]  with lead =
+        lead_ms in samples and zeros outside the signal (tcr_mine_gather): at lead_ms = 0 the window the network saw.  pcm: also as
+        int16.  Rows are in increasing (signal, step) order, the misses after the rest."""
+        step, sr, ncls, dev, lib = self.step_samples, self.frontend.cfg.sample_rate, self.net.num_classes, self.device, self.lib
+        n_samples = int(self.frontend.cfg.n_samples)
+        if source not in ("detections", "peaks"):
+            raise TcrError(f"mine: source must be 'detections' or 'peaks', got {source!r}")
+        kinds = [kinds] if isinstance(kinds, str) else list(kinds)
+        bad = [x for x in kinds if x not in MINE_KINDS[:4]]
+        if bad:
+            raise TcrError(f"mine: unknown kinds {bad} (known: {list(MINE_KINDS[:4])})")
+        if int(k) < 0:
+            raise TcrError(f"mine: k must be >= 0 (got {k})")
+        ragged, _, ev_steps = self._sweep_inputs(out, events, None, tolerance_ms, labels)
+        if ragged:
+            offsets = out.offsets
+            packed, lengths, _ = _ragged_signals("mine", "signal", signals)
+            flat = out
+        else:
+            N, steps = int(out.probs.shape[0]), int(out.probs.shape[1])
+            offsets = np.arange(N + 1, dtype=np.int64) * steps
+            if isinstance(signals, torch.Tensor) and signals.dim() == 2:
+                packed, lengths = signals.reshape(-1), np.full(int(signals.shape[0]), int(signals.shape[1]), np.int64)
+            else:
+                packed, lengths, _ = _ragged_signals("mine", "signal", signals)
+            flat = RaggedScanOutput(*(None if t is None else t.reshape(N * steps, *t.shape[2:]) for t in out), offsets)
+        N = len(offsets) - 1
+        if lengths.size != N or (lengths != np.diff(offsets) * step).any():
+            raise TcrError(f"mine: the signals' lengths {lengths.tolist()} are not the scan's ({(np.diff(offsets) * step).tolist()} samples)")
+        self.net._check_tensor(packed, "mine samples")
+        sample_off = np.zeros(N + 1, np.int64)
+        np.cumsum(lengths, out=sample_off[1:])
+        # the events in the order of their step ranges (`_sweep_inputs` sorts by start, then end): their times and the CSR's offsets
+        ev_ms, ev_off = [], np.zeros(N + 1, np.int64)
+        if events is not None:
+            for n, evs in enumerate(events):
+                se = np.array([(float(e[0]), float(e[1])) for e in evs], np.float64).reshape(-1, 2)
+                ev_ms.append(se[np.lexsort((se[:, 1], se[:, 0]))])
+                ev_off[n + 1] = ev_off[n] + len(evs)
+        ev_ms = np.concatenate(ev_ms) if ev_ms else np.zeros((0, 2), np.float64)
+        ev_sig = np.repeat(np.arange(N), np.diff(ev_off))
+        rows = {name: [] for name in ("pstep", "label", "value", "kind", "event")}
+
+        def add(pstep, label, value, kind, event):
+            for name, x in zip(rows, (pstep, label, value, kind, event)):
+                rows[name].append(np.asarray(x))
+
+        if source == "detections":
+            md = mine_detections(flat.top, flat.score, flat.is_new, offsets, ncls, ev_steps, lib, self._mine_workspace(int(offsets[-1]), False))
+            want = [MINE_KINDS.index(x) for x in kinds if x != "miss"]
+            kind = md.kind
+            if classes is not None and want:
+                keep = torch.from_numpy(_class_mask("mine", classes, ncls).astype(np.bool_)).to(dev)[md.label.long()]
+                kind = torch.where(keep, kind, torch.full_like(kind, 31))
+            if want and int(k) > 0:
+                picked = select_top(md.value, k, kind, want, lib, self._mine_workspace(int(md.value.numel()), True))
+                add(*(t[picked].cpu().numpy() for t in (md.step, md.label, md.value, md.kind, md.event)))
+            if "miss" in kinds and md.event_hit is not None:
+                missed = np.flatnonzero(md.event_hit.cpu().numpy() < 0)
+                if classes is not None:
+                    ev_label = np.concatenate([e[:, 2] for e in ev_steps]) if ev_steps else np.zeros(0, np.int64)
+                    missed = missed[_class_mask("mine", classes, ncls)[ev_label[missed]] != 0]
+                sig = ev_sig[missed]
+                last = np.minimum(_last_steps(ev_ms[missed, 1], step, sr), np.diff(offsets)[sig] - 1)
+                ok = last >= 0
+                ev_label = np.concatenate([e[:, 2] for e in ev_steps]) if ev_steps else np.zeros(0, np.int64)
+                add(offsets[sig[ok]] + last[ok], ev_label[missed[ok]], np.full(int(ok.sum()), np.nan, np.float32),
+                    np.full(int(ok.sum()), 3, np.uint8), missed[ok])
+        else:
+            if on not in ("probs", "smoothed"):
+                raise TcrError(f"mine: on must be 'probs' or 'smoothed', got {on!r}")
+            radius = max(1, self.suppression_steps if radius_ms is None else ms_to_steps(radius_ms, self.step_ms))
+            exclude = None
+            if events is not None:
+                clip_ms, exclude = 1000.0 * n_samples / sr, []
+                for n in range(N):
+                    se = ev_ms[ev_off[n]:ev_off[n + 1]]
+                    first, last = _first_steps(se[:, 0], step, sr), np.minimum(_last_steps(se[:, 1] + clip_ms, step, sr), int(offsets[n + 1] - offsets[n]) - 1)
+                    keep = last >= first
+                    order = np.argsort(first[keep], kind="stable")
+                    first, last = first[keep][order], last[keep][order]
+                    if first.size:                  # a range opens where it does not touch the ones before it
+                        reach = np.maximum.accumulate(last)
+                        opens = np.flatnonzero(np.concatenate([[True], first[1:] > reach[:-1] + 1]))
+                        first, last = first[opens], np.maximum.reduceat(last, opens)
+                    exclude.append(np.stack([first, last], axis=1))
+            cls = list(range(2, ncls)) if classes is None else [int(c) for c in classes]
+            mp = mine_peaks(getattr(flat, on), offsets, floor, radius, cls, exclude, None, lib, self._mine_workspace(int(offsets[-1]) * ncls, False))
+            if int(k) > 0 and mp.count > 0:
+                picked = select_top(mp.value, k, lib=lib, workspace=self._mine_workspace(int(mp.value.numel()), True))
+                m = int(picked.numel())
+                add(mp.step[picked].cpu().numpy(), mp.label[picked].cpu().numpy(), mp.value[picked].cpu().numpy(), np.full(m, 4, np.uint8),
+                    np.full(m, -1, np.int32))
+        cat = lambda name, dt: np.concatenate([x.astype(dt) for x in rows[name]]) if rows[name] else np.zeros(0, dt)
+        pstep, label, value = cat("pstep", np.int64), cat("label", np.int32), cat("value", np.float32)
+        kind, event = cat("kind", np.uint8), cat("event", np.int32)
+        signal = (np.searchsorted(offsets, pstep, side="right") - 1).astype(np.int32)
+        i = pstep - offsets[signal]
+        lead = int(round(float(lead_ms) * sr / 1000.0))
+        first = (i + 1) * step + lead - n_samples
+        clips, pcm16 = gather_clips(packed, sample_off, signal, first.astype(np.int64), n_samples, True, bool(pcm), lib)
+        start_ms = np.where(event >= 0, ev_ms[np.maximum(event, 0), 0] if len(ev_ms) else np.nan, np.nan) if len(event) else np.zeros(0)
+        return MinedClips(clips, pcm16, signal, i, _step_ms(i, step, sr), label, value, kind, event, np.asarray(start_ms, np.float64), lib, sr)
 
 # ---- detection sweeps ------------------------------------------------------------------------------------------------------------
 class SweepResult(NamedTuple):
@@ -675,3 +806,263 @@ class CascadeScanner:
         out = self.scan_ragged((samples.reshape(-1), [L] * N))
         steps = L // self.second.step_samples
         return ScanOutput(*(t.view(N, steps, *t.shape[1:]) for t in out.tensors()))
+
+
+# ---- mining hard examples --------------------------------------------------------------------------------------------------------
+MINE_KINDS = ("false_accept", "hit", "duplicate", "miss", "peak")      # `MinedClips.kind` codes; the first three are tcr_mine_detections'
+
+
+def _stream_of(dev):
+    return torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+
+
+def _mine_offsets(what: str, offsets, total: int) -> np.ndarray:
+    if isinstance(offsets, torch.Tensor):
+        if offsets.dtype != torch.int64:
+            raise TcrError(f"{what} expects int64 offsets, got {offsets.dtype}")
+        offsets = offsets.detach().cpu().numpy()
+    off = np.asarray(offsets)
+    if off.dtype != np.int64:
+        raise TcrError(f"{what} expects int64 offsets, got {off.dtype}")
+    off = np.ascontiguousarray(off.reshape(-1))
+    if off.size < 2 or off[0] != 0 or (np.diff(off) < 0).any() or int(off[-1]) != total:
+        raise TcrError(f"{what}: offsets must run from 0 to {total} without decreasing")
+    return off
+
+
+def _mine_workspace(what: str, lib, n: int, ranked: bool, dev, have: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 tensor of tcr_mine_workspace_bytes(n, ranked); `have` when that is one and large enough."""
+    nws = lib.tcr_mine_workspace_bytes(n, int(ranked))
+    if nws == 0:
+        raise TcrError(f"{what}: {lib.tcr_last_error().decode()}")
+    if have is not None and have.dtype == torch.int32 and have.device == dev and have.numel() * 4 >= nws:
+        return have
+    return torch.empty((nws + 3) // 4, dtype=torch.int32, device=dev)
+
+
+def _class_mask(what: str, classes, ncls: int) -> np.ndarray:
+    cls = np.asarray(list(classes), dtype=np.int64).reshape(-1)
+    if cls.size and (cls.min() < 0 or cls.max() >= ncls):
+        raise TcrError(f"{what}: classes outside 0..{ncls - 1}: {cls.tolist()}")
+    mask = np.zeros(max(ncls, 1), np.uint8)
+    mask[cls] = 1
+    return mask
+
+
+class MinedDetections(NamedTuple):
+    """tcr_mine_detections' tables, on the device, one row per candidate in increasing packed step: step int64, label int32, value
+    float32 (the score), kind uint8 (0 false accept, 1 hit, 2 duplicate), event int32 (the covering event's index in the signals'
+    sorted events one after the other, -1: none); event_hit int64 [events] (the packed step that hit the event, -1: a miss; None
+    without events)."""
+    step: torch.Tensor
+    label: torch.Tensor
+    value: torch.Tensor
+    kind: torch.Tensor
+    event: torch.Tensor
+    event_hit: Optional[torch.Tensor]
+
+
+def mine_detections(top: torch.Tensor, score: torch.Tensor, is_new: torch.Tensor, offsets, num_classes: int,
+                    events: Optional[Sequence[Sequence[Tuple[int, int, int]]]] = None, lib=None,
+                    workspace: Optional[torch.Tensor] = None) -> MinedDetections:
+    """The raw form of tcr_mine_detections: the detections of packed top / score / is_new [total_steps] (a ragged scan's or a
+    redetect's; offsets host int64 [N + 1] in steps) classified against events (`detection_sweep`'s: per signal inclusive step ranges
+    (first, last, label), disjoint).  The rule is the sweep's; see `MinedDetections`.  Reads one integer back (the number of
+    candidates), so the call waits for the device."""
+    if lib is None:
+        lib = _lib.get()
+    if top.dim() != 1 or score.shape != top.shape or is_new.shape != top.shape:
+        raise TcrError(f"mine_detections expects packed top, score and is_new [total_steps], got {tuple(top.shape)}, {tuple(score.shape)} "
+                       f"and {tuple(is_new.shape)}")
+    if top.dtype != torch.int32 or is_new.dtype != torch.int32 or score.dtype != torch.float32 or \
+            not (top.is_contiguous() and score.is_contiguous() and is_new.is_contiguous()):
+        raise TcrError("mine_detections expects contiguous int32 top, float32 score and int32 is_new")
+    total, ncls, dev = int(top.shape[0]), int(num_classes), top.device
+    soff = _mine_offsets("mine_detections", offsets, total)
+    N = int(soff.size) - 1
+    _, ev_args, keep = _pack_events(events, N, ncls, dev)
+    n_events = int(keep[0][-1].item()) if keep else 0
+    i64 = dict(dtype=torch.int64, device=dev)
+    step, label = torch.empty(total, **i64), torch.empty(total, dtype=torch.int32, device=dev)
+    value, kind = torch.empty(total, dtype=torch.float32, device=dev), torch.empty(total, dtype=torch.uint8, device=dev)
+    event, count = torch.empty(total, dtype=torch.int32, device=dev), torch.zeros(1, **i64)
+    hit = torch.empty(max(n_events, 1), **i64) if keep else None
+    n = 0
+    if total > 0:
+        ws = _mine_workspace("mine_detections", lib, total, False, dev, workspace)
+        off_dev = torch.from_numpy(soff).to(dev)
+        lib.check(lib.tcr_mine_detections(N, off_dev.data_ptr(), total, ncls, top.data_ptr(), score.data_ptr(), is_new.data_ptr(), *ev_args,
+                                          n_events, ws.data_ptr(), ws.numel() * 4, step.data_ptr(), label.data_ptr(), value.data_ptr(),
+                                          kind.data_ptr(), event.data_ptr(), count.data_ptr(), None if hit is None else hit.data_ptr(),
+                                          _stream_of(dev)), "tcr_mine_detections")
+        n = int(count.item())
+    elif hit is not None:
+        hit.fill_(-1)
+    return MinedDetections(step[:n], label[:n], value[:n], kind[:n], event[:n], None if hit is None else hit[:n_events])
+
+
+class MinedPeaks(NamedTuple):
+    """tcr_mine_peaks' tables, on the device, in (packed step, class) order: step int64, label int32, value float32 -- the first
+    `capacity` candidates; count: how many there are in all."""
+    step: torch.Tensor
+    label: torch.Tensor
+    value: torch.Tensor
+    count: int
+
+
+def mine_peaks(values: torch.Tensor, offsets, floor: float, radius: int, classes: Sequence[int],
+               exclude: Optional[Sequence[Sequence[Tuple[int, int]]]] = None, capacity: Optional[int] = None, lib=None,
+               workspace: Optional[torch.Tensor] = None) -> MinedPeaks:
+    """The raw form of tcr_mine_peaks: the local maxima of values [total_steps, C] (float32 on the device: a ragged scan's probs or
+    smoothed; offsets host int64 [N + 1] in steps) over the classes `classes`: values[p, c] >= floor, above every value of its class
+    in the `radius` steps of its signal before it, at or above those in the `radius` steps after it (NaNs ignored), outside `exclude`
+    (per signal, inclusive step ranges (first, last), sorted and disjoint).  capacity: the rows stored (None: all of them; a second
+    call only when there are more than 2^24).  Reads the count back, so the call waits for the device."""
+    if lib is None:
+        lib = _lib.get()
+    if values.dim() != 2 or values.dtype != torch.float32 or not values.is_contiguous():
+        raise TcrError(f"mine_peaks expects contiguous float32 values [total_steps, classes], got {values.dtype} {tuple(values.shape)}")
+    total, ncls, dev = int(values.shape[0]), int(values.shape[1]), values.device
+    soff = _mine_offsets("mine_peaks", offsets, total)
+    N = int(soff.size) - 1
+    cmask = _class_mask("mine_peaks", classes, ncls)
+    ex_args, keep = [None, None, None], []
+    if exclude is not None:
+        if len(exclude) != N:
+            raise TcrError(f"mine_peaks: exclusion ranges for {len(exclude)} signals, the scan has {N}")
+        off, rows = np.zeros(N + 1, np.int32), []
+        for n, ranges in enumerate(exclude):
+            a = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+            if (a[:, 1] < a[:, 0]).any() or (a[1:, 0] <= a[:-1, 1]).any():
+                raise TcrError(f"mine_peaks: signal {n}: the exclusion ranges are not sorted and disjoint: {a.tolist()}")
+            rows.append(a)
+            off[n + 1] = off[n] + len(a)
+        a = np.concatenate(rows + [np.zeros((1, 2), np.int64)])
+        keep = [torch.from_numpy(x).to(dev) for x in (off, np.ascontiguousarray(a[:, 0]), np.ascontiguousarray(a[:, 1]))]
+        ex_args = [t.data_ptr() for t in keep]
+    empty = MinedPeaks(torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                       torch.empty(0, dtype=torch.float32, device=dev), 0)
+    if total == 0:
+        return empty
+    ws = _mine_workspace("mine_peaks", lib, total * ncls, False, dev, workspace)
+    off_dev, cmask_dev = torch.from_numpy(soff).to(dev), torch.from_numpy(cmask).to(dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    # (two peaks of a class and signal are more than `radius` steps apart: the first try holds them all unless that is past 2^24 rows)
+    bound = (total // (max(int(radius), 1) + 1) + N) * max(int(cmask.sum()), 1)
+    cap = min(total * ncls, bound, 1 << 24) if capacity is None else int(capacity)
+    while True:
+        room = max(cap, 1)
+        step, label = torch.empty(room, dtype=torch.int64, device=dev), torch.empty(room, dtype=torch.int32, device=dev)
+        value = torch.empty(room, dtype=torch.float32, device=dev)
+        lib.check(lib.tcr_mine_peaks(N, off_dev.data_ptr(), total, ncls, values.data_ptr(), cmask_dev.data_ptr(), float(floor), int(radius),
+                                     *ex_args, ws.data_ptr(), ws.numel() * 4, cap, step.data_ptr(), label.data_ptr(), value.data_ptr(),
+                                     count.data_ptr(), _stream_of(dev)), "tcr_mine_peaks")
+        n = int(count.item())
+        if capacity is not None or n <= cap:
+            break
+        cap = n
+    m = min(n, cap)
+    return MinedPeaks(step[:m], label[:m], value[:m], n)
+
+
+def select_top(value: torch.Tensor, k: int, kind: Optional[torch.Tensor] = None, kinds: Sequence[int] = (), lib=None,
+               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The raw form of tcr_mine_select: the indices (int64 on the device, increasing) of the k best of value [n] (float32 on the
+    device): the larger value first, -0 equal to +0, then the lower index.  kind (uint8 [n]) with kinds: only candidates whose kind
+    is one of `kinds` are eligible.  Exact, no sort.  Reads the number picked back, so the call waits for the device."""
+    if lib is None:
+        lib = _lib.get()
+    if value.dim() != 1 or value.dtype != torch.float32 or not value.is_contiguous():
+        raise TcrError(f"select_top expects contiguous float32 values [n], got {value.dtype} {tuple(value.shape)}")
+    n, dev = int(value.shape[0]), value.device
+    mask = 0
+    if kind is not None:
+        if kind.dtype != torch.uint8 or tuple(kind.shape) != (n,) or not kind.is_contiguous():
+            raise TcrError(f"select_top expects contiguous uint8 kinds [{n}], got {kind.dtype} {tuple(kind.shape)}")
+        for c in kinds:
+            if not 0 <= int(c) < 32:
+                raise TcrError(f"select_top: kind {c} outside 0..31")
+            mask |= 1 << int(c)
+    k = int(k)
+    room = max(min(k, n), 1)
+    picked, count = torch.empty(room, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
+    ws = _mine_workspace("select_top", lib, n, True, dev, workspace) if n > 0 and k > 0 else None
+    lib.check(lib.tcr_mine_select(n, value.data_ptr(), None if kind is None else kind.data_ptr(), mask, k,
+                                  None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4, picked.data_ptr(),
+                                  count.data_ptr(), _stream_of(dev)), "tcr_mine_select")
+    return picked[:int(count.item())]
+
+
+def _index_arg(what: str, name: str, x, dtype, dev) -> torch.Tensor:
+    want = {torch.int32: np.int32, torch.int64: np.int64}[dtype]
+    if isinstance(x, torch.Tensor):
+        if x.dtype != dtype:
+            raise TcrError(f"{what} expects {str(dtype).split('.')[-1]} {name}, got {str(x.dtype).split('.')[-1]}")
+        return x.to(dev).contiguous().reshape(-1)
+    a = np.asarray(x)
+    if a.dtype != want:
+        raise TcrError(f"{what} expects {np.dtype(want).name} {name}, got {a.dtype}")
+    return torch.from_numpy(np.ascontiguousarray(a.reshape(-1))).to(dev)
+
+
+def gather_clips(samples: torch.Tensor, sample_offsets, clip_signal, clip_first, n_samples: int, floats: bool = True, pcm: bool = False,
+                 lib=None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """The raw form of tcr_mine_gather: clip i = n_samples samples of signal clip_signal[i] (int32) from its sample clip_first[i]
+    (int64, relative to the signal's start; negative or past the end: zeros there) of the packed float32 `samples` (sample_offsets:
+    int64 [N + 1]).  Returns (float32 [n, n_samples] bitwise the samples or None, int16 [n, n_samples] or None) on the device; the
+    int16 rows are clamp(rint(x * 32768), -32768, 32767), which inverts the int16 decode."""
+    if lib is None:
+        lib = _lib.get()
+    if samples.dim() != 1 or samples.dtype != torch.float32 or not samples.is_contiguous():
+        raise TcrError(f"gather_clips expects contiguous packed float32 samples, got {samples.dtype} {tuple(samples.shape)}")
+    dev = samples.device
+    soff = _mine_offsets("gather_clips", sample_offsets, int(samples.shape[0]))
+    sig, first = _index_arg("gather_clips", "clip_signal", clip_signal, torch.int32, dev), \
+        _index_arg("gather_clips", "clip_first", clip_first, torch.int64, dev)
+    n = int(sig.shape[0])
+    if int(first.shape[0]) != n:
+        raise TcrError(f"gather_clips: {n} clip_signal for {int(first.shape[0])} clip_first")
+    m = int(n_samples)
+    out = torch.empty((n, max(m, 0)), dtype=torch.float32, device=dev) if floats else None
+    out_pcm = torch.empty((n, max(m, 0)), dtype=torch.int16, device=dev) if pcm else None
+    if n == 0:                  # (nothing to launch; an empty tensor has no address to pass)
+        return out, out_pcm
+    off_dev = torch.from_numpy(soff).to(dev)
+    lib.check(lib.tcr_mine_gather(int(soff.size) - 1, off_dev.data_ptr(), samples.data_ptr(), n, sig.data_ptr(), first.data_ptr(), m,
+                                  None if out is None else out.data_ptr(), None if out_pcm is None else out_pcm.data_ptr(),
+                                  _stream_of(dev)), "tcr_mine_gather")
+    return out, out_pcm
+
+
+class MinedClips:
+    """What `KeywordScanner.mine` returns.  clips float32 [n, n_samples] on the device (bitwise the signals' samples, zeros outside
+    them), pcm int16 [n, n_samples] on the device or None; host arrays, one entry per clip: signal, step (within the signal), time_ms
+    (the end of the step's window, `sweep`'s stamp), label (the detection's or peak's class; a miss: the event's), value (the score
+    or peak value; NaN for a miss), kind (an index into `MINE_KINDS`), event (the index of the covering / missed event among the
+    signals' events sorted by start, one signal after the other; -1: none) and event_start_ms (NaN: none)."""
+
+    def __init__(self, clips, pcm, signal, step, time_ms, label, value, kind, event, event_start_ms, lib, sample_rate: int):
+        self.clips, self.pcm = clips, pcm
+        self.signal, self.step, self.time_ms, self.label, self.value = signal, step, time_ms, label, value
+        self.kind, self.event, self.event_start_ms = kind, event, event_start_ms
+        self.lib, self.sample_rate = lib, sample_rate
+
+    def __len__(self) -> int:
+        return int(self.signal.size)
+
+    def kind_names(self) -> Sequence[str]:
+        return [MINE_KINDS[k] for k in self.kind]
+
+    def to_pool(self, device=None):
+        """The clips as the training input stage's int16 pool (`datasets.augmentation_factory.PcmPool`: one device tensor and
+        offsets), without a trip through the host; needs `mine(..., pcm=True)`."""
+        from .datasets.augmentation_factory import PcmPool
+        if self.pcm is None:
+            raise TcrError("MinedClips.to_pool: the clips were mined without pcm=True")
+        n, m = int(self.pcm.shape[0]), int(self.pcm.shape[1])
+        pool = PcmPool.__new__(PcmPool)
+        pool.lib, pool.device = self.lib, self.pcm.device if device is None else torch.device(device)
+        pool.lengths = np.full(n, m, np.int64)
+        pool.offsets = np.arange(n, dtype=np.int64) * m
+        pool.data = self.pcm.reshape(-1).to(pool.device) if n else torch.zeros(1, dtype=torch.int16, device=pool.device)
+        return pool
