@@ -8,6 +8,8 @@ FusedBatchNorm with biased batch variance and Bessel-corrected moving variance, 
   * Res8 / Res15 (/Narrow)      audio_nets/res.py:6-123
   * KWSModel architectures       audio_nets/kws.py:65-757 (all but low_latency_svdf)
 
+  * graph_forward                any graph given node by node, from the same pieces (tests/test_g2d_configs.py)
+
 written directly from those files (F.conv2d / F.batch_norm / F.max_pool2d / autograd), independently of the product's graph builders.
 Tensors are NCHW; weights keep the TF HWIO layout under the TF variable names.
 """
@@ -51,6 +53,24 @@ def _relu(x):
     return F.relu(x)
 
 
+class follow_kinks:
+    """`with follow_kinks(kept) as log:` -- the forwards of the block count ReLU inputs within tau of zero and take the side `kept`
+    gives for exactly those (see KINK_LOG); on leaving, every entry of `kept` must have been consumed."""
+
+    def __init__(self, kept):
+        self.kept = kept
+
+    def __enter__(self):
+        KINK_LOG.update(on=True, near=0, total=0, decide=self.kept, idx=0, followed=0)
+        return KINK_LOG
+
+    def __exit__(self, *exc):
+        KINK_LOG.update(on=False, decide=None)
+        if exc[0] is None and self.kept is not None and KINK_LOG["idx"] != len(self.kept):
+            raise ValueError(f"the oracle ran {KINK_LOG['idx']} ReLUs, the graph has {len(self.kept)}")
+        return False
+
+
 def _same_pads(length: int, k_eff: int, stride: int):
     out = -(-length // stride)
     total = max((out - 1) * stride + k_eff - length, 0)
@@ -84,6 +104,17 @@ def max_pool(x, kernel, stride, padding):
         pl, pr = _same_pads(x.shape[3], kernel[1], stride[1])
         x = F.pad(x, (pl, pr, pt, pb), value=float("-inf"))
     return F.max_pool2d(x, kernel, stride)
+
+
+def avg_pool(x, kernel, stride, padding):
+    """tf.nn.avg_pool: a SAME window is clipped to the plane and divides by the number of IN-PLANE elements -- the sum over the
+    zero-padded plane over the same sum of a plane of ones (not torch's count_include_pad, which pads symmetrically)."""
+    if padding != "SAME":
+        return F.avg_pool2d(x, kernel, stride)
+    pt, pb = _same_pads(x.shape[2], kernel[0], stride[0])
+    pl, pr = _same_pads(x.shape[3], kernel[1], stride[1])
+    pool = lambda v: F.avg_pool2d(F.pad(v, (pl, pr, pt, pb)), kernel, stride, divisor_override=1)
+    return pool(x) / pool(torch.ones((1, 1) + tuple(x.shape[2:]), dtype=x.dtype))
 
 
 class _Masks:
@@ -231,12 +262,66 @@ def kws_forward(params, x, architecture, is_training=False, masks=None):
     return {"logits": logits, "probs": F.softmax(logits, dim=-1), "new_stats": {}}
 
 
+# ---- a graph given node by node (what engine.Graph2D's builder calls describe) ------------------------------------------------------
+def graph_forward(spec, params, stats, x, is_training=False, masks=None):
+    """x [N, H, W] (one input channel) through `spec` = {"nodes": [node, ...], "logits": id}; a node is a dict with "op" and its inputs as
+    ids into the list (-1: the network input):
+      conv      in, k (kh, kw), cout, stride, rate, pad "SAME" | "VALID", relu, w, b (variable names; b None: no bias)
+      bn        in, prefix, center, scale, relu, decay, eps
+      pool      in, kind "max" | "avg", k (None: the whole plane), stride, pad
+      add       a, b, relu
+      dropout   in, keep
+      tfilt     in, w              one filter of the plane's length per channel -> [C, 1, 1] (the SVDF time filters, kws.py:604-612)
+      gsum      in, group, relu, b sum of `group` consecutive channels of a 1 x 1 node + bias (the SVDF rank sum, kws.py:613-628)
+    Returns what res_forward returns.  ReLUs go through _relu in node order, dropout masks are taken in node order."""
+    new_stats = dict(stats)
+    drop = _Masks(masks)
+    x4 = x.unsqueeze(1)
+    outs = []
+    val = lambda i: x4 if i < 0 else outs[i]
+    for n in spec["nodes"]:
+        op = n["op"]
+        if op == "conv":
+            y = conv2d(val(n["in"]), params[n["w"]], tuple(n["stride"]), tuple(n["rate"]), n["pad"], params[n["b"]] if n.get("b") else None)
+        elif op == "bn":
+            y = batch_norm(val(n["in"]), n["prefix"], params, stats, new_stats, is_training, n.get("decay", 0.997), n.get("eps", 0.001),
+                           n["center"], n["scale"])
+        elif op == "pool":
+            h = val(n["in"])
+            k = tuple(n["k"]) if n.get("k") else tuple(h.shape[2:])
+            stride, pad = (tuple(n["stride"]), n["pad"]) if n.get("k") else ((1, 1), "VALID")
+            y = max_pool(h, k, stride, pad) if n["kind"] == "max" else avg_pool(h, k, stride, pad)
+        elif op == "add":
+            y = val(n["a"]) + val(n["b"])
+        elif op == "dropout":
+            y = drop.apply(val(n["in"]), n["keep"], is_training)
+        elif op == "tfilt":
+            h = val(n["in"])
+            act = h.flatten(2).permute(1, 0, 2)                                    # [filters, B, T], as kws_forward's SVDF branch has it
+            y = torch.einsum("kbt,kt->kb", act, params[n["w"]].reshape(act.shape[0], -1)).t()[:, :, None, None]
+        elif op == "gsum":
+            h = val(n["in"])
+            out = h.flatten(1).t()                                                 # [units * rank, B]
+            y = out.reshape(-1, n["group"], h.shape[0]).sum(dim=1).t()             # [B, units]
+            if n.get("b"):
+                y = y + params[n["b"]]
+            y = y[:, :, None, None]
+        else:
+            raise ValueError(op)
+        outs.append(_relu(y) if n.get("relu") else y)
+    logits = outs[spec["logits"]].flatten(1)
+    return {"logits": logits, "probs": F.softmax(logits, dim=-1), "new_stats": new_stats}
+
+
 # ---- loss / gradients ------------------------------------------------------------------------------------------------------
-def loss_and_grads(forward_fn, params_np: Dict[str, np.ndarray], labels_np: np.ndarray, weight_decay: float = 0.0):
-    """(out, model_loss, total_loss, grads of the MODEL loss) through autograd.  forward_fn(params as float64 tensors) -> dict."""
+def loss_and_grads(forward_fn, params_np: Dict[str, np.ndarray], labels_np: np.ndarray, weight_decay: float = 0.0, label_smoothing: float = 0.0):
+    """(out, model_loss, total_loss, grads of the MODEL loss) through autograd.  forward_fn(params as float64 tensors) -> dict.
+    label_smoothing: tf.losses.softmax_cross_entropy's rule, y * (1 - s) + s / num_classes."""
     params = {k: torch.tensor(np.asarray(v), dtype=DT, requires_grad=True) for k, v in params_np.items()}
     out = forward_fn(params)
     y = torch.tensor(labels_np, dtype=DT)
+    if label_smoothing > 0.0:
+        y = y * (1.0 - label_smoothing) + label_smoothing / y.shape[-1]
     model = torch.mean(-(y * F.log_softmax(out["logits"], dim=-1)).sum(dim=-1))          # factory/audio_nets.py:168-173
     l2 = weight_decay * sum(0.5 * (v ** 2).sum() for k, v in params.items() if R.is_l2_param(k))    # :175-180
     model.backward()
