@@ -9,12 +9,14 @@
 //     in the registers and without selects: lanes 8..15 of a unit run pass one on (-1)^n x[n] (the sign lives in their window
 //     table), so their register j holds bin j ^ 8 (shift theorem) and "registers 0..7" are the diagonal blocks of the transpose for
 //     every lane; what they receive sits in register n ^ 8, i.e. pass two sees its input rotated by 8 and its odd outputs negated
-//     -- put right by eight packed multiplies with a per-lane +-1;
+//     -- put right by eight packed multiplies with a per-lane +-1 (nfft 512), or by the same +-1 riding on the even / odd
+//     recombination's operands (nfft 1024: no instruction of its own);
 //   * the power spectrum reuses the tile's space, the item sums are compact, the log-mel block is [mel][16 frames] per wave with an
 //     XOR swizzle (conflict-free for the log phase's column writes and the DCT's B-fragment reads without padding);
 //   * the next round's samples are requested AFTER the real-FFT split (the FFT registers are dead by then), the DCT's A fragments
 //     are fetched per chunk (L1 / L2 hits) instead of living in 48 registers.
-// Results are bitwise those of frontend_pk.hip (same operations in the same order on every value).
+// Results are bitwise those of frontend_pk.hip (same operations in the same order on every value; the first pass leaves out its adds of
+// the FFT's zero padding, pk3_window_dft4 below, which moves the sign of zeros in front of the squares at most).
 #include "frontend_plan.h"
 #include "frontend_args.h"
 
@@ -43,13 +45,12 @@ __device__ __forceinline__ void pk3_dft4(v2& a, v2& b, v2& c, v2& d) {
     d = c_addmi(t1, t3);
 }
 
-// 16-point forward DFT in registers, natural order in and out (4 x 4 Cooley-Tukey) -- the operation order of frontend_pk.hip's.
-__device__ __forceinline__ void pk3_dft16(v2 (&v)[16]) {
+// 16-point forward DFT in registers, natural order in and out (4 x 4 Cooley-Tukey) -- the operation order of frontend_pk.hip's:
+// the four 4-point DFTs over n0 (pk3_dft16 below, or pk3_window_dft4 for the windowed first pass), then this.
+__device__ __forceinline__ void pk3_dft16_tail(v2 (&v)[16]) {
     constexpr float C1 = 0.92387953251128673848f;   // cos(pi/8)
     constexpr float S1 = 0.38268343236508978178f;   // sin(pi/8)
     constexpr float R2 = 0.70710678118654752440f;   // sqrt(1/2)
-#pragma unroll
-    for (int n0 = 0; n0 < 4; ++n0) pk3_dft4(v[n0], v[n0 + 4], v[n0 + 8], v[n0 + 12]);
     v[1 + 4] = c_mulk(v[1 + 4], (v2){C1, -S1});         // W^1
     v[1 + 8] = c_mulk(v[1 + 8], (v2){R2, -R2});         // W^2
     v[1 + 12] = c_mulk(v[1 + 12], (v2){S1, -C1});       // W^3
@@ -69,6 +70,50 @@ __device__ __forceinline__ void pk3_dft16(v2 (&v)[16]) {
             v[4 * i + j] = v[4 * j + i];
             v[4 * j + i] = t;
         }
+}
+
+__device__ __forceinline__ void pk3_dft16(v2 (&v)[16]) {
+#pragma unroll
+    for (int n0 = 0; n0 < 4; ++n0) pk3_dft4(v[n0], v[n0 + 4], v[n0 + 8], v[n0 + 12]);
+    pk3_dft16_tail(v);
+}
+
+// The window multiply and the four 4-point DFTs of the FIRST radix-16 pass, for QV live inputs (x[q] w[q], q < QV; inputs QV .. 15
+// are the zero padding of the FFT and are neither formed nor added).
+// Which products fuse into the butterflies' first adds decides the bits, so it is spelled out and not left to the optimiser (whose
+// choice moved when the adds around it changed): with t0 = a + c, t1 = a - c (t2, t3 from b, d likewise) the product of the FIRST
+// operand (a = input n0, b = input n0 + 4) rides in the add as one fused multiply-add, the second operand's is rounded on its own.
+// `fp contract(on)` forms exactly the fused multiply-adds that are written as one expression, and none across statements (the host
+// emulator's target has no fused multiply-add, there the same expressions stay a multiply and an add, as they always were).
+// A padded second operand: a + 0 and a - 0 are a, for every a but -0 (which a + 0 would turn into +0).  A zero's sign cannot reach an
+// output: add, multiply and fused multiply-add of values that differ only in the sign of a zero differ at most in the sign of a zero,
+// and the spectrum is squared (x x + y y is +0 for every zero x, y) before anything else reads it.
+template <int QV>
+__device__ __forceinline__ void pk3_window_dft4(const v2 (&x)[QV], const v2 (&w)[QV], v2 (&v)[16]) {
+#pragma clang fp contract(on)
+    static_assert(QV >= 8 && QV <= 16, "inputs n0 and n0 + 4 of every 4-point DFT are live");
+#pragma unroll
+    for (int n0 = 0; n0 < 4; ++n0) {
+        v2 t0, t1, t2, t3;
+        if (n0 + 8 < QV) {
+            const v2 c = x[n0 + 8] * w[n0 + 8];
+            t0 = x[n0] * w[n0] + c;
+            t1 = x[n0] * w[n0] - c;
+        } else {
+            t0 = t1 = x[n0] * w[n0];
+        }
+        if (n0 + 12 < QV) {
+            const v2 d = x[n0 + 12] * w[n0 + 12];
+            t2 = x[n0 + 4] * w[n0 + 4] + d;
+            t3 = x[n0 + 4] * w[n0 + 4] - d;
+        } else {
+            t2 = t3 = x[n0 + 4] * w[n0 + 4];
+        }
+        v[n0] = t0 + t2;
+        v[n0 + 8] = t0 - t2;
+        v[n0 + 4] = c_submi(t1, t3);
+        v[n0 + 12] = c_addmi(t1, t3);
+    }
 }
 
 __device__ __forceinline__ void pk3_real_pair_power(v2 zk, v2 zn, v2 wmi, float& p_lo, float& p_hi) {
@@ -137,15 +182,18 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
     const v2* tw256 = reinterpret_cast<const v2*>(a.tw256);
     const v2* tw_real = reinterpret_cast<const v2*>(a.tw_real);
     const v2* tw_combine = reinterpret_cast<const v2*>(a.tw_combine);
-    // round-invariant per-lane tables that stay in registers: the real-FFT split's and the even / odd recombination's twiddles.  The
-    // window (20 registers) and the inter-pass twiddles (32) are re-read every round from L1 -- the vector-memory path is otherwise
-    // idle (ten sample loads per round), the LDS pipe is not -- so that 3 waves per SIMD (<= 168 registers) hold without scratch.
+    // round-invariant per-lane tables that stay in registers (64): the inter-pass twiddles (32), the real-FFT split's and the even /
+    // odd recombination's (16 + 16).  The window (20 - 32 registers) does not: it is read from its LDS copy (s_wnd) every round, held
+    // for the length of the window multiply, so that 3 waves per SIMD (<= 168 registers) hold without scratch.
     v2 tw[16], twr[8], twc[8];
     float sgn;
     int item_d[kItemsLds ? 1 : TRIPS], band_i[kBandsLds ? 1 : NMEL / LPF];
     {
         const int lf = tid % LPF, l = tid & 15, h = l >> 3;
-        sgn = h ? -1.f : 1.f;
+        // the (-1)^h of the second pass's odd outputs.  nfft 1024: every odd output goes through the row swap into a lane of the frame's
+        // second unit (same l, so same h) -- as its own odd register, or as the first unit's that it receives -- and the lanes of the
+        // first unit keep and receive even registers only: the sign is applied there, behind the swap (s_fold below)
+        sgn = h && (SUB == 1 || lf >= 16) ? -1.f : 1.f;
 #pragma unroll
         for (int j = 0; j < 16; ++j) tw[j] = tw256[l * 16 + (j ^ (8 * h))];    // lanes 8..15: register j holds bin j ^ 8 after the first pass
 #pragma unroll
@@ -153,7 +201,7 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
             const int k = lf + LPF * i;
             const v2 w = tw_real[k];
             twr[i] = (v2){w.y, -w.x};           // -i W^k
-            twc[i] = (SUB == 2) ? tw_combine[k] : (v2){1.f, 0.f};
+            twc[i] = (SUB == 2) ? tw_combine[k] * sgn : (v2){1.f, 0.f};
         }
         if (!kItemsLds) {
 #pragma unroll
@@ -219,10 +267,9 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
             v2 wnd[QV];
 #pragma unroll
             for (int q = 0; q < QV; ++q) wnd[q] = lds_read_unpaired(wsrc + q * LPF);     // (ds_read_b64 each)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) v[q] = q < QV ? xa[q] * wnd[q] : (v2){0.f, 0.f};
+            pk3_window_dft4<QV>(xa, wnd, v);
         }
-        pk3_dft16(v);                                           // register j: bin j ^ 8h of this lane's 16 samples
+        pk3_dft16_tail(v);                                      // register j: bin j ^ 8h of this lane's 16 samples
 #pragma unroll
         for (int j = 0; j < 16; ++j) v[j] = c_mul(v[j], tw[j]);
         // ---------------- transpose through half a tile, two passes (diagonal blocks, then off-diagonal blocks) ----------------
@@ -244,8 +291,8 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
         }
         // ---------------- second radix-16 pass: register n holds input n ^ 8h -> odd outputs carry (-1)^h ----------------
         pk3_dft16(v);
-        {
-            const v2 s2 = (v2){sgn, sgn};
+        const v2 s2 = (v2){sgn, sgn};
+        if (SUB == 1) {
 #pragma unroll
             for (int k1 = 1; k1 < 16; k1 += 2) v[k1] = v[k1] * s2;
         }
@@ -260,26 +307,39 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
                     float ex = v[2 * i].x, ey = v[2 * i].y, ox = v[2 * i + 1].x, oy = v[2 * i + 1].y;
                     row_swap(ex, ox, lane);
                     row_swap(ey, oy, lane);
-                    const v2 t = c_mul((v2){ox, oy}, twc[i]);
+                    // s_fold: with s = this lane's sign, Z = s e +- (s o) w.  The sign rides on the operations that read e and o instead of
+                    // eight multiplies in front of them: o (s w) negates the same inputs of the same multiply / fused multiply-adds as
+                    // (s o) w, and fma(e, s, +-t) rounds s e +- t once, s e being exact -- the same value, zeros' signs included.
+                    const v2 t = c_mul((v2){ox, oy}, twc[i]);   // (twc carries s)
                     const v2 e = (v2){ex, ey};
-                    v[2 * i] = e + t;                       // Z[k_i]
-                    v[2 * i + 1] = e - t;                   // Z[k_i + 256]
+                    v[2 * i] = __builtin_elementwise_fma(e, s2, t);         // Z[k_i]
+                    v[2 * i + 1] = __builtin_elementwise_fma(e, s2, -t);    // Z[k_i + 256]
                 }
             }
+            // Bins k_i = lf + LPF i and NC - k_i of a lane are LPF floats apart from one i to the next: two bins of the lower half, then
+            // two of the upper half, go out next to each other, so that each pair is ONE two-address store (ds_write2_b32: one address
+            // register and one issue for two dwords) -- the lower / upper stores of one i alternate bases the compiler cannot tell apart.
+            float* Plo = P + lf;                            // bin lf + LPF i at + LPF i
+            float* Phi = P + (NC - LPF * 7 - lf);           // bin NC - lf - LPF i at + LPF (7 - i)
             v2 prev = v[0];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int k = lf + LPF * i;                 // 0 .. NC/2-1
-                const v2 zk = SUB == 2 ? v[2 * i] : v[i];
-                const v2 src = SUB == 2 ? v[15 - 2 * i] : v[15 - i];
-                const v2 g = (v2){lane_gather(src.x, partner), lane_gather(src.y, partner)};
-                const v2 zn = lf == 0 ? prev : g;
-                prev = g;
-                float plo, phi;
-                pk3_real_pair_power(zk, zn, twr[i], plo, phi);
-                if (MAG) { plo = sqrtf(plo); phi = sqrtf(phi); }
-                P[k] = plo;
-                P[NC - k] = phi;
+            for (int i2 = 0; i2 < 8; i2 += 2) {
+                float plo[2], phi[2];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int i = i2 + j;                   // bin k = lf + LPF i: 0 .. NC/2-1
+                    const v2 zk = SUB == 2 ? v[2 * i] : v[i];
+                    const v2 src = SUB == 2 ? v[15 - 2 * i] : v[15 - i];
+                    const v2 g = (v2){lane_gather(src.x, partner), lane_gather(src.y, partner)};
+                    const v2 zn = lf == 0 ? prev : g;
+                    prev = g;
+                    pk3_real_pair_power(zk, zn, twr[i], plo[j], phi[j]);
+                    if (MAG) { plo[j] = sqrtf(plo[j]); phi[j] = sqrtf(phi[j]); }
+                }
+                Plo[LPF * i2] = plo[0];
+                Plo[LPF * (i2 + 1)] = plo[1];
+                Phi[LPF * (7 - i2)] = phi[0];
+                Phi[LPF * (6 - i2)] = phi[1];
             }
             if (lf == 0) {                                  // the self-paired middle bin k = NC/2
                 const v2 z = SUB == 2 ? v[1] : v[8];
