@@ -792,6 +792,54 @@ int tcr_mine_gather(int n_signals, const int64_t* sample_offsets /* DEVICE [N + 
                     const int32_t* clip_signal, const int64_t* clip_first, int n_samples, float* out /* or NULL */,
                     int16_t* out_pcm /* or NULL */, void* stream);
 
+/* Phrase detection: multi-word phrases ("go left", "stop ... no") scored from a scan's word posteriors, as a transform of posteriors --
+ * values [steps][num_classes] in, out [steps][P + 1] phrase posteriors out, the last column a background class -- so that
+ * tcr_detect_redetect, tcr_detect_sweep(_ragged), tcr_detect_grid and tcr_mine_* apply to phrases unchanged with num_classes = P + 1.
+ * The background does for phrases what _silence_ does for words: it is on top when no phrase scores, so the detector's
+ * top != prev_label rule lets the same phrase fire again later.
+ * values: float32 per signal, a scan's or a redetect's smoothed (probs is allowed).  Precondition: finite values in [0, 1]; outside
+ * that range the results are unspecified, the call stays memory-safe.  Phrase q is the classes phrase_words[phrase_offsets[q] ..
+ * phrase_offsets[q + 1] - 1] = c_1 .. c_n, 1 <= n <= TCR_PHRASE_MAX_WORDS, repeats allowed.  For step i of a signal (counted from the
+ * signal's first step) and w = window_steps let h = max(0, i - w + 1), and f(a, b) the float32 product a * b (TCR_PHRASE_PRODUCT) or
+ * fminf(a, b) (TCR_PHRASE_MIN):
+ *   ordered = 1:  conf_q[i] = max over h <= t_1 <= t_2 <= .. <= t_n <= i of f(..f(f(v[t_1][c_1], v[t_2][c_2]), v[t_3][c_3]).., v[t_n][c_n]),
+ *                 the fold running left to right, evaluated as the DP  E_1(t) = max(E_1(t - 1), v[t][c_1]),
+ *                 E_m(t) = max(E_m(t - 1), f(E_{m-1}(t), v[t][c_m]))  over t = h .. i with m ascending inside each t, started afresh for
+ *                 every i: conf_q[i] = E_n(i).  Both are the same bits, because float32 multiply and min are monotone in each
+ *                 non-negative argument; the product is not re-associated.
+ *   ordered = 0:  conf_q[i] = the fold over m = 1 .. n, in this order, of  max over h <= t <= i of v[t][c_m]  (Chen et al. 2014).
+ *   out[i][q] = conf_q[i] for q < P,  out[i][P] = 1.0f - max over q of conf_q[i].
+ * A signal's first steps never read another signal's rows.  No normalisation (an n-th root) is applied: with TCR_PHRASE_PRODUCT a
+ * per-word confidence p corresponds to a threshold of p^n; TCR_PHRASE_MIN keeps thresholds on the single-word scale.
+ * How: a workgroup per tile of TCR_PHRASE_TILE steps of one signal stages the tile's rows and the up to w - 1 rows in front of them
+ * in LDS, the U distinct word classes only, one column after the other; a lane per step then walks its window with the DP state in
+ * registers.  (TCR_PHRASE_TILE + w - 1) x U floats stay within 64 KB, which bounds the window:
+ * tcr_phrase_window_max(U) = 16384 / U - 255 (U = 4: 3841, U = 12: 1110; below 1 -- no window at all -- from U = 65 on, and for
+ * U < 1).  There is no path above the limit.  phrase_offsets / phrase_words are HOST tables, read before the call returns (they
+ * travel as kernel arguments); every other pointer is device memory.  The entries only enqueue a kernel on `stream` -- no copy, no
+ * wait -- so they can be captured into a graph like tcr_detect_redetect.  The ragged form takes step_offsets as
+ * tcr_detect_redetect_ragged does (DEVICE int64 [N + 1], from 0, non-decreasing, step_offsets[N] == total_steps: preconditions).
+ * Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched, out is not written): a null step_offsets (ragged) / values /
+ * phrase_offsets / phrase_words / cfg / out, N, steps (dense), total_steps (ragged) or num_classes <= 0, n_phrases outside
+ * 1 .. TCR_PHRASE_MAX, phrase_offsets that do not start at 0 or decrease, a phrase of 0 or more than TCR_PHRASE_MAX_WORDS words, a word
+ * outside 0 .. num_classes - 1, window_steps < 1 or above tcr_phrase_window_max(U) for the U distinct word classes of the call,
+ * ordered outside 0 / 1, an unknown combine, steps in all x (P + 1) or x num_classes >= 2^31. */
+#define TCR_PHRASE_MAX_WORDS 8
+#define TCR_PHRASE_MAX 64               /* phrases per call */
+#define TCR_PHRASE_TILE 256
+enum { TCR_PHRASE_PRODUCT = 0, TCR_PHRASE_MIN = 1 };
+typedef struct tcr_phrase_cfg {
+    int32_t window_steps, ordered, combine;
+} tcr_phrase_cfg;
+int tcr_phrase_window_max(int n_distinct_classes);      /* largest window_steps the staged kernel takes; < 1: none */
+int tcr_phrase_scores(int n_signals, int64_t steps, int num_classes, const float* values /* [N][steps][C] */, int n_phrases,
+                      const int32_t* phrase_offsets /* HOST [P + 1] */, const int32_t* phrase_words /* HOST */,
+                      const tcr_phrase_cfg* cfg, float* out /* [N][steps][P + 1] */, void* stream);
+int tcr_phrase_scores_ragged(int n_signals, const int64_t* step_offsets /* DEVICE [N + 1] */, int64_t total_steps, int num_classes,
+                             const float* values /* packed [total_steps][C] */, int n_phrases, const int32_t* phrase_offsets /* HOST */,
+                             const int32_t* phrase_words /* HOST */, const tcr_phrase_cfg* cfg, float* out /* [total_steps][P + 1] */,
+                             void* stream);
+
 /* Sample-rate conversion: a rational-ratio polyphase FIR in front of the detectors (which take float32 at the model's rate).
  * in_rate -> out_rate, g = gcd: up = L = out_rate / g, down = M = in_rate / g; taps = P per phase (even, or 1); table float32
  * [up][taps], designed on the host (tcresnet_amd.resampling.design_table: windowed sinc, fc = rolloff / max(1, M / L), Kaiser

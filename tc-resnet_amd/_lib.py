@@ -16,6 +16,10 @@ MAX_BLOCKS = 16
 GRID_TILE = 256            # == TCR_GRID_TILE: steps per tile of tcr_detect_grid's smoothing kernel
 MINE_TILE = 256            # == TCR_MINE_TILE: steps per tile of tcr_mine_peaks
 MINE_RADIUS_MAX = 2560     # == TCR_MINE_RADIUS_MAX: the largest radius tcr_mine_peaks takes
+PHRASE_TILE = 256          # == TCR_PHRASE_TILE: steps per tile of tcr_phrase_scores
+PHRASE_MAX = 64            # == TCR_PHRASE_MAX: phrases per call
+PHRASE_MAX_WORDS = 8       # == TCR_PHRASE_MAX_WORDS
+PHRASE_PRODUCT, PHRASE_MIN = 0, 1      # tcr_phrase_cfg.combine
 ABI_VERSION = 3            # == TCR_ABI_VERSION of include/tcresnet_hip.h these prototypes were written against
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_HERE, "lib", "libtcresnet_hip.so")
@@ -56,6 +60,11 @@ class DetectPoint(C.Structure):
 class ResampleCfg(C.Structure):
     """tcr_resample_cfg."""
     _fields_ = [("up", C.c_int32), ("down", C.c_int32), ("taps", C.c_int32), ("in_format", C.c_int32), ("in_step", C.c_int32)]
+
+
+class PhraseCfg(C.Structure):
+    """tcr_phrase_cfg."""
+    _fields_ = [("window_steps", C.c_int32), ("ordered", C.c_int32), ("combine", C.c_int32)]
 
 
 FAMILY_TCRESNET, FAMILY_DSCNN, FAMILY_G2D = 0, 1, 2
@@ -223,6 +232,9 @@ _PROTOTYPES = {
                                  _P, _P]),
     "tcr_mine_select": (C.c_int, [C.c_int64, _P, _P, C.c_uint32, C.c_int64, _P, C.c_size_t, _P, _P, _P]),
     "tcr_mine_gather": (C.c_int, [C.c_int, _P, _P, C.c_int64, _P, _P, C.c_int, _P, _P, _P]),
+    "tcr_phrase_window_max": (C.c_int, [C.c_int]),
+    "tcr_phrase_scores": (C.c_int, [C.c_int, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.POINTER(PhraseCfg), _P, _P]),
+    "tcr_phrase_scores_ragged": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.POINTER(PhraseCfg), _P, _P]),
     "tcr_resample": (C.c_int, [C.POINTER(ResampleCfg), _P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64,
                                _P]),
     "tcr_resample_span": (C.c_int, [C.POINTER(ResampleCfg), C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -200,8 +200,9 @@ def summary_line(rec: Recordings, counts: Dict[str, int], extra: Optional[Dict[s
                        "detections_per_hour": total / hours if hours > 0 else None, **(extra or {})})
 
 
-def add_detector_flags(p, each: str = "signal", threshold: bool = True, offline: bool = True) -> None:
-    """The model, input and detector flags of the three tools; `offline`: the scanning tools' --max_windows and --chunk_seconds."""
+def add_detector_flags(p, each: str = "signal", threshold: bool = True, offline: bool = True, phrases: bool = False) -> None:
+    """The model, input and detector flags of the three tools; `offline`: the scanning tools' --max_windows and --chunk_seconds;
+    `phrases`: scan_audio.py's and sweep_audio.py's --phrases flags (`open_phrases`)."""
     p.add_argument("--frozen", required=True, help="frozen artifact (.npz) of any model family exported with include_preprocess")
     p.add_argument("--wav", required=True, nargs="+", help=f"16-bit PCM WAV files, one {each} each")
     p.add_argument("--frames_per_step", type=int, default=1, help="new front-end frames per step (k)")
@@ -227,6 +228,14 @@ def add_detector_flags(p, each: str = "signal", threshold: bool = True, offline:
         p.add_argument("--cascade_pad_ms", type=float, default=None,
                        help="cascade: audio selected in front of and behind every flag (default: --average_window_ms minus one step)")
         p.add_argument("--second_frames_per_step", type=int, default=1, help="cascade: --second_frozen's frames per step")
+    if phrases:
+        p.add_argument("--phrases", default=None,
+                       help='detect phrases instead of single words: "go left;stop no" (words: --labels names or class indices), or @FILE '
+                            "with one phrase per line (scanning.PhraseDetector); not with --chunk_seconds / --ragged_chunk_seconds")
+        p.add_argument("--phrase_window_ms", type=float, default=1500.0, help="phrases: the window a phrase's words must fall in")
+        p.add_argument("--phrase_unordered", action="store_true", help="phrases: the words in any order (default: in the given order)")
+        p.add_argument("--phrase_combine", choices=("product", "min"), default="product",
+                       help="phrases: a phrase's score is the product or the minimum of its words' posteriors")
 
 
 def detector_settings(args) -> dict:
@@ -284,6 +293,32 @@ def open_cascade(args):
     first = FrozenModel.load(args.frozen).scanner(**settings)
     second = FrozenModel.load(args.second_frozen).scanner(**dict(settings, frames_per_step=args.second_frames_per_step))
     return CascadeScanner(first, second, args.enter_threshold, pad_before_ms=args.cascade_pad_ms, pad_after_ms=args.cascade_pad_ms)
+
+
+def check_phrase_flags(args) -> None:
+    """--phrases is refused with the chunked runs (before any model is loaded)."""
+    if getattr(args, "phrases", None) is not None and (args.chunk_seconds is not None or args.ragged_chunk_seconds is not None):
+        raise SystemExit("--phrases scores whole scans: it cannot be combined with --chunk_seconds or --ragged_chunk_seconds (a chunk's "
+                         "first steps would need the previous chunk's rows)")
+
+
+def open_phrases(args, scanner):
+    """The `scanning.PhraseDetector` of --phrases over `scanner`'s outputs (None without the flag): its threshold and suppression are
+    the detector flags', its labels the phrase names and _background_.  Refused with the chunked runs: a chunk's first steps would
+    need the previous chunk's rows."""
+    check_phrase_flags(args)
+    spec = getattr(args, "phrases", None)
+    if spec is None:
+        return None
+    if spec.startswith("@"):
+        with open(spec[1:]) as fh:
+            lines = [x.strip() for x in fh]
+    else:
+        lines = [x.strip() for x in spec.split(";")]
+    phrases = [x.split() for x in lines if x]
+    from .scanning import PhraseDetector
+    return PhraseDetector(scanner, phrases, window_ms=args.phrase_window_ms, ordered=not args.phrase_unordered, combine=args.phrase_combine,
+                          labels=args.labels.split(",") if args.labels else None)
 
 
 def label_names(args, det) -> List[str]:

@@ -4,6 +4,7 @@
                          [--average_window_ms MS] [--detection_threshold P] [--suppression_ms MS] [--min_count N]
                          [--max_windows B] [--summary] [--chunk_seconds X | --ragged | --ragged_chunk_seconds X]
                          [--second_frozen MODEL2.npz --enter_threshold P [--cascade_pad_ms MS] [--second_frames_per_step K]]
+                         [--phrases "w1 w2;w3 w4" | @FILE [--phrase_window_ms MS] [--phrase_unordered] [--phrase_combine product|min]]
 
 The files (16-bit PCM) come from `audio_input.Recordings`, zero-padded to the longest, and are scanned in one
 `scanning.KeywordScanner` call; samples that do not fill a whole step are dropped (noted on stderr).  A file at another sample rate
@@ -24,7 +25,11 @@ every step, the steps where one of its keyword classes (every class from 2 on) r
 of them (default: the averaging window minus one step), are computed again by MODEL2 at --second_frames_per_step, and the detector
 -- the detector flags are the second stage's -- runs on the merged posteriors (`scanning.CascadeScanner`); both models must have the
 same sample rate, classes and step (frames per step x hop).  --summary then gains selected_steps and total_steps.  With
---enter_threshold -inf every step is MODEL2's and stdout is MODEL2's own --ragged run, byte for byte."""
+--enter_threshold -inf every step is MODEL2's and stdout is MODEL2's own --ragged run, byte for byte.  With --phrases "go left;stop no"
+(or @FILE, one phrase per line; words are --labels names or class indices) the lines and the summary are those of a
+`scanning.PhraseDetector` over the scan: label is the phrase, score its posterior -- the best product (--phrase_combine min: minimum)
+of its words' smoothed posteriors within --phrase_window_ms, in the given order unless --phrase_unordered -- with the detector
+flags' threshold and suppression; on the one-call run, --ragged and a cascade, not with --chunk_seconds / --ragged_chunk_seconds."""
 from __future__ import annotations
 
 import argparse
@@ -34,18 +39,18 @@ from typing import List, Optional
 
 if __package__ in (None, ""):           # run as a script: import the package through the repository's shim
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from tcresnet_amd.audio_input import (Recordings, add_detector_flags, cascade_argv, label_names, open_cascade, open_detector,
-                                          print_detections, print_detections_ragged, summary_line)
+    from tcresnet_amd.audio_input import (Recordings, add_detector_flags, cascade_argv, check_phrase_flags, label_names, open_cascade,
+                                          open_detector, open_phrases, print_detections, print_detections_ragged, summary_line)
     from tcresnet_amd.deploy import FrozenModel
 else:
-    from .audio_input import (Recordings, add_detector_flags, cascade_argv, label_names, open_cascade, open_detector, print_detections,
-                              print_detections_ragged, summary_line)
+    from .audio_input import (Recordings, add_detector_flags, cascade_argv, check_phrase_flags, label_names, open_cascade, open_detector,
+                              open_phrases, print_detections, print_detections_ragged, summary_line)
     from .deploy import FrozenModel
 
 
 def parse_arguments(arguments: Optional[List[str]] = None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    add_detector_flags(p)
+    add_detector_flags(p, phrases=True)
     p.add_argument("--summary", action="store_true", help="one JSON line of totals on stderr")
     return p.parse_args(cascade_argv(arguments))
 
@@ -53,8 +58,11 @@ def parse_arguments(arguments: Optional[List[str]] = None):
 def main_cascade(args, cascade) -> int:
     rec = Recordings(args.wav, cascade.second)
     names, counts, extra = label_names(args, cascade.second), {}, {"selected_steps": 0, "total_steps": 0}
+    phrases = open_phrases(args, cascade.second)
     if rec.n_steps > 0:
         out = cascade.scan_ragged(rec.packed())
+        if phrases is not None:
+            out, names = phrases.detect(out), phrases.labels
         print_detections_ragged(rec, out, names, counts)
         extra = {"selected_steps": int(out.selected.numel()), "total_steps": int(out.top.shape[0])}
     if args.summary:
@@ -63,13 +71,22 @@ def main_cascade(args, cascade) -> int:
 
 
 def main(args) -> int:
+    check_phrase_flags(args)
     cascade = open_cascade(args)
     if cascade is not None:
         return main_cascade(args, cascade)
     det, run = open_detector(FrozenModel.load(args.frozen), args)
     rec = Recordings(args.wav, det)
     names, counts = label_names(args, det), {}
-    if args.ragged_chunk_seconds is not None:
+    phrases = open_phrases(args, det)
+    if phrases is not None:                             # (the one-call runs only: `open_phrases` refuses the chunked ones)
+        if args.ragged:
+            if rec.n_steps > 0:
+                print_detections_ragged(rec, phrases.detect(det.scan_ragged(rec.packed())), phrases.labels, counts)
+        else:
+            for i0, samples in rec.chunks(None):
+                print_detections(rec, phrases.detect(run(samples)), i0, phrases.labels, counts)
+    elif args.ragged_chunk_seconds is not None:
         for i0, packed, lengths in rec.ragged_chunks(args.ragged_chunk_seconds):
             print_detections_ragged(rec, run((packed, lengths)), names, counts, i0)
     elif args.ragged:

@@ -6,6 +6,7 @@ curve (false rejects against false accepts per hour) from one scan.
                           [--frames_per_step k] [--labels l0,l1,...] [--average_window_ms MS] [--suppression_ms MS]
                           [--min_count N] [--max_windows B] [--chunk_seconds X | --ragged | --ragged_chunk_seconds X]
                           [--second_frozen MODEL2.npz --enter_threshold P [--cascade_pad_ms MS] [--second_frames_per_step K]]
+                          [--phrases "w1 w2;w3 w4" | @FILE [--phrase_window_ms MS] [--phrase_unordered] [--phrase_combine product|min]]
 
 The files are read as scan_audio.py reads them (`audio_input.Recordings`: 16-bit PCM, converted to the model's sample rate on the
 device where it differs, only whole steps), zero-padded to the longest and scanned in one call; one `KeywordScanner.sweep` then
@@ -25,7 +26,11 @@ hit of an event counts as a hit, later ones as duplicates, every other detection
 stdout: CSV with a header, one row per threshold over the --keywords (default: every label that does not start with '_'):
 threshold,hits,events,false_accepts,duplicates,frr,fa_per_hour  (frr = 1 - hits / events); --per_label: one row per keyword and
 threshold, with a leading label column.  stderr: one JSON line, the hours scanned and the operating point: the threshold of the
-lowest FRR with fa_per_hour <= --target_fa_per_hour (null when none is)."""
+lowest FRR with fa_per_hour <= --target_fa_per_hour (null when none is).
+
+With --phrases (scan_audio.py's flags: `scanning.PhraseDetector`) the curve is the phrase detector's over the scan: the events' labels
+and the --keywords are phrase names (the words joined by a space; default: every phrase, never _background_), on the one-call run,
+--ragged and a cascade; not with --chunk_seconds / --ragged_chunk_seconds."""
 from __future__ import annotations
 
 import argparse
@@ -39,11 +44,13 @@ import numpy as np
 
 if __package__ in (None, ""):           # run as a script: import the package through the repository's shim
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from tcresnet_amd.audio_input import Recordings, add_detector_flags, cascade_argv, label_names, open_cascade, open_detector
+    from tcresnet_amd.audio_input import (Recordings, add_detector_flags, cascade_argv, check_phrase_flags, label_names, open_cascade,
+                                          open_detector, open_phrases)
     from tcresnet_amd.deploy import FrozenModel
     from tcresnet_amd.scanning import RaggedScanOutput, ScanOutput
 else:
-    from .audio_input import Recordings, add_detector_flags, cascade_argv, label_names, open_cascade, open_detector
+    from .audio_input import (Recordings, add_detector_flags, cascade_argv, check_phrase_flags, label_names, open_cascade, open_detector,
+                              open_phrases)
     from .deploy import FrozenModel
     from .scanning import RaggedScanOutput, ScanOutput
 
@@ -62,7 +69,7 @@ def parse_thresholds(spec: str) -> np.ndarray:
 
 def parse_arguments(arguments: Optional[List[str]] = None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    add_detector_flags(p, threshold=False)
+    add_detector_flags(p, threshold=False, phrases=True)
     p.add_argument("--events", required=True, help="CSV of labelled keyword events: file,start_ms,end_ms,label")
     p.add_argument("--thresholds", default="0:0.99:0.01", help="LO:HI:STEP or a comma-separated list")
     p.add_argument("--tolerance_ms", type=float, default=1000.0, help="a detection up to this long after an event's end still hits it")
@@ -92,12 +99,14 @@ def read_events(path: str, wavs: List[str]):
 
 def main(args) -> int:
     import torch
+    check_phrase_flags(args)
     cascade, extra = open_cascade(args), {}
     if cascade is not None:
         scanner, run = cascade.second, None
     else:
         scanner, run = open_detector(FrozenModel.load(args.frozen), args)
-    names = label_names(args, scanner)
+    phrases = open_phrases(args, scanner)
+    names = label_names(args, scanner) if phrases is None else phrases.labels
     keywords = args.keywords.split(",") if args.keywords else [x for x in names if not x.startswith("_")]
     unknown = [k for k in keywords if k not in names]
     if unknown:
@@ -108,7 +117,17 @@ def main(args) -> int:
     if rec.n_steps == 0:
         raise SystemExit("no whole step of audio in the files")
     events = read_events(args.events, args.wav)
-    if cascade is not None:
+    if phrases is not None:                             # (the one-call runs only: `open_phrases` refuses the chunked ones)
+        if cascade is not None:
+            out = cascade.scan_ragged(rec.packed())
+            extra = {"selected_steps": int(out.selected.numel()), "total_steps": int(out.top.shape[0])}
+            res = phrases.sweep(out, thresholds, events=events, tolerance_ms=args.tolerance_ms)
+        elif args.ragged:
+            res = phrases.sweep(scanner.scan_ragged(rec.packed()), thresholds, events=events, tolerance_ms=args.tolerance_ms)
+        else:
+            _, samples = next(iter(rec.chunks(None)))
+            res = phrases.sweep(run(samples), thresholds, events=events, lengths=rec.lengths, tolerance_ms=args.tolerance_ms)
+    elif cascade is not None:
         out = cascade.scan_ragged(rec.packed())
         extra = {"selected_steps": int(out.selected.numel()), "total_steps": int(out.top.shape[0])}
         res = scanner.sweep(out, thresholds, events=events, tolerance_ms=args.tolerance_ms, labels=names)

@@ -65,6 +65,9 @@ def parse_arguments(arguments: Optional[List[str]] = None):
     args = sweep_audio.parse_arguments(rest)
     if args.chunk_seconds is not None or args.ragged_chunk_seconds is not None:
         raise SystemExit(CHUNK_REFUSAL)
+    if args.phrases is not None:
+        raise SystemExit("--phrases is sweep_audio.py's and scan_audio.py's: this tool tunes the word detector (a phrase detector's grid: "
+                         "scanning.PhraseDetector.tune)")
     try:
         args.grid_window_ms = _floats(lists.get("average_window_ms", args.average_window_ms))
         args.grid_min_count = [int(x) for x in str(lists.get("min_count", args.min_count)).split(",")]
