@@ -122,6 +122,22 @@ __device__ __forceinline__ void pk3_real_pair_power(v2 zk, v2 zn, v2 wmi, float&
     pk_sq_pair(A, C, p_lo, p_hi);
 }
 
+// What an instance takes out of its round loop: per-round bookkeeping whose result is the same in every round of a chunk, or follows
+// from the previous round's by an addition.  Each item holds registers through the round body (the compiler then hoists the masks,
+// shifts, compares and LDS addresses made from a descriptor as well, which is most of the saving and most of the registers), so an
+// instance takes an item only where it stays at three waves per SIMD without scratch it did not have; the table behind the choice
+// is profiles/fe_carry_kernel_regs.txt, the counts are in OPTLOG.md "Front-end round bookkeeping".
+constexpr int kPk3Carry = 1;        // frame coordinates stepped from round to round (frame_next) instead of worked out from the frame number
+constexpr int kPk3BandsReg = 2;     // the bands' item ranges in registers for a chunk's rounds (else one LDS read per band and round)
+constexpr int kPk3ItemsReg = 4;     // the trips' item descriptors likewise (else one LDS read per trip and round)
+constexpr int pk3_round_policy(int nc, int qv) {
+#ifdef TCR_PK3_POLICY
+    return TCR_PK3_POLICY;          // (what-if builds: one policy for every instance, TCR_BUILD_EXTRA=-DTCR_PK3_POLICY=n)
+#endif
+    if (nc == 512) return qv == 10 ? kPk3BandsReg | kPk3ItemsReg : 0;   // 15 / 16 live inputs: at the 168-register ceiling as they are
+    return qv == 16 ? kPk3ItemsReg : kPk3Carry | kPk3ItemsReg;           // nfft 512: four bands per lane, their hoisted unpacking spills
+}
+
 }  // namespace
 
 // LDS of one workgroup (bytes): 4 waves x (tile / power 4608 + item sums FPWV x 832 + log-mel 4096) + slopes + items
@@ -145,7 +161,8 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
     constexpr int PLD = NBINS + (LPF >= 32 ? 31 : 15);      // power-spectrum row stride (frontend_pk.hip)
     static_assert(FPWV * PLD <= 2 * TILEW, "the power spectrum of a wave's frames lives in its tile space");
     constexpr int kMelItemBins = mel_item_bins(NC);
-    constexpr bool kItemsLds = true;        // the trips' item descriptors: one ds_read_b32 per trip instead of TRIPS registers
+    constexpr int kPolicy = pk3_round_policy(NC, QV);
+    constexpr bool kCarry = kPolicy & kPk3Carry, kBandsReg = kPolicy & kPk3BandsReg, kItemsReg = kPolicy & kPk3ItemsReg;
     constexpr int NIT = mel_items_fast(NC);         // items of the unrolled trips; the launcher sends filterbanks with more to frontend_pk.hip
     constexpr int USZ = NIT + 8; static_assert(NIT + 3 <= USZ, "the log phase reads up to three cells from a band's first item");
                        // item sums of one frame (+ the cell of the empty slots, mel_dummy_item, + the log phase's read-ahead)
@@ -156,9 +173,8 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
     __shared__ v2 s_ud[4 * FPWV * USZ];
     __shared__ float s_lm[4 * NMEL * 16];
     __shared__ v4 s_wit[kMelItemBins / 2 * NIT];    // [bin pair][item]: the slopes of bins 2 bp and 2 bp + 1 in one ds_read_b128
-    __shared__ int s_items[kItemsLds ? NIT : 1];
-    constexpr bool kBandsLds = true;                // the bands' item ranges from LDS (one ds_read_b32 per band and round instead of 2 - 4 registers)
-    __shared__ int s_band[kBandsLds ? NMEL : 1];
+    __shared__ int s_items[NIT];            // the trips' item descriptors
+    __shared__ int s_band[NMEL];            // the bands' item ranges: first item | first item of the next band << 8 | of the one after << 16
     __shared__ v2 s_wnd[QV * LPF];          // signed window [q][lane of the frame]: samples 2 (SUB (l + 16 q) + u), + 1
 
     const int tid = threadIdx.x;
@@ -171,9 +187,8 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
             const v2 w0 = wit[2 * bp * NIT + it] * fold, w1 = wit[(2 * bp + 1) * NIT + it] * fold;
             s_wit[i] = (v4){w0.x, w0.y, w1.x, w1.y};
         }
-        if (kItemsLds)
-            for (int i = tid; i < NIT; i += 256) s_items[i] = a.mel_items[i];
-        if (kBandsLds && tid < NMEL) s_band[tid] = a.mel_ifirst[tid] | (a.mel_ifirst[tid + 1] << 8) | (a.mel_ifirst[tid + 2] << 16);
+        for (int i = tid; i < NIT; i += 256) s_items[i] = a.mel_items[i];
+        if (tid < NMEL) s_band[tid] = a.mel_ifirst[tid] | (a.mel_ifirst[tid + 1] << 8) | (a.mel_ifirst[tid + 2] << 16);
         for (int i = tid; i < QV * LPF; i += 256) {
             const int q = i / LPF, lfi = i % LPF;
             s_wnd[i] = *reinterpret_cast<const v2*>(a.window_sgn + 2 * (SUB * ((lfi & 15) + 16 * q) + (lfi >> 4)));
@@ -187,7 +202,6 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
     // for the length of the window multiply, so that 3 waves per SIMD (<= 168 registers) hold without scratch.
     v2 tw[16], twr[8], twc[8];
     float sgn;
-    int item_d[kItemsLds ? 1 : TRIPS], band_i[kBandsLds ? 1 : NMEL / LPF];
     {
         const int lf = tid % LPF, l = tid & 15, h = l >> 3;
         // the (-1)^h of the second pass's odd outputs.  nfft 1024: every odd output goes through the row swap into a lane of the frame's
@@ -203,17 +217,6 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
             twr[i] = (v2){w.y, -w.x};           // -i W^k
             twc[i] = (SUB == 2) ? tw_combine[k] * sgn : (v2){1.f, 0.f};
         }
-        if (!kItemsLds) {
-#pragma unroll
-            for (int tr = 0; tr < TRIPS; ++tr) item_d[kItemsLds ? 0 : tr] = a.mel_items[lf + LPF * tr];
-        }
-        if (!kBandsLds) {
-#pragma unroll
-            for (int i = 0; i < NMEL / LPF; ++i) {
-                const int m = lf + LPF * i;
-                band_i[kBandsLds ? 0 : i] = a.mel_ifirst[m] | (a.mel_ifirst[m + 1] << 8) | (a.mel_ifirst[m + 2] << 16);
-            }
-        }
     }
     const v2 wm = tw_real[NC / 2];
     const v2 twmid = (v2){wm.y, -wm.x};
@@ -223,20 +226,38 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
     const int fpwv = rounds * FPWV;         // frames per chunk and wave (the columns of its DCT tile)
     const int fpw = 4 * fpwv;               // frames per chunk
     v2 xa[QV];
-    auto load_frame = [&](int chunk, int rr, v2 (&dst)[QV]) {
+    // The samples of frame g = chunk * fpw + wave * fpwv + rr * FPWV + fw: utterance n = g / n_frames, frame t = g % n_frames, from
+    // this lane's first sample on (fsrc; the QV loads sit at constant offsets behind it).  frame_at works the coordinates out from g;
+    // frame_next (kCarry) steps those of the previous round by FPWV frames: within a chunk a lane's g goes up by exactly FPWV per
+    // round, i.e. by FPWV / n_frames utterances and step_r = FPWV % n_frames frames with at most one wrap of t behind them
+    // (step_r < n_frames), whatever n_frames is (the streaming instance at k = 1 wraps every round).  Integer and address work only.
+    int ft = 0;
+    const float* fsrc = a.wav;
+    const int step_r = FPWV % a.n_frames;
+    const ptrdiff_t step_src = (ptrdiff_t)(FPWV / a.n_frames) * a.n_samples + (ptrdiff_t)step_r * a.hop;
+    const ptrdiff_t step_src_wrap = step_src + a.n_samples - (ptrdiff_t)a.n_frames * a.hop;
+    auto frame_at = [&](int chunk, int rr) {
         const int tid = (int)threadIdx.x;
         const int lf = tid % LPF, u = lf >> 4, l = tid & 15, fw = (tid & 63) / LPF;
         int g = chunk * fpw + wave * fpwv + rr * FPWV + fw;
         g = min(g, a.total_frames - 1);
         int n = (int)(((float)g + 0.5f) * inv_frames);          // g / n_frames: float multiply + one-step fix-up
         n += (n + 1) * a.n_frames <= g ? 1 : (n * a.n_frames > g ? -1 : 0);
-        const int t = g - n * a.n_frames;
-        const float* src = a.wav + (size_t)n * a.n_samples + (size_t)t * a.hop;
+        ft = g - n * a.n_frames;
+        fsrc = a.wav + (size_t)n * a.n_samples + (size_t)ft * a.hop + 2 * (SUB * l + u);
+    };
+    auto frame_next = [&]() {
+        const unsigned t = (unsigned)(ft + step_r), tm = t - (unsigned)a.n_frames;      // (tm: t wrapped, or past 2^31 where t < n_frames)
+        fsrc += tm < t ? step_src_wrap : step_src;
+        ft = (int)min(t, tm);
+    };
+    auto load_frame = [&](v2 (&dst)[QV]) {
 #pragma unroll
-        for (int q = 0; q < QV; ++q) dst[q] = *reinterpret_cast<const v2*>(src + 2 * (SUB * (l + 16 * q) + u));     // (8-byte aligned: launcher)
+        for (int q = 0; q < QV; ++q) dst[q] = *reinterpret_cast<const v2*>(fsrc + 2 * SUB * 16 * q);        // (8-byte aligned: launcher)
     };
     const int nchunks = (a.total_frames + fpw - 1) / fpw;
-    load_frame(blockIdx.x, 0, xa);
+    frame_at(blockIdx.x, 0);
+    load_frame(xa);
     __syncthreads();                        // the slope table / item list staged above (the only workgroup barrier)
     // De-phasing: the twelve waves of a CU start together and do identical work, so they would stay in lock step -- all in their VALU
     // phases, then all queueing at the LDS.  A one-off delay of (workgroup generation * 4 + wave) * stagger * 64 cycles spreads them over a round.
@@ -256,6 +277,17 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
     v2* T = s_t + wave * TILEW + (lane >> 4) * UNITSZ;
     float* Pw = reinterpret_cast<float*>(s_t + wave * TILEW);
     float* LM = s_lm + wave * (NMEL * 16);
+    // Round-invariant descriptors of this lane, per instance (pk3_round_policy) in registers for the length of a chunk's rounds -- read
+    // here, from the opaque lane geometry, so that they are dead in the DCT section -- or re-read from LDS in every round.
+    int item_d[kItemsReg ? TRIPS : 1], band_i[kBandsReg ? NMEL / LPF : 1];
+    if (kItemsReg) {
+#pragma unroll
+        for (int tr = 0; tr < TRIPS; ++tr) item_d[kItemsReg ? tr : 0] = s_items[lf + LPF * tr];
+    }
+    if (kBandsReg) {
+#pragma unroll
+        for (int i = 0; i < NMEL / LPF; ++i) band_i[kBandsReg ? i : 0] = s_band[lf + LPF * i];
+    }
 #pragma unroll 1
     for (int r = 0; r < rounds; ++r) {
         // ---------------- window + first radix-16 pass ----------------
@@ -351,29 +383,28 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
             if (lf < PLD - NBINS) P[NBINS + lf] = 0.f;      // row pad: read (times a zero slope) past an item's end; the space held tile data
         }
         // ---------------- the next round's samples (the FFT registers are free) ----------------
-        if (r + 1 < rounds) load_frame(chunk, r + 1, xa);
-        else if (chunk + (int)gridDim.x < nchunks) load_frame(chunk + gridDim.x, 0, xa);
+        // (a chunk's first round, and every round of a chunk that reaches past the last frame -- the clamp --, from g)
+        {
+            const bool jump = r + 1 == rounds;
+            const int ch = jump ? chunk + (int)gridDim.x : chunk;
+            if (ch < nchunks) {
+                if (kCarry && !jump && (ch + 1) * fpw <= a.total_frames) frame_next();
+                else frame_at(ch, jump ? 0 : r + 1);
+                load_frame(xa);
+            }
+        }
         wave_sync();
         // ---------------- sparse mel: one item (<= 8 bins of one segment) per lane and trip, one packed FMA per bin ----------------
         v2* UD = s_ud + (wave * FPWV + fw) * USZ;
         int bi_pre[NMEL / LPF];                             // the bands' item ranges: requested with the trips' operands, used by the log phase
-        if (kBandsLds) {
 #pragma unroll
-            for (int i = 0; i < NMEL / LPF; ++i) bi_pre[i] = s_band[lf + LPF * i];
-        }
+        for (int i = 0; i < NMEL / LPF; ++i) bi_pre[i] = kBandsReg ? band_i[kBandsReg ? i : 0] : s_band[lf + LPF * i];
         {
             const float* P = Pw + fw * PLD;
 #pragma unroll
             for (int tr = 0; tr < TRIPS; ++tr) {            // (unrolled: the trips' descriptor and operand reads overlap instead of TRIPS dependent LDS round trips in a row)
                 const int it = lf + LPF * tr;
-                int d;
-                if (kItemsLds) {
-                    d = s_items[it];
-                } else {
-                    d = item_d[0];
-#pragma unroll
-                    for (int q = 1; q < TRIPS; ++q) d = tr == q ? item_d[kItemsLds ? 0 : q] : d;
-                }
+                const int d = kItemsReg ? item_d[kItemsReg ? tr : 0] : s_items[it];     // (tr: a constant of the unrolled trip)
                 const float* pk = P + (d & 1023);
                 const v4* wk = s_wit + it;
                 float p[kMelItemBins];
@@ -401,7 +432,7 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
             float up[NB][MAXC], dn[NB][MAXC];
 #pragma unroll
             for (int i = 0; i < NB; ++i) {                  // every band's cells first (single ds_read_b64 each), the sums behind them
-                const int bi = kBandsLds ? bi_pre[i] : band_i[kBandsLds ? 0 : i];
+                const int bi = bi_pre[i];
                 const int i0 = bi & 255, i1 = (bi >> 8) & 255;
 #pragma unroll
                 for (int cc = 0; cc < MAXC; ++cc) {
@@ -412,7 +443,7 @@ __global__ __launch_bounds__(256, 3) void frontend_pk3_kernel(const FrontendArgs
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
                 const int m = lf + LPF * i;
-                const int bi = kBandsLds ? bi_pre[i] : band_i[kBandsLds ? 0 : i];
+                const int bi = bi_pre[i];
                 const int i0 = bi & 255, i1 = (bi >> 8) & 255, i2 = bi >> 16;
                 // (nfft 1024: a segment has <= MAXC items -- the launcher sends other filterbanks to frontend_pk.hip --, so no loop behind
                 //  the unconditional reads; nfft 512: the reference filterbank has a few 3-item segments, the loops stay)
