@@ -792,6 +792,53 @@ int tcr_mine_gather(int n_signals, const int64_t* sample_offsets /* DEVICE [N + 
                     const int32_t* clip_signal, const int64_t* clip_first, int n_samples, float* out /* or NULL */,
                     int16_t* out_pcm /* or NULL */, void* stream);
 
+/* Composing labelled test recordings: dataset clips pasted at known times onto looping background noise, written straight into the
+ * packed layout tcr_scan_ragged and tcr_mine_gather take, from the int16 pools of the training input stage (tcr_augment_fwd's).
+ * Every pointer is device memory; everything is enqueued on `stream` -- no copy, no wait.
+ *
+ * tcr_pcm_energy: sumsq[j] (int64 [n_clips]) = the sum of v * v over the clip_len[j] (int64) int16 samples from pcm[clip_off[j]]
+ * (int64) on.  Integer arithmetic, exact: the result does not depend on the launch shape, the order of the additions or the
+ * device.  clip_len[j] <= 0 gives 0.  One launch for the whole table, thousands of one-second clips and minute-long recordings
+ * alike: the pool is read with 16-byte loads at a clip's aligned elements, a long clip is shared out over several workgroups in
+ * groups of 16384 samples, and every group's sum is added to the table (zeroed first, on `stream`) by one 64-bit integer atomic.
+ * n_clips == 0: a successful no-op.
+ * Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched): n_clips < 0, a null pcm / clip_off / clip_len / sumsq, more than 2^31
+ * workgroups' worth of clips. */
+int tcr_pcm_energy(const int16_t* pcm, const int64_t* clip_off, const int64_t* clip_len, int64_t n_clips, int64_t* sumsq, void* stream);
+
+/* tcr_compose: N = n_signals recordings; recording n is the packed samples sample_offsets[n] .. sample_offsets[n + 1] - 1 (int64
+ * [N + 1], from 0, non-decreasing; total_samples == sample_offsets[N], which the host knows: preconditions).
+ * Foreground: place_offsets (int32 [N + 1]) is a CSR over the placements; placement j of recording n puts the place_len[j] (int32)
+ * samples from pcm[place_clip_off[j]] (int64) on at the recording's samples place_first[j] .. place_first[j] + place_len[j] - 1,
+ * scaled by place_gain[j] (float32).  place_first (int64) may be negative or run past the recording's end: the part outside the
+ * recording is dropped, a neighbouring recording is never written or read.  Preconditions: within a recording the placements are
+ * sorted by place_first and disjoint, place_first[j] + place_len[j] <= place_first[j + 1] (touching is allowed; place_len[j] == 0
+ * is allowed and places nothing); gains and volumes are finite.
+ * Background: recording n loops the bg_len[n] (int64, >= 1) samples from bg[bg_off[n]] (int64) on, starting bg_phase[n] (int64,
+ * 0 <= phase < bg_len[n]) samples in: at its sample i the background is bg[bg_off[n] + (bg_phase[n] + i) mod bg_len[n]], times
+ * bg_vol[n] (float32 [N]).  bg_vol NULL: no background anywhere (bg, bg_off, bg_len and bg_phase are not read); bg_vol[n] == 0:
+ * recording n's background is not read.
+ * Per sample i of recording n, in float32, never contracted into an fma -- tcr_augment_fwd's operations in its order:
+ *     fg  = (float)pcm[place_clip_off[j] + i - place_first[j]] * (1 / 32768.f) * place_gain[j]   if placement j covers i, else 0.f
+ *     out = bg_vol[n] != 0 ? clip(((float)bgsample * (1 / 32768.f)) * bg_vol[n] + fg, -1, 1)  :  clip(fg, -1, 1)
+ * out (float32 [total_samples], or NULL): that value.  out_pcm (int16 [total_samples], or NULL): tcr_mine_gather's rounding of it,
+ * clamp(rint(x * 32768), -32768, 32767) with ties to even.
+ * How: the packed samples are cut into tiles of TCR_COMPOSE_TILE, a few consecutive ones per workgroup, so the work is proportional to
+ * total_samples whatever the recordings' lengths, and every store but the last of the total is a 16-byte one (out_pcm: 8-byte).  The recordings a tile touches,
+ * each one's first placement that reaches the tile and its background phase at the tile's first sample (the one 64-bit modulo per
+ * tile and recording) are wave-uniform: binary searches through scalar loads, carried forward from tile to tile within a workgroup.  The lanes walk the placements that intersect the
+ * tile and find the background sample by a compare against the loop's wrap point (bg_len >= TCR_COMPOSE_TILE) or a 32-bit modulo.
+ * total_samples == 0: a successful no-op.
+ * Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched, nothing written): out and out_pcm both NULL, N <= 0, total_samples < 0,
+ * a null sample_offsets / pcm / place_offsets / place_clip_off / place_len / place_first / place_gain, bg_vol without bg / bg_off /
+ * bg_len / bg_phase, an out that is not 16-byte aligned or an out_pcm that is not 8-byte aligned, more than 2^31 tiles. */
+#define TCR_COMPOSE_TILE 2048
+int tcr_compose(int n_signals, const int64_t* sample_offsets /* DEVICE [N + 1] */, int64_t total_samples, const int16_t* pcm,
+                const int32_t* place_offsets /* [N + 1] */, const int64_t* place_clip_off, const int32_t* place_len,
+                const int64_t* place_first, const float* place_gain, const int16_t* bg /* or NULL */, const int64_t* bg_off,
+                const int64_t* bg_len, const int64_t* bg_phase, const float* bg_vol /* [N] or NULL */, float* out /* or NULL */,
+                int16_t* out_pcm /* or NULL */, void* stream);
+
 /* Phrase detection: multi-word phrases ("go left", "stop ... no") scored from a scan's word posteriors, as a transform of posteriors --
  * values [steps][num_classes] in, out [steps][P + 1] phrase posteriors out, the last column a background class -- so that
  * tcr_detect_redetect, tcr_detect_sweep(_ragged), tcr_detect_grid and tcr_mine_* apply to phrases unchanged with num_classes = P + 1.
@@ -916,7 +963,8 @@ enum { TCR_TUNE_CONV_PATH = 0,   /* 0 auto: implicit-GEMM MFMA conv where the sh
        TCR_TUNE_DW_WGRAD = 31,   /* DS-CNN depthwise filter gradient, stride-1 units on 13 x 5 maps: 0 the row kernel (a wave owns four channels, their x / dz planes as contiguous float4 through wave-private LDS; default since round 5), 1 the gather kernel of rounds 2-4 (another summation order: equal to rounding). */
        TCR_TUNE_DW_FWD = 32,     /* DS-CNN depthwise conv (eval and training forward), stride-1 layers on 13 x 5 maps: 0 the row kernels (x / y blocks of 16 planes as contiguous float4 through LDS; also the global pooling's block-copy kernel and the row-per-lane stencil of the fused conv_1 + depthwise eval kernel; default since round 5), 1 the zero-padded-image kernels of rounds 2-4.  Bitwise the same outputs and statistics. */
        TCR_TUNE_WGRAD_PIPE = 33, /* 16-byte-load filter gradients (conv_wgrad_mfma4_kernel): 0 software-pipelined -- the operands of a wave's NEXT trip (the next 16 / 8 positions, or the next utterance's first) are requested before the current trip's MFMAs, two register sets alternating (round 6; bitwise the old kernel: same trips, same order; default), 1 every trip loads, waits, multiplies (rounds 3-5) */
-       TCR_TUNE_COUNT = 34 };
+       TCR_TUNE_COMPOSE_RUN = 34, /* tcr_compose: tiles of TCR_COMPOSE_TILE packed samples a workgroup composes one after the other, the recording and placement positions carried from tile to tile (0: default 4; 1: every tile finds them by binary search).  Bitwise the same output. */
+       TCR_TUNE_COUNT = 35 };
 int tcr_tune(int knob, int value);
 
 /* Host-side view of how the fused eval kernel's resident-weight layers deal their work (no launch): the run of wave `wave` of `nw` in a

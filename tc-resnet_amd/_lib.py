@@ -16,6 +16,7 @@ MAX_BLOCKS = 16
 GRID_TILE = 256            # == TCR_GRID_TILE: steps per tile of tcr_detect_grid's smoothing kernel
 MINE_TILE = 256            # == TCR_MINE_TILE: steps per tile of tcr_mine_peaks
 MINE_RADIUS_MAX = 2560     # == TCR_MINE_RADIUS_MAX: the largest radius tcr_mine_peaks takes
+COMPOSE_TILE = 2048        # == TCR_COMPOSE_TILE: packed samples per workgroup of tcr_compose
 PHRASE_TILE = 256          # == TCR_PHRASE_TILE: steps per tile of tcr_phrase_scores
 PHRASE_MAX = 64            # == TCR_PHRASE_MAX: phrases per call
 PHRASE_MAX_WORDS = 8       # == TCR_PHRASE_MAX_WORDS
@@ -232,6 +233,8 @@ _PROTOTYPES = {
                                  _P, _P]),
     "tcr_mine_select": (C.c_int, [C.c_int64, _P, _P, C.c_uint32, C.c_int64, _P, C.c_size_t, _P, _P, _P]),
     "tcr_mine_gather": (C.c_int, [C.c_int, _P, _P, C.c_int64, _P, _P, C.c_int, _P, _P, _P]),
+    "tcr_pcm_energy": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P]),
+    "tcr_compose": (C.c_int, [C.c_int, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "tcr_phrase_window_max": (C.c_int, [C.c_int]),
     "tcr_phrase_scores": (C.c_int, [C.c_int, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.POINTER(PhraseCfg), _P, _P]),
     "tcr_phrase_scores_ragged": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.POINTER(PhraseCfg), _P, _P]),

@@ -591,5 +591,6 @@ int launch_frontend_pk3_stream(int nc, const FrontendArgs& a, int n_items, hipSt
 #include "detect_grid.hip"
 #include "scan_select.hip"
 #include "mine.hip"
+#include "compose.hip"
 #include "phrase.hip"
 #include "resample.hip"
