@@ -21,10 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import TcrError
-
-
-def _stream_of(dev):
-    return torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+from .runtime import stream_of
 
 
 def pcm_energy(data: torch.Tensor, offsets, lengths, lib=None) -> torch.Tensor:
@@ -43,7 +40,7 @@ def pcm_energy(data: torch.Tensor, offsets, lengths, lib=None) -> torch.Tensor:
     out = torch.zeros(off.size, dtype=torch.int64, device=dev)
     if off.size:
         d_off, d_len = torch.from_numpy(np.ascontiguousarray(off)).to(dev), torch.from_numpy(np.ascontiguousarray(lens)).to(dev)
-        lib.check(lib.tcr_pcm_energy(data.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), int(off.size), out.data_ptr(), _stream_of(dev)),
+        lib.check(lib.tcr_pcm_energy(data.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), int(off.size), out.data_ptr(), stream_of(dev)),
                   "tcr_pcm_energy")
     return out
 
@@ -312,5 +309,5 @@ class Composer:
             p = lambda t: None if t is None else t.data_ptr()
             lib.check(lib.tcr_compose(N, keep[0].data_ptr(), total, self.pool.data.data_ptr(), *(t.data_ptr() for t in keep[1:]),
                                       self.background.data.data_ptr() if mixed else None, *([t.data_ptr() for t in bgt] or [None] * 4),
-                                      p(out), p(out_pcm), _stream_of(dev)), "tcr_compose")
+                                      p(out), p(out_pcm), stream_of(dev)), "tcr_compose")
         return ComposedRecordings(out, out_pcm, plan, self.label_names)

@@ -1,0 +1,194 @@
+"""Phrase detection from a scan's posteriors on the device (tcr_phrase_scores): `phrase_scores` over raw tensors, and `PhraseDetector`,
+which scores a `KeywordScanner`'s outputs into posteriors over P phrases and a background class and runs a `detection.DetectionStage`
+of P + 1 classes over them: the detector rule, `sweep`, `tune` and `mine`."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import TcrError
+from .detection import CascadeOutput, DetectionStage, RaggedScanOutput, ScanOutput, _new_tensors, ms_to_steps
+from .mining import MinedClips
+from .runtime import stream_of
+from .scoring import GridResult, SweepResult, _offsets
+
+BACKGROUND_LABEL = "_background_"
+PHRASE_COMBINERS = {"product": _lib.PHRASE_PRODUCT, "min": _lib.PHRASE_MIN}
+
+
+def phrase_scores(values: torch.Tensor, phrases: Sequence[Sequence[int]], window_steps: int, ordered: bool = True,
+                  combine: str = "product", step_offsets=None, lib=None) -> torch.Tensor:
+    """The raw form of tcr_phrase_scores(_ragged): values float32 on the device, [N, steps, C], or with step_offsets (host int64
+    [N + 1]) packed [total_steps, C] -- a scan's smoothed (or probs); phrases: lists of class indices.  Returns the phrase posteriors,
+    values' shape with P + 1 columns (the last: the background, 1 - the best phrase's score); see include/tcresnet_hip.h for the
+    score.  The call only enqueues a kernel."""
+    lib = _lib.get() if lib is None else lib
+    if combine not in PHRASE_COMBINERS:
+        raise TcrError(f"phrase_scores: combine must be one of {sorted(PHRASE_COMBINERS)}, got {combine!r}")
+    ragged = step_offsets is not None
+    if values.dtype != torch.float32 or not values.is_contiguous() or values.dim() != (2 if ragged else 3):
+        raise TcrError(f"phrase_scores expects contiguous float32 values {'[total_steps, C]' if ragged else '[N, steps, C]'}, got "
+                       f"{values.dtype} {tuple(values.shape)}")
+    words = [[int(c) for c in q] for q in phrases]
+    off = np.zeros(len(words) + 1, np.int32)
+    np.cumsum([len(q) for q in words], out=off[1:])
+    flat = np.ascontiguousarray(np.array([c for q in words for c in q] or [0], np.int32))
+    cfg = _lib.PhraseCfg(int(window_steps), int(bool(ordered)), PHRASE_COMBINERS[combine])
+    dev, ncls, P = values.device, int(values.shape[-1]), len(words)
+    out = torch.empty((*values.shape[:-1], P + 1), dtype=torch.float32, device=dev)
+    if ragged:
+        soff = _offsets("phrase_scores", "offsets", step_offsets, int(values.shape[0]), int64_only=True)
+        if int(values.shape[0]) == 0:
+            return out
+        off_dev = torch.from_numpy(soff).to(dev)
+        lib.check(lib.tcr_phrase_scores_ragged(int(soff.size) - 1, off_dev.data_ptr(), int(values.shape[0]), ncls, values.data_ptr(), P,
+                                               off.ctypes.data, flat.ctypes.data, C.byref(cfg), out.data_ptr(), stream_of(dev)),
+                  "tcr_phrase_scores_ragged")
+        return out
+    lib.check(lib.tcr_phrase_scores(int(values.shape[0]), int(values.shape[1]), ncls, values.data_ptr(), P, off.ctypes.data,
+                                    flat.ctypes.data, C.byref(cfg), out.data_ptr(), stream_of(dev)), "tcr_phrase_scores")
+    return out
+
+
+class PhraseSweepResult(SweepResult):
+    """A `SweepResult` over P phrases and the background class: `curve` and `operating_point` score the phrases only unless told
+    otherwise (the background's firings are how a phrase gets to fire again, not detections)."""
+    __slots__ = ()
+
+    def curve(self, classes: Optional[Sequence[int]] = None) -> Dict[str, np.ndarray]:
+        return super().curve(range(int(self.detections.shape[2]) - 1) if classes is None else classes)
+
+
+class PhraseGridResult(GridResult):
+    """A `GridResult` whose points' results are `PhraseSweepResult`s: `best` scores the phrases only by default."""
+
+    def result(self, j: int) -> PhraseSweepResult:
+        return PhraseSweepResult(*super().result(j))
+
+
+class PhraseDetector:
+    """Multi-word phrases ("go left", "stop ... no") detected from a scan's posteriors on the device (tcr_phrase_scores): a phrase's
+    score at a step is the best product (combine="product"; Chen et al. 2014) or minimum ("min") of its words' posteriors over the
+    last window_ms of steps, the words in order (ordered=True; Prabhavalkar et al. 2015) or each at its own maximum.  The scores are
+    posteriors over the phrases and a background class (1 - the best phrase's score), so the keyword stages apply to them with
+    P + 1 classes: `detect` is the detector rule over them, `sweep`, `tune` and `mine` are the scanner's.
+
+    scanner: the `KeywordScanner` whose outputs are scored (a cascade: its second scanner); phrases: a dict name -> words, or a list
+    of word lists (name: the words joined by a space); a word is a class index or one of `labels` (the model's class names).
+    window_ms becomes steps like the scanner's other ms settings (at least one); detection_threshold / suppression_ms: None takes the
+    scanner's.  `labels` here are the phrase names and "_background_" last.  With "product" a per-word confidence p corresponds to a
+    threshold of p ** n for a phrase of n words; "min" keeps thresholds on the single-word scale."""
+
+    def __init__(self, scanner, phrases, window_ms: float = 1500, ordered: bool = True, combine: str = "product",
+                 detection_threshold: Optional[float] = None, suppression_ms: Optional[float] = None,
+                 labels: Optional[Sequence[str]] = None):
+        if combine not in PHRASE_COMBINERS:
+            raise TcrError(f"PhraseDetector: combine must be one of {sorted(PHRASE_COMBINERS)}, got {combine!r}")
+        ncls = scanner.net.num_classes
+        known = {str(x): c for c, x in enumerate(labels)} if labels is not None else {}
+        items = list(phrases.items()) if isinstance(phrases, dict) else [(None, q) for q in phrases]
+        if not 1 <= len(items) <= _lib.PHRASE_MAX:
+            raise TcrError(f"PhraseDetector: {len(items)} phrases (1..{_lib.PHRASE_MAX})")
+        self.names, self.words = [], []
+        for name, q in items:
+            q = q.split() if isinstance(q, str) else list(q)
+            name = " ".join(str(x) for x in q) if name is None else str(name)
+            if not q:
+                raise TcrError(f"PhraseDetector: phrase {name!r} is empty")
+            if len(q) > _lib.PHRASE_MAX_WORDS:
+                raise TcrError(f"PhraseDetector: phrase {name!r} has {len(q)} words (1..{_lib.PHRASE_MAX_WORDS})")
+            cls = []
+            for x in q:
+                c = known.get(x) if isinstance(x, str) else int(x)
+                if c is None and isinstance(x, str) and labels is None and x.isdigit():
+                    c = int(x)
+                if c is None or not 0 <= c < ncls:
+                    raise TcrError(f"PhraseDetector: phrase {name!r}: unknown word {x!r} (classes 0..{ncls - 1}"
+                                   f"{'' if labels is None else ', labels ' + str(list(known))})")
+                cls.append(c)
+            if name in self.names or name == BACKGROUND_LABEL:
+                raise TcrError(f"PhraseDetector: duplicate phrase name {name!r}")
+            self.names.append(name)
+            self.words.append(cls)
+        self.scanner, self.lib, self.device = scanner, scanner.lib, scanner.device
+        self.labels = self.names + [BACKGROUND_LABEL]
+        self.ordered, self.combine = bool(ordered), combine
+        self.window_steps = max(1, ms_to_steps(window_ms, scanner.step_ms))
+        distinct = len({c for q in self.words for c in q})
+        w_max = self.lib.tcr_phrase_window_max(distinct)
+        if self.window_steps > w_max:
+            raise TcrError(f"PhraseDetector: window_ms {window_ms:g} is {self.window_steps} steps, above the {w_max} that "
+                           f"tcr_phrase_window_max allows for {distinct} distinct words")
+        st = scanner.stage
+        self.det = det = st.detect_cfg(0.0, 1, detection_threshold, suppression_ms)     # (one vector per decision: a posterior is its whole input)
+        self.stage = DetectionStage(st.lib, st.device, len(self.labels), st.step_samples, st.sample_rate, st.clip_samples, det)
+
+    @property
+    def num_classes(self) -> int:
+        """P + 1: the phrases and the background."""
+        return len(self.labels)
+
+    def _values(self, out, on: str) -> torch.Tensor:
+        if on not in ("smoothed", "probs"):
+            raise TcrError(f"PhraseDetector: on must be 'smoothed' or 'probs', got {on!r}")
+        v, ncls = getattr(out, on), self.scanner.net.num_classes
+        want_dim = 2 if isinstance(out, RaggedScanOutput) else 3
+        if v is None or v.dim() != want_dim or int(v.shape[-1]) != ncls:
+            raise TcrError(f"PhraseDetector: the output's {on} {None if v is None else tuple(v.shape)} is not a scan of the scanner's {ncls} "
+                           "classes")
+        self.scanner.net._check_tensor(v, f"phrase {on}")
+        return v
+
+    def scores(self, out, on: str = "smoothed") -> torch.Tensor:
+        """The phrase posteriors of `out` (a `ScanOutput`, `RaggedScanOutput` or `CascadeOutput` of the scanner): float32 shaped
+        like out.probs with P + 1 columns, from out's `on` ("smoothed", or "probs")."""
+        v = self._values(out, on)
+        return phrase_scores(v, self.words, self.window_steps, self.ordered, self.combine,
+                             out.offsets if isinstance(out, RaggedScanOutput) else None, self.lib)
+
+    def _is_detected(self, out) -> bool:
+        return out.logits is None and out.probs is not None and out.smoothed is out.probs and int(out.probs.shape[-1]) == self.num_classes
+
+    def detect(self, out, on: str = "smoothed"):
+        """The phrase detections of a scan: the same kind of output object over P + 1 classes -- logits None, probs and smoothed the
+        phrase posteriors (one tensor), top / score / is_new the detector rule over them (tcr_detect_redetect with average_steps =
+        min_count = 1 and this detector's threshold and suppression): a phrase fires when it is on top above the threshold, and again
+        only after the background (or another phrase) has been."""
+        ph = self.scores(out, on)
+        ragged = isinstance(out, RaggedScanOutput)
+        if ragged and int(ph.shape[0]) == 0:                # (no rows in all: nothing to launch, and the library refuses the call)
+            det = RaggedScanOutput(None, ph, ph, *_new_tensors((0,), 0, self.device, 0), out.offsets)
+        else:
+            posteriors = RaggedScanOutput(None, ph, None, None, None, None, out.offsets) if ragged else ScanOutput(None, ph, None, None, None, None)
+            det = self.stage.redetect(posteriors, smoothed=False)
+        if isinstance(out, CascadeOutput):
+            return CascadeOutput(*det.tensors(), out.offsets, out.selected, out.first)
+        return det
+
+    def _detected(self, out):
+        return out if self._is_detected(out) else self.detect(out)
+
+    def sweep(self, out, thresholds, events=None, lengths=None, tolerance_ms: float = 1000.0, return_fired: bool = False) -> PhraseSweepResult:
+        """`KeywordScanner.sweep` over the phrase detections of `out` (a scan's output, or `detect`'s): `detection_sweep` over their
+        top / score with P + 1 classes and this detector's suppression.  Events are (start_ms, end_ms, phrase name or index)."""
+        return PhraseSweepResult(*self.stage.sweep(self._detected(out), thresholds, events, lengths, tolerance_ms, return_fired, self.labels))
+
+    def tune(self, out, thresholds, suppression_ms: Sequence[float] = (), events=None, lengths=None,
+             tolerance_ms: float = 1000.0) -> PhraseGridResult:
+        """`KeywordScanner.tune` over the phrase posteriors of `out`: suppression_ms x thresholds in one `detection_grid` call (the
+        window and min_count stay one step).  Point j equals `sweep` of a detector built with suppression_ms[j]."""
+        g = self.stage.tune(self._detected(out), thresholds, suppression_ms=suppression_ms, events=events, lengths=lengths,
+                            tolerance_ms=tolerance_ms, labels=self.labels)
+        return PhraseGridResult(g.points, g.dropped, g.detections, g.hits, g.duplicates, g.thresholds, g.events, g.hours)
+
+    def mine(self, out, signals, events=None, k: int = 1000, source: str = "detections", kinds: Sequence[str] = ("false_accept",),
+             classes: Optional[Sequence[int]] = None, **kw) -> MinedClips:
+        """`KeywordScanner.mine` over the phrase detections of `out` (`signals`: the audio the scan read): the phrases that fired
+        outside any event, the missed events, the near misses.  classes: phrase indices (default: every phrase, never the
+        background); a clip ends at the step that fired (lead_ms moves it)."""
+        cls = list(range(len(self.names))) if classes is None else [int(c) for c in classes]
+        return self.stage.mine(self._detected(out), signals, events, k, source, kinds, cls, labels=self.labels, **kw)

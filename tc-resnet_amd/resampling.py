@@ -71,7 +71,7 @@ class Resampler:
         self.reset()
 
     def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else None
+        return runtime.stream_of(self.device)
 
     # ---- positions (host integers) ----------------------------------------------------------------------------------------------
     def out_length(self, n_in: int) -> int:

@@ -18,7 +18,9 @@ from typing import Iterable, NamedTuple, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from ._lib import FAMILY_DSCNN, FAMILY_G2D, FAMILY_TCRESNET, DetectCfg, ModelRef, TcrError, padded_len
+from ._lib import FAMILY_DSCNN, FAMILY_G2D, FAMILY_TCRESNET, ModelRef, TcrError, padded_len
+from .detection import (DEFAULT_MAX_WINDOWS, DetectionStage, _new_tensors, _ragged_scan_output, _ragged_signals,  # noqa: F401
+                        _scan_output, ms_to_steps)
 from .engine import DSCNN, Frontend, Graph2D, TCResNet
 
 Network = Union[TCResNet, DSCNN, Graph2D]
@@ -35,60 +37,10 @@ class StreamOutput(NamedTuple):
     is_new: torch.Tensor
 
 
-def ms_to_steps(ms: float, step_ms: float) -> int:
-    """Milliseconds -> whole steps (nearest)."""
-    return int(round(float(ms) / step_ms))
-
-
-def _ragged_signals(what: str, noun: str, signals, count: Optional[int] = None):
-    """The `signals` argument of `what` (scan_ragged, push_ragged) -> (packed, lengths, offsets in samples [N + 1]): a list of 1-D
-    tensors, one per `noun`, or (packed, lengths).  count: the signals the caller expects (None: any number, a list not empty)."""
-    if isinstance(signals, tuple) and len(signals) == 2 and isinstance(signals[0], torch.Tensor):
-        packed, lengths = signals[0], np.asarray(signals[1], dtype=np.int64).reshape(-1)
-        if packed.dim() != 1:
-            raise TcrError(f"{what} expects a packed 1-D tensor, got shape {tuple(packed.shape)}")
-    else:
-        signals = list(signals)
-        for n, x in enumerate(signals):
-            if not isinstance(x, torch.Tensor) or x.dim() != 1:
-                raise TcrError(f"{what} expects 1-D tensors, {noun} {n} is {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
-        lengths = np.array([int(x.shape[0]) for x in signals], dtype=np.int64)
-        if count is None and not signals:
-            raise TcrError(f"{what}: no signals")
-        packed = signals[0] if len(signals) == 1 else (torch.cat(signals) if signals else None)
-    if count is not None and int(lengths.size) != count:
-        raise TcrError(f"{what} expects {count} signals (one per stream, empty for a stream without steps), got {int(lengths.size)}")
-    offsets = np.zeros(int(lengths.size) + 1, dtype=np.int64)
-    np.cumsum(lengths, out=offsets[1:])
-    if int(offsets[-1]) != int(packed.shape[0]) and (lengths >= 0).all():
-        raise TcrError(f"{what}: the lengths sum to {int(offsets[-1])} samples, the packed tensor has {int(packed.shape[0])}")
-    return packed, lengths, offsets
-
-
-def _scan_output(n: int, steps: int, ncls: int, dev):
-    """A scanning.ScanOutput of new tensors for n signals x steps."""
-    from .scanning import ScanOutput
-    f32 = dict(dtype=torch.float32, device=dev)
-    i32 = dict(dtype=torch.int32, device=dev)
-    return ScanOutput(torch.empty((n, steps, ncls), **f32), torch.empty((n, steps, ncls), **f32), torch.empty((n, steps, ncls), **f32),
-                      torch.empty((n, steps), **i32), torch.empty((n, steps), **f32), torch.empty((n, steps), **i32))
-
-
-def _ragged_scan_output(lengths: np.ndarray, offsets: np.ndarray, step: int, ncls: int, dev):
-    """A scanning.RaggedScanOutput of new tensors for signals of `lengths` samples (`offsets`: their running sum) at `step` samples a
-    step; without rows when a length is no whole number of steps (the call refuses then, and the outputs are not written)."""
-    from .scanning import RaggedScanOutput
-    ok = lengths.size > 0 and bool((lengths >= 0).all()) and not (lengths % step).any()
-    total = int(offsets[-1]) // step if ok else 0
-    f32 = dict(dtype=torch.float32, device=dev)
-    i32 = dict(dtype=torch.int32, device=dev)
-    return RaggedScanOutput(torch.empty((total, ncls), **f32), torch.empty((total, ncls), **f32), torch.empty((total, ncls), **f32),
-                            torch.empty(total, **i32), torch.empty(total, **f32), torch.empty(total, **i32), offsets // step)
-
-
 class _Detection:
     """What `StreamingDetector` and `scanning.KeywordScanner` share: the argument checks, the detector settings in steps, the model
-    reference of the C calls and the weight / fold rules (see `StreamingDetector`)."""
+    reference of the C calls, the weight / fold rules (see `StreamingDetector`) and `stage`, the `detection.DetectionStage` over the net's
+    classes that `sweep` (and the scanner's `redetect`, `tune`, `mine`) delegate to."""
 
     def _setup(self, what: str, noun: str, net: Network, frontend: Frontend, frames_per_step: int, average_window_ms: float,
                min_count: int, detection_threshold: float, suppression_ms: float) -> None:
@@ -110,14 +62,10 @@ class _Detection:
         if not 1 <= self.k <= cfg.n_frames:
             raise TcrError(f"{what}: frames per step k = {self.k} outside 1..T = {cfg.n_frames}")
         self.step_samples = self.k * cfg.hop
-        self.step_ms = 1000.0 * self.step_samples / cfg.sample_rate
-        self.det = self._detect_cfg(average_window_ms, min_count, detection_threshold, suppression_ms)
+        self.stage = st = DetectionStage(self.lib, self.device, net.num_classes, self.step_samples, cfg.sample_rate, cfg.n_samples)
+        self.step_ms = st.step_ms
+        st.det = self.det = st.detect_cfg(average_window_ms, min_count, detection_threshold, suppression_ms)
         self._what, self._noun = what, noun
-
-    def _detect_cfg(self, average_window_ms: float, min_count: int, detection_threshold: float, suppression_ms: float) -> DetectCfg:
-        """The detector settings in steps (the nearest whole number; the averaging ring holds at least one vector)."""
-        return DetectCfg(max(1, ms_to_steps(average_window_ms, self.step_ms)), int(min_count),
-                         max(0, ms_to_steps(suppression_ms, self.step_ms)), float(detection_threshold))
 
     def _bind_frozen(self, frozen_ss: Optional[torch.Tensor]) -> None:
         net = self.net
@@ -198,66 +146,7 @@ class _Detection:
         `out` may be a scanning.RaggedScanOutput (`KeywordScanner.scan_ragged`): every signal is walked over its own rows, its events
         are relative to its own start, `fired` is [T, total_steps] and `hours` come from each signal's steps; `lengths` is refused,
         because the scan's lengths are the lengths."""
-        from .scanning import detection_sweep
-        ragged, valid, ev_steps = self._sweep_inputs(out, events, lengths, tolerance_ms, labels)
-        step, sr = self.step_samples, self.frontend.cfg.sample_rate
-        if ragged:
-            return detection_sweep(out.top, out.score, thresholds, self.suppression_steps, self.net.num_classes, ev_steps, None,
-                                   step / sr, return_fired, self.lib, step_offsets=out.offsets)
-        return detection_sweep(out.top, out.score, thresholds, self.suppression_steps, self.net.num_classes, ev_steps, valid,
-                               step / sr, return_fired, self.lib)
-
-    def _sweep_inputs(self, out, events, lengths, tolerance_ms: float, labels: Optional[Sequence[str]]):
-        """`sweep`'s (and `KeywordScanner.tune`'s) arguments in steps: (out is ragged, every signal's valid steps, the events as
-        inclusive step ranges per signal or None); the shapes come from out.probs where out.top is None."""
-        from .scanning import RaggedScanOutput, _first_steps, _last_steps
-        step, sr = self.step_samples, self.frontend.cfg.sample_rate
-        shape = out.top.shape if out.top is not None else out.probs.shape
-        ragged = isinstance(out, RaggedScanOutput)
-        if ragged:
-            if lengths is not None:
-                raise TcrError("sweep: lengths given with a ragged scan (the scan's lengths are the lengths)")
-            N, steps, valid = len(out), 0, out.steps
-            lengths = (valid * step).tolist()           # (the events below are checked against each signal's own end)
-        elif lengths is None:
-            N, steps = int(shape[0]), int(shape[1])
-            valid = np.full(N, steps, np.int64)
-        else:
-            N, steps = int(shape[0]), int(shape[1])
-            lens = np.asarray(lengths, np.int64).reshape(-1)
-            if lens.shape != (N,):
-                raise TcrError(f"sweep: {lens.size} lengths for {N} signals")
-            if (lens < 0).any() or (lens // step > steps).any():
-                raise TcrError(f"sweep: lengths outside 0..{steps * step} samples (the scan's): {lens.tolist()}")
-            valid = lens // step
-        ev_steps = None
-        if events is not None:
-            if len(events) != N:
-                raise TcrError(f"sweep: events for {len(events)} signals, the scan has {N}")
-            names = {str(x): c for c, x in enumerate(labels)} if labels is not None else {}
-            ncls, tol = self.net.num_classes, float(tolerance_ms)
-            ev_steps = []
-            for n, evs in enumerate(events):
-                length_ms = 1000.0 * (float(lengths[n]) if lengths is not None else float(steps * step)) / sr
-                cls = [names.get(e[2]) if isinstance(e[2], str) else int(e[2]) for e in evs]
-                for e, c in zip(evs, cls):
-                    if c is None or not 0 <= c < ncls:
-                        raise TcrError(f"sweep: signal {n}: event {tuple(e)} has an unknown label {e[2]!r}")
-                se = np.array([(float(e[0]), float(e[1])) for e in evs], np.float64).reshape(-1, 2)
-                bad = np.flatnonzero(~(se[:, 1] >= se[:, 0]))
-                if bad.size:
-                    raise TcrError(f"sweep: signal {n}: event {tuple(evs[bad[0]])} ends before it starts")
-                bad = np.flatnonzero(se[:, 0] > length_ms)
-                if bad.size:
-                    raise TcrError(f"sweep: signal {n}: event {tuple(evs[bad[0]])} starts past the signal's end ({length_ms:g} ms)")
-                order = np.lexsort((se[:, 1], se[:, 0]))
-                se, cls = se[order], np.asarray(cls, np.int64).reshape(-1)[order]
-                ov = np.flatnonzero(se[1:, 0] <= se[:-1, 1] + tol)
-                if ov.size:
-                    a, b = evs[order[ov[0]]], evs[order[ov[0] + 1]]
-                    raise TcrError(f"sweep: signal {n}: events {tuple(a)} and {tuple(b)} overlap with tolerance_ms = {tol:g}")
-                ev_steps.append(np.stack([_first_steps(se[:, 0], step, sr), _last_steps(se[:, 1] + tol, step, sr), cls], axis=1))
-        return ragged, valid, ev_steps
+        return self.stage.sweep(out, thresholds, events, lengths, tolerance_ms, return_fired, labels)
 
 
 class StreamingDetector(_Detection):
@@ -287,10 +176,7 @@ class StreamingDetector(_Detection):
         self._setup("StreamingDetector", "detector", net, frontend, frames_per_step, average_window_ms, min_count, detection_threshold,
                     suppression_ms)
         self.n_streams = int(n_streams)
-        if max_windows is None:
-            from .scanning import DEFAULT_MAX_WINDOWS
-            max_windows = DEFAULT_MAX_WINDOWS
-        self.max_windows, self.max_signals = int(max_windows), self.n_streams
+        self.max_windows, self.max_signals = int(DEFAULT_MAX_WINDOWS if max_windows is None else max_windows), self.n_streams
         self._scan_ws: Optional[torch.Tensor] = None
         self._ragged_ws: Optional[torch.Tensor] = None
         cfg = frontend.cfg
@@ -308,10 +194,7 @@ class StreamingDetector(_Detection):
         dev, ncls = self.device, net.num_classes
         self.state = torch.empty(nstate // 4, dtype=torch.float32, device=dev)
         self.workspace = torch.empty(nws // 4, dtype=torch.float32, device=dev)
-        f32 = dict(dtype=torch.float32, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        self.out = StreamOutput(torch.empty((S, ncls), **f32), torch.empty((S, ncls), **f32), torch.empty((S, ncls), **f32),
-                                torch.empty(S, **i32), torch.empty(S, **f32), torch.empty(S, **i32))
+        self.out = StreamOutput(*_new_tensors((S,), ncls, dev))
         self._reset_dev = torch.zeros(S, dtype=torch.uint8, device=dev)
         self._pending: Optional[np.ndarray] = None
         lib.check(lib.tcr_stream_init_m(C.byref(cfg), frontend.plan.data_ptr(), C.byref(ref), S, self.k, C.byref(self.det),

@@ -82,7 +82,7 @@ def check_detections(lib, c, thresholds=THRESHOLDS):
     Sc = scanning()
     sc, out, events = c["sc"], c["out"], c["events"]
     off, ncls = out.offsets, 12
-    _, _, ev_steps = sc._sweep_inputs(out, events, None, 0.0, None)
+    _, _, ev_steps = sc.stage.event_steps(out, events, None, 0.0, None)
     seen = set()
     for t in thresholds:
         r = sc.redetect(out, detection_threshold=t)

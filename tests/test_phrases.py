@@ -264,7 +264,7 @@ def test_sweep_tune_and_mine_reuse_the_keyword_stages(emu_lib):
     events = [[(18 * step_ms, 40 * step_ms, "two three")], [(27 * step_ms, 50 * step_ms, "three two"), (99 * step_ms, 120 * step_ms, 0)]]
     res = ph.sweep(out, thr, events=events, tolerance_ms=0.0)
     assert isinstance(res, Sc.PhraseSweepResult)
-    ev_steps = ph._view._sweep_inputs(det, events, None, 0.0, ph.labels)[2]
+    ev_steps = ph.stage.event_steps(det, events, None, 0.0, ph.labels)[2]
     raw = Sc.detection_sweep(det.top, det.score, thr, ph.det.suppression_steps, 3, ev_steps, None, scanner.step_samples / 16000.0, lib=emu_lib)
     for f in ("detections", "hits", "duplicates"):
         assert torch.equal(getattr(res, f), getattr(raw, f)), f
