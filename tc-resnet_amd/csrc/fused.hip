@@ -264,8 +264,6 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
     constexpr int WSTEP = 4 * COUT, XSTEP = 4 * TPI;
     const int out_sz = L.out_sz;
     const int res_sz = L.res_sz;
-    const float* scale = a.ss + L.ss_off;
-    const float* shift = scale + L.c_pad;
     int gg[NTJ], tt[NTJ];
     const float* xp[NTJ];
 #pragma unroll
@@ -276,12 +274,18 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
         xp[nt] = xin + gg[nt] * in_sz + q * TPI + tt[nt] * S + kHalo - PADLO;
     }
     const float* wp = w + q * COUT + min(m * 16 + r, COUT - 1);
+    // This lane's four output channels cob .. cob + 3: COUT % 4 == 0, so they are inside Cout or beyond it TOGETHER; a quad beyond it is
+    // clamped as a whole (its results go to the pad).  Scale / shift come through ONE buffer descriptor on the table -- a 32-bit lane
+    // offset and uniform offsets, eight loads off one address register -- where eight per-lane 64-bit addresses were built per job.
+    static_assert(COUT % 4 == 0, "a lane's four output channels are valid or invalid together");
+    const int cob = min(m * 16 + q * 4, COUT - 4);
+    const buf_rsrc sr = make_rsrc(a.ss);
+    const unsigned sl = (unsigned)cob * 4u;
     float sc[4], sh[4];
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
-        const int co = min(m * 16 + q * 4 + reg, COUT - 1);
-        sc[reg] = scale[co];
-        sh[reg] = shift[co];
+        sc[reg] = buf_load_f32(sr, sl, (unsigned)(L.ss_off + reg) * 4u);
+        sh[reg] = buf_load_f32(sr, sl, (unsigned)(L.ss_off + L.c_pad + reg) * 4u);
     }
     f32x4 acc[NTJ];
 #pragma unroll
@@ -293,16 +297,19 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
         // trade roles (taps unrolled by two: no copies): the NEXT tap's fragments are requested -- through a buffer descriptor: uniform
         // base + constant lane offset + uniform tap offset, no vector address arithmetic -- before this tap's LDS reads and MFMAs.  Same
         // accumulation order: bitwise.
-        const buf_rsrc wr = make_rsrc(w);
+        // (ONE descriptor on the parameter arena for every layer, the layer's offset in the uniform part: a descriptor per layer is four
+        //  scalar registers per layer held across the group loop)
+        const buf_rsrc wr = make_rsrc(a.params);
         const unsigned wl = (unsigned)(q * COUT + min(m * 16 + r, COUT - 1)) * 4u;
+        const unsigned wo = (unsigned)L.w_off * 4u;
         float w0[C4], w1[C4];
 #pragma unroll
-        for (int c4 = 0; c4 < C4; ++c4) w0[c4] = buf_load_f32(wr, wl, (unsigned)(c4 * WSTEP) * 4u);
+        for (int c4 = 0; c4 < C4; ++c4) w0[c4] = buf_load_f32(wr, wl, wo + (unsigned)(c4 * WSTEP) * 4u);
         auto tap = [&](const int j, const float (&wu)[C4], float (&wf)[C4], const bool fill) {
             TCR_WHATIF_PRIO(32768, 2);
             if (fill && !TCR_WHATIF(4096)) {
 #pragma unroll
-                for (int c4 = 0; c4 < C4; ++c4) wf[c4] = buf_load_f32(wr, wl, (unsigned)(((j + 1) * C4 + c4) * WSTEP) * 4u);
+                for (int c4 = 0; c4 < C4; ++c4) wf[c4] = buf_load_f32(wr, wl, wo + (unsigned)(((j + 1) * C4 + c4) * WSTEP) * 4u);
             }
             float b[NTJ][C4];
             if (TCR_WHATIF(8192) && j > 0) {
@@ -337,13 +344,22 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
             tap(K - 1, w1, w0, false);
         }
     } else {
-    // rolled taps, two half-tap weight sets refilled for the next tap (the round-2 loop)
+    // rolled taps, two half-tap weight sets refilled for the next tap (the round-2 loop).  Weights in global memory (`w` is
+    // a.params + L.w_off) are read through the buffer descriptor as in the lookahead form (constant lane offset + the tap's uniform
+    // offset: no 64-bit vector address per load); the small-batch kernel's weights are in LDS.
     constexpr int H0 = C4 / 2, H1 = C4 - H0;
+    const buf_rsrc wr = make_rsrc(a.params);
+    const unsigned wl = (unsigned)(q * COUT + min(m * 16 + r, COUT - 1)) * 4u;
+    const unsigned wo = (unsigned)L.w_off * 4u;
+    auto wld = [&](const int step) {
+        if constexpr (WLDS) return wp[step * WSTEP];
+        else return buf_load_f32(wr, wl, wo + (unsigned)(step * WSTEP) * 4u);
+    };
     float wa[H0 > 0 ? H0 : 1], wb[H1];
 #pragma unroll
-    for (int c4 = 0; c4 < H0; ++c4) wa[c4] = wp[c4 * WSTEP];
+    for (int c4 = 0; c4 < H0; ++c4) wa[c4] = wld(c4);
 #pragma unroll
-    for (int c4 = 0; c4 < H1; ++c4) wb[c4] = wp[(H0 + c4) * WSTEP];
+    for (int c4 = 0; c4 < H1; ++c4) wb[c4] = wld(H0 + c4);
     // (throughput kernels: rolled taps -- 128-register budget; small-batch kernel: unrolled, the LDS operand and weight reads of the
     //  following taps move ahead of the MFMAs)
     constexpr int kTapUnroll = WLDS ? K : 1;
@@ -362,7 +378,7 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
 #pragma unroll
                 for (int nt = 0; nt < NTJ; ++nt) acc[nt] = TCR_MFMA(wa[c4], b[nt][c4], acc[nt]);
 #pragma unroll
-            for (int c4 = 0; c4 < H0; ++c4) wa[c4] = wp[(jn * C4 + c4) * WSTEP];
+            for (int c4 = 0; c4 < H0; ++c4) wa[c4] = wld(jn * C4 + c4);
         }
         {
             float b[NTJ][H1];
@@ -375,36 +391,38 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
 #pragma unroll
                 for (int nt = 0; nt < NTJ; ++nt) acc[nt] = TCR_MFMA(wb[c4], b[nt][c4], acc[nt]);
 #pragma unroll
-            for (int c4 = 0; c4 < H1; ++c4) wb[c4] = wp[(jn * C4 + H0 + c4) * WSTEP];
+            for (int c4 = 0; c4 < H1; ++c4) wb[c4] = wld(jn * C4 + H0 + c4);
         }
     }
     }
     // ---- epilogue: folded BN (+ shortcut) (+ ReLU) -> LDS rows ----
-    const int dump = a.buf_off[2] + a.group * a.buf_sz[2] + (q * 16 + r);
+    // One address per tile and a channel pitch that is 0 in the lanes that store into the pad (the pad holds one float per lane): the four
+    // stores of a tile walk one pointer by that pitch, one add each, where every store chose between its row and the pad behind an exec-mask branch.
+    const int dump = a.buf_off[2] + a.group * a.buf_sz[2] + (q * 16 + r) - a.buf_off[L.out_buf];
     const float lo = L.relu ? 0.f : -3.4e38f;
+    const bool cv = COUT % 16 == 0 || m * 16 + q * 4 < COUT;
     float rv[NTJ][4];
     if (HAS_RES) {
 #pragma unroll
-        for (int nt = 0; nt < NTJ; ++nt)
+        for (int nt = 0; nt < NTJ; ++nt) {
+            const int rb = gg[nt] * res_sz + cob * TPO + kHalo + tt[nt];       // (clamped position, clamped quad: inside the rows)
 #pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int co = min(m * 16 + q * 4 + reg, COUT - 1);
-                rv[nt][reg] = res[gg[nt] * res_sz + co * TPO + kHalo + tt[nt]];
-            }
+            for (int reg = 0; reg < 4; ++reg) rv[nt][reg] = res[rb + reg * TPO];
+        }
     }
 #pragma unroll
     for (int nt = 0; nt < NTJ; ++nt) {
-        const bool pv = cc[nt] < npos;
+        const bool ok = cc[nt] < npos && cv && !TCR_WHATIF(32);
         const f32x4 ac = acc[nt];
-        const int base = gg[nt] * out_sz + kHalo + tt[nt];
+        float* po = yout + (ok ? gg[nt] * out_sz + kHalo + tt[nt] + cob * TPO : dump);
+        const int pitch = ok ? TPO : 0;
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
-            const int co = m * 16 + q * 4 + reg;
             float v = fmaf(ac[reg], sc[reg], sh[reg]);
             if (HAS_RES) v = fmaxf(v + rv[nt][reg], 0.f);       // tc_resnet.py:40-41
             else v = fmaxf(v, lo);
-            const bool ok = pv && (COUT % 16 == 0 || co < COUT) && !(TCR_WHATIF(32) && v != 12345.f);
-            yout[ok ? base + co * TPO : dump - a.buf_off[L.out_buf]] = v;
+            *po = v;
+            po += pitch;
         }
     }
 }
@@ -539,14 +557,14 @@ __device__ __forceinline__ void fused_layer_r(const FusedArgs& a, const FusedLay
     const int il_end = (IL && rem > 0 && rem <= 16) ? 2 * full : nt16;
     const FusedRun run = fused_deal_run(NRT, nt16, NW, wave);
     const int m = run.m;
-    const float* scale = a.ss + L.ss_off;
-    const float* shift = scale + L.c_pad;
+    static_assert(COUT % 4 == 0, "a lane's four output channels are valid or invalid together");
+    const buf_rsrc sr = make_rsrc(a.ss);                        // (scale / shift of the lane's channel quad: as fused_job_s)
+    const unsigned sl = (unsigned)min(m * 16 + q * 4, COUT - 4) * 4u;
     float sc[4], sh[4];
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
-        const int co = min(m * 16 + q * 4 + reg, COUT - 1);
-        sc[reg] = scale[co];
-        sh[reg] = shift[co];
+        sc[reg] = buf_load_f32(sr, sl, (unsigned)(L.ss_off + reg) * 4u);
+        sh[reg] = buf_load_f32(sr, sl, (unsigned)(L.ss_off + L.c_pad + reg) * 4u);
     }
     // this lane's position in column tile c -> (utterance of the group, frame); computed twice per unit, in front of the taps for the operand
     // address and again behind them for the stores, so that nothing but the address is live across the 9 x C4 MFMAs (the 128-register budget)
@@ -580,23 +598,23 @@ __device__ __forceinline__ void fused_layer_r(const FusedArgs& a, const FusedLay
         const bool pv = place(c, re, g, t);
         const int dump = a.buf_off[2] + a.group * a.buf_sz[2] + (qe * 16 + re) - a.buf_off[L.out_buf];
         const float lo = L.relu ? 0.f : -3.4e38f;
+        const int cob = min(m * 16 + qe * 4, COUT - 4);
         float rv[4];
         if (HAS_RES) {
+            const int rb = g * res_sz + cob * TPO + kHalo + t;
 #pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int co = min(m * 16 + qe * 4 + reg, COUT - 1);
-                rv[reg] = res[g * res_sz + co * TPO + kHalo + t];
-            }
+            for (int reg = 0; reg < 4; ++reg) rv[reg] = res[rb + reg * TPO];
         }
-        const int base = g * out_sz + kHalo + t;
+        const bool ok = pv && (COUT % 16 == 0 || m * 16 + qe * 4 < COUT) && !TCR_WHATIF(32);
+        float* po = yout + (ok ? g * out_sz + kHalo + t + cob * TPO : dump);
+        const int pitch = ok ? TPO : 0;
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
-            const int co = m * 16 + qe * 4 + reg;
             float v = fmaf(acc[reg], sc[reg], sh[reg]);
             if (HAS_RES) v = fmaxf(v + rv[reg], 0.f);       // tc_resnet.py:40-41
             else v = fmaxf(v, lo);
-            const bool ok = pv && (COUT % 16 == 0 || co < COUT) && !(TCR_WHATIF(32) && v != 12345.f);
-            yout[ok ? base + co * TPO : dump] = v;
+            *po = v;
+            po += pitch;
         }
     }
 }
@@ -822,6 +840,12 @@ __device__ __forceinline__ void fused_head(const FusedArgs& a, float* lds, const
 // TCResNet8-1.0 on 40 coefficients with every layer shape fixed at compile time (T0 = 49 or 98 frames): the flagship
 // configurations of BASELINE.json.  Same walk, same LDS plan (FusedArgs), bitwise the generic kernel's results.
 #define TCR_WAVES_PER_SIMD_4 TCR_WAVES_PER_SIMD(4)     // two 8-wave workgroups per CU: <= 128 VGPRs
+// Row LI of the layer table, read WHERE the layer runs: the index carries an opaque wave-uniform zero, so the row's fields are scalar
+// loads from the kernel-argument segment in front of the layer.  Indexed by the constant alone, every row of the table is loaded at the
+// kernel's entry and held across the group loop -- more scalar registers than there are: they were spilled into VGPR lanes at the entry
+// (v_writelane) and fetched back (v_readlane) inside the layers' loops.
+// (AT: per instance -- the forms that fit their scalar registers without it keep the plain index, see profiles/net_valu_kernel_regs.txt)
+#define TCR_LAYER_ROW(AT, LI) a.layer[(LI) + ((AT) ? __builtin_amdgcn_readfirstlane(opaque_zero()) : 0)]
 // WD < 0: the round-2 layer (A/B arm, TCR_TUNE_NET_FUSED = 4).  HALO: some consumer convolves this layer's rows (K > 1) and so reads
 // their zero halo; the shortcut convs' outputs (only ever a residual term) and the last block output (only pooled) skip the zero pass.
 template <int NW, int K, int S, int CIN, int COUT, int TIN, int WD, bool HAS_RES, bool HALO = true, int NTJ = 2, bool WLDS = false>
@@ -865,11 +889,12 @@ __global__ __launch_bounds__(NW * 64) TCR_WAVES_PER_SIMD_4 void net_fused_tc8_ke
     // (NTJ0 = 6: conv0_1 -- block 0's nine-tap layer of 24 input channels -- in its resident-weight form, fused_layer_r; every other layer as NTJ0 = 3)
     constexpr bool RES = WD >= 0 && NTJ0 == 6;
     constexpr int NTJU = RES ? 3 : NTJ0;
-#define TCR_TC8(LI, K_, S_, CI_, CO_, T_) fused_layer_sel<NW, K_, S_, CI_, CO_, T_, WD, (LI == 3 || LI == 6 || LI == 9), (K_ != 1 && LI != 9), ((LI >= 1 && LI <= 3 && NTJU == 4) ? 4 : (((NTJU == 0 || NTJU == 3) && K_ == 9) ? NTJU : 2))>(a, a.layer[LI], lds + a.buf_off[a.layer[LI].in_buf], a.layer[LI].in_sz, lds, ng, wave, r, q)
+#define TCR_TC8(LI, K_, S_, CI_, CO_, T_) do { const FusedLayer& L_ = TCR_LAYER_ROW(WD >= 0, LI); \
+        fused_layer_sel<NW, K_, S_, CI_, CO_, T_, WD, (LI == 3 || LI == 6 || LI == 9), (K_ != 1 && LI != 9), ((LI >= 1 && LI <= 3 && NTJU == 4) ? 4 : (((NTJU == 0 || NTJU == 3) && K_ == 9) ? NTJU : 2))>(a, L_, lds + a.buf_off[L_.in_buf], L_.in_sz, lds, ng, wave, r, q); } while (0)
     // (resident form of layer LI: halo zeros of its output rows, then the walk out of the set WS_ requested in front of the barrier)
-#define TCR_TC8_R(LI, S_, CI_, T_, WS_) do { \
-        fused_zero_halo<NT, 24, (T_ + S_ - 1) / S_>(lds + a.buf_off[a.layer[LI].out_buf], a.layer[LI].out_sz, ng, tid); \
-        fused_layer_r<NW, 9, S_, CI_, 24, T_, (LI == 3)>(a, a.layer[LI], lds + a.buf_off[a.layer[LI].in_buf], a.layer[LI].in_sz, lds, ng, wave, r, q, WS_); } while (0)
+#define TCR_TC8_R(LI, S_, CI_, T_, WS_) do { const FusedLayer& L_ = TCR_LAYER_ROW(true, LI); \
+        fused_zero_halo<NT, 24, (T_ + S_ - 1) / S_>(lds + a.buf_off[L_.out_buf], L_.out_sz, ng, tid); \
+        fused_layer_r<NW, 9, S_, CI_, 24, T_, (LI == 3)>(a, L_, lds + a.buf_off[L_.in_buf], L_.in_sz, lds, ng, wave, r, q, WS_); } while (0)
     for (int grp = blockIdx.x; grp < (TCR_WHATIF(512) ? 0 : a.n_groups); grp += gridDim.x) {
         const int n0 = grp * a.group;
         const int ng = min(a.group, a.batch - n0);
@@ -879,15 +904,16 @@ __global__ __launch_bounds__(NW * 64) TCR_WAVES_PER_SIMD_4 void net_fused_tc8_ke
 #endif
         if constexpr (WD < 0) fused_layer_sel<NW, 3, 1, 40, 16, T0, WD, false>(a, a.layer[0], a.feat + (size_t)n0 * row, row, lds, ng, wave, r, q);
         else if (!TCR_WHATIF(64)) {
-            fused_zero_halo<NT, 16, T0>(lds + a.buf_off[a.layer[0].out_buf], a.layer[0].out_sz, ng, tid);
-            fused_conv0_s<NW, T0>(a, a.layer[0], a.feat + (size_t)n0 * row, row, lds, ng, wave, r, q);
+            const FusedLayer& L0 = TCR_LAYER_ROW(true, 0);
+            fused_zero_halo<NT, 16, T0>(lds + a.buf_off[L0.out_buf], L0.out_sz, ng, tid);
+            fused_conv0_s<NW, T0>(a, L0, a.feat + (size_t)n0 * row, row, lds, ng, wave, r, q);
         }
         if constexpr (RES) {
             float ws3[9 * 6];
             TCR_TC8_BARRIER;
             TCR_TC8(1, 1, 2, 16, 24, T0);
             TCR_TC8(2, 9, 2, 16, 24, T0);
-            fused_resident_request<NW, 9, 24, 24>(a, a.layer[3], wave, r, q, ws3);      // (no job state is live here: the set costs no register of the budget)
+            fused_resident_request<NW, 9, 24, 24>(a, TCR_LAYER_ROW(true, 3), wave, r, q, ws3);      // (no job state is live here: the set costs no register of the budget)
             TCR_TC8_BARRIER;
             TCR_TC8_R(3, 1, 24, T1, ws3);
             TCR_TC8_BARRIER;
@@ -1039,7 +1065,8 @@ __global__ __launch_bounds__(NW * 64) TCR_WAVES_PER_SIMD_4 void net_fused_tc14w_
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, q = lane >> 4;
     const int row = a.in_c * a.in_tp;
-#define TCR_L(LI, K_, S_, CI_, CO_, T_, RES_, HALO_) fused_layer_sel<NW, K_, S_, CI_, CO_, T_, 0, RES_, HALO_, (K_ == 9 ? NTJ0 : 2)>(a, a.layer[LI], lds + a.buf_off[a.layer[LI].in_buf], a.layer[LI].in_sz, lds, ng, wave, r, q)
+#define TCR_L(LI, K_, S_, CI_, CO_, T_, RES_, HALO_) do { const FusedLayer& L_ = TCR_LAYER_ROW(NTJ0 == 13, LI); \
+        fused_layer_sel<NW, K_, S_, CI_, CO_, T_, 0, RES_, HALO_, (K_ == 9 ? NTJ0 : 2)>(a, L_, lds + a.buf_off[L_.in_buf], L_.in_sz, lds, ng, wave, r, q); } while (0)
     for (int grp = blockIdx.x; grp < a.n_groups; grp += gridDim.x) {
         const int n0 = grp * a.group;
         const int ng = min(a.group, a.batch - n0);
