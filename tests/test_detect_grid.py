@@ -1,6 +1,6 @@
 """Detector tuning from one scan (tcr_detect_redetect, tcr_detect_grid, KeywordScanner.redetect / tune, tune_audio.py): the detector
 tail run again on stored probabilities is bitwise the scan with those settings, and a grid's counts are the per-point sweeps'.
-Emulator (`-m "not gpu"`) and MI355X (`-m gpu`)."""
+Emulator (`-m "not gpu"`) and MI355X (`-m gpu`): the checks against the NumPy rule are functions of `lib` and run on both."""
 import csv
 import ctypes as C
 import io
@@ -116,8 +116,7 @@ def assert_same(got, want, what=""):
 
 
 # ---- 1. redetect against the rule ------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("ncls", [3, 5, 12])
-def test_redetect_equals_numpy_rule(emu_lib, ncls):
+def check_redetect_equals_numpy_rule(lib, ncls):
     N, steps = 3, 70
     rng = np.random.RandomState(100 + ncls)
     probs = np.stack([softmax_rows(rng, steps, ncls, runs=True) for _ in range(N)])
@@ -126,14 +125,19 @@ def test_redetect_equals_numpy_rule(emu_lib, ncls):
         for mc in sorted({1, W}):
             for supp in (0, 7):
                 want = [np.stack(x) for x in zip(*(np_detect(probs[n], W, mc, supp, thr) for n in range(N)))]
-                got = redetect_lib(emu_lib, probs, (W, mc, supp, thr))
+                got = redetect_lib(lib, probs, (W, mc, supp, thr))
                 for name, g, w in zip(("smoothed", "top", "score", "is_new"), got, want):
                     assert_same(g, w, (name, W, mc, supp))
                 assert want[3].sum() >= N
-                nov = redetect_lib(emu_lib, probs, (W, mc, supp, thr), smoothed=False)
+                nov = redetect_lib(lib, probs, (W, mc, supp, thr), smoothed=False)
                 assert (nov[0] == -7.0).all()                                    # smoothed == NULL: not written
                 for g, w in zip(nov[1:], want[1:]):
                     assert_same(g, w, ("no smoothed", W, mc, supp))
+
+
+@pytest.mark.parametrize("ncls", [3, 5, 12])
+def test_redetect_equals_numpy_rule(emu_lib, ncls):
+    check_redetect_equals_numpy_rule(emu_lib, ncls)
 
 
 # ---- 2. redetect of a real scan -------------------------------------------------------------------------------------------------------
@@ -184,7 +188,7 @@ def grid_lib(lib, probs, points, thr, offsets=None, events=None, valid=None, ws=
     return d.cpu().numpy(), h.cpu().numpy(), u.cpu().numpy()
 
 
-def test_ragged_signal_never_reads_its_predecessor(emu_lib):
+def check_ragged_signal_never_reads_its_predecessor(lib):
     ncls, W = 12, 9
     rng = np.random.RandomState(7)
     lens = [TILE + 30, TILE + 5]
@@ -193,17 +197,21 @@ def test_ragged_signal_never_reads_its_predecessor(emu_lib):
     off = [0, lens[0], sum(lens)]
     det, thr = (W, 2, 5, 0.2), [0.1, 0.2, 0.3]
     points = [(W, 2, 5), (W, 1, 0), (3, 1, 5)]
-    got = redetect_lib(emu_lib, probs, det, offsets=off)
-    alone = redetect_lib(emu_lib, probs[None, lens[0]:], det)
+    got = redetect_lib(lib, probs, det, offsets=off)
+    alone = redetect_lib(lib, probs[None, lens[0]:], det)
     for g, a in zip(got, alone):
         assert not np.isnan(g[lens[0]:].astype(np.float64)).any()
         assert_same(g[lens[0]:], a[0])
     assert np.isnan(got[0][lens[0] - 1]).all()            # (the poison is where it was put)
-    grid = grid_lib(emu_lib, probs, points, thr, offsets=off)
-    grid_alone = grid_lib(emu_lib, probs[None, lens[0]:], points, thr)
+    grid = grid_lib(lib, probs, points, thr, offsets=off)
+    grid_alone = grid_lib(lib, probs[None, lens[0]:], points, thr)
     for g, a in zip(grid, grid_alone):
         assert np.array_equal(g[:, 1], a[:, 0])
     assert grid_alone[0].sum() > 0
+
+
+def test_ragged_signal_never_reads_its_predecessor(emu_lib):
+    check_ragged_signal_never_reads_its_predecessor(emu_lib)
 
 
 # ---- 4. the grid equals the per-point sweeps -------------------------------------------------------------------------------------------
@@ -233,10 +241,9 @@ def assert_inputs_discriminate(points, tables):
     assert only(2) and only(1)
 
 
-def check_grid(lib, ncls, windows, seed, lens_ragged, thr):
+def check_grid(lib, ncls, windows, seed, lens_ragged, thr, steps=2 * TILE + 1):
     rng = np.random.RandomState(seed)
     points = [p for p in itertools.product(windows, (1, 3), (0, 25)) if p[1] <= p[0]]
-    steps = 2 * TILE + 1
     # dense with valid_steps (its edges 0, 1 and steps among them)
     valid = [0, 1, TILE - 1, TILE, TILE + 1, steps]
     made = [rows_with_events(rng, steps, ncls) for _ in valid]
@@ -274,21 +281,35 @@ def check_grid(lib, ncls, windows, seed, lens_ragged, thr):
 
 
 RAGGED_LENS = [TILE - 1, 0, TILE, 1, TILE + 1, 2 * TILE + 1]
+GRID_THR = [0.1, 0.2, 0.3, 0.45, 2.0]
+
+
+def check_grid_at_the_lds_limit_and_above(lib):
+    """60 classes: W = 13 is the last window the LDS-staged kernel takes, W = 14 the first of the per-pair path."""
+    assert w_max(60) == 13 and w_max(12) == 1089
+    check_grid(lib, 60, (13, 14), 22, RAGGED_LENS, [0.02, 0.05, 0.1, 0.2])
+
+
+def check_grid_eight_wide_body_and_long_halo(lib):
+    """Windows around the eight-at-a-time body of smooth_mean, and one whose halo (W - 1 = 256 rows) is longer than a tile."""
+    check_grid(lib, 12, (7, 8, 9, 257), 23, RAGGED_LENS + [3 * TILE + 1], GRID_THR, steps=3 * TILE + 1)
 
 
 def test_grid_equals_per_point_sweeps(emu_lib):
-    check_grid(emu_lib, 12, (3, 50), 21, RAGGED_LENS, [0.1, 0.2, 0.3, 0.45, 2.0])
+    check_grid(emu_lib, 12, (3, 50), 21, RAGGED_LENS, GRID_THR)
 
 
 def test_grid_at_the_lds_limit_and_above(emu_lib):
-    """60 classes: W = 13 is the last window the LDS-staged kernel takes, W = 14 the first of the per-pair path."""
-    assert w_max(60) == 13 and w_max(12) == 1089
-    check_grid(emu_lib, 60, (13, 14), 22, RAGGED_LENS, [0.02, 0.05, 0.1, 0.2])
+    check_grid_at_the_lds_limit_and_above(emu_lib)
+
+
+def test_grid_eight_wide_body_and_long_halo(emu_lib):
+    check_grid_eight_wide_body_and_long_halo(emu_lib)
 
 
 # ---- 5. workspace batching ---------------------------------------------------------------------------------------------------------------
-def test_grid_workspace_batches(emu_lib):
-    lib, ncls = emu_lib, 12
+def check_grid_workspace_batches(lib):
+    ncls = 12
     rng = np.random.RandomState(5)
     probs = np.stack([softmax_rows(rng, TILE + 40, ncls, runs=True) for _ in range(2)])
     points = [(3, 1, 0), (3, 3, 0), (20, 1, 9), (20, 3, 9), (50, 3, 0)]
@@ -304,6 +325,10 @@ def test_grid_workspace_batches(emu_lib):
         grid_lib(lib, probs, points, thr, ws=one - 1)
     assert lib.tcr_detect_grid_workspace_bytes(0, 1) == 0 and lib.tcr_last_error()
     assert lib.tcr_detect_grid_workspace_bytes(10, 0) == 0 and lib.tcr_last_error()
+
+
+def test_grid_workspace_batches(emu_lib):
+    check_grid_workspace_batches(emu_lib)
 
 
 # ---- 6. refusals ---------------------------------------------------------------------------------------------------------------------------
@@ -418,6 +443,37 @@ def test_scanner_tune_best_equals_brute_force(emu_lib):
 
 
 # ---- MI355X -------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("ncls", [3, 5, 12])
+def test_gpu_redetect_equals_numpy_rule(hip_lib, ncls):
+    check_redetect_equals_numpy_rule(hip_lib, ncls)
+
+
+@pytest.mark.gpu
+def test_gpu_ragged_signal_never_reads_its_predecessor(hip_lib):
+    check_ragged_signal_never_reads_its_predecessor(hip_lib)
+
+
+@pytest.mark.gpu
+def test_gpu_grid_equals_per_point_sweeps(hip_lib):
+    check_grid(hip_lib, 12, (3, 50), 21, RAGGED_LENS, GRID_THR)
+
+
+@pytest.mark.gpu
+def test_gpu_grid_at_the_lds_limit_and_above(hip_lib):
+    check_grid_at_the_lds_limit_and_above(hip_lib)
+
+
+@pytest.mark.gpu
+def test_gpu_grid_eight_wide_body_and_long_halo(hip_lib):
+    check_grid_eight_wide_body_and_long_halo(hip_lib)
+
+
+@pytest.mark.gpu
+def test_gpu_grid_workspace_batches(hip_lib):
+    check_grid_workspace_batches(hip_lib)
+
+
 @pytest.mark.gpu
 def test_gpu_redetect_and_grid_equal_device_scans(hip_lib):
     """4 x 30 s at 4020 (1500 steps: six tiles a signal), a 2 x 2 x 2 grid, 16 thresholds; dense, and ragged with an empty signal."""
