@@ -887,6 +887,56 @@ int tcr_phrase_scores_ragged(int n_signals, const int64_t* step_offsets /* DEVIC
                              const int32_t* phrase_words /* HOST */, const tcr_phrase_cfg* cfg, float* out /* [total_steps][P + 1] */,
                              void* stream);
 
+/* Streaming phrase detection: tcr_phrase_scores and the detector over its posteriors with the phrase window and the detector carried
+ * across calls, for S live streams (what tcr_stream_step / tcr_stream_scan / tcr_stream_scan_ragged wrote in smoothed or probs goes
+ * in as it comes).  State is caller-owned device memory of tcr_phrase_stream_state_bytes (0: invalid arguments, see tcr_last_error),
+ * filled by tcr_phrase_stream_init (every stream: no rows seen, prev_label = -1); it belongs to one (n_streams, num_classes, phrase
+ * tables, cfg), and the same values must be passed to every push.
+ * tcr_phrase_stream_push: values [S][steps][num_classes], `steps` new rows for every stream -> post [S][steps][P + 1], top / score /
+ * is_new [S][steps].  tcr_phrase_stream_push_ragged: stream s brings m_s = step_offsets[s + 1] - step_offsets[s] >= 0 rows, values and
+ * the four outputs packed [total_steps][..] with stream s's rows at step_offsets[s] .. (DEVICE int64 [S + 1], from 0, non-decreasing,
+ * step_offsets[S] == total_steps: preconditions, the host does not read the table).
+ * Contract: for stream s let R_s be all rows pushed to it since its init or last reset, in order.  The post rows a call writes for s
+ * are bitwise the corresponding (last) rows of tcr_phrase_scores(1, len(R_s), ..) over R_s -- the float32 operations and their order
+ * are the ones fixed above, evaluated over the same rows oldest first -- and top / score / is_new are bitwise tcr_detect_redetect
+ * over those posteriors with `det` (num_classes = P + 1): the rule of tcr_stream_step at average_steps = min_count = 1, with n,
+ * prev_label and prev_step carried.  So any way of cutting a stream into pushes gives the outputs of one whole scan, and after a call
+ * the state is what any other split of the same rows leaves; dense, ragged and one-step (steps = 1) calls mix freely on one state.
+ * reset [S] uint8 or NULL: reset[s] != 0 returns stream s to the initial state before its first row of this call.  In a ragged call
+ * a stream with m_s == 0 is untouched -- its state is byte for byte what it was -- and reset[s] is IGNORED for it (pass the flag again
+ * with the call that brings the stream's next row).  Streams are independent.  Precondition: fewer than 2^31 rows per stream since
+ * its reset.
+ * State: the detector integers [5][S] int32 as tcr_stream_step keeps them (head, count, prev_label, prev_step, n; at one vector per
+ * decision head stays 0 and count 1, and n is the rows the stream has seen), rounded up to 256 bytes, then a ring of the last w - 1
+ * rows, the U distinct word classes only, planar over the streams: float32 [w - 1][U][S], row r of a stream (counted from its
+ * reset) in slot r mod (w - 1).  A call writes only the slots of its new rows (the last w - 1 of them), in a launch of its own behind
+ * every reader of the old rows.
+ * How: a call that brings at most 4 rows per stream on average (a server's one-step pushes) runs a lane per row, phrases dealt to the
+ * waves of a workgroup, every window walked from the ring and `values` in global memory -- consecutive lanes are consecutive streams,
+ * so a dense one-step push reads consecutive addresses; a larger call (a recording in chunks) runs tcr_phrase_scores' tile kernel with
+ * the up to w - 1 rows in front of a stream's first tile staged from the ring.  The window limit stays tcr_phrase_window_max(U).
+ * Like the entries above these only enqueue kernels on `stream` (tcr_phrase_stream_init: a memset and a kernel) -- no copy, no wait,
+ * the phrase tables travel as kernel arguments -- so they can be captured into a graph.
+ * Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched, the state and the outputs are untouched): everything tcr_phrase_scores
+ * refuses (n_streams for N); a null state, det, post, top, score or is_new, a null step_offsets (ragged); det->average_steps != 1 or
+ * det->min_count != 1; det->suppression_steps < 0; n_streams <= 0; steps (ragged: total_steps) <= 0; steps in all x (P + 1) or
+ * x num_classes >= 2^31. */
+size_t tcr_phrase_stream_state_bytes(int n_streams, int num_classes, int n_phrases, const int32_t* phrase_offsets /* HOST [P + 1] */,
+                                     const int32_t* phrase_words /* HOST */, const tcr_phrase_cfg* cfg);
+int tcr_phrase_stream_init(int n_streams, int num_classes, int n_phrases, const int32_t* phrase_offsets /* HOST */,
+                           const int32_t* phrase_words /* HOST */, const tcr_phrase_cfg* cfg, void* state, void* stream);
+int tcr_phrase_stream_push(int n_streams, int64_t steps, int num_classes, const float* values /* [S][steps][C] */, int n_phrases,
+                           const int32_t* phrase_offsets /* HOST */, const int32_t* phrase_words /* HOST */, const tcr_phrase_cfg* cfg,
+                           const tcr_detect_cfg* det, const uint8_t* reset /* [S] or NULL */, void* state,
+                           float* post /* [S][steps][P + 1] */, int32_t* top, float* score, int32_t* is_new /* [S][steps] */,
+                           void* stream);
+int tcr_phrase_stream_push_ragged(int n_streams, const int64_t* step_offsets /* DEVICE [S + 1] */, int64_t total_steps,
+                                  int num_classes, const float* values /* packed [total_steps][C] */, int n_phrases,
+                                  const int32_t* phrase_offsets /* HOST */, const int32_t* phrase_words /* HOST */,
+                                  const tcr_phrase_cfg* cfg, const tcr_detect_cfg* det, const uint8_t* reset /* [S] or NULL */,
+                                  void* state, float* post /* [total_steps][P + 1] */, int32_t* top, float* score,
+                                  int32_t* is_new /* [total_steps] */, void* stream);
+
 /* Sample-rate conversion: a rational-ratio polyphase FIR in front of the detectors (which take float32 at the model's rate).
  * in_rate -> out_rate, g = gcd: up = L = out_rate / g, down = M = in_rate / g; taps = P per phase (even, or 1); table float32
  * [up][taps], designed on the host (tcresnet_amd.resampling.design_table: windowed sinc, fc = rolloff / max(1, M / L), Kaiser

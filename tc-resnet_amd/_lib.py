@@ -238,6 +238,12 @@ _PROTOTYPES = {
     "tcr_phrase_window_max": (C.c_int, [C.c_int]),
     "tcr_phrase_scores": (C.c_int, [C.c_int, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.POINTER(PhraseCfg), _P, _P]),
     "tcr_phrase_scores_ragged": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.POINTER(PhraseCfg), _P, _P]),
+    "tcr_phrase_stream_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(PhraseCfg)]),
+    "tcr_phrase_stream_init": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(PhraseCfg), _P, _P]),
+    "tcr_phrase_stream_push": (C.c_int, [C.c_int, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.POINTER(PhraseCfg), C.POINTER(DetectCfg), _P, _P, _P,
+                                         _P, _P, _P, _P]),
+    "tcr_phrase_stream_push_ragged": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.POINTER(PhraseCfg), C.POINTER(DetectCfg),
+                                                _P, _P, _P, _P, _P, _P, _P]),
     "tcr_resample": (C.c_int, [C.POINTER(ResampleCfg), _P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64,
                                _P]),
     "tcr_resample_span": (C.c_int, [C.POINTER(ResampleCfg), C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

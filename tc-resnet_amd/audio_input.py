@@ -202,7 +202,7 @@ def summary_line(rec: Recordings, counts: Dict[str, int], extra: Optional[Dict[s
 
 def add_detector_flags(p, each: str = "signal", threshold: bool = True, offline: bool = True, phrases: bool = False) -> None:
     """The model, input and detector flags of the three tools; `offline`: the scanning tools' --max_windows and --chunk_seconds;
-    `phrases`: scan_audio.py's and sweep_audio.py's --phrases flags (`open_phrases`)."""
+    `phrases`: the --phrases flags of scan_audio.py, sweep_audio.py and stream_audio.py (`open_phrases`)."""
     p.add_argument("--frozen", required=True, help="frozen artifact (.npz) of any model family exported with include_preprocess")
     p.add_argument("--wav", required=True, nargs="+", help=f"16-bit PCM WAV files, one {each} each")
     p.add_argument("--frames_per_step", type=int, default=1, help="new front-end frames per step (k)")
@@ -231,7 +231,7 @@ def add_detector_flags(p, each: str = "signal", threshold: bool = True, offline:
     if phrases:
         p.add_argument("--phrases", default=None,
                        help='detect phrases instead of single words: "go left;stop no" (words: --labels names or class indices), or @FILE '
-                            "with one phrase per line (scanning.PhraseDetector); not with --chunk_seconds / --ragged_chunk_seconds")
+                            "with one phrase per line (scanning.PhraseDetector)" + ("; not with --chunk_seconds / --ragged_chunk_seconds" if offline else ""))
         p.add_argument("--phrase_window_ms", type=float, default=1500.0, help="phrases: the window a phrase's words must fall in")
         p.add_argument("--phrase_unordered", action="store_true", help="phrases: the words in any order (default: in the given order)")
         p.add_argument("--phrase_combine", choices=("product", "min"), default="product",
@@ -296,16 +296,18 @@ def open_cascade(args):
 
 
 def check_phrase_flags(args) -> None:
-    """--phrases is refused with the chunked runs (before any model is loaded)."""
-    if getattr(args, "phrases", None) is not None and (args.chunk_seconds is not None or args.ragged_chunk_seconds is not None):
+    """--phrases is refused with the scanning tools' chunked runs (before any model is loaded); a tool without those flags
+    (stream_audio.py) has nothing to refuse."""
+    chunked = getattr(args, "chunk_seconds", None) is not None or getattr(args, "ragged_chunk_seconds", None) is not None
+    if getattr(args, "phrases", None) is not None and chunked:
         raise SystemExit("--phrases scores whole scans: it cannot be combined with --chunk_seconds or --ragged_chunk_seconds (a chunk's "
                          "first steps would need the previous chunk's rows)")
 
 
 def open_phrases(args, scanner):
-    """The `scanning.PhraseDetector` of --phrases over `scanner`'s outputs (None without the flag): its threshold and suppression are
-    the detector flags', its labels the phrase names and _background_.  Refused with the chunked runs: a chunk's first steps would
-    need the previous chunk's rows."""
+    """The `scanning.PhraseDetector` of --phrases over `scanner`'s outputs (a `KeywordScanner`, or stream_audio.py's
+    `StreamingDetector`; None without the flag): its threshold and suppression are the detector flags', its labels the phrase names
+    and _background_.  Refused with the scanning tools' chunked runs, which do not carry a phrase state yet."""
     check_phrase_flags(args)
     spec = getattr(args, "phrases", None)
     if spec is None:

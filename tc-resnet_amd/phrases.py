@@ -1,6 +1,8 @@
 """Phrase detection from a scan's posteriors on the device (tcr_phrase_scores): `phrase_scores` over raw tensors, and `PhraseDetector`,
 which scores a `KeywordScanner`'s outputs into posteriors over P phrases and a background class and runs a `detection.DetectionStage`
-of P + 1 classes over them: the detector rule, `sweep`, `tune` and `mine`."""
+of P + 1 classes over them: the detector rule, `sweep`, `tune` and `mine`.  `PhraseDetector.streaming` gives the same detector over the
+pushes of a `StreamingDetector` (`StreamingPhraseDetector`, tcr_phrase_stream_push): the phrase window and the detector are carried on
+the device, so any way of cutting the streams into pushes gives, bitwise, `detect` of the whole scan."""
 from __future__ import annotations
 
 import ctypes as C
@@ -15,6 +17,7 @@ from .detection import CascadeOutput, DetectionStage, RaggedScanOutput, ScanOutp
 from .mining import MinedClips
 from .runtime import stream_of
 from .scoring import GridResult, SweepResult, _offsets
+from .streaming import StreamOutput, reset_mask
 
 BACKGROUND_LABEL = "_background_"
 PHRASE_COMBINERS = {"product": _lib.PHRASE_PRODUCT, "min": _lib.PHRASE_MIN}
@@ -150,6 +153,11 @@ class PhraseDetector:
         return phrase_scores(v, self.words, self.window_steps, self.ordered, self.combine,
                              out.offsets if isinstance(out, RaggedScanOutput) else None, self.lib)
 
+    def streaming(self, n_streams: int) -> "StreamingPhraseDetector":
+        """This detector over the pushes of a `StreamingDetector` of n_streams streams: the same phrases, window, order, combine,
+        threshold and suppression, carried across pushes (`StreamingPhraseDetector`)."""
+        return StreamingPhraseDetector(self, n_streams)
+
     def _is_detected(self, out) -> bool:
         return out.logits is None and out.probs is not None and out.smoothed is out.probs and int(out.probs.shape[-1]) == self.num_classes
 
@@ -192,3 +200,108 @@ class PhraseDetector:
         background); a clip ends at the step that fired (lead_ms moves it)."""
         cls = list(range(len(self.names))) if classes is None else [int(c) for c in classes]
         return self.stage.mine(self._detected(out), signals, events, k, source, kinds, cls, labels=self.labels, **kw)
+
+
+class StreamingPhraseDetector:
+    """`PhraseDetector.detect` over live streams (tcr_phrase_stream_push): `push` takes what a `StreamingDetector` of the same streams
+    returned from `push`, `push_many` or `push_ragged` and returns the phrase detections of those steps.  The last window_steps - 1
+    rows of every stream's word posteriors and the detector's integers stay on the device, so however the streams are cut into
+    pushes, every stream's rows are bitwise `detector.detect` of one scan of everything pushed to it since its start or last `reset`;
+    the three forms mix freely.  Build it with `PhraseDetector.streaming(n_streams)`.
+
+    The outputs have `PhraseDetector.detect`'s form over P + 1 classes: logits None, probs and smoothed the phrase posteriors (one
+    tensor), top / score / is_new the detector rule.  A `StreamOutput` (one step) gives this object's own [S, ..] tensors, overwritten
+    by the next one-step push (copy what must survive it); a `ScanOutput` / `RaggedScanOutput` gives a new one, so outputs
+    concatenated over steps go into `PhraseDetector.sweep` / `tune` / `mine` unchanged."""
+
+    def __init__(self, detector: PhraseDetector, n_streams: int):
+        self.detector, self.lib, self.device = detector, detector.lib, detector.device
+        self.n_streams = S = int(n_streams)
+        if S <= 0:
+            raise TcrError(f"StreamingPhraseDetector: n_streams must be positive (got {S})")
+        self.labels, self.num_classes = detector.labels, detector.num_classes
+        self._classes = detector.scanner.net.num_classes
+        words = detector.words
+        self._off = np.zeros(len(words) + 1, np.int32)
+        np.cumsum([len(q) for q in words], out=self._off[1:])
+        self._flat = np.ascontiguousarray(np.array([c for q in words for c in q], np.int32))
+        self._cfg = _lib.PhraseCfg(detector.window_steps, int(detector.ordered), PHRASE_COMBINERS[detector.combine])
+        lib, dev = self.lib, self.device
+        nstate = lib.tcr_phrase_stream_state_bytes(S, self._classes, *self._tables())
+        if nstate == 0:
+            raise TcrError(f"StreamingPhraseDetector: {lib.tcr_last_error().decode()}")
+        self.state = torch.empty(nstate // 4, dtype=torch.float32, device=dev)
+        post, top, score, is_new = _new_tensors((S,), self.num_classes, dev, 1)
+        self.out = StreamOutput(None, post, post, top, score, is_new)
+        self._reset_dev = torch.zeros(S, dtype=torch.uint8, device=dev)
+        self._pending: Optional[np.ndarray] = None
+        lib.check(lib.tcr_phrase_stream_init(S, self._classes, *self._tables(), self.state.data_ptr(), stream_of(dev)), "tcr_phrase_stream_init")
+
+    def _tables(self):
+        return len(self._off) - 1, self._off.ctypes.data, self._flat.ctypes.data, C.byref(self._cfg)
+
+    def reset(self, mask_or_indices) -> None:
+        """Return streams to the start (no rows seen, no detection yet) at their NEXT pushed row, before it: `StreamingDetector.reset`'s
+        argument and rules -- a bool / uint8 mask of S entries or stream indices; a reset stays pending for a stream that has no
+        rows in a ragged push."""
+        mask = reset_mask(mask_or_indices, self.n_streams)
+        self._pending = mask if self._pending is None else (self._pending | mask)
+
+    def _take_reset(self) -> Optional[int]:
+        if self._pending is None:
+            return None
+        self._reset_dev.copy_(torch.from_numpy(self._pending.astype(np.uint8)))
+        self._pending = None
+        return self._reset_dev.data_ptr()
+
+    def _values(self, out, on: str) -> torch.Tensor:
+        if on not in ("smoothed", "probs"):
+            raise TcrError(f"StreamingPhraseDetector: on must be 'smoothed' or 'probs', got {on!r}")
+        v, S, ncls = getattr(out, on), self.n_streams, self._classes
+        if v is None or int(v.shape[-1]) != ncls:
+            raise TcrError(f"StreamingPhraseDetector: the output's {on} {None if v is None else tuple(v.shape)} is not over the detector's "
+                           f"{ncls} classes")
+        if isinstance(out, RaggedScanOutput):
+            ok = v.dim() == 2 and len(out) == S
+        else:
+            ok = v.dim() == (2 if isinstance(out, StreamOutput) else 3) and int(v.shape[0]) == S
+        if not ok:
+            raise TcrError(f"StreamingPhraseDetector: the output's {on} {tuple(v.shape)} is not a push of {S} streams")
+        self.detector.scanner.net._check_tensor(v, f"phrase {on}")
+        return v
+
+    def push(self, out, on: str = "smoothed"):
+        """The phrase detections of the steps in `out`, what the `StreamingDetector` returned: a `StreamOutput` (`push`: one step ->
+        this object's own `StreamOutput`), a `ScanOutput` (`push_many` -> a new `ScanOutput`) or a `RaggedScanOutput` (`push_ragged` ->
+        a new `RaggedScanOutput` with out's offsets), read from out's `on` ("smoothed", or "probs").  Pending `reset`s apply before a
+        stream's first row of the call.  The call only enqueues kernels."""
+        v = self._values(out, on)
+        lib, dev, S, K = self.lib, self.device, self.n_streams, self.num_classes
+        det = C.byref(self.detector.det)
+        if isinstance(out, RaggedScanOutput):
+            post, top, score, is_new = _new_tensors((int(v.shape[0]),), K, dev, 1)
+            res = RaggedScanOutput(None, post, post, top, score, is_new, out.offsets)
+            if int(v.shape[0]) == 0:                            # (no rows in all: nothing to launch; the resets stay pending)
+                return res
+            off_dev = torch.from_numpy(res.offsets).to(dev)
+            pending, reset_ptr = self._pending, self._take_reset()
+            self._pending = pending                             # (until the call has run; it ignores the flag of a stream without rows)
+            lib.check(lib.tcr_phrase_stream_push_ragged(S, off_dev.data_ptr(), int(v.shape[0]), self._classes, v.data_ptr(), *self._tables(), det,
+                                                        reset_ptr, self.state.data_ptr(), post.data_ptr(), top.data_ptr(), score.data_ptr(),
+                                                        is_new.data_ptr(), stream_of(dev)), "tcr_phrase_stream_push_ragged")
+            if pending is not None:
+                left = pending & (res.steps == 0)
+                self._pending = left if left.any() else None
+            return res
+        if isinstance(out, StreamOutput):
+            res, steps = self.out, 1
+        else:
+            steps = int(v.shape[1])
+            post, top, score, is_new = _new_tensors((S, steps), K, dev, 1)
+            res = ScanOutput(None, post, post, top, score, is_new)
+            if steps == 0:
+                return res
+        lib.check(lib.tcr_phrase_stream_push(S, steps, self._classes, v.data_ptr(), *self._tables(), det, self._take_reset(), self.state.data_ptr(),
+                                             res.probs.data_ptr(), res.top.data_ptr(), res.score.data_ptr(), res.is_new.data_ptr(),
+                                             stream_of(dev)), "tcr_phrase_stream_push")
+        return res

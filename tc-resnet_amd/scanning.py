@@ -25,7 +25,7 @@ class, on which the detector rule, `sweep`, `tune` and `mine` run with P + 1 cla
 
 This module holds the scanners and the cascade; the rest is importable from here and lives in `detection` (the outputs, the ms / step
 arithmetic and `DetectionStage`: `redetect`, `sweep`, `tune`, `mine` over a scan's outputs, no network needed), `scoring` (`detection_sweep`,
-`detection_grid`, their results), `mining` (`mine_*`, `select_top`, `gather_clips`, `MinedClips`) and `phrases` (`PhraseDetector`).
+`detection_grid`, their results), `mining` (`mine_*`, `select_top`, `gather_clips`, `MinedClips`) and `phrases` (`PhraseDetector`, `StreamingPhraseDetector`).
 """
 from __future__ import annotations
 
@@ -42,7 +42,7 @@ from .detection import (DEFAULT_MAX_WINDOWS, CascadeOutput, RaggedScanOutput, Sc
                         _scan_output, ms_to_steps)
 from .engine import Frontend
 from .mining import MINE_KINDS, MinedClips, MinedDetections, MinedPeaks, gather_clips, mine_detections, mine_peaks, select_top  # noqa: F401
-from .phrases import BACKGROUND_LABEL, PHRASE_COMBINERS, PhraseDetector, PhraseGridResult, PhraseSweepResult, phrase_scores  # noqa: F401
+from .phrases import BACKGROUND_LABEL, PHRASE_COMBINERS, PhraseDetector, PhraseGridResult, PhraseSweepResult, StreamingPhraseDetector, phrase_scores  # noqa: F401
 from .runtime import stream_of
 from .scoring import GridPoint, GridResult, SweepResult, _class_mask, _offsets, detection_grid, detection_sweep  # noqa: F401
 from .streaming import Network, _Detection

@@ -37,6 +37,24 @@ class StreamOutput(NamedTuple):
     is_new: torch.Tensor
 
 
+def reset_mask(mask_or_indices, n_streams: int) -> np.ndarray:
+    """The `reset` argument of the streaming detectors as a bool mask [n_streams]: a bool / uint8 mask of that many entries, or
+    stream indices (any other integer type)."""
+    if isinstance(mask_or_indices, torch.Tensor):
+        mask_or_indices = mask_or_indices.cpu().numpy()
+    arr = np.asarray(mask_or_indices if not isinstance(mask_or_indices, (set, frozenset)) else sorted(mask_or_indices))
+    if arr.dtype in (np.bool_, np.uint8):
+        if arr.shape != (n_streams,):
+            raise TcrError(f"reset mask must have {n_streams} entries, got shape {arr.shape}")
+        return arr.astype(bool)
+    idx = arr.astype(np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() >= n_streams):
+        raise TcrError(f"reset: stream index outside 0..{n_streams - 1}")
+    mask = np.zeros(n_streams, bool)
+    mask[idx] = True
+    return mask
+
+
 class _Detection:
     """What `StreamingDetector` and `scanning.KeywordScanner` share: the argument checks, the detector settings in steps, the model
     reference of the C calls, the weight / fold rules (see `StreamingDetector`) and `stage`, the `detection.DetectionStage` over the net's
@@ -205,19 +223,7 @@ class StreamingDetector(_Detection):
     def reset(self, mask_or_indices: Union[np.ndarray, torch.Tensor, Iterable[int]]) -> None:
         """Return streams to the initial state (a silent clip, empty ring, no detection yet) at the NEXT push, before its samples
         are appended.  A bool / uint8 mask of S entries, or stream indices (any other integer type)."""
-        if isinstance(mask_or_indices, torch.Tensor):
-            mask_or_indices = mask_or_indices.cpu().numpy()
-        arr = np.asarray(mask_or_indices if not isinstance(mask_or_indices, (set, frozenset)) else sorted(mask_or_indices))
-        if arr.dtype in (np.bool_, np.uint8):
-            if arr.shape != (self.n_streams,):
-                raise TcrError(f"reset mask must have {self.n_streams} entries, got shape {arr.shape}")
-            mask = arr.astype(bool)
-        else:
-            idx = arr.astype(np.int64).reshape(-1)
-            if idx.size and (idx.min() < 0 or idx.max() >= self.n_streams):
-                raise TcrError(f"reset: stream index outside 0..{self.n_streams - 1}")
-            mask = np.zeros(self.n_streams, bool)
-            mask[idx] = True
+        mask = reset_mask(mask_or_indices, self.n_streams)
         self._pending = mask if self._pending is None else (self._pending | mask)
 
     def _take_reset(self) -> Optional[int]:
