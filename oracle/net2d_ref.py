@@ -31,7 +31,7 @@ DT = torch.float64
 # `KINK_LOG["decide"]`: optional list, one entry per ReLU in call order, of boolean tensors "the implementation under test kept
 # this element" -- consulted ONLY for the elements within `tau` of zero, so that the float64 gradient is taken on the same side of
 # those kinks as the implementation's (every other element keeps its own sign; a wrong mask elsewhere is still caught).
-KINK_LOG = {"on": False, "tau": 1e-5, "near": 0, "total": 0, "decide": None, "idx": 0, "followed": 0}
+KINK_LOG = {"on": False, "tau": 1e-5, "near": 0, "total": 0, "decide": None, "idx": 0, "followed": 0, "min": float("inf")}
 
 
 def _relu(x):
@@ -40,6 +40,7 @@ def _relu(x):
         n_near = int(near.sum())
         KINK_LOG["near"] += n_near
         KINK_LOG["total"] += x.numel()
+        KINK_LOG["min"] = min(KINK_LOG["min"], float(x.detach().abs().min()))     # the closest ReLU input so far
         dec = KINK_LOG["decide"]
         if dec is not None:
             kept = dec[KINK_LOG["idx"]]

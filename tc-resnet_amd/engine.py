@@ -387,7 +387,7 @@ class TCResNet(_Base):
         tensors): validates, folds BN and allocates once -- through one ordinary `forward_waveform` -- and returns a zero-argument callable
         that issues the single C-ABI call with the pointers bound, on the stream that was current when it was prepared.  What a C / C++
         host of the ABI does per utterance; `forward_waveform` itself spends more time in Python than the GPU spends on the utterance.
-        The callable refuses to run once the variables or moving statistics have changed (prepare again) -- the folded table it bound
+        The callable refuses to run once the variables or moving statistics have changed or been rebound (prepare again) -- the folded table it bound
         belongs to the weights it was prepared for."""
         logits, probs = out
         self.forward_waveform(frontend, wav, out=out, feat=feat)
@@ -405,7 +405,8 @@ class TCResNet(_Base):
         params, stats, kver = self.params, self.stats, (self.params._version, self.stats._version, self._kver)
 
         def call(_keep=keep):
-            if (params._version, stats._version, self._kver) != kver:
+            # (`is`: the arenas the pointers were taken from are still the net's -- `net.params = other` leaves the bound one untouched)
+            if self.params is not params or self.stats is not stats or (params._version, stats._version, self._kver) != kver:
                 raise TcrError("waveform_call: the variables / moving statistics changed since the call was prepared; prepare it again")
             rc = fn(*args)
             if rc:
