@@ -712,6 +712,55 @@ int tcr_scan_select(int n_signals, const int64_t* step_offsets /* DEVICE [N + 1]
                     int pad_before, int pad_after, void* workspace, size_t ws_bytes, int64_t* selected /* DEVICE */,
                     int64_t* n_selected /* DEVICE [1] */, uint8_t* mask /* [total_steps] or NULL */, void* stream);
 
+/* Streaming cascades: the causal cascade -- tcr_scan_select at pad_before = 0, a second model on the selected steps, its detector
+ * over the merged posteriors -- carried from step to step over S concurrent streams.  A stream cannot be rescored before its flag,
+ * so pad_before is 0 by definition: at a flag the detector's average mixes first-stage rows from before it with second-stage rows
+ * from it on.  Per step: the first detector's tcr_stream_step_m (unchanged, its own state), tcr_stream_select over its probs or
+ * smoothed, a read-back of n_selected by the host (one small copy and wait per step: a cascade step cannot be captured into a
+ * graph), then tcr_stream_step_selected_m of the second detector with the first one's logits / probs as fill rows.  The steps
+ * stacked over time are bitwise the cascade scan of the whole signals at pad_before = 0.
+ *
+ * tcr_stream_select: values [S][num_classes] are the first stage's probs or smoothed of this step.  Stream s is FLAGGED when some
+ * class c with class_mask[c] != 0 has values[s][c] >= enter (a float32 compare: a NaN never flags), and SELECTED when it was flagged
+ * at this step or at one of the pad_after steps before it since its last reset.  The carried state is since [S] int32 (DEVICE): the
+ * steps since the stream's last flag, saturating, INT32_MAX = never; tcr_stream_select_init sets every entry to never, and reset [S]
+ * uint8 (or NULL) sets a stream's entry to never BEFORE the step, as tcr_stream_step applies resets.  selected (DEVICE int64, room
+ * for S) receives the selected stream indices in increasing order, n_selected (DEVICE [1]) their number, mask (DEVICE [S] or NULL) 1
+ * at the selected streams and 0 elsewhere.  enter = -inf selects every stream whose masked values are not all NaN, +inf none.  No
+ * floating-point arithmetic beyond the compare; the order comes from prefix sums in kernels of their own (no atomics, no workgroup
+ * waits for another).  Everything is enqueued on `stream` -- no copy, no wait.
+ * Workspace: tcr_stream_select_workspace_bytes(S) (0: S <= 0); TCR_ERR_WORKSPACE below it.
+ * Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched): null values / class_mask / since / workspace / selected / n_selected,
+ * S <= 0, num_classes outside 1 .. 256, NaN enter, a negative pad_after.
+ *
+ * tcr_stream_step_selected_m: a step of tcr_stream_step_m (the same arguments up to ws_bytes, the same outputs) on an ordinary
+ * tcr_stream_init_m state, in which the network runs only on the n_selected (HOST) streams of selected (DEVICE int64, strictly
+ * increasing, in 0 .. S - 1: preconditions), at batch n_selected, on their windows gathered into the workspace.  For any selection
+ * the stage / shift and the front-end run for all S streams, so the window and the tail of every stream are bitwise what
+ * tcr_stream_step_m leaves; a selected stream's logits / probs row is bitwise that step's row (a window's result does not depend on
+ * its batch); every other stream's row is its row of fill_logits / fill_probs [S][num_classes], bit for bit; and the detector
+ * (tcr_stream_step's rule, the ring and the five integers of this state) runs over the merged probs of all S streams.  With all S
+ * streams selected the call is bitwise tcr_stream_step_m, for the six outputs and every byte of `state` (the fill rows may then be
+ * NULL); with n_selected == 0 no gather and no network kernel is launched.  Calls of tcr_stream_step_m, tcr_stream_scan_m and
+ * tcr_stream_step_selected_m may be mixed on one state in any order.  Fill rows that alias the outputs are undefined.
+ * Workspace: tcr_stream_selected_workspace_bytes_m (the staging rows, the gathered windows, the compact rows and the network at
+ * batch S; 0: invalid arguments); TCR_ERR_WORKSPACE below it.  Everything is enqueued on `stream`.
+ * Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched): everything tcr_stream_step_m refuses, n_selected outside 0 .. S, null
+ * selected with n_selected > 0, null fill rows with n_selected < S. */
+int tcr_stream_select_init(int n_streams, int32_t* since /* DEVICE [S] */, void* stream);
+size_t tcr_stream_select_workspace_bytes(int n_streams);
+int tcr_stream_select(int n_streams, int num_classes, const float* values /* [S][C] */, const uint8_t* class_mask /* DEVICE [C] */,
+                      float enter, int pad_after, const uint8_t* reset /* [S] or NULL */, int32_t* since /* [S] */, void* workspace,
+                      size_t ws_bytes, int64_t* selected /* DEVICE [S] */, int64_t* n_selected /* DEVICE [1] */,
+                      uint8_t* mask /* [S] or NULL */, void* stream);
+size_t tcr_stream_selected_workspace_bytes_m(const tcr_frontend_cfg* cfg, const tcr_model_ref* model, int n_streams, int k);
+int tcr_stream_step_selected_m(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_model_ref* model, int n_streams, int k,
+                               const tcr_detect_cfg* det, const float* samples, const uint8_t* reset, void* state, void* workspace,
+                               size_t ws_bytes, const int64_t* selected /* DEVICE */, int64_t n_selected /* HOST */,
+                               const float* fill_logits, const float* fill_probs /* [S][C]; NULL allowed when n_selected == S */,
+                               float* logits, float* probs, float* smoothed, int32_t* top, float* score, int32_t* is_new,
+                               void* stream);
+
 /* Hard-example mining: the windows a scan got wrong, the best of them, and their audio.  All layouts are the ragged ones: step_offsets
  * is a DEVICE table as tcr_detect_redetect_ragged takes it (a dense scan: step_offsets[n] = n x steps); every pointer is device memory
  * unless marked HOST; everything is enqueued on `stream` -- no copy, no wait -- and every result is deterministic: the tables are

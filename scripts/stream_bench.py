@@ -7,6 +7,13 @@ followed by the engine's forward_infer.
     python scripts/stream_bench.py [--iters 400] [--reps 5] [--out profiles/stream_bench.json]
     python scripts/stream_bench.py --model DSCNN-L [--out profiles/stream_bench_dscnn_l.json]
     python scripts/stream_bench.py --trace_one 4096         # one config, a few steps (for rocprofv3 --kernel-trace --stats)
+    python scripts/stream_bench.py --cascade [--out profiles/stream_cascade_bench.json]
+
+--cascade: a streaming cascade (streaming.StreamingCascade) over S = 4096 streams, TCResNet8-1.0 at 30 / 10 ms and k = 2 in front of
+DS-CNN-L at 40 / 20 ms and k = 1 (both steps are 320 samples), pad_after = 0.  The enter thresholds are quantiles of the first stage's
+keyword peak over a warm-up, so that about 0 %, 1 %, 5 %, 25 % and 100 % of the streams are selected per step; per threshold the
+cascade push, the same three calls without the read-back of n_selected (a fixed count: what the read-back costs), and, in the same
+run, first.push alone and second.push alone.  The audio is noise at a level of its own per stream and step, cycled from 16 buffers.
 
 Each number is the median over --reps windows of --iters back-to-back calls, timed with device events after a warm-up of the
 same calls.  Weights are random (timing does not depend on them)."""
@@ -76,6 +83,75 @@ def time_calls(fn, iters):
     return a.elapsed_time(b) * 1000.0 / iters        # us per call
 
 
+def cascade_leg(args, dev):
+    from tcresnet_amd.streaming import StreamingCascade
+    S, n_buf = args.cascade_streams, 16
+    fe1, net1 = build(480, 160, "TCResNet8", 1.0, dev)
+    _, fe2, net2 = build_model("DSCNN-L", dev)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    bufs = [((torch.rand((S, 320), device=dev, generator=gen) - 0.5) * torch.rand((S, 1), device=dev, generator=gen) * 1.2).contiguous()
+            for _ in range(n_buf)]
+    state = {"i": 0}
+
+    def audio():
+        state["i"] = (state["i"] + 1) % n_buf
+        return bufs[state["i"]]
+
+    first, second = StreamingDetector(net1, fe1, S, frames_per_step=2), StreamingDetector(net2, fe2, S)
+    peaks = []
+    for i in range(args.warmup + 4 * n_buf):
+        x = audio()
+        out = first.push(x)
+        second.push(x)
+        if i >= args.warmup:
+            peaks.append(out.probs[:, 2:].max(dim=1).values.cpu().numpy())
+    peaks = np.concatenate(peaks)
+
+    def median_of(fn):
+        ts = [time_calls(fn, args.iters) for _ in range(args.reps)]
+        return round(statistics.median(ts), 2), [round(min(ts), 2), round(max(ts), 2)]
+
+    alone = {}
+    for name, det in (("first_push_us", first), ("second_push_us", second)):
+        alone[name], alone[name + "_range"] = median_of(lambda: det.push(audio()))
+    print(json.dumps(alone), flush=True)
+    rows = []
+    for target in (0.0, 0.01, 0.05, 0.25, 1.0):
+        enter = float("inf") if target == 0.0 else float("-inf") if target == 1.0 else float(np.quantile(peaks, 1.0 - target))
+        cas = StreamingCascade(first, second, enter, pad_after_ms=0)
+        counts, fixed = [], {"n": 0}
+
+        def push():
+            cas.push(audio())
+            counts.append(cas.n_selected)
+
+        def push_no_readback():
+            x = audio()
+            out1 = first.push(x)
+            cas.lib.tcr_stream_select(S, 12, out1.probs.data_ptr(), cas._cmask.data_ptr(), cas.enter_threshold, cas.pad_after, None,
+                                      cas._since.data_ptr(), cas._ws.data_ptr(), cas._ws.numel() * 4, cas._selected.data_ptr(),
+                                      cas._count.data_ptr(), cas.mask.data_ptr(), second.net._stream())
+            second.push_selected(x, cas._selected, fixed["n"], out1.logits, out1.probs)
+
+        for _ in range(args.warmup):
+            push()
+        torch.cuda.synchronize()
+        del counts[:]
+        t_push, r_push = median_of(push)
+        fixed["n"] = int(round(float(np.mean(counts))))
+        t_fixed, r_fixed = median_of(push_no_readback)
+        row = {"S": S, "first": "TCResNet8-1.0 3010 k=2", "second": "DSCNN-L 4020 k=1", "target_fraction": target, "enter": enter,
+               "selected_fraction": round(float(np.mean(counts)) / S, 4), "cascade_push_us": t_push, "cascade_push_us_range": r_push,
+               "no_readback_us": t_fixed, "no_readback_us_range": r_fixed,
+               "readback_share": round(max(t_push - t_fixed, 0.0) / t_push, 3), **alone}
+        row["vs_second_alone"] = round(t_push / alone["second_push_us"], 3)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if args.out:
+        with open(args.out, "w") as fh:
+            json.dump({"device": torch.cuda.get_device_name(0), "iters": args.iters, "reps": args.reps, "rows": rows}, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--iters", type=int, default=400)
@@ -84,8 +160,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace_one", type=int, default=0, help="S: run a few steps of 4020 TCResNet8-1.0 only (profiler run)")
     ap.add_argument("--model", default="TCResNet8", choices=MODELS)
+    ap.add_argument("--cascade", action="store_true", help="the streaming cascade leg (see above)")
+    ap.add_argument("--cascade_streams", type=int, default=4096)
     args = ap.parse_args()
     dev = torch.device("cuda")
+    if args.cascade:
+        cascade_leg(args, dev)
+        return
     if args.trace_one:
         fe, net = build(640, 320, "TCResNet8", 1.0, dev)
         S = args.trace_one

@@ -226,6 +226,12 @@ _PROTOTYPES = {
     "tcr_scan_steps_plan": (C.c_int, [C.POINTER(FrontendCfg), C.POINTER(ModelRef), C.c_int, _P, C.c_int, _P, C.c_int64, C.c_size_t, _P]),
     "tcr_scan_select_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "tcr_scan_select": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, _P, C.c_float, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, _P, _P]),
+    "tcr_stream_select_init": (C.c_int, [C.c_int, _P, _P]),
+    "tcr_stream_select_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "tcr_stream_select": (C.c_int, [C.c_int, C.c_int, _P, _P, C.c_float, C.c_int, _P, _P, _P, C.c_size_t, _P, _P, _P, _P]),
+    "tcr_stream_selected_workspace_bytes_m": (C.c_size_t, [C.POINTER(FrontendCfg), C.POINTER(ModelRef), C.c_int, C.c_int]),
+    "tcr_stream_step_selected_m": (C.c_int, [C.POINTER(FrontendCfg), _P, C.POINTER(ModelRef), C.c_int, C.c_int, C.POINTER(DetectCfg), _P, _P,
+                                             _P, _P, C.c_size_t, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "tcr_mine_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "tcr_mine_detections": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, C.c_size_t, _P, _P, _P, _P, _P,
                                       _P, _P, _P]),

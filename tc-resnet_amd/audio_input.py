@@ -228,6 +228,18 @@ def add_detector_flags(p, each: str = "signal", threshold: bool = True, offline:
         p.add_argument("--cascade_pad_ms", type=float, default=None,
                        help="cascade: audio selected in front of and behind every flag (default: --average_window_ms minus one step)")
         p.add_argument("--second_frames_per_step", type=int, default=1, help="cascade: --second_frozen's frames per step")
+        p.add_argument("--cascade_pad_before_ms", type=float, default=None,
+                       help="cascade: audio selected in front of every flag, when it differs from --cascade_pad_ms behind it (default: "
+                            "--cascade_pad_ms's value; 0: the causal cascade stream_audio.py computes)")
+    else:
+        p.add_argument("--second_frozen", default=None,
+                       help="streaming cascade: --frozen steps every stream and flags, this artifact's network runs only on the flagged "
+                            "streams (StreamingCascade); the detector flags configure the final detector, which is this model's")
+        p.add_argument("--enter_threshold", type=float, default=None,
+                       help="cascade: a stream is flagged when a keyword class (every class from 2 on) of --frozen reaches this probability")
+        p.add_argument("--cascade_pad_ms", type=float, default=None,
+                       help="cascade: audio a stream stays selected behind a flag (default: --average_window_ms minus one step)")
+        p.add_argument("--second_frames_per_step", type=int, default=1, help="cascade: --second_frozen's frames per step")
     if phrases:
         p.add_argument("--phrases", default=None,
                        help='detect phrases instead of single words: "go left;stop no" (words: --labels names or class indices), or @FILE '
@@ -278,12 +290,9 @@ def open_cascade(args):
     """The `scanning.CascadeScanner` of --second_frozen / --enter_threshold (None without them): --frozen at --frames_per_step is the
     first stage, --second_frozen at --second_frames_per_step the second, and the detector flags are the second's.  Accepted with
     --ragged only: a cascade carries no state from chunk to chunk."""
+    check_cascade_flags(args)
     if getattr(args, "second_frozen", None) is None:
-        if getattr(args, "enter_threshold", None) is not None or getattr(args, "cascade_pad_ms", None) is not None:
-            raise SystemExit("--enter_threshold and --cascade_pad_ms belong to a cascade: give --second_frozen")
         return None
-    if args.enter_threshold is None:
-        raise SystemExit("--second_frozen needs --enter_threshold")
     if args.chunk_seconds is not None or args.ragged_chunk_seconds is not None or not args.ragged:
         raise SystemExit("--second_frozen (a cascade) runs with --ragged only: not with the padded one-call run, --chunk_seconds or "
                          "--ragged_chunk_seconds, because no state is carried")
@@ -292,7 +301,33 @@ def open_cascade(args):
     settings = detector_settings(args)
     first = FrozenModel.load(args.frozen).scanner(**settings)
     second = FrozenModel.load(args.second_frozen).scanner(**dict(settings, frames_per_step=args.second_frames_per_step))
-    return CascadeScanner(first, second, args.enter_threshold, pad_before_ms=args.cascade_pad_ms, pad_after_ms=args.cascade_pad_ms)
+    before = args.cascade_pad_ms if getattr(args, "cascade_pad_before_ms", None) is None else args.cascade_pad_before_ms
+    return CascadeScanner(first, second, args.enter_threshold, pad_before_ms=before, pad_after_ms=args.cascade_pad_ms)
+
+
+def check_cascade_flags(args) -> None:
+    """The cascade flags belong together (checked before any model is opened): --enter_threshold, --cascade_pad_ms and
+    --cascade_pad_before_ms need --second_frozen, and --second_frozen needs --enter_threshold."""
+    if getattr(args, "second_frozen", None) is None:
+        if any(getattr(args, f, None) is not None for f in ("enter_threshold", "cascade_pad_ms", "cascade_pad_before_ms")):
+            raise SystemExit("--enter_threshold, --cascade_pad_ms and --cascade_pad_before_ms belong to a cascade: give --second_frozen")
+    elif args.enter_threshold is None:
+        raise SystemExit("--second_frozen needs --enter_threshold")
+
+
+def open_streaming_cascade(args, n_streams: int):
+    """stream_audio.py's `streaming.StreamingCascade` of --second_frozen / --enter_threshold over n_streams streams (None without
+    them): --frozen at --frames_per_step is the first stage, --second_frozen at --second_frames_per_step the second, the detector
+    flags are the second's, and --cascade_pad_ms is the audio a stream stays selected behind a flag."""
+    check_cascade_flags(args)
+    if getattr(args, "second_frozen", None) is None:
+        return None
+    from .deploy import FrozenModel
+    from .streaming import StreamingCascade
+    settings = detector_settings(args)
+    first = FrozenModel.load(args.frozen).streaming(n_streams, **settings)
+    second = FrozenModel.load(args.second_frozen).streaming(n_streams, **dict(settings, frames_per_step=args.second_frames_per_step))
+    return StreamingCascade(first, second, args.enter_threshold, pad_after_ms=args.cascade_pad_ms)
 
 
 def check_phrase_flags(args) -> None:

@@ -594,3 +594,4 @@ int launch_frontend_pk3_stream(int nc, const FrontendArgs& a, int n_items, hipSt
 #include "compose.hip"
 #include "phrase.hip"
 #include "resample.hip"
+#include "stream_cascade.hip"

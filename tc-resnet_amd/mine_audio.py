@@ -6,7 +6,7 @@ event, the events never hit, the windows that came close (`KeywordScanner.mine`,
                          [--lead_ms MS] [--as_label NAME] [--tolerance_ms MS] [--keywords l0,l1,...] [--detection_threshold T]
                          [--frames_per_step k] [--labels l0,l1,...] [--average_window_ms MS] [--suppression_ms MS] [--min_count N]
                          [--max_windows B]
-                         [--second_frozen MODEL2.npz --enter_threshold P [--cascade_pad_ms MS] [--second_frames_per_step K]]
+                         [--second_frozen MODEL2.npz --enter_threshold P [--cascade_pad_ms MS] [--cascade_pad_before_ms MS] [--second_frames_per_step K]]
 
 The model, input, detector and cascade flags are sweep_audio.py's, and so is EVENTS.csv (optional here: without it every detection
 is a false accept).  The files are always scanned at their own lengths in one `KeywordScanner.scan_ragged` call (--ragged is implied);

@@ -3,7 +3,7 @@
     python scan_audio.py --frozen MODEL.npz --wav a.wav [b.wav ...] [--frames_per_step k] [--labels l0,l1,...]
                          [--average_window_ms MS] [--detection_threshold P] [--suppression_ms MS] [--min_count N]
                          [--max_windows B] [--summary] [--chunk_seconds X | --ragged | --ragged_chunk_seconds X]
-                         [--second_frozen MODEL2.npz --enter_threshold P [--cascade_pad_ms MS] [--second_frames_per_step K]]
+                         [--second_frozen MODEL2.npz --enter_threshold P [--cascade_pad_ms MS] [--cascade_pad_before_ms MS] [--second_frames_per_step K]]
                          [--phrases "w1 w2;w3 w4" | @FILE [--phrase_window_ms MS] [--phrase_unordered] [--phrase_combine product|min]]
 
 The files (16-bit PCM) come from `audio_input.Recordings`, zero-padded to the longest, and are scanned in one
@@ -22,7 +22,8 @@ not with --chunk_seconds or --ragged) is that run in bounded host memory: every 
 its next whole steps, none once it has ended -- and the chunks go to one `StreamingDetector.push_ragged`; stdout and the --summary
 line are those of --ragged, byte for byte.  A cascade (--ragged with --second_frozen MODEL2.npz and --enter_threshold P): --frozen scans
 every step, the steps where one of its keyword classes (every class from 2 on) reaches P, and --cascade_pad_ms of audio on both sides
-of them (default: the averaging window minus one step), are computed again by MODEL2 at --second_frames_per_step, and the detector
+of them (default: the averaging window minus one step; --cascade_pad_before_ms MS: another amount in front of them, 0 being the
+causal cascade stream_audio.py computes on live streams), are computed again by MODEL2 at --second_frames_per_step, and the detector
 -- the detector flags are the second stage's -- runs on the merged posteriors (`scanning.CascadeScanner`); both models must have the
 same sample rate, classes and step (frames per step x hop).  --summary then gains selected_steps and total_steps.  With
 --enter_threshold -inf every step is MODEL2's and stdout is MODEL2's own --ragged run, byte for byte.  With --phrases "go left;stop no"

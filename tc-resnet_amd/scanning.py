@@ -253,7 +253,8 @@ class CascadeScanner:
     every flag are selected with it (default: the second scanner's averaging window minus one step on both sides, so every vector the
     detector smooths at a flagged step, and for a window after it, is the second model's).  The scanners must share library, device,
     sample rate, num_classes and the step: k1 * hop1 == k2 * hop2 samples (a 30 / 10 ms first stage at k = 2 pairs with a 40 / 20 ms
-    second stage at k = 1).  No state is carried between calls."""
+    second stage at k = 1).  No state is carried between calls; `streaming.StreamingCascade` is the cascade over live streams (the
+    causal one: pad_before = 0), whose pushes are bitwise this scanner's scan at pad_before_ms = 0."""
 
     def __init__(self, first: KeywordScanner, second: KeywordScanner, enter_threshold: float,
                  keyword_classes: Optional[Sequence[int]] = None, pad_before_ms: Optional[float] = None,

@@ -197,6 +197,7 @@ class StreamingDetector(_Detection):
         self.max_windows, self.max_signals = int(DEFAULT_MAX_WINDOWS if max_windows is None else max_windows), self.n_streams
         self._scan_ws: Optional[torch.Tensor] = None
         self._ragged_ws: Optional[torch.Tensor] = None
+        self._sel_ws: Optional[torch.Tensor] = None
         cfg = frontend.cfg
         S, lib = self.n_streams, self.lib
         if S <= 0:
@@ -257,6 +258,48 @@ class StreamingDetector(_Detection):
         self._check_samples(samples)
         ref = self._call_ref()
         self.lib.check(self.lib.tcr_stream_step_m(*self._args(samples, ref, self._take_reset(), self.net._stream())), "tcr_stream_step")
+        self._after_call()
+        return self.out
+
+    def push_selected(self, samples: torch.Tensor, selected: torch.Tensor, n_selected: int, fill_logits: Optional[torch.Tensor],
+                      fill_probs: Optional[torch.Tensor]) -> StreamOutput:
+        """One step in which the network runs only on the streams `selected[:n_selected]` (int64 on the device, strictly increasing
+        stream indices; n_selected a host integer): tcr_stream_step_selected_m.  Every stream's window and tail advance exactly as `push`
+        advances them; a selected stream's logits / probs rows are `push`'s rows bitwise, every other stream's rows are its rows of
+        fill_logits / fill_probs [S, classes] (float32 on the device; None allowed when all S are selected, which is `push` bitwise),
+        and the detector runs over the merged probs.  The fill rows must not be this detector's `out` tensors.  Mixes freely with
+        `push`, `push_many` and `push_ragged`; the weight / fold rules and pending resets are `push`'s.  The workspace of these steps is
+        allocated on the first call."""
+        self._check_samples(samples)
+        S, ncls, lib, fe = self.n_streams, self.net.num_classes, self.lib, self.frontend
+        n = int(n_selected)
+        if not 0 <= n <= S:
+            raise TcrError(f"push_selected: n_selected {n} outside 0..{S}")
+        if selected.dtype != torch.int64 or selected.dim() != 1 or int(selected.numel()) < n or not selected.is_contiguous() \
+                or selected.device.type != self.device.type:
+            raise TcrError(f"push_selected expects selected: contiguous int64 [>= {n}] on the device, got {selected.dtype} "
+                           f"{tuple(selected.shape)} on {selected.device}")
+        for name, t in (("fill_logits", fill_logits), ("fill_probs", fill_probs)):
+            if t is None:
+                if n < S:
+                    raise TcrError(f"push_selected: {name} is None with {n} of {S} streams selected")
+                continue
+            if tuple(t.shape) != (S, ncls):
+                raise TcrError(f"push_selected expects {name} [{S}, {ncls}], got {tuple(t.shape)}")
+            self.net._check_tensor(t, name)
+        if self._sel_ws is None:
+            nws = lib.tcr_stream_selected_workspace_bytes_m(C.byref(fe.cfg), C.byref(self._ref()), S, self.k)
+            if nws == 0:
+                raise TcrError(f"StreamingDetector.push_selected: {lib.tcr_last_error().decode()}")
+            self._sel_ws = torch.empty(nws // 4, dtype=torch.float32, device=self.device)
+        ref = self._call_ref()
+        o, ws = self.out, self._sel_ws
+        lib.check(lib.tcr_stream_step_selected_m(
+            C.byref(fe.cfg), fe.plan.data_ptr(), C.byref(ref), S, self.k, C.byref(self.det), samples.data_ptr(), self._take_reset(),
+            self.state.data_ptr(), ws.data_ptr(), ws.numel() * 4, selected.data_ptr(), n,
+            None if fill_logits is None else fill_logits.data_ptr(), None if fill_probs is None else fill_probs.data_ptr(),
+            o.logits.data_ptr(), o.probs.data_ptr(), o.smoothed.data_ptr(), o.top.data_ptr(), o.score.data_ptr(), o.is_new.data_ptr(),
+            self.net._stream()), "tcr_stream_step_selected")
         self._after_call()
         return self.out
 
@@ -362,3 +405,97 @@ class StreamingDetector(_Detection):
                 check(rc, "tcr_stream_step")
             return out
         return call
+
+
+class StreamingCascade:
+    """The causal cascade over S live streams: `first` (a cheap `StreamingDetector`) steps every stream, the streams at or shortly
+    behind one of its flags are selected, `second` (an expensive one) runs its network on those only (`push_selected`), and `second`'s
+    detector runs over the merged posteriors.  The pushes stacked over time are bitwise
+    `scanning.CascadeScanner(first, second, enter_threshold, keyword_classes, pad_before_ms=0, pad_after_ms=pad_after_ms, on=on)`'s
+    scan of the whole signals, on all six outputs and on the selection.
+
+    A stream is flagged when a class of keyword_classes (default: every class from 2 on) reaches enter_threshold in the first stage's
+    `on` ("probs" or "smoothed") at this step, and selected when it was flagged at this step or within pad_after_ms of audio before it
+    (default: the second detector's averaging window minus one step) since its last reset.  A stream cannot be rescored before its
+    flag, so pad_before is 0 by definition: at a flag the detector's average mixes first-stage rows from before it with second-stage
+    rows from it on.  The detectors must share library, device, sample rate, num_classes, n_streams and the step (k1 * hop1 == k2 *
+    hop2 samples).  Both keep their own state; every stream's second-stage window advances at every push, selected or not.
+
+    Every push reads the number of selected streams back to the host (one small copy and wait, as a cascade scan pays per call), so a
+    cascade push cannot be captured into a graph.  After a push: `mask` (uint8 [S]), `n_selected`, `selected` (an int64 view of the
+    selected stream indices, increasing) and `first_out` (the first detector's `out`).  The output is the second detector's `out`, a
+    `StreamOutput`: `scanning.StreamingPhraseDetector.push` takes it unchanged."""
+
+    def __init__(self, first: StreamingDetector, second: StreamingDetector, enter_threshold: float,
+                 keyword_classes: Optional[Sequence[int]] = None, pad_after_ms: Optional[float] = None, on: str = "probs"):
+        what = "StreamingCascade"
+        if first.lib is not second.lib or first.device != second.device:
+            raise TcrError(f"{what}: the two detectors must use the same library and device")
+        r1, r2 = first.frontend.cfg.sample_rate, second.frontend.cfg.sample_rate
+        if r1 != r2:
+            raise TcrError(f"{what}: the detectors run at different sample rates ({r1} and {r2} Hz)")
+        if first.step_samples != second.step_samples:
+            raise TcrError(f"{what}: the detectors' steps differ ({first.step_samples} and {second.step_samples} samples): "
+                           "k1 * hop1 must equal k2 * hop2")
+        if first.net.num_classes != second.net.num_classes:
+            raise TcrError(f"{what}: the detectors' models have {first.net.num_classes} and {second.net.num_classes} classes")
+        if first.n_streams != second.n_streams:
+            raise TcrError(f"{what}: the detectors hold {first.n_streams} and {second.n_streams} streams")
+        if on not in ("probs", "smoothed"):
+            raise TcrError(f"{what}: on must be 'probs' or 'smoothed', got {on!r}")
+        if np.isnan(float(enter_threshold)):
+            raise TcrError(f"{what}: enter_threshold is NaN")
+        ncls = second.net.num_classes
+        self.keyword_classes = list(range(2, ncls)) if keyword_classes is None else [int(c) for c in keyword_classes]
+        if any(not 0 <= c < ncls for c in self.keyword_classes):
+            raise TcrError(f"{what}: keyword_classes outside 0..{ncls - 1}: {self.keyword_classes}")
+        self.pad_before = 0
+        self.pad_after = second.average_steps - 1 if pad_after_ms is None else ms_to_steps(pad_after_ms, second.step_ms)
+        if self.pad_after < 0:
+            raise TcrError(f"{what}: negative pads ({pad_after_ms} ms after)")
+        self.first, self.second, self.lib, self.device = first, second, second.lib, second.device
+        self.enter_threshold, self.on = float(enter_threshold), on
+        self.n_streams, self.step_samples = second.n_streams, second.step_samples
+        S, dev, lib = self.n_streams, self.device, self.lib
+        cmask = np.zeros(ncls, np.uint8)
+        cmask[self.keyword_classes] = 1
+        self._cmask = torch.from_numpy(cmask).to(dev)
+        self._since = torch.empty(S, dtype=torch.int32, device=dev)
+        self._selected = torch.zeros(S, dtype=torch.int64, device=dev)
+        self._count = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.mask = torch.zeros(S, dtype=torch.uint8, device=dev)
+        self._reset_dev = torch.zeros(S, dtype=torch.uint8, device=dev)
+        self._pending: Optional[np.ndarray] = None
+        nws = lib.tcr_stream_select_workspace_bytes(S)
+        if nws == 0:
+            raise TcrError(f"{what}: {lib.tcr_last_error().decode()}")
+        self._ws = torch.empty(nws // 4, dtype=torch.int32, device=dev)
+        self.n_selected, self.selected, self.first_out = 0, self._selected[:0], first.out
+        lib.check(lib.tcr_stream_select_init(S, self._since.data_ptr(), second.net._stream()), "tcr_stream_select_init")
+
+    def reset(self, mask_or_indices) -> None:
+        """Return streams to the initial state at the NEXT push, before its samples are appended: both detectors
+        (`StreamingDetector.reset`) and the selection (never flagged)."""
+        mask = reset_mask(mask_or_indices, self.n_streams)
+        self.first.reset(mask)
+        self.second.reset(mask)
+        self._pending = mask if self._pending is None else (self._pending | mask)
+
+    def push(self, samples: torch.Tensor) -> StreamOutput:
+        """Append samples [S, step_samples] (float32, on the device) to every stream; one step of both detectors.  first.push, the
+        selection (tcr_stream_select), the read-back of the number of selected streams, second.push_selected with the first stage's
+        logits / probs as fill rows.  Nothing selected: the second network does not run."""
+        lib, S = self.lib, self.n_streams
+        reset_ptr = None
+        if self._pending is not None:
+            self._reset_dev.copy_(torch.from_numpy(self._pending.astype(np.uint8)))
+            self._pending, reset_ptr = None, self._reset_dev.data_ptr()
+        out1 = self.first.push(samples)
+        values = getattr(out1, self.on)
+        lib.check(lib.tcr_stream_select(S, int(values.shape[1]), values.data_ptr(), self._cmask.data_ptr(), self.enter_threshold,
+                                        self.pad_after, reset_ptr, self._since.data_ptr(), self._ws.data_ptr(), self._ws.numel() * 4,
+                                        self._selected.data_ptr(), self._count.data_ptr(), self.mask.data_ptr(),
+                                        self.second.net._stream()), "tcr_stream_select")
+        n = int(self._count.item())
+        self.n_selected, self.selected, self.first_out = n, self._selected[:n], out1
+        return self.second.push_selected(samples, self._selected, n, out1.logits, out1.probs)

@@ -5,7 +5,7 @@ curve (false rejects against false accepts per hour) from one scan.
                           [--tolerance_ms MS] [--keywords l0,l1,...] [--per_label] [--target_fa_per_hour F]
                           [--frames_per_step k] [--labels l0,l1,...] [--average_window_ms MS] [--suppression_ms MS]
                           [--min_count N] [--max_windows B] [--chunk_seconds X | --ragged | --ragged_chunk_seconds X]
-                          [--second_frozen MODEL2.npz --enter_threshold P [--cascade_pad_ms MS] [--second_frames_per_step K]]
+                          [--second_frozen MODEL2.npz --enter_threshold P [--cascade_pad_ms MS] [--cascade_pad_before_ms MS] [--second_frames_per_step K]]
                           [--phrases "w1 w2;w3 w4" | @FILE [--phrase_window_ms MS] [--phrase_unordered] [--phrase_combine product|min]]
 
 The files are read as scan_audio.py reads them (`audio_input.Recordings`: 16-bit PCM, converted to the model's sample rate on the
