@@ -986,6 +986,73 @@ int tcr_phrase_stream_push_ragged(int n_streams, const int64_t* step_offsets /* 
                                   void* state, float* post /* [total_steps][P + 1] */, int32_t* top, float* score,
                                   int32_t* is_new /* [total_steps] */, void* stream);
 
+/* Capturing detections' audio on live streams: a recorder next to a streaming detector (tcr_stream_step / tcr_stream_scan / _ragged,
+ * tcr_phrase_stream_push*, a cascade: anything that writes top / score / is_new per stream and row) that hands back, for each of the
+ * detector's detections, the clip DetectionStage.mine's gather (tcr_mine_gather) cuts from the whole recording -- bitwise, however
+ * the stream is cut into pushes, although the audio is gone once pushed.
+ * Definition.  A stream's RECORDING is every sample pushed to it since its init or last reset; row i is its i-th step of step_samples
+ * samples.  Row i is a TRIGGER when is_new[i] != 0 and, with a class mask, 0 <= top[i] < num_classes and class_mask[top[i]] != 0.  The
+ * CLIP of trigger row i is
+ *     recording[(i + 1) * step_samples + lead - n_samples  ..  (i + 1) * step_samples + lead)
+ * with zeros outside the recording; lead (samples) may have either sign.  With  D = max(0, ceil(lead / step_samples))  the clip of row
+ * i is EMITTED by the call that brings the stream's row i + D, the first row after which all the clip's samples have been heard; with
+ * lead <= 0 that is the trigger's own call.
+ * Why a ring of  H = n_samples + max(0, -lead)  samples suffices: in the call that emits it a clip ends at or after the end of the
+ * call's first row minus max(0, -lead) samples ((i + 1 - r0) step + lead with i + D >= r0 and D step >= lead > (D - 1) step), so it
+ * starts less than H samples before the call's first sample; everything later is in the call itself.
+ * State (caller-owned device memory of tcr_capture_state_bytes, 16-byte aligned, zeroed by tcr_capture_init: no rows heard, nothing
+ * pending; it belongs to one (n_streams, step_samples, n_samples, lead)): per stream {int64 rows heard, int32 ring slot of the next
+ * sample, int32 0} [S], rounded up to 256 bytes; the triggers of every stream's last D rows, oldest first -- int32 flag [S][D],
+ * int32 label [S][D], float32 score [S][D] -- rounded up to 256 bytes; the ring float32 [S][R], R = H rounded up to 4, sample t of
+ * the recording in slot t mod R.  In all  S (16 + 12 D + 4 R)  bytes and the rounding: 4096 streams at one second of 16 kHz audio are
+ * 262 MB.  After a call the state is what any other split of the same rows leaves.
+ * tcr_capture_push: samples [S][steps * step_samples], top / score / is_new [S][steps], `steps` new rows for every stream.
+ * tcr_capture_push_ragged: stream s brings m_s = step_offsets[s + 1] - step_offsets[s] >= 0 rows (DEVICE int64 [S + 1], from 0,
+ * non-decreasing, step_offsets[S] == total_steps: preconditions, the host does not read the table), samples [total_steps *
+ * step_samples] and the three row arrays [total_steps] packed in stream order.  A stream with m_s == 0 keeps every byte of its
+ * state, and reset[s] is IGNORED for it (pass the flag again with the call that brings its next row).
+ * reset [S] uint8 or NULL: reset[s] != 0 applies before the stream's first row of the call: its pending triggers are dropped, earlier
+ * audio reads as zeros, rows count from 0 again.
+ * Outputs, in (stream, row) order: clip_stream int32, clip_step int64 (the trigger's row, counted from the reset), clip_label int32
+ * (top), clip_score float32 [capacity]; out float32 [capacity][n_samples] and / or out_pcm int16 [capacity][n_samples] (either may be
+ * NULL; the int16 rounding is tcr_mine_gather's own function); n_clips int32 [2]: the clips written, then the clips due.  When more
+ * than `capacity` clips are due the first `capacity` of that order are written and the rest are DROPPED (n_clips[1] tells); this is
+ * not an error.  Rows of the outputs past n_clips[0] are not touched.
+ * tcr_capture_flush: emits the pending clips -- the triggers among the last D rows -- of the streams with mask[s] != 0 (NULL: all),
+ * audio not yet heard reading as zeros (what mining gives for a detection near a recording's end), and clears those triggers, so a
+ * stream that goes on does not emit them again; ring and row count stay.  With lead <= 0 nothing is ever pending (n_clips = 0, 0).
+ * Workspace: tcr_capture_workspace_bytes(total_rows) for a push of total_rows rows in all (dense: S * steps), S * D for a flush; 16-byte
+ * aligned; a larger one serves smaller calls.
+ * How: a flag per row (row j emits the trigger of row j - D, from the call or the carried tail), tcr_scan_select's ordered compaction
+ * into the table, a gather of min(capacity, rows) workgroup rows that exits on the device-side count and reads each clip from the ring
+ * (at most two wrapped stretches) and the call's samples with tcr_mine_gather's 16-byte row code, then the append of the call's last R
+ * samples per stream (16-byte stores when step_samples is a multiple of 4 and samples is 16-byte aligned, single floats otherwise).
+ * Only kernels are enqueued on `stream` (tcr_capture_init: a memset) -- no copy, no wait, nothing read back: the calls can be captured
+ * into a graph.  Precondition: fewer than 2^63 / step_samples rows per stream since its reset.
+ * Refused (TCR_ERR_ARG; tcr_capture_state_bytes / _workspace_bytes return 0): n_streams, step_samples or n_samples <= 0; step_samples,
+ * n_samples or |lead| above 2^28; a state of 10^15 bytes or more (size overflow); total_rows outside 1 .. 2^31 - 1; steps (ragged:
+ * total_steps) <= 0; 2^40 or more samples in a call; a null or misaligned state or workspace; a null samples, top, score, is_new,
+ * n_clips, step_offsets (ragged); a class mask with num_classes <= 0; capacity outside 0 .. 2^31 - 1, or null tables with capacity
+ * > 0.  TCR_ERR_WORKSPACE: a workspace smaller than tcr_capture_workspace_bytes of the call's rows. */
+size_t tcr_capture_state_bytes(int n_streams, int step_samples, int n_samples, int lead);
+size_t tcr_capture_workspace_bytes(int64_t total_rows);
+int tcr_capture_init(int n_streams, int step_samples, int n_samples, int lead, void* state, void* stream);
+int tcr_capture_push(int n_streams, int64_t steps, int step_samples, int n_samples, int lead,
+                     const float* samples /* [S][steps * step_samples] */, const int32_t* top, const float* score,
+                     const int32_t* is_new /* [S][steps] */, const uint8_t* class_mask /* [num_classes] or NULL */, int num_classes,
+                     const uint8_t* reset /* [S] or NULL */, void* state, void* workspace, size_t ws_bytes, int64_t capacity,
+                     float* out /* [capacity][n_samples] or NULL */, int16_t* out_pcm /* or NULL */, int32_t* clip_stream,
+                     int64_t* clip_step, int32_t* clip_label, float* clip_score, int32_t* n_clips /* DEVICE [2] */, void* stream);
+int tcr_capture_push_ragged(int n_streams, const int64_t* step_offsets /* DEVICE [S + 1] */, int64_t total_steps, int step_samples,
+                            int n_samples, int lead, const float* samples /* packed */, const int32_t* top, const float* score,
+                            const int32_t* is_new /* [total_steps] */, const uint8_t* class_mask /* [num_classes] or NULL */,
+                            int num_classes, const uint8_t* reset /* [S] or NULL */, void* state, void* workspace, size_t ws_bytes,
+                            int64_t capacity, float* out, int16_t* out_pcm, int32_t* clip_stream, int64_t* clip_step,
+                            int32_t* clip_label, float* clip_score, int32_t* n_clips /* DEVICE [2] */, void* stream);
+int tcr_capture_flush(int n_streams, const uint8_t* mask /* [S] or NULL: all */, int step_samples, int n_samples, int lead, void* state,
+                      void* workspace, size_t ws_bytes, int64_t capacity, float* out, int16_t* out_pcm, int32_t* clip_stream,
+                      int64_t* clip_step, int32_t* clip_label, float* clip_score, int32_t* n_clips /* DEVICE [2] */, void* stream);
+
 /* Sample-rate conversion: a rational-ratio polyphase FIR in front of the detectors (which take float32 at the model's rate).
  * in_rate -> out_rate, g = gcd: up = L = out_rate / g, down = M = in_rate / g; taps = P per phase (even, or 1); table float32
  * [up][taps], designed on the host (tcresnet_amd.resampling.design_table: windowed sinc, fc = rolloff / max(1, M / L), Kaiser

@@ -250,6 +250,14 @@ _PROTOTYPES = {
                                          _P, _P, _P, _P]),
     "tcr_phrase_stream_push_ragged": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.POINTER(PhraseCfg), C.POINTER(DetectCfg),
                                                 _P, _P, _P, _P, _P, _P, _P]),
+    "tcr_capture_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tcr_capture_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "tcr_capture_init": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "tcr_capture_push": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_size_t,
+                                   C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "tcr_capture_push_ragged": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P,
+                                          C.c_size_t, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "tcr_capture_flush": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "tcr_resample": (C.c_int, [C.POINTER(ResampleCfg), _P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64,
                                _P]),
     "tcr_resample_span": (C.c_int, [C.POINTER(ResampleCfg), C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -593,5 +593,6 @@ int launch_frontend_pk3_stream(int nc, const FrontendArgs& a, int n_items, hipSt
 #include "mine.hip"
 #include "compose.hip"
 #include "phrase.hip"
+#include "capture.hip"
 #include "resample.hip"
 #include "stream_cascade.hip"

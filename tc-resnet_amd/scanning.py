@@ -25,7 +25,8 @@ class, on which the detector rule, `sweep`, `tune` and `mine` run with P + 1 cla
 
 This module holds the scanners and the cascade; the rest is importable from here and lives in `detection` (the outputs, the ms / step
 arithmetic and `DetectionStage`: `redetect`, `sweep`, `tune`, `mine` over a scan's outputs, no network needed), `scoring` (`detection_sweep`,
-`detection_grid`, their results), `mining` (`mine_*`, `select_top`, `gather_clips`, `MinedClips`) and `phrases` (`PhraseDetector`, `StreamingPhraseDetector`).
+`detection_grid`, their results), `mining` (`mine_*`, `select_top`, `gather_clips`, `MinedClips`), `phrases` (`PhraseDetector`, `StreamingPhraseDetector`) and `capturing`
+(`StreamingRecorder`, `CapturedClips`).
 """
 from __future__ import annotations
 
@@ -38,6 +39,7 @@ import torch
 
 from . import _lib
 from ._lib import TcrError
+from .capturing import CapturedClips, CapturedHost, StreamingRecorder  # noqa: F401
 from .detection import (DEFAULT_MAX_WINDOWS, CascadeOutput, RaggedScanOutput, ScanOutput, _ragged_scan_output, _ragged_signals,  # noqa: F401
                         _scan_output, ms_to_steps)
 from .engine import Frontend

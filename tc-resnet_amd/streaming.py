@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from ._lib import FAMILY_DSCNN, FAMILY_G2D, FAMILY_TCRESNET, ModelRef, TcrError, padded_len
+from .capturing import CapturedClips, CapturedHost, StreamingRecorder  # noqa: F401
 from .detection import (DEFAULT_MAX_WINDOWS, DetectionStage, _new_tensors, _ragged_scan_output, _ragged_signals,  # noqa: F401
                         _scan_output, ms_to_steps)
 from .engine import DSCNN, Frontend, Graph2D, TCResNet
