@@ -986,6 +986,107 @@ int tcr_phrase_stream_push_ragged(int n_streams, const int64_t* step_offsets /* 
                                   void* state, float* post /* [total_steps][P + 1] */, int32_t* top, float* score,
                                   int32_t* is_new /* [total_steps] */, void* stream);
 
+/* Enrolled keywords (template matching): keywords the model was not trained on, detected by query-by-example -- the feature rows of a
+ * few recorded examples are kept as templates and matched against the running rows by subsequence dynamic time warping.  Like the
+ * phrase entries this is a transform of posteriors: values [steps][F] float32 feature rows in (a scan's smoothed or probs with
+ * F = num_classes; any other float32 rows of F <= TCR_DTW_MAX_FEATURES columns), out [steps][K + 1] posteriors over K keywords and a
+ * background class out, and lengths [steps][K] int32 (or NULL), so that tcr_detect_redetect, tcr_detect_sweep(_ragged),
+ * tcr_detect_grid and tcr_mine_* apply to enrolled keywords unchanged with num_classes = K + 1.
+ * The score.  Every operation is float32, evaluated as written, no multiply-add fused.  Template q has L_q frames T[j][f] (templates:
+ * DEVICE, packed [total_frames][F], template q's frames at frame_offsets[q] .. frame_offsets[q + 1] - 1).  A signal's rows are
+ * v_t[f], t counted from the signal's first step (a stream: from its init or last reset).
+ *   local distance:  d(j, t) = a_{F-1},  a_0 = |T[j][0] - v_t[0]|,  a_f = a_{f-1} + |T[j][f] - v_t[f]|, f ascending (no multiply).
+ *   before a signal's first row:  D[j] = +inf, n[j] = 0 for every j.
+ *   step t, for every j from the previous column D', n' only, three candidates in priority order:
+ *     1. diag: (D'[j-1], n'[j-1]) if j >= 1, else (0, 0) -- the free start: a path may begin at any step;
+ *     2. stay: (D'[j], n'[j]);
+ *     3. skip: (D'[j-2], n'[j-2]) if j >= 2, (0, 0) if j == 1, (+inf, 0) if j == 0;
+ *     best = diag; if stay.D < best.D: best = stay; if skip.D < best.D: best = skip (strict: ties keep the earlier candidate);
+ *     D[j] = d(j, t) + best.D,  n[j] = min(best.n, INT32_MAX - 1) + 1.
+ *   per template:  cost_q(t) = D[L_q - 1], len_q(t) = n[L_q - 1] (the steps on the best path: the match spans t - len + 1 .. t);
+ *     conf_q(t) = fmaxf(1 - cost_q(t) * scale[q], 0), and 0 instead if cfg.max_steps > 0 and len_q(t) > cfg.max_steps (+inf costs give
+ *     0 by the same expression).  scale: HOST float32 [Q], every entry finite and > 0 (0.5 / L_q maps the mean total variation of
+ *     probability rows onto [0, 1]).
+ *   per keyword:  keyword k owns templates keyword_offsets[k] .. keyword_offsets[k + 1] - 1 (at least one).  out[t][k] = the maximum of
+ *     their conf in ascending template order with strict > (the first maximum wins), lengths[t][k] = the winning template's len,
+ *     out[t][K] = 1 - max_k out[t][k] (the background: what it is for phrases).
+ * A signal's first steps never read another signal's rows or state.  For values outside [0, 1] or non-finite ones the results are
+ * unspecified, the call stays memory-safe.  The cost is summed per step and normalised by L through scale, so it prefers short paths:
+ * that is what lengths and max_steps are for.
+ * How: one wave per (signal, keyword) walks the keyword's templates one after the other over the signal's rows; a lane owns
+ * ceil(L / 64) <= 4 consecutive frames with D and n in registers and its template frames in LDS, the rows come through an LDS tile
+ * fetched one tile ahead, and the neighbour's last two (D, n) pairs are handed over by two shuffles a step.  A second small kernel
+ * writes the background.  The walk is sequential in t: the parallelism of a call is N x K waves (a single long recording with one
+ * keyword runs on one wave).  Limits: Q <= TCR_DTW_MAX_TEMPLATES, F <= TCR_DTW_MAX_FEATURES, L_q <= tcr_dtw_frames_max(F) =
+ * min(256, 4096 / F) (256 up to F = 16, 64 at F = 64; 0 for F outside 1 .. 64); there is no path above them.  frame_offsets,
+ * keyword_offsets and scale are HOST tables, read before the call returns (they travel as kernel arguments); every other pointer is
+ * device memory.  The entries only enqueue kernels on `stream` -- no copy, no wait -- so they can be captured into a graph.  The
+ * ragged form takes step_offsets as tcr_detect_redetect_ragged does (DEVICE int64 [N + 1], from 0, non-decreasing, step_offsets[N]
+ * == total_steps: preconditions).
+ * Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched, out and lengths are not written): a null step_offsets (ragged) / values
+ * / templates / frame_offsets / keyword_offsets / scale / cfg / out; N, steps (dense), total_steps (ragged) or n_features <= 0;
+ * n_features above TCR_DTW_MAX_FEATURES; n_templates outside 1 .. TCR_DTW_MAX_TEMPLATES; n_keywords outside 1 .. n_templates; offsets
+ * that do not start at 0 or decrease; keyword_offsets that does not end at n_templates; a keyword without a template; a template of 0
+ * or more than tcr_dtw_frames_max(n_features) frames; a scale <= 0 or non-finite; max_steps < 0; steps in all x (K + 1) or x
+ * n_features >= 2^31. */
+#define TCR_DTW_MAX_TEMPLATES 64
+#define TCR_DTW_MAX_FEATURES 64
+typedef struct tcr_dtw_cfg {
+    int32_t max_steps;          /* > 0: a match of more steps scores 0; 0: no limit */
+} tcr_dtw_cfg;
+int tcr_dtw_frames_max(int n_features);                 /* the largest template, in frames; 0: n_features outside 1 .. 64 */
+int tcr_dtw_scores(int n_signals, int64_t steps, int n_features, const float* values /* [N][steps][F] */, int n_templates,
+                   const float* templates /* DEVICE [total_frames][F] */, const int32_t* frame_offsets /* HOST [Q + 1] */, int n_keywords,
+                   const int32_t* keyword_offsets /* HOST [K + 1] */, const float* scale /* HOST [Q] */, const tcr_dtw_cfg* cfg,
+                   float* out /* [N][steps][K + 1] */, int32_t* lengths /* [N][steps][K] or NULL */, void* stream);
+int tcr_dtw_scores_ragged(int n_signals, const int64_t* step_offsets /* DEVICE [N + 1] */, int64_t total_steps, int n_features,
+                          const float* values /* packed [total_steps][F] */, int n_templates, const float* templates /* DEVICE */,
+                          const int32_t* frame_offsets /* HOST */, int n_keywords, const int32_t* keyword_offsets /* HOST */,
+                          const float* scale /* HOST */, const tcr_dtw_cfg* cfg, float* out /* [total_steps][K + 1] */,
+                          int32_t* lengths /* [total_steps][K] or NULL */, void* stream);
+
+/* Streaming template matching: tcr_dtw_scores and the detector over its posteriors with the DTW column and the detector carried across
+ * calls, for S live streams -- the tcr_phrase_stream_* entries' arguments and meaning, with the template tables for the phrase tables
+ * and `lengths` ([..][K] int32 or NULL) next to post.  State is caller-owned device memory of tcr_dtw_stream_state_bytes (0: invalid
+ * arguments, see tcr_last_error), filled by tcr_dtw_stream_init (every stream: the initial column, no rows seen, prev_label = -1);
+ * it belongs to one (n_streams, n_features, tables, cfg), and the same values must be passed to every push.
+ * Contract: for stream s let R_s be all rows pushed to it since its init or last reset, in order.  The post and lengths rows a call
+ * writes for s are bitwise the corresponding (last) rows of tcr_dtw_scores(1, len(R_s), ..) over R_s, and top / score / is_new are
+ * bitwise tcr_detect_redetect over those posteriors with `det` (num_classes = K + 1, average_steps = min_count = 1), with n,
+ * prev_label and prev_step carried.  The recurrence reads the previous column only, so any way of cutting a stream into pushes gives
+ * the outputs of one whole scan, a one-step push costs one step, and dense, ragged and one-step calls mix freely on one state.
+ * reset [S] uint8 or NULL: reset[s] != 0 returns stream s to the initial state before its first row of this call.  In a ragged call a
+ * stream with m_s == 0 is untouched -- its state is byte for byte what it was -- and reset[s] is IGNORED for it (pass the flag again
+ * with the call that brings the stream's next row).  Streams are independent.  Precondition: fewer than 2^31 rows per stream since
+ * its reset.
+ * State (opaque to callers; for the record): the detector integers [5][S] int32 as tcr_stream_step keeps them, rounded up to 256
+ * bytes, then D float32 and n int32, each [total_frames x S]: template q's block at frame_offsets[q] x S, stream s's L_q values at
+ * s x L_q inside it.  tcr_dtw_stream_state_bytes = that rounding + 8 x total_frames x S.
+ * A push is tcr_dtw_scores' two kernels on the carried columns, then detect_smooth_kernel at one vector per decision and
+ * scan_suppress_kernel; tcr_dtw_stream_init is a memset and a kernel.  No copy, no wait: the entries can be captured into a graph.
+ * Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched, the state and the outputs are untouched): everything tcr_dtw_scores
+ * refuses (n_streams for N; lengths may be NULL); a null state, det, post, top, score or is_new; det->average_steps != 1 or
+ * det->min_count != 1; det->suppression_steps < 0. */
+size_t tcr_dtw_stream_state_bytes(int n_streams, int n_features, int n_templates, const float* templates /* DEVICE */,
+                                  const int32_t* frame_offsets /* HOST [Q + 1] */, int n_keywords, const int32_t* keyword_offsets /* HOST */,
+                                  const float* scale /* HOST [Q] */, const tcr_dtw_cfg* cfg);
+int tcr_dtw_stream_init(int n_streams, int n_features, int n_templates, const float* templates /* DEVICE */,
+                        const int32_t* frame_offsets /* HOST */, int n_keywords, const int32_t* keyword_offsets /* HOST */,
+                        const float* scale /* HOST */, const tcr_dtw_cfg* cfg, void* state, void* stream);
+int tcr_dtw_stream_push(int n_streams, int64_t steps, int n_features, const float* values /* [S][steps][F] */, int n_templates,
+                        const float* templates /* DEVICE */, const int32_t* frame_offsets /* HOST */, int n_keywords,
+                        const int32_t* keyword_offsets /* HOST */, const float* scale /* HOST */, const tcr_dtw_cfg* cfg,
+                        const tcr_detect_cfg* det, const uint8_t* reset /* [S] or NULL */, void* state,
+                        float* post /* [S][steps][K + 1] */, int32_t* lengths /* [S][steps][K] or NULL */, int32_t* top, float* score,
+                        int32_t* is_new /* [S][steps] */, void* stream);
+int tcr_dtw_stream_push_ragged(int n_streams, const int64_t* step_offsets /* DEVICE [S + 1] */, int64_t total_steps, int n_features,
+                               const float* values /* packed [total_steps][F] */, int n_templates, const float* templates /* DEVICE */,
+                               const int32_t* frame_offsets /* HOST */, int n_keywords, const int32_t* keyword_offsets /* HOST */,
+                               const float* scale /* HOST */, const tcr_dtw_cfg* cfg, const tcr_detect_cfg* det,
+                               const uint8_t* reset /* [S] or NULL */, void* state, float* post /* [total_steps][K + 1] */,
+                               int32_t* lengths /* [total_steps][K] or NULL */, int32_t* top, float* score,
+                               int32_t* is_new /* [total_steps] */, void* stream);
+
 /* Capturing detections' audio on live streams: a recorder next to a streaming detector (tcr_stream_step / tcr_stream_scan / _ragged,
  * tcr_phrase_stream_push*, a cascade: anything that writes top / score / is_new per stream and row) that hands back, for each of the
  * detector's detections, the clip DetectionStage.mine's gather (tcr_mine_gather) cuts from the whole recording -- bitwise, however

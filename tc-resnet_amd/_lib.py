@@ -21,6 +21,8 @@ PHRASE_TILE = 256          # == TCR_PHRASE_TILE: steps per tile of tcr_phrase_sc
 PHRASE_MAX = 64            # == TCR_PHRASE_MAX: phrases per call
 PHRASE_MAX_WORDS = 8       # == TCR_PHRASE_MAX_WORDS
 PHRASE_PRODUCT, PHRASE_MIN = 0, 1      # tcr_phrase_cfg.combine
+DTW_MAX_TEMPLATES = 64     # == TCR_DTW_MAX_TEMPLATES: templates per call
+DTW_MAX_FEATURES = 64      # == TCR_DTW_MAX_FEATURES: columns of a feature row
 ABI_VERSION = 3            # == TCR_ABI_VERSION of include/tcresnet_hip.h these prototypes were written against
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_HERE, "lib", "libtcresnet_hip.so")
@@ -68,6 +70,11 @@ class PhraseCfg(C.Structure):
     _fields_ = [("window_steps", C.c_int32), ("ordered", C.c_int32), ("combine", C.c_int32)]
 
 
+class DtwCfg(C.Structure):
+    """tcr_dtw_cfg."""
+    _fields_ = [("max_steps", C.c_int32)]
+
+
 FAMILY_TCRESNET, FAMILY_DSCNN, FAMILY_G2D = 0, 1, 2
 
 
@@ -82,6 +89,7 @@ class TensorInfo(C.Structure):
 
 
 _P = C.c_void_p
+_DTW_TABLES = (C.c_int, _P, _P, C.c_int, _P, _P, C.POINTER(DtwCfg))
 _PROTOTYPES = {
     # name: (restype, argtypes)
     "tcr_abi_version": (C.c_int, []),
@@ -261,6 +269,15 @@ _PROTOTYPES = {
     "tcr_resample": (C.c_int, [C.POINTER(ResampleCfg), _P, C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64,
                                _P]),
     "tcr_resample_span": (C.c_int, [C.POINTER(ResampleCfg), C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    # (the template tables of the tcr_dtw_* entries: n_templates, templates, frame_offsets, n_keywords, keyword_offsets, scale, cfg)
+    "tcr_dtw_frames_max": (C.c_int, [C.c_int]),
+    "tcr_dtw_scores": (C.c_int, [C.c_int, C.c_int64, C.c_int, _P, *_DTW_TABLES, _P, _P, _P]),
+    "tcr_dtw_scores_ragged": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, *_DTW_TABLES, _P, _P, _P]),
+    "tcr_dtw_stream_state_bytes": (C.c_size_t, [C.c_int, C.c_int, *_DTW_TABLES]),
+    "tcr_dtw_stream_init": (C.c_int, [C.c_int, C.c_int, *_DTW_TABLES, _P, _P]),
+    "tcr_dtw_stream_push": (C.c_int, [C.c_int, C.c_int64, C.c_int, _P, *_DTW_TABLES, C.POINTER(DetectCfg), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "tcr_dtw_stream_push_ragged": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, *_DTW_TABLES, C.POINTER(DetectCfg), _P, _P, _P, _P, _P, _P,
+                                             _P, _P]),
 }
 
 ABI_SYMBOLS = tuple(_PROTOTYPES.keys())

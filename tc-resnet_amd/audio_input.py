@@ -248,6 +248,11 @@ def add_detector_flags(p, each: str = "signal", threshold: bool = True, offline:
         p.add_argument("--phrase_unordered", action="store_true", help="phrases: the words in any order (default: in the given order)")
         p.add_argument("--phrase_combine", choices=("product", "min"), default="product",
                        help="phrases: a phrase's score is the product or the minimum of its words' posteriors")
+        p.add_argument("--templates", default=None,
+                       help="detect enrolled keywords instead of the model's words: a TEMPLATES.npz of enroll_audio.py (scanning.TemplateDetector); "
+                            "not with --phrases" + (" or --chunk_seconds / --ragged_chunk_seconds" if offline else ""))
+        p.add_argument("--template_max_stretch", type=float, default=3.0,
+                       help="templates: a match longer than this many times the longest template scores 0 (<= 0: no limit)")
 
 
 def detector_settings(args) -> dict:
@@ -337,16 +342,32 @@ def check_phrase_flags(args) -> None:
     if getattr(args, "phrases", None) is not None and chunked:
         raise SystemExit("--phrases scores whole scans: it cannot be combined with --chunk_seconds or --ragged_chunk_seconds (a chunk's "
                          "first steps would need the previous chunk's rows)")
+    if getattr(args, "templates", None) is not None:
+        if getattr(args, "phrases", None) is not None:
+            raise SystemExit("--templates and --phrases are two detectors over the scan's posteriors: give one of them")
+        if chunked:
+            raise SystemExit("--templates scores whole scans: it cannot be combined with --chunk_seconds or --ragged_chunk_seconds (a chunk's "
+                             "first steps would need the previous chunk's DTW column)")
+
+
+def open_templates(args, scanner):
+    """The `scanning.TemplateDetector` of --templates over `scanner`'s outputs (None without the flag): the enrolled keywords of an
+    enroll_audio.py file, its threshold and suppression the detector flags', its labels the keyword names and _background_."""
+    path = getattr(args, "templates", None)
+    if path is None:
+        return None
+    from .templates import KeywordTemplates, TemplateDetector
+    return TemplateDetector(scanner, KeywordTemplates.load(path), max_stretch=args.template_max_stretch)
 
 
 def open_phrases(args, scanner):
     """The `scanning.PhraseDetector` of --phrases over `scanner`'s outputs (a `KeywordScanner`, or stream_audio.py's
-    `StreamingDetector`; None without the flag): its threshold and suppression are the detector flags', its labels the phrase names
-    and _background_.  Refused with the scanning tools' chunked runs, which do not carry a phrase state yet."""
+    `StreamingDetector`; with --templates instead: `open_templates`' `scanning.TemplateDetector`, which has the same methods; None
+    without either flag): its threshold and suppression are the detector flags', its labels the phrase names and _background_.  Refused with the scanning tools' chunked runs, which do not carry a phrase state yet."""
     check_phrase_flags(args)
     spec = getattr(args, "phrases", None)
     if spec is None:
-        return None
+        return open_templates(args, scanner)            # (--templates: the same place in the tools, the same methods)
     if spec.startswith("@"):
         with open(spec[1:]) as fh:
             lines = [x.strip() for x in fh]

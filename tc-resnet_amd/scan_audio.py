@@ -5,6 +5,7 @@
                          [--max_windows B] [--summary] [--chunk_seconds X | --ragged | --ragged_chunk_seconds X]
                          [--second_frozen MODEL2.npz --enter_threshold P [--cascade_pad_ms MS] [--cascade_pad_before_ms MS] [--second_frames_per_step K]]
                          [--phrases "w1 w2;w3 w4" | @FILE [--phrase_window_ms MS] [--phrase_unordered] [--phrase_combine product|min]]
+                         [--templates TEMPLATES.npz [--template_max_stretch X]]
 
 The files (16-bit PCM) come from `audio_input.Recordings`, zero-padded to the longest, and are scanned in one
 `scanning.KeywordScanner` call; samples that do not fill a whole step are dropped (noted on stderr).  A file at another sample rate
@@ -30,7 +31,10 @@ same sample rate, classes and step (frames per step x hop).  --summary then gain
 (or @FILE, one phrase per line; words are --labels names or class indices) the lines and the summary are those of a
 `scanning.PhraseDetector` over the scan: label is the phrase, score its posterior -- the best product (--phrase_combine min: minimum)
 of its words' smoothed posteriors within --phrase_window_ms, in the given order unless --phrase_unordered -- with the detector
-flags' threshold and suppression; on the one-call run, --ragged and a cascade, not with --chunk_seconds / --ragged_chunk_seconds."""
+flags' threshold and suppression; on the one-call run, --ragged and a cascade, not with --chunk_seconds / --ragged_chunk_seconds.
+With --templates TEMPLATES.npz (written by enroll_audio.py; not with --phrases) they are those of a `scanning.TemplateDetector` instead:
+label is an enrolled keyword, score 1 - the cost of the best match of one of its templates that ends at the step, 0 for a match of
+more than --template_max_stretch (default 3) times the longest template's steps; on the same runs as --phrases."""
 from __future__ import annotations
 
 import argparse

@@ -23,9 +23,12 @@ hit, the windows that came close (`mine_detections`, `mine_peaks`, `select_top`,
 A `PhraseDetector` scores multi-word phrases from a scan's posteriors (tcr_phrase_scores): posteriors over the phrases and a background
 class, on which the detector rule, `sweep`, `tune` and `mine` run with P + 1 classes.
 
+A `TemplateDetector` does the same for keywords enrolled from a few recorded examples (`KeywordTemplates`), matched against the scan's
+posteriors by subsequence dynamic time warping (tcr_dtw_scores).
+
 This module holds the scanners and the cascade; the rest is importable from here and lives in `detection` (the outputs, the ms / step
 arithmetic and `DetectionStage`: `redetect`, `sweep`, `tune`, `mine` over a scan's outputs, no network needed), `scoring` (`detection_sweep`,
-`detection_grid`, their results), `mining` (`mine_*`, `select_top`, `gather_clips`, `MinedClips`), `phrases` (`PhraseDetector`, `StreamingPhraseDetector`) and `capturing`
+`detection_grid`, their results), `mining` (`mine_*`, `select_top`, `gather_clips`, `MinedClips`), `phrases` (`PhraseDetector`, `StreamingPhraseDetector`), `templates` (`KeywordTemplates`, `TemplateDetector`, `StreamingTemplateDetector`) and `capturing`
 (`StreamingRecorder`, `CapturedClips`).
 """
 from __future__ import annotations
@@ -48,6 +51,7 @@ from .phrases import BACKGROUND_LABEL, PHRASE_COMBINERS, PhraseDetector, PhraseG
 from .runtime import stream_of
 from .scoring import GridPoint, GridResult, SweepResult, _class_mask, _offsets, detection_grid, detection_sweep  # noqa: F401
 from .streaming import Network, _Detection
+from .templates import KeywordTemplates, StreamingTemplateDetector, TemplateDetector, dtw_scores  # noqa: F401
 
 DEFAULT_MAX_SIGNALS = 65536
 

@@ -3,6 +3,7 @@
     python stream_audio.py --frozen MODEL.npz --wav a.wav [b.wav ...] [--frames_per_step k] [--labels l0,l1,...]
                            [--average_window_ms MS] [--detection_threshold P] [--suppression_ms MS] [--min_count N]
                            [--phrases "w1 w2;w3 w4" | @FILE [--phrase_window_ms MS] [--phrase_unordered] [--phrase_combine product|min]]
+                           [--templates TEMPLATES.npz [--template_max_stretch X]]
                            [--second_frozen MODEL2.npz --enter_threshold P [--cascade_pad_ms MS] [--second_frames_per_step K]]
                            [--capture_dir DIR [--capture_lead_ms MS]]
 
@@ -13,7 +14,9 @@ is done.  Samples that do not fill a whole step are dropped (noted on stderr).  
 file,time_ms,label,score  -- time_ms is the end of the window that fired (every stream starts as if it had heard one clip of
 silence).  With --phrases "go left;stop no" (or @FILE, one phrase per line; words are --labels names or class indices) every step's
 output goes on through a `scanning.StreamingPhraseDetector` and the lines are its detections -- label is the phrase, score its
-posterior -- exactly those scan_audio.py --phrases prints for the same files and flags.  A streaming cascade (--second_frozen
+posterior -- exactly those scan_audio.py --phrases prints for the same files and flags; with --templates TEMPLATES.npz (written by
+enroll_audio.py; not with --phrases) through a `scanning.StreamingTemplateDetector`, and the lines are exactly those scan_audio.py
+--templates prints: label is an enrolled keyword.  A streaming cascade (--second_frozen
 MODEL2.npz and --enter_threshold P; `streaming.StreamingCascade`): --frozen steps every stream, and MODEL2's network runs only on the
 streams where one of --frozen's keyword classes (every class from 2 on) reaches P at this step or did within --cascade_pad_ms of audio
 before it (default: --average_window_ms minus one step); the other streams' posteriors are --frozen's, and the detector flags

@@ -7,6 +7,7 @@ curve (false rejects against false accepts per hour) from one scan.
                           [--min_count N] [--max_windows B] [--chunk_seconds X | --ragged | --ragged_chunk_seconds X]
                           [--second_frozen MODEL2.npz --enter_threshold P [--cascade_pad_ms MS] [--cascade_pad_before_ms MS] [--second_frames_per_step K]]
                           [--phrases "w1 w2;w3 w4" | @FILE [--phrase_window_ms MS] [--phrase_unordered] [--phrase_combine product|min]]
+                          [--templates TEMPLATES.npz [--template_max_stretch X]]
 
 The files are read as scan_audio.py reads them (`audio_input.Recordings`: 16-bit PCM, converted to the model's sample rate on the
 device where it differs, only whole steps), zero-padded to the longest and scanned in one call; one `KeywordScanner.sweep` then
@@ -30,7 +31,9 @@ lowest FRR with fa_per_hour <= --target_fa_per_hour (null when none is).
 
 With --phrases (scan_audio.py's flags: `scanning.PhraseDetector`) the curve is the phrase detector's over the scan: the events' labels
 and the --keywords are phrase names (the words joined by a space; default: every phrase, never _background_), on the one-call run,
---ragged and a cascade; not with --chunk_seconds / --ragged_chunk_seconds."""
+--ragged and a cascade; not with --chunk_seconds / --ragged_chunk_seconds.  With --templates (scan_audio.py's flags:
+`scanning.TemplateDetector` over an enroll_audio.py file; not with --phrases) it is the template detector's: the events' labels and the
+--keywords are the enrolled keywords' names, on the same runs."""
 from __future__ import annotations
 
 import argparse

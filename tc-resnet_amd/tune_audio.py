@@ -68,6 +68,9 @@ def parse_arguments(arguments: Optional[List[str]] = None):
     if args.phrases is not None:
         raise SystemExit("--phrases is sweep_audio.py's and scan_audio.py's: this tool tunes the word detector (a phrase detector's grid: "
                          "scanning.PhraseDetector.tune)")
+    if args.templates is not None:
+        raise SystemExit("--templates is sweep_audio.py's and scan_audio.py's: this tool tunes the word detector (a template detector's "
+                         "grid: scanning.TemplateDetector.tune)")
     try:
         args.grid_window_ms = _floats(lists.get("average_window_ms", args.average_window_ms))
         args.grid_min_count = [int(x) for x in str(lists.get("min_count", args.min_count)).split(",")]
