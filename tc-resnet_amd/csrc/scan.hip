@@ -120,7 +120,7 @@ struct ScanState {
     float* ring;                // [W][S][C]
     int* ist;                   // [5][S]: head, count, prev_label, prev_step, n
     const uint8_t* reset;       // [S] or null
-    int tail_len;
+    int tail_len;               // >= 0 (StreamGeom::tail_len)
 };
 
 __device__ __forceinline__ bool scan_fresh(const ScanState& st, int64_t s) { return !st.window || (st.reset && st.reset[s]); }
@@ -156,7 +156,9 @@ __device__ __forceinline__ int ragged_signal(const int64_t* off, int n_sig, int6
 }
 
 // Staging row r = group q0 + r: x from new frame g G k + k - T on, i.e. from sample (g G + 1) k hop of  zeros(n_prefix) ++ signal ++
-// zeros  (n_prefix = the clip's n_samples = T hop + tail_len), with the stream's tail in the last tail_len samples of the prefix.
+// zeros  (n_prefix = the clip's n_samples = T hop + win - hop + remainder), with the stream's tail in the last tail_len samples of the
+// prefix.  The rows are placed by sample position, so a hop > win whose steps begin in the gap between two frames (stream.hip:
+// tail_len = 0, skip > 0) needs nothing here: every new frame then lies within the call's samples, and no tail is read.
 // One thread per staged sample.
 __global__ __launch_bounds__(256) void scan_stage_kernel(const ScanChunkArgs a) {
     const int64_t total = a.rows * a.stride;

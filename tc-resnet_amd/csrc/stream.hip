@@ -9,6 +9,9 @@
 //   * the k new frames are computed by frontend_pk3_kernel's streaming instance from a staging row that holds exactly the samples
 //     they cover: tail ++ new, where tail = the last  win - hop + ((n_samples - win) mod hop)  samples heard (the new clip ends
 //     (n_samples - win) mod hop samples behind its last frame, so the staging row's first sample is the first new frame's first).
+//     With hop > win that count can be negative: the first  hop - win - ((n_samples - win) mod hop)  samples of a step lie in the gap
+//     between two frames and belong to none.  The state then keeps no tail (tail_len = 0) and the staging row starts that many
+//     samples (skip) into the step's new ones.  tail_len and skip are never both positive.
 // Nothing is accumulated: every column comes from raw samples, so the window does not drift however long a stream runs.
 //
 // Kernels of a step: stream_stage_kernel (reset, staging row, tail, window shift; one workgroup per stream, so the in-place shift has
@@ -37,24 +40,31 @@ namespace tcr {
 
 namespace {
 
-constexpr int kMaxTail = 1024;          // tail_len <= win - 1 < nfft <= 1024
+constexpr int kMaxTail = 1024;          // 0 <= tail_len <= win - 1 < nfft <= 1024 (hop > win: max(win - hop + remainder, 0))
 constexpr int kShiftRegs = 8;           // window elements per thread and pass of the shift
 
 struct StreamGeom {
     int S, k, T, tp, n_coef, classes, W;
-    int tail_len, stage_stride;
+    int tail_len, skip, stage_stride;   // samples kept per stream; samples of a step in front of its first new frame (hop > win)
     int64_t win_off, zw_off, tail_off, ring_off, ist_off, state_floats;         // state offsets in floats
     int64_t stage_floats, plane_off, net_ws_off, ws_floats;                     // workspace
 };
 
 int64_t align64(int64_t v) { return (v + 63) / 64 * 64; }     // floats -> 256 bytes
 
+// Where a step's new samples start, counted from the first new frame's first sample: win - hop + ((n_samples - win) mod hop).
+// Positive: that many samples heard before the step are part of the new frames (the tail).  Negative (hop > win only): the step's
+// first -that many samples belong to no frame.
+int stream_tail_samples(const tcr_frontend_cfg& cfg) { return cfg.win - cfg.hop + (cfg.n_samples - cfg.win) % cfg.hop; }
+
 StreamGeom stream_geom(const tcr_frontend_cfg& cfg, const tcr_model_ref& m, const ModelIO& io, int S, int k, int W) {
     StreamGeom g{};
     const int classes = io.classes;
     g.S = S; g.k = k; g.T = cfg.n_frames; g.tp = tcr_padded_len(cfg.n_frames); g.n_coef = cfg.n_coef; g.classes = classes; g.W = W;
-    g.tail_len = cfg.win - cfg.hop + (cfg.n_samples - cfg.win) % cfg.hop;
-    g.stage_stride = (g.tail_len + k * cfg.hop + 3) / 4 * 4;
+    const int behind = stream_tail_samples(cfg);
+    g.tail_len = std::max(behind, 0);
+    g.skip = std::max(-behind, 0);
+    g.stage_stride = (g.tail_len + k * cfg.hop - g.skip + 3) / 4 * 4;          // >= (k - 1) hop + win: the k new frames
     int64_t o = 0;
     g.win_off = o; o = align64(o + (int64_t)S * g.n_coef * g.tp);
     g.zw_off = o; o = align64(o + (int64_t)g.n_coef * g.tp);
@@ -89,6 +99,10 @@ int stream_check(const tcr_frontend_cfg* cfg, const tcr_model_ref* m, int S, int
     TCR_REQUIRE((cfg->hop & 1) == 0 && frontend_pk3_supports(cfg->nfft / 2, cfg->win, 0),
                 "%s: the streaming front-end (frontend_pk3_kernel) does not cover window %d / hop %d / %d mel bands at nfft %d; another "
                 "kernel would not give the offline features bitwise", what, cfg->win, cfg->hop, cfg->n_mel, cfg->nfft);
+    // (an odd clip: the offline front-end runs its general kernel, frontend.hip's `aligned`; the streaming instance would decline late)
+    TCR_REQUIRE((cfg->n_samples & 1) == 0, "%s: the streaming front-end (frontend_pk3_kernel) does not cover a clip of %d samples (an odd "
+                "clip length: the offline front-end runs another kernel on it, which would not give the streamed features bitwise)", what,
+                cfg->n_samples);
     {
         const int n_items = frontend_mel_item_count(*cfg), n_fast = mel_items_fast(cfg->nfft / 2);
         char why[160];
@@ -102,8 +116,8 @@ int stream_check(const tcr_frontend_cfg* cfg, const tcr_model_ref* m, int S, int
                     "nfft %d (%s); another kernel would not give the offline features bitwise", what, cfg->lower_hz, cfg->upper_hz,
                     cfg->sample_rate, cfg->nfft, why);
     }
-    TCR_REQUIRE(cfg->win - cfg->hop + (cfg->n_samples - cfg->win) % cfg->hop <= kMaxTail, "%s: window %d / hop %d leave a tail of more "
-                "than %d samples", what, cfg->win, cfg->hop, kMaxTail);
+    TCR_REQUIRE(stream_tail_samples(*cfg) <= kMaxTail, "%s: window %d / hop %d leave a tail of more than %d samples", what, cfg->win,
+                cfg->hop, kMaxTail);
     if (det) {
         TCR_REQUIRE(det->average_steps >= 1, "%s: average_steps (the ring of probability vectors) must be >= 1 (got %d)", what, det->average_steps);
         TCR_REQUIRE(det->min_count >= 1 && det->min_count <= det->average_steps, "%s: min_count %d outside 1..average_steps = %d", what,
@@ -122,11 +136,20 @@ struct StageArgs {
     const float* zw;            // [n_coef][tp]
     float* tail;                // [S][tail_len]
     float* stage;               // [S][stage_stride]
-    int khop, tail_len, stage_stride, n_coef, tp, T, k;
+    int khop, tail_len, skip, stage_stride, n_coef, tp, T, k;
 };
 
-// One workgroup per stream: reset, staging row tail ++ new samples, the new tail, the window's columns k..T-1 moved to 0..T-k-1 (the
-// front-end then writes columns T-k..T-1).  The old tail is read into LDS before the new one is written; the shift moves the window
+// The staging arguments of a step over the state at st (tcr_stream_step, tcr_stream_step_selected_m).
+static StageArgs stage_args(const StreamGeom& g, const tcr_frontend_cfg& cfg, const float* samples, const uint8_t* reset, float* st, float* stage) {
+    StageArgs sa;
+    sa.samples = samples; sa.reset = reset; sa.window = st + g.win_off; sa.zw = st + g.zw_off; sa.tail = st + g.tail_off; sa.stage = stage;
+    sa.khop = g.k * cfg.hop; sa.tail_len = g.tail_len; sa.skip = g.skip; sa.stage_stride = g.stage_stride; sa.n_coef = g.n_coef; sa.tp = g.tp;
+    sa.T = g.T; sa.k = g.k;
+    return sa;
+}
+
+// One workgroup per stream: reset, staging row tail ++ new samples (from sample `skip` of the new ones on: tail_len = 0 then), the new
+// tail, the window's columns k..T-1 moved to 0..T-k-1 (the front-end then writes columns T-k..T-1).  The old tail is read into LDS before the new one is written; the shift moves the window
 // in passes of 256 x kShiftRegs elements in row order, each read into registers before a barrier and written behind it -- a later
 // pass only reads columns (>= t + k of a row) that no earlier pass writes.
 __global__ __launch_bounds__(256) void stream_stage_kernel(const StageArgs a) {
@@ -139,7 +162,8 @@ __global__ __launch_bounds__(256) void stream_stage_kernel(const StageArgs a) {
     for (int i = tid; i < a.tail_len; i += 256) s_tail[i] = rst ? 0.f : tail[i];
     __syncthreads();
     float* stage = a.stage + (size_t)s * a.stage_stride;
-    for (int i = tid; i < a.tail_len + a.khop; i += 256) stage[i] = i < a.tail_len ? s_tail[i] : src[i - a.tail_len];
+    const float* fresh = src + a.skip;          // the new samples from the first new frame's first sample on
+    for (int i = tid; i < a.tail_len + a.khop - a.skip; i += 256) stage[i] = i < a.tail_len ? s_tail[i] : fresh[i - a.tail_len];
     for (int i = tid; i < a.tail_len; i += 256) {
         const int j = i + a.khop;
         tail[i] = j < a.tail_len ? s_tail[j] : src[j - a.tail_len];
@@ -359,9 +383,7 @@ int stream_step(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_mod
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* st = static_cast<float*>(state);
     float* ws = static_cast<float*>(workspace);
-    StageArgs sa;
-    sa.samples = samples; sa.reset = reset; sa.window = st + g.win_off; sa.zw = st + g.zw_off; sa.tail = st + g.tail_off; sa.stage = ws;
-    sa.khop = k * cfg->hop; sa.tail_len = g.tail_len; sa.stage_stride = g.stage_stride; sa.n_coef = g.n_coef; sa.tp = g.tp; sa.T = g.T; sa.k = k;
+    const StageArgs sa = stage_args(g, *cfg, samples, reset, st, ws);
     hipLaunchKernelGGL(stream_stage_kernel, dim3(g.S), dim3(256), 0, s, sa);
     TCR_TRY(check_launch("stream_stage_kernel"));
     TCR_TRY(stream_frontend(*cfg, plan_dev, ws, g.stage_stride, g.S, k, st + g.win_off, s));

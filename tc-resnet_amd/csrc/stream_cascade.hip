@@ -262,9 +262,7 @@ extern "C" int tcr_stream_step_selected_m(const tcr_frontend_cfg* cfg, const voi
     float* st = static_cast<float*>(state);
     float* ws = static_cast<float*>(workspace);
     const int n = (int)n_selected;
-    StageArgs sa;
-    sa.samples = samples; sa.reset = reset; sa.window = st + g.win_off; sa.zw = st + g.zw_off; sa.tail = st + g.tail_off; sa.stage = ws;
-    sa.khop = k * cfg->hop; sa.tail_len = g.tail_len; sa.stage_stride = g.stage_stride; sa.n_coef = g.n_coef; sa.tp = g.tp; sa.T = g.T; sa.k = k;
+    const StageArgs sa = stage_args(g, *cfg, samples, reset, st, ws);
     hipLaunchKernelGGL(stream_stage_kernel, dim3(g.S), dim3(256), 0, s, sa);
     TCR_TRY(check_launch("stream_stage_kernel"));
     TCR_TRY(stream_frontend(*cfg, plan_dev, ws, g.stage_stride, g.S, k, st + g.win_off, s));

@@ -31,7 +31,7 @@ def state_parts(det):
     """The state's regions (stream.hip, StreamGeom): window [S, n_coef, Tp], tail [S, tail_len], ring [W, S, C], integers [5, S]."""
     cfg, S, W, ncls = det.frontend.cfg, det.n_streams, det.average_steps, det.net.num_classes
     tp = T._lib.padded_len(cfg.n_frames)
-    tail_len = cfg.win - cfg.hop + (cfg.n_samples - cfg.win) % cfg.hop
+    tail_len = max(cfg.win - cfg.hop + (cfg.n_samples - cfg.win) % cfg.hop, 0)     # (hop > win: no tail is kept when it is negative)
     o = align64(S * cfg.n_coef * tp)
     o = align64(o + cfg.n_coef * tp)
     tail_off = o

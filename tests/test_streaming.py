@@ -42,7 +42,7 @@ class Clips:
     def step(self, x, reset_idx=()):
         for i in reset_idx:
             self.clip[i] = 0.0
-        self.clip = torch.cat([self.clip[:, x.shape[1]:], x], dim=1).contiguous()
+        self.clip = torch.cat([self.clip, x], dim=1)[:, -self.clip.shape[1]:].contiguous()     # (a step may be longer than a clip)
         return self.clip
 
 
