@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from ._lib import TcrError
-from .detection import RaggedScanOutput, _ragged_signals, _step_ms
+from .detection import PendingResets, RaggedScanOutput, _ragged_signals, _step_ms, reset_mask
 from .runtime import stream_of
 from .scoring import _class_mask
 
@@ -78,7 +78,7 @@ def _stage_of(detector):
     raise TcrError(f"StreamingRecorder: {type(detector).__name__} has no detection stage and stream count")
 
 
-class StreamingRecorder:
+class StreamingRecorder(PendingResets):
     """The clips behind a streaming detector's detections.  `detector`: a `StreamingDetector`, `StreamingCascade` or
     `StreamingPhraseDetector` (anything with a `stage` -- its own, its `second`'s or its `detector`'s -- and `n_streams`): it supplies
     the stream count, the step, the sample rate, the class count and the clip length (n_samples overrides that).  lead_ms: the clip
@@ -117,9 +117,8 @@ class StreamingRecorder:
         self._stream, self._step = torch.zeros(cap, dtype=torch.int32, device=dev), torch.zeros(cap, dtype=torch.int64, device=dev)
         self._label, self._score = torch.zeros(cap, dtype=torch.int32, device=dev), torch.zeros(cap, dtype=torch.float32, device=dev)
         self._count = torch.zeros(2, dtype=torch.int32, device=dev)
-        self._reset_dev = torch.zeros(S, dtype=torch.uint8, device=dev)
+        self._init_resets(dev)
         self._mask_dev = torch.zeros(S, dtype=torch.uint8, device=dev)
-        self._pending: Optional[np.ndarray] = None
         self._ws: Optional[torch.Tensor] = None
         self._workspace(max(S, S * self.delay_steps))
         lib.check(lib.tcr_capture_init(S, self.step_samples, n, self.lead, self.state.data_ptr(), stream_of(dev)), "tcr_capture_init")
@@ -132,21 +131,6 @@ class StreamingRecorder:
         if self._ws is None or self._ws.numel() * 4 < nws:
             self._ws = torch.empty((nws + 3) // 4, dtype=torch.int32, device=self.device)
         return self._ws
-
-    def reset(self, mask_or_indices) -> None:
-        """Start streams' recordings afresh at their NEXT pushed row, before it (pending triggers dropped, earlier audio reads as
-        zeros, steps count from 0): `StreamingDetector.reset`'s argument and rules -- a reset stays pending for a stream that has no
-        rows in a ragged push.  Reset the recorder whenever the detector is."""
-        from .streaming import reset_mask
-        mask = reset_mask(mask_or_indices, self.n_streams)
-        self._pending = mask if self._pending is None else (self._pending | mask)
-
-    def _take_reset(self) -> Optional[int]:
-        if self._pending is None:
-            return None
-        self._reset_dev.copy_(torch.from_numpy(self._pending.astype(np.uint8)))
-        self._pending = None
-        return self._reset_dev.data_ptr()
 
     def _outputs(self):
         return (self.capacity, self._clips.data_ptr(), None if self._pcm is None else self._pcm.data_ptr(), self._stream.data_ptr(),
@@ -195,15 +179,12 @@ class StreamingRecorder:
                 return CapturedClips(self)
             ws = self._workspace(total)
             off_dev = torch.from_numpy(out.offsets).to(self.device)
-            pending, reset_ptr = self._pending, self._take_reset()
-            self._pending = pending                             # (until the call has run; it ignores the flag of a stream without rows)
+            reset_ptr = self._begin_ragged_reset()
             lib.check(lib.tcr_capture_push_ragged(S, off_dev.data_ptr(), total, *head, packed.data_ptr(), out.top.data_ptr(),
                                                   out.score.data_ptr(), out.is_new.data_ptr(), self._cmask.data_ptr(), self.num_classes,
                                                   reset_ptr, self.state.data_ptr(), ws.data_ptr(), ws.numel() * 4, *self._outputs()),
                       "tcr_capture_push_ragged")
-            if pending is not None:
-                left = pending & (rows == 0)
-                self._pending = left if left.any() else None
+            self._end_ragged_reset(rows)
             return CapturedClips(self)
         if not isinstance(samples, torch.Tensor):
             raise TcrError("StreamingRecorder.push: a dense output needs the samples tensor [S, rows * step_samples] it was computed from")
@@ -223,7 +204,6 @@ class StreamingRecorder:
         """The pending clips (detections of the last `delay_steps` rows, whose lead has not been heard yet) of the streams in `mask`
         (`reset`'s argument forms; None: all), audio not yet heard as zeros -- what `mine` gives for a detection near a recording's end.
         They are forgotten, so a stream that goes on does not return them again; the recordings go on as they were."""
-        from .streaming import reset_mask
         mask_ptr = None
         if mask is not None:
             self._mask_dev.copy_(torch.from_numpy(reset_mask(mask, self.n_streams).astype(np.uint8)))

@@ -151,9 +151,7 @@ int detect_point_check(const char* what, int W, int min_count, int suppression) 
 
 // n_signals, steps (dense) / total_steps (ragged) and num_classes of a probs array
 int detect_shape_check(const char* what, bool ragged, int n_signals, int64_t steps, int64_t total_steps, int num_classes) {
-    TCR_REQUIRE(n_signals > 0, "%s: the number of signals must be positive (got %d)", what, n_signals);
-    TCR_REQUIRE(ragged ? total_steps > 0 : steps > 0, "%s: the number of steps must be positive (got %lld)", what,
-                (long long)(ragged ? total_steps : steps));
+    TCR_TRY(detect_rows_check(what, ragged, n_signals, steps, total_steps, "signals"));
     TCR_REQUIRE(num_classes > 0 && num_classes <= kSweepMaxClasses, "%s: num_classes %d outside 1..%d", what, num_classes, kSweepMaxClasses);
     const int64_t rows = ragged ? total_steps : steps * n_signals;
     TCR_REQUIRE((ragged || steps < ((int64_t)1 << 31)) && rows < ((int64_t)1 << 31) && rows * num_classes < ((int64_t)1 << 31),
@@ -182,9 +180,27 @@ int redetect(const char* what, bool ragged, int n_signals, int64_t steps, const 
     da.suppression = det->suppression_steps; da.threshold = det->threshold; da.step_off = ragged ? step_offsets : nullptr;
     const int64_t rows = ragged ? total_steps : steps * n_signals;
     TCR_TRY(smoothed ? smooth_launch<kSmoothAll>(da, ragged, rows, s) : smooth_launch<kSmoothNoVector>(da, ragged, rows, s));
-    const auto suppress = ragged ? scan_suppress_kernel<true> : scan_suppress_kernel<false>;
-    hipLaunchKernelGGL(suppress, dim3(n_signals), dim3(256), 0, s, da);
-    return check_launch("scan_suppress_kernel");
+    return suppress_launch(da, ragged, s);
+}
+
+// The carried detector tail over posteriors (tcr_phrase_stream_push*, tcr_dtw_stream_push*): redetect's detector at one vector per
+// decision, from the integers `ist` of a stream state.  Refuses what the tail cannot run (`noun`: what the posteriors are over) and fills
+// `da`, in front of the caller's first launch (a refused call writes nothing); the caller then launches its posteriors,
+// smooth_launch<kSmoothNoVector>(da, ..), what must lie behind the readers of its old state, and suppress_launch(da, ..).
+int posterior_tail_args(const char* what, const char* noun, const tcr_detect_cfg* det, const uint8_t* reset, int* ist, const float* post,
+                        int32_t* top, float* score, int32_t* is_new, bool ragged, int64_t steps, int64_t total_steps, const int64_t* step_off,
+                        int n_streams, int num_classes, ScanDetectArgs& da) {
+    TCR_REQUIRE(det->average_steps == 1 && det->min_count == 1,
+                "%s: the detector over %s posteriors takes one vector per decision: average_steps and min_count must be 1 (got %d, %d)", what, noun,
+                det->average_steps, det->min_count);
+    TCR_REQUIRE(det->suppression_steps >= 0, "%s: suppression_steps must be >= 0 (got %d)", what, det->suppression_steps);
+    da.probs = post; da.smoothed = nullptr; da.top = top; da.score = score; da.is_new = is_new;
+    da.st = ScanState{};
+    da.st.window = reinterpret_cast<float*>(ist);       // (not read: non-null says that there is a state to start from)
+    da.st.ist = ist; da.st.reset = reset;
+    da.steps = ragged ? total_steps : steps; da.N = n_streams; da.C = num_classes; da.W = 1; da.min_count = 1;
+    da.suppression = det->suppression_steps; da.threshold = det->threshold; da.step_off = ragged ? step_off : nullptr;
+    return TCR_OK;
 }
 
 size_t grid_row_bytes(int64_t total_steps) { return (size_t)round_up64(total_steps * 4, 256); }

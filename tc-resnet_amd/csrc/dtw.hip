@@ -33,7 +33,9 @@
 // and n int32 [total_frames x S], template q's block at frame_offsets[q] x S and stream s's L_q values at s x L_q inside it.  A push
 // is four launches in stream order: dtw_kernel<.., CARRIED>, dtw_bg_kernel, detect_smooth_kernel at one vector per decision
 // (tcr_detect_redetect's own instance) and scan_suppress_kernel (scan.hip) from the carried integers.  A stream without rows in a
-// ragged call is skipped by all of them: its state stays byte for byte, its reset flag is ignored.
+// ragged call is skipped by all of them: its state stays byte for byte, its reset flag is ignored.  The last two are the carried
+// posterior tail phrase.hip shares (posterior_tail_args, detect_grid.hip, in front of the first launch; suppress_launch, scan.hip); the
+// integers' size, initial values and the row checks are scan.hip's (detect_state_ints_bytes, detect_ints_init, detect_*_check).
 //
 // Limits: F <= TCR_DTW_MAX_FEATURES, Q <= TCR_DTW_MAX_TEMPLATES, L <= tcr_dtw_frames_max(F) = min(256, 4096 / F) (four frames a lane,
 // and a wave's template frames within 32 KB of LDS: 256 up to F = 16, 64 at F = 64); there is no path above them.  frame_offsets,
@@ -242,8 +244,7 @@ __global__ __launch_bounds__(256) void dtw_bg_kernel(const DtwArgs a) {
 // every stream: no rows seen, no detection yet (head, count, prev_label, prev_step, n), every D +inf (the memset in front left n = 0)
 __global__ __launch_bounds__(256) void dtw_init_kernel(int* ist, float* st_D, int S, int64_t n_D) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < 5 * (int64_t)S) ist[i] = i / S == 2 ? -1 : 0;
-    else if (i - 5 * (int64_t)S < n_D) st_D[i - 5 * (int64_t)S] = INFINITY;
+    if (!detect_ints_init(ist, S, i) && i - 5 * (int64_t)S < n_D) st_D[i - 5 * (int64_t)S] = INFINITY;
 }
 
 namespace {
@@ -281,15 +282,6 @@ int dtw_tables(const char* what, int n_features, int n_templates, const float* t
     return TCR_OK;
 }
 
-// the sizes of a call's rows: steps (dense) / total_steps (ragged) x the wider of the input and output rows
-int dtw_size_check(const char* what, bool ragged, int n_signals, int64_t steps, int64_t total_steps, int n_features, int n_keywords) {
-    const int64_t rows = ragged ? total_steps : steps * n_signals;
-    const int widest = n_features > n_keywords + 1 ? n_features : n_keywords + 1;
-    TCR_REQUIRE((ragged || steps < ((int64_t)1 << 31)) && rows < ((int64_t)1 << 31) && rows * widest < ((int64_t)1 << 31),
-                "%s: %lld steps in all x %d columns is too large", what, (long long)rows, widest);
-    return TCR_OK;
-}
-
 // dtw_kernel over the call's (signal, keyword) pairs and the background behind it
 template <bool CARRIED>
 int dtw_launch(const DtwArgs& a, bool ragged, hipStream_t s) {
@@ -303,29 +295,21 @@ int dtw_launch(const DtwArgs& a, bool ragged, hipStream_t s) {
     return check_launch("dtw_bg_kernel");
 }
 
-int dtw_rows_check(const char* what, bool ragged, int n, int64_t steps, int64_t total_steps, const char* whose) {
-    TCR_REQUIRE(n > 0, "%s: the number of %s must be positive (got %d)", what, whose, n);
-    TCR_REQUIRE(ragged ? total_steps > 0 : steps > 0, "%s: the number of steps must be positive (got %lld)", what,
-                (long long)(ragged ? total_steps : steps));
-    return TCR_OK;
-}
-
 int dtw_scores(const char* what, bool ragged, int n_signals, int64_t steps, const int64_t* step_offsets, int64_t total_steps, int n_features,
                const float* values, int n_templates, const float* templates, const int32_t* frame_offsets, int n_keywords,
                const int32_t* keyword_offsets, const float* scale, const tcr_dtw_cfg* cfg, float* out, int32_t* lengths, void* stream) {
     TCR_REQUIRE((!ragged || step_offsets) && values && out, "%s: null argument", what);
     DtwArgs a{};
     TCR_TRY(dtw_tables(what, n_features, n_templates, templates, frame_offsets, n_keywords, keyword_offsets, scale, cfg, a));
-    TCR_TRY(dtw_rows_check(what, ragged, n_signals, steps, total_steps, "signals"));
-    TCR_TRY(dtw_size_check(what, ragged, n_signals, steps, total_steps, n_features, n_keywords));
+    TCR_TRY(detect_rows_check(what, ragged, n_signals, steps, total_steps, "signals"));
+    TCR_TRY(detect_size_check(what, ragged, n_signals, steps, total_steps, n_features, n_keywords + 1));
     a.values = values; a.out = out; a.lengths = lengths; a.step_off = ragged ? step_offsets : nullptr;
     a.steps = steps; a.total = ragged ? total_steps : steps * n_signals; a.N = n_signals;
     return dtw_launch<false>(a, ragged, static_cast<hipStream_t>(stream));
 }
 
 // The stream state: | the detector integers [5][S] int32 (scan.hip's layout; at one vector per decision head stays 0 and count 1, and n
-// is the rows the stream has seen), rounded up to 256 bytes | D float32 [total_frames x S] | n int32 [total_frames x S] |.
-size_t dtw_state_ints_bytes(int S) { return (size_t)round_up64((int64_t)S * 5 * sizeof(int32_t), 256); }
+// is the rows the stream has seen), detect_state_ints_bytes(S) | D float32 [total_frames x S] | n int32 [total_frames x S] |.
 
 int dtw_stream_geom(const char* what, int n_streams, int n_features, int n_templates, const float* templates, const int32_t* frame_offsets,
                     int n_keywords, const int32_t* keyword_offsets, const float* scale, const tcr_dtw_cfg* cfg, DtwArgs& a) {
@@ -342,35 +326,25 @@ int dtw_stream_push(const char* what, bool ragged, int n_streams, int64_t steps,
     TCR_REQUIRE((!ragged || step_offsets) && values && det && state && post && top && score && is_new, "%s: null argument", what);
     DtwArgs a{};
     TCR_TRY(dtw_stream_geom(what, n_streams, n_features, n_templates, templates, frame_offsets, n_keywords, keyword_offsets, scale, cfg, a));
-    TCR_TRY(dtw_rows_check(what, ragged, n_streams, steps, total_steps, "streams"));
-    TCR_REQUIRE(det->average_steps == 1 && det->min_count == 1,
-                "%s: the detector over template posteriors takes one vector per decision: average_steps and min_count must be 1 (got %d, %d)", what,
-                det->average_steps, det->min_count);
-    TCR_REQUIRE(det->suppression_steps >= 0, "%s: suppression_steps must be >= 0 (got %d)", what, det->suppression_steps);
-    TCR_TRY(dtw_size_check(what, ragged, n_streams, steps, total_steps, n_features, n_keywords));
+    TCR_TRY(detect_rows_check(what, ragged, n_streams, steps, total_steps, "streams"));
+    ScanDetectArgs da;
+    TCR_TRY(posterior_tail_args(what, "template", det, reset, static_cast<int*>(state), post, top, score, is_new, ragged, steps, total_steps,
+                                step_offsets, n_streams, n_keywords + 1, da));
+    TCR_TRY(detect_size_check(what, ragged, n_streams, steps, total_steps, n_features, n_keywords + 1));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t rows = ragged ? total_steps : steps * n_streams;
     const size_t n_D = (size_t)a.frame_off[a.Q] * n_streams;
     a.values = values; a.out = post; a.lengths = lengths; a.step_off = ragged ? step_offsets : nullptr;
     a.steps = steps; a.total = rows;
-    a.st_D = reinterpret_cast<float*>(static_cast<char*>(state) + dtw_state_ints_bytes(n_streams));
+    a.st_D = reinterpret_cast<float*>(static_cast<char*>(state) + detect_state_ints_bytes(n_streams));
     a.st_n = reinterpret_cast<int32_t*>(a.st_D + n_D);
     a.reset = reset;
     // 1. the posteriors and lengths, from the carried columns; the columns after the call's rows
     TCR_TRY(dtw_launch<true>(a, ragged, s));
     // 2. top / score and the candidate flags: tcr_detect_redetect's own smoothing instance at one vector per decision
-    ScanDetectArgs da;
-    da.probs = post; da.smoothed = nullptr; da.top = top; da.score = score; da.is_new = is_new;
-    da.st = ScanState{};
-    da.st.window = a.st_D;                              // (not read: non-null says that there is a state to start from)
-    da.st.ist = static_cast<int*>(state); da.st.reset = reset;
-    da.steps = ragged ? total_steps : steps; da.N = n_streams; da.C = n_keywords + 1; da.W = 1; da.min_count = 1;
-    da.suppression = det->suppression_steps; da.threshold = det->threshold; da.step_off = a.step_off;
     TCR_TRY(smooth_launch<kSmoothNoVector>(da, ragged, rows, s));
     // 3. the suppression walk from the carried detector, and the integers (n += the stream's rows)
-    const auto suppress = ragged ? scan_suppress_kernel<true> : scan_suppress_kernel<false>;
-    hipLaunchKernelGGL(suppress, dim3(n_streams), dim3(256), 0, s, da);
-    return check_launch("scan_suppress_kernel");
+    return suppress_launch(da, ragged, s);
 }
 
 }  // namespace
@@ -402,7 +376,7 @@ extern "C" size_t tcr_dtw_stream_state_bytes(int n_streams, int n_features, int 
     if (dtw_stream_geom("tcr_dtw_stream_state_bytes", n_streams, n_features, n_templates, templates, frame_offsets, n_keywords, keyword_offsets,
                         scale, cfg, a) != TCR_OK)
         return 0;
-    return dtw_state_ints_bytes(n_streams) + (size_t)a.frame_off[a.Q] * n_streams * 8;
+    return detect_state_ints_bytes(n_streams) + (size_t)a.frame_off[a.Q] * n_streams * 8;
 }
 
 extern "C" int tcr_dtw_stream_init(int n_streams, int n_features, int n_templates, const float* templates, const int32_t* frame_offsets,
@@ -413,7 +387,7 @@ extern "C" int tcr_dtw_stream_init(int n_streams, int n_features, int n_template
     DtwArgs a{};
     TCR_TRY(dtw_stream_geom(what, n_streams, n_features, n_templates, templates, frame_offsets, n_keywords, keyword_offsets, scale, cfg, a));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t ints = dtw_state_ints_bytes(n_streams), n_D = (size_t)a.frame_off[a.Q] * n_streams;
+    const size_t ints = detect_state_ints_bytes(n_streams), n_D = (size_t)a.frame_off[a.Q] * n_streams;
     if (hipMemsetAsync(state, 0, ints + n_D * 8, s) != hipSuccess) {
         set_error("%s: hipMemsetAsync failed", what);
         return TCR_ERR_HIP;

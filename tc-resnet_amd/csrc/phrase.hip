@@ -35,6 +35,8 @@
 //      before the row counts move;
 //   4. scan_suppress_kernel (scan.hip) from the carried integers: is_new, and the integers (n += m_s).
 //   A stream without rows in a ragged call is skipped by all four: its state stays byte for byte, its reset flag is ignored.
+//   2 and 4 are the carried posterior tail dtw.hip shares (posterior_tail_args, detect_grid.hip, in front of launch 1; suppress_launch,
+//   scan.hip); the integers' size, initial values and the row checks are scan.hip's (detect_state_ints_bytes, detect_ints_init, detect_*_check).
 //
 // The LDS limit: (TCR_PHRASE_TILE + w - 1) x U floats of dynamic LDS within 64 KB a workgroup (no static LDS next to it), i.e.
 // tcr_phrase_window_max(U) = 16384 / U - 255 (U = 4: 3841, U = 12: 1110, U = 64: 1; none above).  There is no path above it.
@@ -319,8 +321,7 @@ __global__ __launch_bounds__(256) void phrase_hist_kernel(const PhraseArgs a) {
 
 // every stream: no rows seen, no detection yet (head, count, prev_label, prev_step, n)
 __global__ __launch_bounds__(256) void phrase_init_kernel(int* ist, int S) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < 5 * S) ist[i] = i / S == 2 ? -1 : 0;
+    detect_ints_init(ist, S, (int64_t)blockIdx.x * 256 + threadIdx.x);
 }
 
 namespace {
@@ -368,15 +369,6 @@ int phrase_tables(const char* what, int num_classes, int n_phrases, const int32_
     return TCR_OK;
 }
 
-// the sizes of a call's rows: steps (dense) / total_steps (ragged) x the wider of the input and output rows
-int phrase_size_check(const char* what, bool ragged, int n_signals, int64_t steps, int64_t total_steps, int num_classes, int n_phrases) {
-    const int64_t rows = ragged ? total_steps : steps * n_signals;
-    const int widest = num_classes > n_phrases + 1 ? num_classes : n_phrases + 1;
-    TCR_REQUIRE((ragged || steps < ((int64_t)1 << 31)) && rows < ((int64_t)1 << 31) && rows * widest < ((int64_t)1 << 31),
-                "%s: %lld steps in all x %d columns is too large", what, (long long)rows, widest);
-    return TCR_OK;
-}
-
 // phrase_kernel over the call's tiles: CARRIED from the stream state in `a`
 template <bool CARRIED>
 int phrase_tile_launch(const char* what, const PhraseArgs& a, bool ragged, int64_t total_steps, hipStream_t s) {
@@ -396,12 +388,10 @@ int phrase_scores(const char* what, bool ragged, int n_signals, int64_t steps, c
                   const float* values, int n_phrases, const int32_t* phrase_offsets, const int32_t* phrase_words, const tcr_phrase_cfg* cfg,
                   float* out, void* stream) {
     TCR_REQUIRE((!ragged || step_offsets) && values && phrase_offsets && phrase_words && cfg && out, "%s: null argument", what);
-    TCR_REQUIRE(n_signals > 0, "%s: the number of signals must be positive (got %d)", what, n_signals);
-    TCR_REQUIRE(ragged ? total_steps > 0 : steps > 0, "%s: the number of steps must be positive (got %lld)", what,
-                (long long)(ragged ? total_steps : steps));
+    TCR_TRY(detect_rows_check(what, ragged, n_signals, steps, total_steps, "signals"));
     PhraseArgs a{};
     TCR_TRY(phrase_tables(what, num_classes, n_phrases, phrase_offsets, phrase_words, cfg, a));
-    TCR_TRY(phrase_size_check(what, ragged, n_signals, steps, total_steps, num_classes, n_phrases));
+    TCR_TRY(detect_size_check(what, ragged, n_signals, steps, total_steps, num_classes, n_phrases + 1));
     a.values = values; a.out = out; a.step_off = ragged ? step_offsets : nullptr;
     a.steps = steps; a.tiles = ragged ? 0 : ceil_div64(steps, kPhraseTile);
     a.N = n_signals;
@@ -409,8 +399,7 @@ int phrase_scores(const char* what, bool ragged, int n_signals, int64_t steps, c
 }
 
 // The stream state: | the detector integers [5][S] int32 (scan.hip's layout: head, count, prev_label, prev_step, n; at average_steps = 1
-// head stays 0 and count 1, and n doubles as the rows the stream has seen), rounded up to 256 bytes | ring [w - 1][U][S] float32 |.
-size_t phrase_state_ints_bytes(int S) { return (size_t)round_up64((int64_t)S * 5 * sizeof(int32_t), 256); }
+// head stays 0 and count 1, and n doubles as the rows the stream has seen), detect_state_ints_bytes(S) | ring [w - 1][U][S] float32 |.
 
 // what tcr_phrase_stream_state_bytes / _init / _push* check about (S, C, tables, cfg); fills a's tables, N and H
 int phrase_stream_geom(const char* what, int n_streams, int num_classes, int n_phrases, const int32_t* phrase_offsets, const int32_t* phrase_words,
@@ -431,23 +420,20 @@ int phrase_stream_push(const char* what, bool ragged, int n_streams, int64_t ste
                        float* score, int32_t* is_new, void* stream) {
     TCR_REQUIRE((!ragged || step_offsets) && values && phrase_offsets && phrase_words && cfg && det && state && post && top && score && is_new,
                 "%s: null argument", what);
-    TCR_REQUIRE(n_streams > 0, "%s: the number of streams must be positive (got %d)", what, n_streams);
-    TCR_REQUIRE(ragged ? total_steps > 0 : steps > 0, "%s: the number of steps must be positive (got %lld)", what,
-                (long long)(ragged ? total_steps : steps));
+    TCR_TRY(detect_rows_check(what, ragged, n_streams, steps, total_steps, "streams"));
     PhraseArgs a{};
     TCR_TRY(phrase_stream_geom(what, n_streams, num_classes, n_phrases, phrase_offsets, phrase_words, cfg, a));
-    TCR_REQUIRE(det->average_steps == 1 && det->min_count == 1,
-                "%s: the detector over phrase posteriors takes one vector per decision: average_steps and min_count must be 1 (got %d, %d)", what,
-                det->average_steps, det->min_count);
-    TCR_REQUIRE(det->suppression_steps >= 0, "%s: suppression_steps must be >= 0 (got %d)", what, det->suppression_steps);
-    TCR_TRY(phrase_size_check(what, ragged, n_streams, steps, total_steps, num_classes, n_phrases));
+    ScanDetectArgs da;
+    TCR_TRY(posterior_tail_args(what, "phrase", det, reset, static_cast<int*>(state), post, top, score, is_new, ragged, steps, total_steps,
+                                step_offsets, n_streams, n_phrases + 1, da));
+    TCR_TRY(detect_size_check(what, ragged, n_streams, steps, total_steps, num_classes, n_phrases + 1));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t rows = ragged ? total_steps : steps * n_streams;
     a.values = values; a.out = post; a.step_off = ragged ? step_offsets : nullptr;
     a.steps = steps; a.tiles = ragged ? 0 : ceil_div64(steps, kPhraseTile);
     a.total = rows;
-    a.ist = static_cast<int*>(state);
-    a.ring = reinterpret_cast<float*>(static_cast<char*>(state) + phrase_state_ints_bytes(n_streams));
+    a.ist = da.st.ist;
+    a.ring = reinterpret_cast<float*>(static_cast<char*>(state) + detect_state_ints_bytes(n_streams));
     a.reset = reset;
     // 1. the posteriors, from the old ring and the old row counts
     if (rows <= (int64_t)kPhraseLaneRows * n_streams) {
@@ -458,13 +444,6 @@ int phrase_stream_push(const char* what, bool ragged, int n_streams, int64_t ste
         TCR_TRY(phrase_tile_launch<true>(what, a, ragged, total_steps, s));
     }
     // 2. top / score and the candidate flags: tcr_detect_redetect's own smoothing instance at one vector per decision
-    ScanDetectArgs da;
-    da.probs = post; da.smoothed = nullptr; da.top = top; da.score = score; da.is_new = is_new;
-    da.st = ScanState{};
-    da.st.window = a.ring;                              // (not read: non-null says that there is a state to start from)
-    da.st.ist = a.ist; da.st.reset = reset;
-    da.steps = ragged ? total_steps : steps; da.N = n_streams; da.C = n_phrases + 1; da.W = 1; da.min_count = 1;
-    da.suppression = det->suppression_steps; da.threshold = det->threshold; da.step_off = a.step_off;
     TCR_TRY(smooth_launch<kSmoothNoVector>(da, ragged, rows, s));
     // 3. the new rows into the ring, behind their readers and before the row counts move
     if (a.H > 0) {
@@ -475,9 +454,7 @@ int phrase_stream_push(const char* what, bool ragged, int n_streams, int64_t ste
         TCR_TRY(check_launch("phrase_hist_kernel"));
     }
     // 4. the suppression walk from the carried detector, and the integers (n += the stream's rows)
-    const auto suppress = ragged ? scan_suppress_kernel<true> : scan_suppress_kernel<false>;
-    hipLaunchKernelGGL(suppress, dim3(n_streams), dim3(256), 0, s, da);
-    return check_launch("scan_suppress_kernel");
+    return suppress_launch(da, ragged, s);
 }
 
 }  // namespace
@@ -514,7 +491,7 @@ extern "C" size_t tcr_phrase_stream_state_bytes(int n_streams, int num_classes, 
         return 0;
     }
     if (phrase_stream_geom(what, n_streams, num_classes, n_phrases, phrase_offsets, phrase_words, cfg, a) != TCR_OK) return 0;
-    return phrase_state_ints_bytes(n_streams) + (size_t)a.H * a.U * n_streams * sizeof(float);
+    return detect_state_ints_bytes(n_streams) + (size_t)a.H * a.U * n_streams * sizeof(float);
 }
 
 extern "C" int tcr_phrase_stream_init(int n_streams, int num_classes, int n_phrases, const int32_t* phrase_offsets, const int32_t* phrase_words,
@@ -525,7 +502,7 @@ extern "C" int tcr_phrase_stream_init(int n_streams, int num_classes, int n_phra
     PhraseArgs a{};
     TCR_TRY(phrase_stream_geom(what, n_streams, num_classes, n_phrases, phrase_offsets, phrase_words, cfg, a));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t ints = phrase_state_ints_bytes(n_streams), ring = (size_t)a.H * a.U * n_streams * sizeof(float);
+    const size_t ints = detect_state_ints_bytes(n_streams), ring = (size_t)a.H * a.U * n_streams * sizeof(float);
     if (hipMemsetAsync(state, 0, ints + ring, s) != hipSuccess) {      // (the ring's slots are written before they are read; zeros keep the state's bytes defined)
         set_error("%s: hipMemsetAsync failed", what);
         return TCR_ERR_HIP;

@@ -125,6 +125,16 @@ struct ScanState {
 
 __device__ __forceinline__ bool scan_fresh(const ScanState& st, int64_t s) { return !st.window || (st.reset && st.reset[s]); }
 
+// The detector integers in front of a state of their own (phrase.hip, dtw.hip): [5][S] int32 rounded up to 256 bytes, and entry i of
+// them for streams that have seen no rows and have no detection yet (false: i lies behind the integers).
+inline size_t detect_state_ints_bytes(int S) { return (size_t)round_up64((int64_t)S * 5 * sizeof(int32_t), 256); }
+
+__device__ __forceinline__ bool detect_ints_init(int* ist, int S, int64_t i) {
+    if (i >= 5 * (int64_t)S) return false;
+    ist[i] = i / S == 2 ? -1 : 0;
+    return true;
+}
+
 // a chunk: rows q0 .. q0 + rows - 1 of the call's groups (signal q / groups, group q % groups)
 struct ScanChunkArgs {
     const float* samples;       // [N][L]
@@ -532,6 +542,30 @@ __global__ __launch_bounds__(256) void scan_suppress_kernel(const ScanDetectArgs
 
 namespace {
 
+// scan_suppress_kernel over da's signals: the last launch of every detector tail
+int suppress_launch(const ScanDetectArgs& da, bool ragged, hipStream_t s) {
+    const auto suppress = ragged ? scan_suppress_kernel<true> : scan_suppress_kernel<false>;
+    hipLaunchKernelGGL(suppress, dim3(da.N), dim3(256), 0, s, da);
+    return check_launch("scan_suppress_kernel");
+}
+
+// what the entries over a scan's rows refuse about their number: n signals or streams (`whose`), steps (dense) / total_steps (ragged) ...
+int detect_rows_check(const char* what, bool ragged, int n, int64_t steps, int64_t total_steps, const char* whose) {
+    TCR_REQUIRE(n > 0, "%s: the number of %s must be positive (got %d)", what, whose, n);
+    TCR_REQUIRE(ragged ? total_steps > 0 : steps > 0, "%s: the number of steps must be positive (got %lld)", what,
+                (long long)(ragged ? total_steps : steps));
+    return TCR_OK;
+}
+
+// ... and about their size, at the wider of the input and output rows' columns
+int detect_size_check(const char* what, bool ragged, int n, int64_t steps, int64_t total_steps, int in_cols, int out_cols) {
+    const int64_t rows = ragged ? total_steps : steps * n;
+    const int widest = in_cols > out_cols ? in_cols : out_cols;
+    TCR_REQUIRE((ragged || steps < ((int64_t)1 << 31)) && rows < ((int64_t)1 << 31) && rows * widest < ((int64_t)1 << 31),
+                "%s: %lld steps in all x %d columns is too large", what, (long long)rows, widest);
+    return TCR_OK;
+}
+
 struct ScanOutputs {
     float *logits, *probs, *smoothed;   // [N][steps][C] (ragged: [total_steps][C])
     int32_t* top;                       // [N][steps]
@@ -753,9 +787,7 @@ int scan_run(const ScanCall& c, const ScanState& st, int64_t steps, const std::v
                                 : (ragged ? scan_smooth_kernel<false, true> : scan_smooth_kernel<false, false>);
     hipLaunchKernelGGL(smooth, dim3((unsigned)ceil_div64(total_steps, 256 / g.classes)), dim3(256), 0, s, da);
     TCR_TRY(check_launch("scan_smooth_kernel"));
-    const auto suppress = ragged ? scan_suppress_kernel<true> : scan_suppress_kernel<false>;
-    hipLaunchKernelGGL(suppress, dim3(N), dim3(256), 0, s, da);
-    return check_launch("scan_suppress_kernel");
+    return suppress_launch(da, ragged, s);
 }
 
 // The step offsets so [n + 1] of a ragged call's sample_offsets (HOST [n + 1]), with every refusal about them.

@@ -1,7 +1,7 @@
 """What a scan hands on, and the stage that works on it.  The scans' output containers (`ScanOutput`, `RaggedScanOutput`, `CascadeOutput`),
 the arithmetic between milliseconds, samples and steps, and `DetectionStage`: what runs on a scan's outputs without the network or the
 front-end that made them -- the detector rule with other settings (`redetect`), sweeps and grids against labelled events (`sweep`, `tune`)
-and mining (`mine`).  `streaming.StreamingDetector` and `scanning.KeywordScanner` build one over their model's classes,
+and mining (`mine`) -- and what every streaming class does with `reset` (`PendingResets`, `reset_mask`).  `streaming.StreamingDetector` and `scanning.KeywordScanner` build one over their model's classes,
 `phrases.PhraseDetector` one over its phrases; the raw-tensor functions it calls are in `scoring` and `mining`."""
 from __future__ import annotations
 
@@ -73,6 +73,70 @@ class CascadeOutput(RaggedScanOutput):
 def ms_to_steps(ms: float, step_ms: float) -> int:
     """Milliseconds -> whole steps (nearest)."""
     return int(round(float(ms) / step_ms))
+
+
+def check_on(what: str, on: str, choices=("smoothed", "probs")) -> str:
+    """`on`, one of an output's two posterior tensors; the message names `choices` in their order."""
+    if on not in choices:
+        raise TcrError(f"{what}: on must be {choices[0]!r} or {choices[1]!r}, got {on!r}")
+    return on
+
+
+def reset_mask(mask_or_indices, n_streams: int) -> np.ndarray:
+    """The `reset` argument of the streaming detectors as a bool mask [n_streams]: a bool / uint8 mask of that many entries, or
+    stream indices (any other integer type)."""
+    if isinstance(mask_or_indices, torch.Tensor):
+        mask_or_indices = mask_or_indices.cpu().numpy()
+    arr = np.asarray(mask_or_indices if not isinstance(mask_or_indices, (set, frozenset)) else sorted(mask_or_indices))
+    if arr.dtype in (np.bool_, np.uint8):
+        if arr.shape != (n_streams,):
+            raise TcrError(f"reset mask must have {n_streams} entries, got shape {arr.shape}")
+        return arr.astype(bool)
+    idx = arr.astype(np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() >= n_streams):
+        raise TcrError(f"reset: stream index outside 0..{n_streams - 1}")
+    mask = np.zeros(n_streams, bool)
+    mask[idx] = True
+    return mask
+
+
+class PendingResets:
+    """The pending-reset rule of everything that carries state for `n_streams` streams: `reset` collects flags on the host (`_pending`:
+    None, or a bool array of S entries), the next call takes them to the device (`_reset_dev`, uint8 [S]) and passes that pointer on.
+    A ragged call ignores the flag of a stream it brings no rows for, so there the flags stay pending until the call has run and only
+    those of the streams that had rows are dropped."""
+
+    def _init_resets(self, device) -> None:
+        self._reset_dev = torch.zeros(self.n_streams, dtype=torch.uint8, device=device)
+        self._pending: Optional[np.ndarray] = None
+
+    def reset(self, mask_or_indices) -> None:
+        """Return streams to their initial state at their NEXT pushed row, before it: a bool / uint8 mask of S entries, or stream
+        indices (any other integer type); calls accumulate.  A reset stays pending for a stream that has no rows in a ragged push.
+        The initial state is the class's: a `StreamingDetector`'s silent clip, empty ring and no detection yet; a phrase or template
+        detector's no rows seen and no detection yet; a `StreamingRecorder`'s pending triggers dropped, earlier audio read as zeros and
+        steps counted from 0 (reset the recorder whenever the detector is)."""
+        mask = reset_mask(mask_or_indices, self.n_streams)
+        self._pending = mask if self._pending is None else (self._pending | mask)
+
+    def _begin_ragged_reset(self) -> Optional[int]:
+        """The reset pointer of a ragged call (None: no flags); the flags stay pending until `_end_ragged_reset`."""
+        if self._pending is None:
+            return None
+        self._reset_dev.copy_(torch.from_numpy(self._pending.astype(np.uint8)))
+        return self._reset_dev.data_ptr()
+
+    def _end_ragged_reset(self, rows_per_stream) -> None:
+        """After a ragged call that ran: only the flags of the streams without rows in it are kept."""
+        if self._pending is not None:
+            left = self._pending & (np.asarray(rows_per_stream) == 0)
+            self._pending = left if left.any() else None
+
+    def _take_reset(self) -> Optional[int]:
+        """The reset pointer of a call in which every stream has rows (None: no flags); the flags are cleared."""
+        ptr = self._begin_ragged_reset()
+        self._pending = None
+        return ptr
 
 
 def _ragged_signals(what: str, noun: str, signals, count: Optional[int] = None):
@@ -343,8 +407,7 @@ class DetectionStage:
                 add(offsets[sig[ok]] + last[ok], ev_label[missed[ok]], np.full(int(ok.sum()), np.nan, np.float32),
                     np.full(int(ok.sum()), 3, np.uint8), missed[ok])
         else:
-            if on not in ("probs", "smoothed"):
-                raise TcrError(f"mine: on must be 'probs' or 'smoothed', got {on!r}")
+            check_on("mine", on, ("probs", "smoothed"))
             radius = max(1, self.det.suppression_steps if radius_ms is None else ms_to_steps(radius_ms, self.step_ms))
             exclude = None
             if events is not None:

@@ -13,11 +13,11 @@ import torch
 
 from . import _lib
 from ._lib import TcrError
-from .detection import CascadeOutput, DetectionStage, RaggedScanOutput, ScanOutput, _new_tensors, ms_to_steps
+from .detection import CascadeOutput, DetectionStage, PendingResets, RaggedScanOutput, ScanOutput, _new_tensors, check_on, ms_to_steps
 from .mining import MinedClips
 from .runtime import stream_of
 from .scoring import GridResult, SweepResult, _offsets
-from .streaming import StreamOutput, reset_mask
+from .streaming import StreamOutput
 
 BACKGROUND_LABEL = "_background_"
 PHRASE_COMBINERS = {"product": _lib.PHRASE_PRODUCT, "min": _lib.PHRASE_MIN}
@@ -126,24 +126,30 @@ class PhraseDetector:
         if self.window_steps > w_max:
             raise TcrError(f"PhraseDetector: window_ms {window_ms:g} is {self.window_steps} steps, above the {w_max} that "
                            f"tcr_phrase_window_max allows for {distinct} distinct words")
-        st = scanner.stage
+        self._make_stage(detection_threshold, suppression_ms)
+
+    def _make_stage(self, detection_threshold: Optional[float], suppression_ms: Optional[float]) -> None:
+        """`det` and `stage` over this detector's `labels`, from its scanner's stage."""
+        st = self.scanner.stage
         self.det = det = st.detect_cfg(0.0, 1, detection_threshold, suppression_ms)     # (one vector per decision: a posterior is its whole input)
         self.stage = DetectionStage(st.lib, st.device, len(self.labels), st.step_samples, st.sample_rate, st.clip_samples, det)
+
+    on, _noun = "smoothed", "phrase"            # the rows read by default, and this detector's word for itself in messages
 
     @property
     def num_classes(self) -> int:
         """P + 1: the phrases and the background."""
         return len(self.labels)
 
-    def _values(self, out, on: str) -> torch.Tensor:
-        if on not in ("smoothed", "probs"):
-            raise TcrError(f"PhraseDetector: on must be 'smoothed' or 'probs', got {on!r}")
+    def _values(self, out, on: Optional[str]) -> torch.Tensor:
+        what = type(self).__name__
+        on = check_on(what, self.on if on is None else on)
         v, ncls = getattr(out, on), self.scanner.net.num_classes
         want_dim = 2 if isinstance(out, RaggedScanOutput) else 3
         if v is None or v.dim() != want_dim or int(v.shape[-1]) != ncls:
-            raise TcrError(f"PhraseDetector: the output's {on} {None if v is None else tuple(v.shape)} is not a scan of the scanner's {ncls} "
+            raise TcrError(f"{what}: the output's {on} {None if v is None else tuple(v.shape)} is not a scan of the scanner's {ncls} "
                            "classes")
-        self.scanner.net._check_tensor(v, f"phrase {on}")
+        self.scanner.net._check_tensor(v, f"{self._noun} {on}")
         return v
 
     def scores(self, out, on: str = "smoothed") -> torch.Tensor:
@@ -166,7 +172,10 @@ class PhraseDetector:
         phrase posteriors (one tensor), top / score / is_new the detector rule over them (tcr_detect_redetect with average_steps =
         min_count = 1 and this detector's threshold and suppression): a phrase fires when it is on top above the threshold, and again
         only after the background (or another phrase) has been."""
-        ph = self.scores(out, on)
+        return self._detect(out, self.scores(out, on))
+
+    def _detect(self, out, ph: torch.Tensor):
+        """The detector rule over the posteriors `ph` of `out`, in out's kind of output object."""
         ragged = isinstance(out, RaggedScanOutput)
         if ragged and int(ph.shape[0]) == 0:                # (no rows in all: nothing to launch, and the library refuses the call)
             det = RaggedScanOutput(None, ph, ph, *_new_tensors((0,), 0, self.device, 0), out.offsets)
@@ -202,7 +211,88 @@ class PhraseDetector:
         return self.stage.mine(self._detected(out), signals, events, k, source, kinds, cls, labels=self.labels, **kw)
 
 
-class StreamingPhraseDetector:
+class _PosteriorStream(PendingResets):
+    """What `StreamingPhraseDetector` and `templates.StreamingTemplateDetector` share: a posterior detector (`detector`: a
+    `PhraseDetector` or `TemplateDetector`) over the pushes of a `StreamingDetector` of n_streams streams, its state on the device.  A
+    subclass names its C entries (`_entry` + _state_bytes / _init / _push / _push_ragged), supplies their table arguments (`_tables`) and
+    says whether a push also writes `lengths` (`_has_lengths`: one column per class but the background, after the posteriors)."""
+    _entry = ""
+    _has_lengths = False
+
+    def __init__(self, detector: PhraseDetector, n_streams: int):
+        what = type(self).__name__
+        self.detector, self.lib, self.device = detector, detector.lib, detector.device
+        self.n_streams = S = int(n_streams)
+        if S <= 0:
+            raise TcrError(f"{what}: n_streams must be positive (got {S})")
+        self.labels, self.num_classes = detector.labels, detector.num_classes
+        self._classes = detector.scanner.net.num_classes
+        lib, dev = self.lib, self.device
+        self._push_c, self._push_ragged_c = getattr(lib, self._entry + "_push"), getattr(lib, self._entry + "_push_ragged")
+        nstate = getattr(lib, self._entry + "_state_bytes")(S, self._classes, *self._tables())
+        if nstate == 0:
+            raise TcrError(f"{what}: {lib.tcr_last_error().decode()}")
+        self.state = torch.empty(nstate // 4, dtype=torch.float32, device=dev)
+        post, top, score, is_new = _new_tensors((S,), self.num_classes, dev, 1)
+        self.out = StreamOutput(None, post, post, top, score, is_new)
+        if self._has_lengths:
+            self._own_lengths = self.lengths = self._new_lengths((S,))
+        self._init_resets(dev)
+        lib.check(getattr(lib, self._entry + "_init")(S, self._classes, *self._tables(), self.state.data_ptr(), stream_of(dev)),
+                  self._entry + "_init")
+
+    def _tables(self):
+        raise NotImplementedError
+
+    def _new_lengths(self, rows) -> torch.Tensor:
+        return torch.empty((*rows, self.num_classes - 1), dtype=torch.int32, device=self.device)
+
+    def _values(self, out, on: Optional[str]) -> torch.Tensor:
+        what = type(self).__name__
+        on = check_on(what, self.detector.on if on is None else on)
+        v, S, ncls = getattr(out, on), self.n_streams, self._classes
+        if v is None or int(v.shape[-1]) != ncls:
+            raise TcrError(f"{what}: the output's {on} {None if v is None else tuple(v.shape)} is not over the detector's "
+                           f"{ncls} classes")
+        if isinstance(out, RaggedScanOutput):
+            ok = v.dim() == 2 and len(out) == S
+        else:
+            ok = v.dim() == (2 if isinstance(out, StreamOutput) else 3) and int(v.shape[0]) == S
+        if not ok:
+            raise TcrError(f"{what}: the output's {on} {tuple(v.shape)} is not a push of {S} streams")
+        self.detector.scanner.net._check_tensor(v, f"{self.detector._noun} {on}")
+        return v
+
+    def push(self, out, on: Optional[str] = None):
+        v = self._values(out, on)
+        lib, dev, S, K = self.lib, self.device, self.n_streams, self.num_classes
+        ragged = isinstance(out, RaggedScanOutput)
+        if isinstance(out, StreamOutput):                       # one step: this object's own tensors
+            res, count = self.out, 1
+            if self._has_lengths:
+                self.lengths = self._own_lengths
+        else:
+            rows = (int(v.shape[0]),) if ragged else (S, int(v.shape[1]))
+            count = rows[-1]                                    # the steps of every stream, or (ragged) the rows in all
+            post, top, score, is_new = _new_tensors(rows, K, dev, 1)
+            if self._has_lengths:
+                self.lengths = self._new_lengths(rows)
+            res = RaggedScanOutput(None, post, post, top, score, is_new, out.offsets) if ragged else ScanOutput(None, post, post, top, score, is_new)
+            if count == 0:                                      # (no rows in all: nothing to launch; the resets stay pending)
+                return res
+        head = (self._classes, v.data_ptr(), *self._tables(), C.byref(self.detector.det))
+        outs = (self.state.data_ptr(), res.probs.data_ptr(), *((self.lengths.data_ptr(),) if self._has_lengths else ()), res.top.data_ptr(),
+                res.score.data_ptr(), res.is_new.data_ptr(), stream_of(dev))
+        if ragged:
+            off_dev = torch.from_numpy(res.offsets).to(dev)
+            lib.check(self._push_ragged_c(S, off_dev.data_ptr(), count, *head, self._begin_ragged_reset(), *outs), self._entry + "_push_ragged")
+            self._end_ragged_reset(res.steps)
+        else:
+            lib.check(self._push_c(S, count, *head, self._take_reset(), *outs), self._entry + "_push")
+        return res
+
+
+class StreamingPhraseDetector(_PosteriorStream):
     """`PhraseDetector.detect` over live streams (tcr_phrase_stream_push): `push` takes what a `StreamingDetector` of the same streams
     returned from `push`, `push_many` or `push_ragged` and returns the phrase detections of those steps.  The last window_steps - 1
     rows of every stream's word posteriors and the detector's integers stay on the device, so however the streams are cut into
@@ -213,95 +303,24 @@ class StreamingPhraseDetector:
     tensor), top / score / is_new the detector rule.  A `StreamOutput` (one step) gives this object's own [S, ..] tensors, overwritten
     by the next one-step push (copy what must survive it); a `ScanOutput` / `RaggedScanOutput` gives a new one, so outputs
     concatenated over steps go into `PhraseDetector.sweep` / `tune` / `mine` unchanged."""
+    _entry = "tcr_phrase_stream"
 
     def __init__(self, detector: PhraseDetector, n_streams: int):
-        self.detector, self.lib, self.device = detector, detector.lib, detector.device
-        self.n_streams = S = int(n_streams)
-        if S <= 0:
-            raise TcrError(f"StreamingPhraseDetector: n_streams must be positive (got {S})")
-        self.labels, self.num_classes = detector.labels, detector.num_classes
-        self._classes = detector.scanner.net.num_classes
         words = detector.words
         self._off = np.zeros(len(words) + 1, np.int32)
         np.cumsum([len(q) for q in words], out=self._off[1:])
         self._flat = np.ascontiguousarray(np.array([c for q in words for c in q], np.int32))
         self._cfg = _lib.PhraseCfg(detector.window_steps, int(detector.ordered), PHRASE_COMBINERS[detector.combine])
-        lib, dev = self.lib, self.device
-        nstate = lib.tcr_phrase_stream_state_bytes(S, self._classes, *self._tables())
-        if nstate == 0:
-            raise TcrError(f"StreamingPhraseDetector: {lib.tcr_last_error().decode()}")
-        self.state = torch.empty(nstate // 4, dtype=torch.float32, device=dev)
-        post, top, score, is_new = _new_tensors((S,), self.num_classes, dev, 1)
-        self.out = StreamOutput(None, post, post, top, score, is_new)
-        self._reset_dev = torch.zeros(S, dtype=torch.uint8, device=dev)
-        self._pending: Optional[np.ndarray] = None
-        lib.check(lib.tcr_phrase_stream_init(S, self._classes, *self._tables(), self.state.data_ptr(), stream_of(dev)), "tcr_phrase_stream_init")
+        super().__init__(detector, n_streams)
 
     def _tables(self):
         return len(self._off) - 1, self._off.ctypes.data, self._flat.ctypes.data, C.byref(self._cfg)
-
-    def reset(self, mask_or_indices) -> None:
-        """Return streams to the start (no rows seen, no detection yet) at their NEXT pushed row, before it: `StreamingDetector.reset`'s
-        argument and rules -- a bool / uint8 mask of S entries or stream indices; a reset stays pending for a stream that has no
-        rows in a ragged push."""
-        mask = reset_mask(mask_or_indices, self.n_streams)
-        self._pending = mask if self._pending is None else (self._pending | mask)
-
-    def _take_reset(self) -> Optional[int]:
-        if self._pending is None:
-            return None
-        self._reset_dev.copy_(torch.from_numpy(self._pending.astype(np.uint8)))
-        self._pending = None
-        return self._reset_dev.data_ptr()
-
-    def _values(self, out, on: str) -> torch.Tensor:
-        if on not in ("smoothed", "probs"):
-            raise TcrError(f"StreamingPhraseDetector: on must be 'smoothed' or 'probs', got {on!r}")
-        v, S, ncls = getattr(out, on), self.n_streams, self._classes
-        if v is None or int(v.shape[-1]) != ncls:
-            raise TcrError(f"StreamingPhraseDetector: the output's {on} {None if v is None else tuple(v.shape)} is not over the detector's "
-                           f"{ncls} classes")
-        if isinstance(out, RaggedScanOutput):
-            ok = v.dim() == 2 and len(out) == S
-        else:
-            ok = v.dim() == (2 if isinstance(out, StreamOutput) else 3) and int(v.shape[0]) == S
-        if not ok:
-            raise TcrError(f"StreamingPhraseDetector: the output's {on} {tuple(v.shape)} is not a push of {S} streams")
-        self.detector.scanner.net._check_tensor(v, f"phrase {on}")
-        return v
 
     def push(self, out, on: str = "smoothed"):
         """The phrase detections of the steps in `out`, what the `StreamingDetector` returned: a `StreamOutput` (`push`: one step ->
         this object's own `StreamOutput`), a `ScanOutput` (`push_many` -> a new `ScanOutput`) or a `RaggedScanOutput` (`push_ragged` ->
         a new `RaggedScanOutput` with out's offsets), read from out's `on` ("smoothed", or "probs").  Pending `reset`s apply before a
         stream's first row of the call.  The call only enqueues kernels."""
-        v = self._values(out, on)
-        lib, dev, S, K = self.lib, self.device, self.n_streams, self.num_classes
-        det = C.byref(self.detector.det)
-        if isinstance(out, RaggedScanOutput):
-            post, top, score, is_new = _new_tensors((int(v.shape[0]),), K, dev, 1)
-            res = RaggedScanOutput(None, post, post, top, score, is_new, out.offsets)
-            if int(v.shape[0]) == 0:                            # (no rows in all: nothing to launch; the resets stay pending)
-                return res
-            off_dev = torch.from_numpy(res.offsets).to(dev)
-            pending, reset_ptr = self._pending, self._take_reset()
-            self._pending = pending                             # (until the call has run; it ignores the flag of a stream without rows)
-            lib.check(lib.tcr_phrase_stream_push_ragged(S, off_dev.data_ptr(), int(v.shape[0]), self._classes, v.data_ptr(), *self._tables(), det,
-                                                        reset_ptr, self.state.data_ptr(), post.data_ptr(), top.data_ptr(), score.data_ptr(),
-                                                        is_new.data_ptr(), stream_of(dev)), "tcr_phrase_stream_push_ragged")
-            if pending is not None:
-                left = pending & (res.steps == 0)
-                self._pending = left if left.any() else None
-            return res
-        if isinstance(out, StreamOutput):
-            res, steps = self.out, 1
-        else:
-            steps = int(v.shape[1])
-            post, top, score, is_new = _new_tensors((S, steps), K, dev, 1)
-            res = ScanOutput(None, post, post, top, score, is_new)
-            if steps == 0:
-                return res
-        lib.check(lib.tcr_phrase_stream_push(S, steps, self._classes, v.data_ptr(), *self._tables(), det, self._take_reset(), self.state.data_ptr(),
-                                             res.probs.data_ptr(), res.top.data_ptr(), res.score.data_ptr(), res.is_new.data_ptr(),
-                                             stream_of(dev)), "tcr_phrase_stream_push")
-        return res
+        return super().push(out, on)
+
+

@@ -34,7 +34,6 @@ arithmetic and `DetectionStage`: `redetect`, `sweep`, `tune`, `mine` over a scan
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -50,7 +49,7 @@ from .mining import MINE_KINDS, MinedClips, MinedDetections, MinedPeaks, gather_
 from .phrases import BACKGROUND_LABEL, PHRASE_COMBINERS, PhraseDetector, PhraseGridResult, PhraseSweepResult, StreamingPhraseDetector, phrase_scores  # noqa: F401
 from .runtime import stream_of
 from .scoring import GridPoint, GridResult, SweepResult, _class_mask, _offsets, detection_grid, detection_sweep  # noqa: F401
-from .streaming import Network, _Detection
+from .streaming import Network, _cascade_pair, _Detection
 from .templates import KeywordTemplates, StreamingTemplateDetector, TemplateDetector, dtw_scores  # noqa: F401
 
 DEFAULT_MAX_SIGNALS = 65536
@@ -265,24 +264,7 @@ class CascadeScanner:
     def __init__(self, first: KeywordScanner, second: KeywordScanner, enter_threshold: float,
                  keyword_classes: Optional[Sequence[int]] = None, pad_before_ms: Optional[float] = None,
                  pad_after_ms: Optional[float] = None, on: str = "probs"):
-        if first.lib is not second.lib or first.device != second.device:
-            raise TcrError("CascadeScanner: the two scanners must use the same library and device")
-        r1, r2 = first.frontend.cfg.sample_rate, second.frontend.cfg.sample_rate
-        if r1 != r2:
-            raise TcrError(f"CascadeScanner: the scanners run at different sample rates ({r1} and {r2} Hz)")
-        if first.step_samples != second.step_samples:
-            raise TcrError(f"CascadeScanner: the scanners' steps differ ({first.step_samples} and {second.step_samples} samples): "
-                           "k1 * hop1 must equal k2 * hop2")
-        if first.net.num_classes != second.net.num_classes:
-            raise TcrError(f"CascadeScanner: the scanners' models have {first.net.num_classes} and {second.net.num_classes} classes")
-        if on not in ("probs", "smoothed"):
-            raise TcrError(f"CascadeScanner: on must be 'probs' or 'smoothed', got {on!r}")
-        if math.isnan(float(enter_threshold)):
-            raise TcrError("CascadeScanner: enter_threshold is NaN")
-        ncls = second.net.num_classes
-        self.keyword_classes = list(range(2, ncls)) if keyword_classes is None else [int(c) for c in keyword_classes]
-        if any(not 0 <= c < ncls for c in self.keyword_classes):
-            raise TcrError(f"CascadeScanner: keyword_classes outside 0..{ncls - 1}: {self.keyword_classes}")
+        self.keyword_classes = _cascade_pair("CascadeScanner", "scanner", first, second, enter_threshold, keyword_classes, on)
         self.first, self.second, self.lib, self.device = first, second, second.lib, second.device
         self.enter_threshold, self.on = float(enter_threshold), on
         default = second.average_steps - 1

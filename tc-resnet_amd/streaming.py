@@ -13,15 +13,15 @@ its own for every stream, none included.  Every model family runs: TC-ResNet, DS
 from __future__ import annotations
 
 import ctypes as C
-from typing import Iterable, NamedTuple, Optional, Sequence, Union
+from typing import NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 import torch
 
 from ._lib import FAMILY_DSCNN, FAMILY_G2D, FAMILY_TCRESNET, ModelRef, TcrError, padded_len
 from .capturing import CapturedClips, CapturedHost, StreamingRecorder  # noqa: F401
-from .detection import (DEFAULT_MAX_WINDOWS, DetectionStage, _new_tensors, _ragged_scan_output, _ragged_signals,  # noqa: F401
-                        _scan_output, ms_to_steps)
+from .detection import (DEFAULT_MAX_WINDOWS, DetectionStage, PendingResets, _new_tensors, _ragged_scan_output,  # noqa: F401
+                        _ragged_signals, _scan_output, check_on, ms_to_steps, reset_mask)
 from .engine import DSCNN, Frontend, Graph2D, TCResNet
 
 Network = Union[TCResNet, DSCNN, Graph2D]
@@ -36,24 +36,6 @@ class StreamOutput(NamedTuple):
     top: torch.Tensor
     score: torch.Tensor
     is_new: torch.Tensor
-
-
-def reset_mask(mask_or_indices, n_streams: int) -> np.ndarray:
-    """The `reset` argument of the streaming detectors as a bool mask [n_streams]: a bool / uint8 mask of that many entries, or
-    stream indices (any other integer type)."""
-    if isinstance(mask_or_indices, torch.Tensor):
-        mask_or_indices = mask_or_indices.cpu().numpy()
-    arr = np.asarray(mask_or_indices if not isinstance(mask_or_indices, (set, frozenset)) else sorted(mask_or_indices))
-    if arr.dtype in (np.bool_, np.uint8):
-        if arr.shape != (n_streams,):
-            raise TcrError(f"reset mask must have {n_streams} entries, got shape {arr.shape}")
-        return arr.astype(bool)
-    idx = arr.astype(np.int64).reshape(-1)
-    if idx.size and (idx.min() < 0 or idx.max() >= n_streams):
-        raise TcrError(f"reset: stream index outside 0..{n_streams - 1}")
-    mask = np.zeros(n_streams, bool)
-    mask[idx] = True
-    return mask
 
 
 class _Detection:
@@ -168,7 +150,33 @@ class _Detection:
         return self.stage.sweep(out, thresholds, events, lengths, tolerance_ms, return_fired, labels)
 
 
-class StreamingDetector(_Detection):
+def _cascade_pair(what: str, noun: str, first: _Detection, second: _Detection, enter_threshold: float, keyword_classes, on: str) -> list:
+    """What a cascade's constructor (`what`) checks about its two stages (`noun`s: scanners or detectors) and its flag settings; returns
+    the keyword classes (default: every class from 2 on)."""
+    if first.lib is not second.lib or first.device != second.device:
+        raise TcrError(f"{what}: the two {noun}s must use the same library and device")
+    r1, r2 = first.frontend.cfg.sample_rate, second.frontend.cfg.sample_rate
+    if r1 != r2:
+        raise TcrError(f"{what}: the {noun}s run at different sample rates ({r1} and {r2} Hz)")
+    if first.step_samples != second.step_samples:
+        raise TcrError(f"{what}: the {noun}s' steps differ ({first.step_samples} and {second.step_samples} samples): "
+                       "k1 * hop1 must equal k2 * hop2")
+    ncls = second.net.num_classes
+    if first.net.num_classes != ncls:
+        raise TcrError(f"{what}: the {noun}s' models have {first.net.num_classes} and {ncls} classes")
+    s1, s2 = getattr(first, "n_streams", None), getattr(second, "n_streams", None)      # (scanners hold no streams)
+    if s1 != s2:
+        raise TcrError(f"{what}: the {noun}s hold {s1} and {s2} streams")
+    check_on(what, on, ("probs", "smoothed"))
+    if np.isnan(float(enter_threshold)):
+        raise TcrError(f"{what}: enter_threshold is NaN")
+    classes = list(range(2, ncls)) if keyword_classes is None else [int(c) for c in keyword_classes]
+    if any(not 0 <= c < ncls for c in classes):
+        raise TcrError(f"{what}: keyword_classes outside 0..{ncls - 1}: {classes}")
+    return classes
+
+
+class StreamingDetector(_Detection, PendingResets):
     """S concurrent streams through `frontend` and `net` (a TCResNet, DSCNN or finalized Graph2D whose input is the front-end's
     n_coef x T features), k = frames_per_step new frames per stream and step.
 
@@ -215,26 +223,12 @@ class StreamingDetector(_Detection):
         self.state = torch.empty(nstate // 4, dtype=torch.float32, device=dev)
         self.workspace = torch.empty(nws // 4, dtype=torch.float32, device=dev)
         self.out = StreamOutput(*_new_tensors((S,), ncls, dev))
-        self._reset_dev = torch.zeros(S, dtype=torch.uint8, device=dev)
-        self._pending: Optional[np.ndarray] = None
+        self._init_resets(dev)
         lib.check(lib.tcr_stream_init_m(C.byref(cfg), frontend.plan.data_ptr(), C.byref(ref), S, self.k, C.byref(self.det),
                                         self.state.data_ptr(), self.workspace.data_ptr(), self.workspace.numel() * 4, net._stream()),
                   "tcr_stream_init")
 
     # ---- stream control -----------------------------------------------------------------------------------------------
-    def reset(self, mask_or_indices: Union[np.ndarray, torch.Tensor, Iterable[int]]) -> None:
-        """Return streams to the initial state (a silent clip, empty ring, no detection yet) at the NEXT push, before its samples
-        are appended.  A bool / uint8 mask of S entries, or stream indices (any other integer type)."""
-        mask = reset_mask(mask_or_indices, self.n_streams)
-        self._pending = mask if self._pending is None else (self._pending | mask)
-
-    def _take_reset(self) -> Optional[int]:
-        if self._pending is None:
-            return None
-        self._reset_dev.copy_(torch.from_numpy(self._pending.astype(np.uint8)))
-        self._pending = None
-        return self._reset_dev.data_ptr()
-
     def window(self) -> torch.Tensor:
         """The streams' current window features, planar [S, n_coef, T + 2*HALO] (a view of the state)."""
         cfg = self.frontend.cfg
@@ -347,15 +341,12 @@ class StreamingDetector(_Detection):
         ws = self._ragged_workspace("push_ragged", S)
         ref = self._call_ref()
         out = _ragged_scan_output(lengths, offsets, self.step_samples, net.num_classes, self.device)
-        pending, reset_ptr = self._pending, self._take_reset()
-        self._pending = pending                                 # (until the call has run; it ignores the flag of a stream without steps)
+        reset_ptr = self._begin_ragged_reset()
         lib.check(lib.tcr_stream_scan_ragged_m(C.byref(fe.cfg), fe.plan.data_ptr(), C.byref(ref), S, offsets.ctypes.data, self.k,
                                                C.byref(self.det), packed.data_ptr(), reset_ptr, self.state.data_ptr(), ws.data_ptr(),
                                                ws.numel() * 4, *(t.data_ptr() for t in out.tensors()), net._stream()),
                   "tcr_stream_scan_ragged")
-        if pending is not None:
-            left = pending & (lengths == 0)
-            self._pending = left if left.any() else None
+        self._end_ragged_reset(lengths)
         self._after_call()
         return out
 
@@ -408,7 +399,7 @@ class StreamingDetector(_Detection):
         return call
 
 
-class StreamingCascade:
+class StreamingCascade(PendingResets):
     """The causal cascade over S live streams: `first` (a cheap `StreamingDetector`) steps every stream, the streams at or shortly
     behind one of its flags are selected, `second` (an expensive one) runs its network on those only (`push_selected`), and `second`'s
     detector runs over the merged posteriors.  The pushes stacked over time are bitwise
@@ -429,27 +420,8 @@ class StreamingCascade:
 
     def __init__(self, first: StreamingDetector, second: StreamingDetector, enter_threshold: float,
                  keyword_classes: Optional[Sequence[int]] = None, pad_after_ms: Optional[float] = None, on: str = "probs"):
-        what = "StreamingCascade"
-        if first.lib is not second.lib or first.device != second.device:
-            raise TcrError(f"{what}: the two detectors must use the same library and device")
-        r1, r2 = first.frontend.cfg.sample_rate, second.frontend.cfg.sample_rate
-        if r1 != r2:
-            raise TcrError(f"{what}: the detectors run at different sample rates ({r1} and {r2} Hz)")
-        if first.step_samples != second.step_samples:
-            raise TcrError(f"{what}: the detectors' steps differ ({first.step_samples} and {second.step_samples} samples): "
-                           "k1 * hop1 must equal k2 * hop2")
-        if first.net.num_classes != second.net.num_classes:
-            raise TcrError(f"{what}: the detectors' models have {first.net.num_classes} and {second.net.num_classes} classes")
-        if first.n_streams != second.n_streams:
-            raise TcrError(f"{what}: the detectors hold {first.n_streams} and {second.n_streams} streams")
-        if on not in ("probs", "smoothed"):
-            raise TcrError(f"{what}: on must be 'probs' or 'smoothed', got {on!r}")
-        if np.isnan(float(enter_threshold)):
-            raise TcrError(f"{what}: enter_threshold is NaN")
-        ncls = second.net.num_classes
-        self.keyword_classes = list(range(2, ncls)) if keyword_classes is None else [int(c) for c in keyword_classes]
-        if any(not 0 <= c < ncls for c in self.keyword_classes):
-            raise TcrError(f"{what}: keyword_classes outside 0..{ncls - 1}: {self.keyword_classes}")
+        what, ncls = "StreamingCascade", second.net.num_classes
+        self.keyword_classes = _cascade_pair(what, "detector", first, second, enter_threshold, keyword_classes, on)
         self.pad_before = 0
         self.pad_after = second.average_steps - 1 if pad_after_ms is None else ms_to_steps(pad_after_ms, second.step_ms)
         if self.pad_after < 0:
@@ -465,8 +437,7 @@ class StreamingCascade:
         self._selected = torch.zeros(S, dtype=torch.int64, device=dev)
         self._count = torch.zeros(1, dtype=torch.int64, device=dev)
         self.mask = torch.zeros(S, dtype=torch.uint8, device=dev)
-        self._reset_dev = torch.zeros(S, dtype=torch.uint8, device=dev)
-        self._pending: Optional[np.ndarray] = None
+        self._init_resets(dev)
         nws = lib.tcr_stream_select_workspace_bytes(S)
         if nws == 0:
             raise TcrError(f"{what}: {lib.tcr_last_error().decode()}")
@@ -480,17 +451,14 @@ class StreamingCascade:
         mask = reset_mask(mask_or_indices, self.n_streams)
         self.first.reset(mask)
         self.second.reset(mask)
-        self._pending = mask if self._pending is None else (self._pending | mask)
+        super().reset(mask)
 
     def push(self, samples: torch.Tensor) -> StreamOutput:
         """Append samples [S, step_samples] (float32, on the device) to every stream; one step of both detectors.  first.push, the
         selection (tcr_stream_select), the read-back of the number of selected streams, second.push_selected with the first stage's
         logits / probs as fill rows.  Nothing selected: the second network does not run."""
         lib, S = self.lib, self.n_streams
-        reset_ptr = None
-        if self._pending is not None:
-            self._reset_dev.copy_(torch.from_numpy(self._pending.astype(np.uint8)))
-            self._pending, reset_ptr = None, self._reset_dev.data_ptr()
+        reset_ptr = self._take_reset()
         out1 = self.first.push(samples)
         values = getattr(out1, self.on)
         lib.check(lib.tcr_stream_select(S, int(values.shape[1]), values.data_ptr(), self._cmask.data_ptr(), self.enter_threshold,

@@ -16,11 +16,10 @@ import torch
 
 from . import _lib
 from ._lib import TcrError
-from .detection import CascadeOutput, DetectionStage, RaggedScanOutput, ScanOutput, _first_steps, _last_steps, _new_tensors
-from .phrases import BACKGROUND_LABEL, PhraseDetector
+from .detection import RaggedScanOutput, _first_steps, _last_steps, check_on
+from .phrases import BACKGROUND_LABEL, PhraseDetector, _PosteriorStream
 from .runtime import stream_of
 from .scoring import _offsets
-from .streaming import StreamOutput, reset_mask
 
 
 class _Tables:
@@ -118,8 +117,7 @@ class KeywordTemplates:
         `scanner` and keeps, as a template of keyword `name`, the `on` ("smoothed", or "probs") rows of the steps whose end times lie in
         [start_ms, end_ms] (default: all rows); of more than max_frames rows every r-th, r the smallest integer that fits (default: the
         largest template the library takes).  Returns the template."""
-        if on not in ("smoothed", "probs"):
-            raise TcrError(f"KeywordTemplates.enroll: on must be 'smoothed' or 'probs', got {on!r}")
+        check_on("KeywordTemplates.enroll", on)
         st = scanner.stage
         x = signal if isinstance(signal, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(signal, np.float32))
         if x.dim() != 1 or x.dtype != torch.float32:
@@ -170,11 +168,11 @@ class TemplateDetector(PhraseDetector):
     scanner's classes.  A match of more than max_stretch x the longest template's frames scores 0 (the summed cost prefers short
     paths; max_stretch <= 0: no limit).  detection_threshold / suppression_ms: None takes the scanner's; on: the rows `scores`,
     `detect` and the streaming form read by default.  `labels` are the keyword names and "_background_" last."""
+    _noun = "template"
 
     def __init__(self, scanner, templates: KeywordTemplates, detection_threshold: Optional[float] = None, suppression_ms: Optional[float] = None,
                  max_stretch: float = 3.0, on: str = "smoothed"):
-        if on not in ("smoothed", "probs"):
-            raise TcrError(f"TemplateDetector: on must be 'smoothed' or 'probs', got {on!r}")
+        check_on("TemplateDetector", on)
         ncls = scanner.net.num_classes
         if not isinstance(templates, KeywordTemplates) or len(templates) == 0:
             raise TcrError("TemplateDetector: templates is a KeywordTemplates with at least one template")
@@ -201,21 +199,7 @@ class TemplateDetector(PhraseDetector):
         self.max_steps = int(math.ceil(self.max_stretch * longest)) if self.max_stretch > 0 else 0
         packed = torch.from_numpy(np.ascontiguousarray(np.concatenate(flat), np.float32)).to(self.device)
         self.tables = _Tables("TemplateDetector", packed, frame_off, kw_off, scale, self.max_steps)
-        st = scanner.stage
-        self.det = det = st.detect_cfg(0.0, 1, detection_threshold, suppression_ms)     # (one vector per decision: a posterior is its whole input)
-        self.stage = DetectionStage(st.lib, st.device, len(self.labels), st.step_samples, st.sample_rate, st.clip_samples, det)
-
-    def _values(self, out, on: Optional[str]) -> torch.Tensor:
-        on = self.on if on is None else on
-        if on not in ("smoothed", "probs"):
-            raise TcrError(f"TemplateDetector: on must be 'smoothed' or 'probs', got {on!r}")
-        v, ncls = getattr(out, on), self.scanner.net.num_classes
-        want_dim = 2 if isinstance(out, RaggedScanOutput) else 3
-        if v is None or v.dim() != want_dim or int(v.shape[-1]) != ncls:
-            raise TcrError(f"TemplateDetector: the output's {on} {None if v is None else tuple(v.shape)} is not a scan of the scanner's {ncls} "
-                           "classes")
-        self.scanner.net._check_tensor(v, f"template {on}")
-        return v
+        self._make_stage(detection_threshold, suppression_ms)
 
     def scores(self, out, on: Optional[str] = None, return_lengths: bool = False):
         """The keyword posteriors of `out` (a `ScanOutput`, `RaggedScanOutput` or `CascadeOutput` of the scanner): float32 shaped like
@@ -234,18 +218,11 @@ class TemplateDetector(PhraseDetector):
         min_count = 1 and this detector's threshold and suppression): a keyword fires when it is on top above the threshold, and again
         only after the background (or another keyword) has been.  With return_lengths: (that output, the lengths)."""
         ph, lengths = self.scores(out, on, return_lengths=True)
-        ragged = isinstance(out, RaggedScanOutput)
-        if ragged and int(ph.shape[0]) == 0:                # (no rows in all: nothing to launch, and the library refuses the call)
-            det = RaggedScanOutput(None, ph, ph, *_new_tensors((0,), 0, self.device, 0), out.offsets)
-        else:
-            posteriors = RaggedScanOutput(None, ph, None, None, None, None, out.offsets) if ragged else ScanOutput(None, ph, None, None, None, None)
-            det = self.stage.redetect(posteriors, smoothed=False)
-        if isinstance(out, CascadeOutput):
-            det = CascadeOutput(*det.tensors(), out.offsets, out.selected, out.first)
+        det = self._detect(out, ph)
         return (det, lengths) if return_lengths else det
 
 
-class StreamingTemplateDetector:
+class StreamingTemplateDetector(_PosteriorStream):
     """`TemplateDetector.detect` over live streams (tcr_dtw_stream_push): `push` takes what a `StreamingDetector` of the same streams
     returned from `push`, `push_many` or `push_ragged` and returns the keyword detections of those steps.  The DTW column of every
     (stream, template) and the detector's integers stay on the device, so however the streams are cut into pushes, every stream's rows
@@ -255,92 +232,14 @@ class StreamingTemplateDetector:
     The outputs have `TemplateDetector.detect`'s form over K + 1 classes, and `lengths` holds the lengths of the last push (the same
     leading shape, K columns).  A `StreamOutput` (one step) gives this object's own [S, ..] tensors, overwritten by the next one-step
     push (copy what must survive it); a `ScanOutput` / `RaggedScanOutput` gives new ones."""
+    _entry, _has_lengths = "tcr_dtw_stream", True
 
-    def __init__(self, detector: TemplateDetector, n_streams: int):
-        self.detector, self.lib, self.device = detector, detector.lib, detector.device
-        self.n_streams = S = int(n_streams)
-        if S <= 0:
-            raise TcrError(f"StreamingTemplateDetector: n_streams must be positive (got {S})")
-        self.labels, self.num_classes = detector.labels, detector.num_classes
-        self._classes = detector.scanner.net.num_classes
-        lib, dev, tb = self.lib, self.device, detector.tables
-        nstate = lib.tcr_dtw_stream_state_bytes(S, self._classes, *tb.args())
-        if nstate == 0:
-            raise TcrError(f"StreamingTemplateDetector: {lib.tcr_last_error().decode()}")
-        self.state = torch.empty(nstate // 4, dtype=torch.float32, device=dev)
-        post, top, score, is_new = _new_tensors((S,), self.num_classes, dev, 1)
-        self.out = StreamOutput(None, post, post, top, score, is_new)
-        self._own_lengths = torch.empty((S, self.num_classes - 1), dtype=torch.int32, device=dev)
-        self.lengths = self._own_lengths
-        self._reset_dev = torch.zeros(S, dtype=torch.uint8, device=dev)
-        self._pending: Optional[np.ndarray] = None
-        lib.check(lib.tcr_dtw_stream_init(S, self._classes, *tb.args(), self.state.data_ptr(), stream_of(dev)), "tcr_dtw_stream_init")
-
-    def reset(self, mask_or_indices) -> None:
-        """Return streams to the start (no rows seen, no detection yet) at their NEXT pushed row, before it: `StreamingDetector.reset`'s
-        argument and rules; a reset stays pending for a stream that has no rows in a ragged push."""
-        mask = reset_mask(mask_or_indices, self.n_streams)
-        self._pending = mask if self._pending is None else (self._pending | mask)
-
-    def _take_reset(self) -> Optional[int]:
-        if self._pending is None:
-            return None
-        self._reset_dev.copy_(torch.from_numpy(self._pending.astype(np.uint8)))
-        self._pending = None
-        return self._reset_dev.data_ptr()
-
-    def _values(self, out, on: Optional[str]) -> torch.Tensor:
-        on = self.detector.on if on is None else on
-        if on not in ("smoothed", "probs"):
-            raise TcrError(f"StreamingTemplateDetector: on must be 'smoothed' or 'probs', got {on!r}")
-        v, S, ncls = getattr(out, on), self.n_streams, self._classes
-        if v is None or int(v.shape[-1]) != ncls:
-            raise TcrError(f"StreamingTemplateDetector: the output's {on} {None if v is None else tuple(v.shape)} is not over the detector's "
-                           f"{ncls} classes")
-        if isinstance(out, RaggedScanOutput):
-            ok = v.dim() == 2 and len(out) == S
-        else:
-            ok = v.dim() == (2 if isinstance(out, StreamOutput) else 3) and int(v.shape[0]) == S
-        if not ok:
-            raise TcrError(f"StreamingTemplateDetector: the output's {on} {tuple(v.shape)} is not a push of {S} streams")
-        self.detector.scanner.net._check_tensor(v, f"template {on}")
-        return v
+    def _tables(self):
+        return self.detector.tables.args()
 
     def push(self, out, on: Optional[str] = None):
         """The keyword detections of the steps in `out`, what the `StreamingDetector` returned: a `StreamOutput` (`push`: one step ->
         this object's own `StreamOutput`), a `ScanOutput` (`push_many` -> a new `ScanOutput`) or a `RaggedScanOutput` (`push_ragged` ->
         a new `RaggedScanOutput` with out's offsets), read from out's `on`; `lengths` is set to the call's lengths.  Pending `reset`s
         apply before a stream's first row of the call.  The call only enqueues kernels."""
-        v = self._values(out, on)
-        lib, dev, S, K1 = self.lib, self.device, self.n_streams, self.num_classes
-        tb, det = self.detector.tables, C.byref(self.detector.det)
-        if isinstance(out, RaggedScanOutput):
-            rows = int(v.shape[0])
-            post, top, score, is_new = _new_tensors((rows,), K1, dev, 1)
-            self.lengths = torch.empty((rows, K1 - 1), dtype=torch.int32, device=dev)
-            res = RaggedScanOutput(None, post, post, top, score, is_new, out.offsets)
-            if rows == 0:                                       # (no rows in all: nothing to launch; the resets stay pending)
-                return res
-            off_dev = torch.from_numpy(res.offsets).to(dev)
-            pending, reset_ptr = self._pending, self._take_reset()
-            self._pending = pending                             # (until the call has run; it ignores the flag of a stream without rows)
-            lib.check(lib.tcr_dtw_stream_push_ragged(S, off_dev.data_ptr(), rows, self._classes, v.data_ptr(), *tb.args(), det, reset_ptr,
-                                                     self.state.data_ptr(), post.data_ptr(), self.lengths.data_ptr(), top.data_ptr(),
-                                                     score.data_ptr(), is_new.data_ptr(), stream_of(dev)), "tcr_dtw_stream_push_ragged")
-            if pending is not None:
-                left = pending & (res.steps == 0)
-                self._pending = left if left.any() else None
-            return res
-        if isinstance(out, StreamOutput):
-            res, steps, self.lengths = self.out, 1, self._own_lengths
-        else:
-            steps = int(v.shape[1])
-            post, top, score, is_new = _new_tensors((S, steps), K1, dev, 1)
-            self.lengths = torch.empty((S, steps, K1 - 1), dtype=torch.int32, device=dev)
-            res = ScanOutput(None, post, post, top, score, is_new)
-            if steps == 0:
-                return res
-        lib.check(lib.tcr_dtw_stream_push(S, steps, self._classes, v.data_ptr(), *tb.args(), det, self._take_reset(), self.state.data_ptr(),
-                                          res.probs.data_ptr(), self.lengths.data_ptr(), res.top.data_ptr(), res.score.data_ptr(),
-                                          res.is_new.data_ptr(), stream_of(dev)), "tcr_dtw_stream_push")
-        return res
+        return super().push(out, on)
