@@ -1180,8 +1180,10 @@ typedef struct {
  * table: device float32 [up][taps].  Stateless; nothing is read outside the rows, nothing written outside out's n_out columns.
  * Every pointer is device memory; the launch is enqueued on `stream`.  n_out == 0 or S == 0: a successful no-op.  Refused
  * (TCR_ERR_ARG, tcr_last_error, no launch): null pointers, up / down / taps < 1, odd taps other than 1, unknown in_format,
- * in_step < 1, negative counts, in_pitch < (n_in - 1) in_step + 1, out_pitch < n_out, positions past 2^61 / down, and filters of
- * more taps than a workgroup stages (taps > 6143, or taps + down beyond 14336 samples). */
+ * in_step < 1, negative counts, in_pitch < (n_in - 1) in_step + 1, out_pitch < n_out, positions past 2^61 / down, and what a
+ * workgroup cannot stage: taps > 6143 (a table row), or, with G = min(up, 32, 6144 / (taps | 1)) rows per workgroup,
+ * taps + ceil(G down / up) + 1 > 14336 (the input samples of one row group: e.g. down > 14333 at up = 1, taps = 2); with n_out > 0
+ * and S > 0 also up > 65535 G (more row groups than one launch covers). */
 int tcr_resample(const tcr_resample_cfg* cfg, const float* table, int n_streams, const void* in, int64_t in_pitch, int64_t in_first,
                  int64_t n_in, int64_t out_first, int64_t n_out, float* out, int64_t out_pitch, void* stream);
 /* The input span [first, first + n) that outputs [out_first, out_first + n_out) read: first = floor(out_first M / L) - lead,

@@ -16,7 +16,9 @@
 // and each thread walks the P taps of four outputs of one row from LDS, four independent fmaf chains fed by one coefficient read (b
 // fastest over the lanes: at L = 1 lane l starts M words after lane l - 1).  A table of many rows (44.1 kHz -> 16 kHz: 160 x 178)
 // never sits in LDS whole: a workgroup holds the G <= 32 rows of its residues, and L / G workgroups share one input span through L2.
-// At most 80.3 KB of LDS (24 KB of rows + 56 KB of samples).
+// At most 80.3 KB of LDS (24 KB of rows + 56 KB of samples + the 64 per-row ints): G = min(L, 32, 6144 / (P | 1)) rows, and the host
+// refuses (TCR_ERR_ARG, before any HIP call) what cannot be staged -- P > 6143 (no row fits), or one q of a row group beyond the span,
+// P + ceil(G M / L) + 1 > 14336 -- so no accepted configuration asks for more.
 //
 // Compiled as part of frontend_pk3.hip's translation unit (included at its end, after sweep.hip).
 #pragma once
@@ -172,8 +174,10 @@ extern "C" int tcr_resample(const tcr_resample_cfg* cfg, const float* table, int
     a.G = std::min(std::min(a.L, kRsMaxRows), kRsTableFloats / a.pitch);
     TCR_REQUIRE(a.G >= 1, "tcr_resample: %d taps per phase are more than the kernel stages (%d)", a.P, kRsTableFloats - 1);
     const int64_t rows_span = ((int64_t)a.G * a.M + a.L - 1) / a.L + 1;          // >= floor((r0 + G - 1) M / L) - floor(r0 M / L) + 1
+    // one q (B = 1) must fit: rows_span + P <= kRsSpanFloats.  (Asked of the sum, not of b_fit: a deficit below M truncates to b_fit = 1.)
+    TCR_REQUIRE(a.P + rows_span <= kRsSpanFloats, "tcr_resample: %d taps at %d : %d need more than the %d samples a workgroup stages", a.P,
+                a.L, a.M, kRsSpanFloats);
     const int64_t b_fit = (kRsSpanFloats - a.P - rows_span) / a.M + 1;            // (B - 1) M + rows_span + P <= kRsSpanFloats
-    TCR_REQUIRE(b_fit >= 1, "tcr_resample: %d taps at %d : %d need more than the %d samples a workgroup stages", a.P, a.L, a.M, kRsSpanFloats);
     a.B = (int)std::min<int64_t>(b_fit, std::max(1, kRsTileOutputs / a.G));
     if (a.B > 4) a.B &= ~3;                                                        // (whole four-chain units)
     if (n_out == 0 || n_streams == 0) return TCR_OK;

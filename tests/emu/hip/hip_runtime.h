@@ -258,6 +258,10 @@ inline void run_block() {
     r.cur = -1;
 }
 
+// 0: the blocks of a launch run first to last (the default); 1: last to first.  A kernel whose blocks write disjoint outputs gives the
+// same bits either way; one block overwriting another's outputs shows under one of the two orders.
+inline int& block_order() { static int order = 0; return order; }
+
 inline void launch(dim3 grid, dim3 block, const std::function<void()>& body) {
     Runtime& r = rt();
     r.body = &body;
@@ -265,12 +269,13 @@ inline void launch(dim3 grid, dim3 block, const std::function<void()>& body) {
     if (r.nthreads > 1024 || r.nthreads <= 0) { fprintf(stderr, "[hip-emu] bad block size %d\n", r.nthreads); abort(); }
     gdim() = grid;
     bdim() = block;
-    for (unsigned z = 0; z < grid.z; ++z)
-        for (unsigned y = 0; y < grid.y; ++y)
-            for (unsigned x = 0; x < grid.x; ++x) {
-                bidx() = dim3(x, y, z);
-                run_block();
-            }
+    // x fastest, z slowest; last block first when tcr_emu_block_order(1) asked for it
+    const uint64_t total = (uint64_t)grid.x * grid.y * grid.z;
+    for (uint64_t i = 0; i < total; ++i) {
+        const uint64_t k = block_order() ? total - 1 - i : i;
+        bidx() = dim3((unsigned)(k % grid.x), (unsigned)(k / grid.x % grid.y), (unsigned)(k / ((uint64_t)grid.x * grid.y)));
+        run_block();
+    }
 }
 
 template <class T>
@@ -385,6 +390,12 @@ inline void log_launch(const char* text, const void* fn) {
 extern "C" __attribute__((used, visibility("default"))) inline void tcr_emu_launch_log_clear() {
     emu::launch_log().entries.clear();
     emu::launch_log().dropped = 0;
+}
+// The order in which the blocks of every later launch run (emu::block_order); returns the previous setting.
+extern "C" __attribute__((used, visibility("default"))) inline int tcr_emu_block_order(int reverse) {
+    const int was = emu::block_order();
+    emu::block_order() = reverse ? 1 : 0;
+    return was;
 }
 // The log as newline-separated entries, NUL-terminated, into buf[0 .. cap); a last line "!dropped <n>" when entries did not fit the
 // list.  Returns the bytes the whole text needs (NUL included): call with cap = 0 to size the buffer.
