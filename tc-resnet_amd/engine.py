@@ -38,21 +38,17 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _shape(ti: TensorInfo) -> Tuple[int, ...]:
+    return tuple(ti.shape[i] for i in range(ti.rank))
+
+
 class _Base:
-    _kver = 0            # bumped by every method that lets a kernel write the variables / moving statistics (TCResNet caches its BN fold on it)
+    """What the front-end and the networks share: the current stream and the rule for tensors handed to the library."""
 
     def _stream(self):
         if self.device.type == "cuda":
             return torch.cuda.current_stream(self.device).cuda_stream
         return None
-
-    def tf_shape(self, name: str) -> Tuple[int, ...]:
-        """Shape of variable `name` as the reference's TF graph declares it (what a TF-written checkpoint holds)."""
-        over = getattr(self, "tf_shapes", None)
-        if over and name in over:
-            return tuple(over[name])
-        ti = self.tensors[name]
-        return tuple(ti.shape[i] for i in range(ti.rank))
 
     def _check_tensor(self, t: torch.Tensor, what: str):
         if t.device.type != self.device.type or t.dtype != torch.float32 or not t.is_contiguous():
@@ -144,9 +140,193 @@ def features_to_planar(x: torch.Tensor, lib: Optional[_lib.Library] = None) -> t
     return out
 
 
-class TCResNet(_Base):
+class _Network(_Base):
+    """What the three model families share: the handle, the variable / statistics / gradient arenas and their tensor table, checkpoints,
+    the optimiser layer, the staged (cross-replica BN) run of a pass, and the model reference of the detection calls.  A family sets
+    PREFIX (its C functions are `<PREFIX>_destroy`, `_param_floats`, `_stat_floats`, `_num_tensors`, `_tensor_info`) and FAMILY, creates
+    its handle, and keeps its own forward / backward argument lists: those C signatures differ."""
+
+    PREFIX, FAMILY = "", -1
+
+    def _adopt(self, handle: C.c_void_p):
+        """Own `handle` (destroyed with the object) and look up the family's C functions, once."""
+        self._c = {n: getattr(self.lib, f"{self.PREFIX}_{n}") for n in ("destroy", "param_floats", "stat_floats", "num_tensors", "tensor_info")}
+        self._h = handle
+        self._kver = 0      # bumped by every method that lets a kernel write the variables / moving statistics (TCResNet caches its BN fold on it)
+        self.slots: Dict[str, torch.Tensor] = {}      # optimiser slots (arena-shaped)
+        self._ws: Dict[object, torch.Tensor] = {}
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._c["destroy"](self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def _bind_arenas(self):
+        """Read the tensor table and allocate the arenas (`n_decay` is the family's to set: DS-CNN has no C query for it)."""
+        c, h = self._c, self._h
+        self.n_param, self.n_stat = c["param_floats"](h), c["stat_floats"](h)
+        self.tensors: Dict[str, TensorInfo] = {}
+        for i in range(c["num_tensors"](h)):
+            ti = TensorInfo()
+            self.lib.check(c["tensor_info"](h, i, C.byref(ti)), f"{self.PREFIX}_tensor_info")
+            self.tensors[ti.name.decode()] = ti
+        self.params = torch.zeros(self.n_param, dtype=torch.float32, device=self.device)
+        self.stats = torch.zeros(self.n_stat, dtype=torch.float32, device=self.device)
+        self._grads_buf = torch.zeros(self.n_param + DP_TAIL, dtype=torch.float32, device=self.device)     # arena + the data-parallel tail (parallel.py)
+        self.grads = self._grads_buf[:self.n_param]
+
+    def _call(self, name: str, *args):
+        """One checked C call; a failure is reported under the function's name."""
+        self.lib.check(getattr(self.lib, name)(*args), name)
+
+    # ---- parameters ---------------------------------------------------------------------------
+    def _view(self, name: str) -> torch.Tensor:
+        ti = self.tensors[name]
+        arena = self.params if ti.arena == 0 else self.stats
+        return arena[ti.offset:ti.offset + ti.size].view(_shape(ti))
+
+    def grad_view(self, name: str) -> torch.Tensor:
+        ti = self.tensors[name]
+        assert ti.arena == 0
+        return self.grads[ti.offset:ti.offset + ti.size].view(_shape(ti))
+
+    def trainable_names(self) -> List[str]:
+        return [n for n, ti in self.tensors.items() if ti.arena == 0]
+
+    def total_params(self) -> int:
+        return sum(int(ti.size) for ti in self.tensors.values() if ti.arena == 0)
+
+    def tf_shape(self, name: str) -> Tuple[int, ...]:
+        """Shape of variable `name` as the reference's TF graph declares it (what a TF-written checkpoint holds)."""
+        over = getattr(self, "tf_shapes", None)
+        if over and name in over:
+            return tuple(over[name])
+        return _shape(self.tensors[name])
+
+    def state_dict(self) -> Dict[str, np.ndarray]:
+        """TF variable name -> array in the reference checkpoint shape (SURVEY App. C)."""
+        return {n: self._view(n).detach().cpu().numpy().copy() for n in self.tensors}
+
+    def _fit(self, v: torch.Tensor, ti: TensorInfo) -> torch.Tensor:
+        """A checkpoint array brought to the arena's shape where this family accepts another: [k, Cin, Cout] for [k, 1, Cin, Cout]."""
+        return v.unsqueeze(1) if ti.rank == 4 and v.dim() == 3 else v
+
+    def load_state_dict(self, sd: Dict[str, np.ndarray], strict: bool = True):
+        for n, ti in self.tensors.items():
+            if n not in sd:
+                if strict:
+                    raise KeyError(n)
+                continue
+            v = self._fit(torch.as_tensor(np.asarray(sd[n], dtype=np.float32)), ti)
+            if tuple(v.shape) != _shape(ti):
+                raise TcrError(f"{n}: shape {tuple(v.shape)} != {_shape(ti)}")
+            self._view(n).copy_(v.to(self.device))
+
+    # ---- buffers ------------------------------------------------------------------------------
+    def _cached_ws(self, cache: dict, key, nbytes, zeroed: bool = False) -> torch.Tensor:
+        """`cache[key]`, allocated on first use with the size the zero-argument `nbytes` reports."""
+        ws = cache.get(key)
+        if ws is None:
+            ws = cache[key] = (torch.zeros if zeroed else torch.empty)(nbytes() // 4, dtype=torch.float32, device=self.device)
+        return ws
+
+    def _outputs(self, b: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=self.device)
+        return logits, torch.empty_like(logits)
+
+    def _train_outputs(self, b: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(logits, probs, loss[2]) of a train-mode forward; loss[0] is written by the library: no fill kernel in front of the step."""
+        return (*self._outputs(b), torch.empty(2, dtype=torch.float32, device=self.device))
+
+    def model_ref(self, aux: Optional[torch.Tensor] = None) -> _lib.ModelRef:
+        """The tcr_model_ref of a detection call, with the arenas the net holds now: (family, handle, params, stats).  TC-ResNet alone
+        takes `aux`, its folded BN table, in place of the statistics (None for the size queries and init)."""
+        assert aux is None, f"{type(self).__name__} folds its BN from params / stats in every call: it takes no table"
+        return _lib.ModelRef(self.FAMILY, self._h.value, self.params.data_ptr(), self.stats.data_ptr())
+
+    # ---- cross-replica BN ---------------------------------------------------------------------
+    def _stage_sums(self, fn: str, backward: int, stage: int, ws: torch.Tensor, batch: int) -> torch.Tensor:
+        """The float64 sums (one contiguous range inside the f32 workspace) that stage `stage` of a pass hands to the other replicas;
+        `fn`: the family's `*_stage_sums` (or TC-ResNet's `tcr_net_level_sums`)."""
+        ptr, n = C.c_void_p(), C.c_int64()
+        self._call(fn, self._h, backward, stage, ws.data_ptr(), batch, C.byref(ptr), C.byref(n))
+        off = (ptr.value - ws.data_ptr()) // 4
+        return ws[off:off + 2 * n.value].view(torch.float64)
+
+    def _run_staged(self, sync_hook, backward: int, ws: torch.Tensor, batch: int, whole, staged, n_stages, sums: str):
+        """One forward (`backward` = 0) or backward (1) pass on the current stream.  `whole`, `staged`: (C function name, its arguments in
+        front of the stream / of the stage index and the stream).  Without a `sync_hook` the whole pass is one call; with one
+        (cross-replica BN) it runs stage by stage and the hook all-reduces each stage's sums, `sums` naming the C function that finds
+        them, before the next stage reads them.  `n_stages`: (C function name, its arguments behind the handle), asked only then."""
+        if sync_hook is None:
+            return self._call(*whole, self._stream())
+        ns = getattr(self.lib, n_stages[0])(self._h, *n_stages[1:])
+        for st in range(ns):
+            self._call(*staged, st, self._stream())
+            if st < ns - 1:
+                sync_hook(self._stage_sums(sums, backward, st, ws, batch))
+
+    # ---- optimisers ---------------------------------------------------------------------------
+    def _slot(self, name: str) -> torch.Tensor:
+        if name not in self.slots:
+            self.slots[name] = torch.zeros_like(self.params)
+        return self.slots[name]
+
+    def slot_arena(self, name: str) -> torch.Tensor:
+        """Arena-shaped optimiser slot under its TF name, created with TF's initial value: `RMSProp` (the rms accumulator)
+        starts at one, `ExponentialMovingAverage` as a copy of the variables, every other slot at zero."""
+        if name not in self.slots:
+            if name == "RMSProp":
+                self.slots[name] = torch.ones_like(self.params)
+            elif name == "ExponentialMovingAverage":
+                self.slots[name] = self.params.clone()
+            else:
+                self.slots[name] = torch.zeros_like(self.params)
+        return self.slots[name]
+
+    def ema_init(self):
+        self.slots["ExponentialMovingAverage"] = self.params.clone()
+
+    def sgd_momentum_step(self, lr: float, momentum: float = 0.9, weight_decay: float = 0.0, grad_scale: float = 1.0):
+        m = self._slot("Momentum")
+        self._call("tcr_sgd_momentum_step", self.params.data_ptr(), self.grads.data_ptr(), m.data_ptr(), self.n_param, self.n_decay,
+                   float(lr), float(momentum), float(weight_decay), float(grad_scale), self._stream())
+        self._kver += 1
+
+    def adam_step(self, lr: float, step: int, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                  weight_decay: float = 0.0, grad_scale: float = 1.0):
+        m, v = self._slot("Adam"), self._slot("Adam_1")
+        self._call("tcr_adam_step", self.params.data_ptr(), self.grads.data_ptr(), m.data_ptr(), v.data_ptr(), self.n_param, self.n_decay,
+                   float(lr), float(beta1), float(beta2), float(eps), int(step), float(weight_decay), float(grad_scale), self._stream())
+        self._kver += 1
+
+    def rmsprop_step(self, lr: float, decay: float = 0.9, momentum: float = 0.0, eps: float = 1e-10, weight_decay: float = 0.0,
+                     grad_scale: float = 1.0):
+        """tf.train.RMSPropOptimizer; slot names as in TF (`RMSProp` = rms, initialised to one; `RMSProp_1` = momentum)."""
+        ms, mom = self.slot_arena("RMSProp"), self.slot_arena("RMSProp_1")
+        self._call("tcr_rmsprop_step", self.params.data_ptr(), self.grads.data_ptr(), ms.data_ptr(), mom.data_ptr(), self.n_param, self.n_decay,
+                   float(lr), float(decay), float(momentum), float(eps), float(weight_decay), float(grad_scale), self._stream())
+        self._kver += 1
+
+    def ema_step(self, decay: float):
+        """tf.train.ExponentialMovingAverage(decay).apply(trainables): the shadow arena starts as a copy of the variables'
+        initial values (`ema_init()`, called when the train op is built)."""
+        sh = self.slot_arena("ExponentialMovingAverage")
+        self._call("tcr_ema_step", sh.data_ptr(), self.params.data_ptr(), self.n_param, float(decay), self._stream())
+
+    def l2_loss(self, weight_decay: float) -> torch.Tensor:
+        out = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._call("tcr_l2_loss", self.params.data_ptr(), self.n_decay, float(weight_decay), out.data_ptr(), self._stream())
+        return out[0]
+
+
+class TCResNet(_Network):
     """TC-ResNet parameters + kernels (audio_nets/tc_resnet.py:6-70 of the reference)."""
 
+    PREFIX, FAMILY = "tcr_net", _lib.FAMILY_TCRESNET
     KIND = {0: "weight", 1: "gamma", 2: "beta", 3: "moving_mean", 4: "moving_variance"}
 
     def __init__(self, scope: str, channels: Sequence[int], in_channels: int, t_in: int, num_classes: int,
@@ -163,54 +343,19 @@ class TCResNet(_Base):
         cfg.bn_decay, cfg.bn_eps = float(bn_decay), float(bn_eps)
         handle = C.c_void_p()
         self.lib.check(self.lib.tcr_tcresnet_create(C.byref(cfg), C.byref(handle)), "tcr_tcresnet_create")
-        self.cfg, self._h = cfg, handle
+        self._adopt(handle)
+        self.cfg = cfg
         self.scope, self.channels = scope, list(channels)
         self.num_classes, self.in_channels, self.t_in = int(num_classes), int(in_channels), int(t_in)
-        self.n_param = self.lib.tcr_net_param_floats(handle)
+        self._bind_arenas()
         self.n_decay = self.lib.tcr_net_decay_floats(handle)
-        self.n_stat = self.lib.tcr_net_stat_floats(handle)
-        self.tensors: Dict[str, TensorInfo] = {}
-        for i in range(self.lib.tcr_net_num_tensors(handle)):
-            ti = TensorInfo()
-            self.lib.check(self.lib.tcr_net_tensor_info(handle, i, C.byref(ti)), "tcr_net_tensor_info")
-            self.tensors[ti.name.decode()] = ti
-        self.params = torch.zeros(self.n_param, dtype=torch.float32, device=self.device)
-        self.stats = torch.zeros(self.n_stat, dtype=torch.float32, device=self.device)
-        self._grads_buf = torch.zeros(self.n_param + DP_TAIL, dtype=torch.float32, device=self.device)     # arena + the data-parallel tail (parallel.py)
-        self.grads = self._grads_buf[:self.n_param]
-        self.slots: Dict[str, torch.Tensor] = {}      # optimiser slots (arena-shaped)
-        self._ws: Dict[Tuple[int, int], torch.Tensor] = {}
-        self._kver, self._fold_key, self._fold_ss, self._fold_event, self._fold_stream, self._fold_readers = 0, None, None, None, None, {}
+        self._fold_key, self._fold_ss, self._fold_event, self._fold_stream, self._fold_readers = None, None, None, None, {}
         self._fold_waited = set()
         self._wave_feat: Dict[Tuple[int, int, int], torch.Tensor] = {}
         self.handoff = "level"         # cross-replica BN hand-off granularity: "level" (default) or "unit" (tcr_net_*_stage)
         self.reset_bn()
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self.lib.tcr_net_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
     # ---- parameters ---------------------------------------------------------------------------
-    def _view(self, name: str) -> torch.Tensor:
-        ti = self.tensors[name]
-        arena = self.params if ti.arena == 0 else self.stats
-        return arena[ti.offset:ti.offset + ti.size].view(*[ti.shape[i] for i in range(ti.rank)])
-
-    def grad_view(self, name: str) -> torch.Tensor:
-        ti = self.tensors[name]
-        assert ti.arena == 0
-        return self.grads[ti.offset:ti.offset + ti.size].view(*[ti.shape[i] for i in range(ti.rank)])
-
-    def trainable_names(self) -> List[str]:
-        return [n for n, ti in self.tensors.items() if ti.arena == 0]
-
-    def total_params(self) -> int:
-        return sum(int(ti.size) for ti in self.tensors.values() if ti.arena == 0)
-
     def reset_bn(self):
         for n, ti in self.tensors.items():
             if ti.kind in (1, 4):       # gamma, moving_variance -> 1
@@ -230,34 +375,11 @@ class TCResNet(_Base):
             self._view(n).copy_(w.to(self.device))
         self.reset_bn()
 
-    def state_dict(self) -> Dict[str, np.ndarray]:
-        """TF variable name -> array in the reference checkpoint shape (SURVEY App. C)."""
-        return {n: self._view(n).detach().cpu().numpy().copy() for n in self.tensors}
-
-    def load_state_dict(self, sd: Dict[str, np.ndarray], strict: bool = True):
-        for n, ti in self.tensors.items():
-            if n not in sd:
-                if strict:
-                    raise KeyError(n)
-                continue
-            v = torch.as_tensor(np.asarray(sd[n], dtype=np.float32))
-            shape = tuple(ti.shape[i] for i in range(ti.rank))
-            if ti.rank == 4 and v.dim() == 3:       # [k, Cin, Cout] accepted for [k, 1, Cin, Cout]
-                v = v.unsqueeze(1)
-            if tuple(v.shape) != shape:
-                raise TcrError(f"{n}: shape {tuple(v.shape)} != {shape}")
-            self._view(n).copy_(v.to(self.device))
-
     # ---- workspaces ---------------------------------------------------------------------------
     def workspace(self, batch: int, train: bool) -> torch.Tensor:
-        key = (int(batch), int(train))
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = self.lib.tcr_net_workspace_bytes(self._h, batch, int(train))
-            # (training: zeroed once -- the cross-replica hand-off all-reduces one contiguous range over both float64 sum slots, gap included)
-            ws = (torch.zeros if train else torch.empty)(nbytes // 4, dtype=torch.float32, device=self.device)
-            self._ws[key] = ws
-        return ws
+        # (training: zeroed once -- the cross-replica hand-off all-reduces one contiguous range over both float64 sum slots, gap included)
+        return self._cached_ws(self._ws, (int(batch), int(train)), lambda: self.lib.tcr_net_workspace_bytes(self._h, batch, int(train)),
+                               zeroed=train)
 
     def new_workspace(self, batch: int, train: bool) -> torch.Tensor:
         """A fresh scratch tensor of the size `workspace(batch, train)` has (not cached, not shared)."""
@@ -278,6 +400,11 @@ class TCResNet(_Base):
     def invalidate_folded(self):
         """Call after writing `params` / `stats` through a path torch does not see (a raw pointer handed to another library)."""
         self._kver += 1
+
+    def model_ref(self, aux: Optional[torch.Tensor] = None) -> _lib.ModelRef:
+        """The tcr_model_ref of a detection call: (family, handle, params, `aux`), `aux` the folded BN table the call reads (`fold_bn`'s
+        layout); None for the size queries and init, which read no weights."""
+        return _lib.ModelRef(self.FAMILY, self._h.value, self.params.data_ptr(), _ptr(aux))
 
     def _folded_table(self) -> torch.Tensor:
         """Eval-mode BN folded to (scale, shift) ONCE per weight version (the fold used to be a launch in front of every eval
@@ -313,11 +440,7 @@ class TCResNet(_Base):
         self._check_feat(feat)
         b = feat.shape[0]
         ws = self.workspace(b, False) if workspace is None else workspace
-        if out is not None:
-            logits, probs = out
-        else:
-            logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=self.device)
-            probs = torch.empty_like(logits)
+        logits, probs = out if out is not None else self._outputs(b)
         ranges = torch.empty((b, 2), dtype=torch.float32, device=self.device) if want_ranges else None
         ss = self._folded_table()
         self.lib.check(self.lib.tcr_net_forward_frozen(self._h, self.params.data_ptr(), ss.data_ptr(), feat.data_ptr(), b,
@@ -352,11 +475,7 @@ class TCResNet(_Base):
                 feat = self._wave_feat[key] = torch.empty((b, frontend.cfg.n_coef, padded_len(frontend.cfg.n_frames)), dtype=torch.float32,
                                                           device=self.device)
         ws = self.workspace(b, False)
-        if out is not None:
-            logits, probs = out
-        else:
-            logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=self.device)
-            probs = torch.empty_like(logits)
+        logits, probs = out if out is not None else self._outputs(b)
         ranges = torch.empty((b, 2), dtype=torch.float32, device=self.device) if want_ranges else None
         ver = self._weights_version()
         cur = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else None
@@ -426,8 +545,7 @@ class TCResNet(_Base):
         self._check_tensor(frozen_ss, "frozen table")
         b = feat.shape[0]
         ws = self.workspace(b, False)
-        logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=self.device)
-        probs = torch.empty_like(logits)
+        logits, probs = self._outputs(b)
         ranges = torch.empty((b, 2), dtype=torch.float32, device=self.device) if want_ranges else None
         self.lib.check(self.lib.tcr_net_forward_frozen(self._h, self.params.data_ptr(), frozen_ss.data_ptr(), feat.data_ptr(), b,
                                                        ws.data_ptr(), ws.numel() * 4, logits.data_ptr(), probs.data_ptr(),
@@ -445,130 +563,37 @@ class TCResNet(_Base):
         b = feat.shape[0]
         gb = int(global_batch or b)
         ws = self.workspace(b, True)
-        logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=self.device)
-        probs = torch.empty_like(logits)
-        loss = torch.empty(2, dtype=torch.float32, device=self.device)      # ([0]: written by the library; no fill kernel in front of the step)
+        logits, probs, loss = self._train_outputs(b)
         common = (self._h, self.params.data_ptr(), self.stats.data_ptr(), feat.data_ptr(), labels.data_ptr(), b, gb,
                   float(keep_prob), int(seed), int(sample_offset), float(label_smoothing), ws.data_ptr(), ws.numel() * 4,
                   logits.data_ptr(), probs.data_ptr(), loss.data_ptr())
-        if sync_hook is None:
-            self.lib.check(self.lib.tcr_net_forward_train(*common, self._stream()), "tcr_net_forward_train")
-        elif self.handoff == "unit":      # one hand-off per BN unit (tcr_net_*_stage)
-            ns = self.lib.tcr_net_num_stages(self._h, 0)
-            for st in range(ns):
-                self.lib.check(self.lib.tcr_net_forward_train_stage(*common, st, self._stream()), "tcr_net_forward_train_stage")
-                if st < ns - 1:
-                    sync_hook(self._stage_sums(0, st, ws, b))
-        else:           # cross-replica BN: one hand-off per dependency level (a block's shortcut conv rides with its first conv)
-            nl = self.lib.tcr_net_num_levels(self._h, 0)
-            for lv in range(nl):
-                self.lib.check(self.lib.tcr_net_forward_train_level(*common, lv, self._stream()), "tcr_net_forward_train_level")
-                if lv < nl - 1:
-                    sync_hook(self._level_sums(0, lv, ws, b))
+        unit = self._handoff_unit()
+        self._run_staged(sync_hook, 0, ws, b, ("tcr_net_forward_train", *common), (f"tcr_net_forward_train_{unit}", *common),
+                         (f"tcr_net_num_{unit}s", 0), f"tcr_net_{unit}_sums")
         self._kver += 1          # the moving statistics changed
         self._last = (feat, b, gb, sync_hook)
         return logits, probs, loss[0]
 
-    def _stage_sums(self, backward: int, stage: int, ws: torch.Tensor, batch: int) -> torch.Tensor:
-        ptr, n = C.c_void_p(), C.c_int64()
-        self.lib.check(self.lib.tcr_net_stage_sums(self._h, backward, stage, ws.data_ptr(), batch, C.byref(ptr), C.byref(n)),
-                       "tcr_net_stage_sums")
-        off = (ptr.value - ws.data_ptr()) // 4
-        return ws[off:off + 2 * n.value].view(torch.float64)        # 2*C float64 sums living inside the f32 workspace
-
-    def _level_sums(self, backward: int, level: int, ws: torch.Tensor, batch: int) -> torch.Tensor:
-        ptr, n = C.c_void_p(), C.c_int64()
-        self.lib.check(self.lib.tcr_net_level_sums(self._h, backward, level, ws.data_ptr(), batch, C.byref(ptr), C.byref(n)),
-                       "tcr_net_level_sums")
-        off = (ptr.value - ws.data_ptr()) // 4
-        return ws[off:off + 2 * n.value].view(torch.float64)        # the level's float64 sums (one contiguous range)
+    def _handoff_unit(self) -> str:
+        """What one cross-replica hand-off covers, as the C functions spell it (tcr_net_*_stage / tcr_net_*_level): "stage", a BN unit, or
+        "level", a dependency level (a block's shortcut conv rides with its first conv)."""
+        return "stage" if self.handoff == "unit" else "level"
 
     def backward(self) -> torch.Tensor:
         """Gradient of the mean cross-entropy wrt every trainable, into self.grads (L2 excluded)."""
         feat, b, gb, sync_hook = self._last
         ws = self.workspace(b, True)
-        if sync_hook is None:
-            self.lib.check(self.lib.tcr_net_backward(self._h, self.params.data_ptr(), feat.data_ptr(), b, ws.data_ptr(),
-                                                     ws.numel() * 4, self.grads.data_ptr(), self._stream()), "tcr_net_backward")
-        elif self.handoff == "unit":
-            ns = self.lib.tcr_net_num_stages(self._h, 1)
-            for st in range(ns):
-                self.lib.check(self.lib.tcr_net_backward_stage(self._h, self.params.data_ptr(), feat.data_ptr(), b, gb,
-                                                               ws.data_ptr(), ws.numel() * 4, self.grads.data_ptr(), st,
-                                                               self._stream()), "tcr_net_backward_stage")
-                if st < ns - 1:
-                    sync_hook(self._stage_sums(1, st, ws, b))
-        else:
-            nl = self.lib.tcr_net_num_levels(self._h, 1)
-            for lv in range(nl):
-                self.lib.check(self.lib.tcr_net_backward_level(self._h, self.params.data_ptr(), feat.data_ptr(), b, gb,
-                                                               ws.data_ptr(), ws.numel() * 4, self.grads.data_ptr(), lv,
-                                                               self._stream()), "tcr_net_backward_level")
-                if lv < nl - 1:
-                    sync_hook(self._level_sums(1, lv, ws, b))
+        head, tail = (self._h, self.params.data_ptr(), feat.data_ptr(), b), (ws.data_ptr(), ws.numel() * 4, self.grads.data_ptr())
+        unit = self._handoff_unit()
+        self._run_staged(sync_hook, 1, ws, b, ("tcr_net_backward", *head, *tail), (f"tcr_net_backward_{unit}", *head, gb, *tail),
+                         (f"tcr_net_num_{unit}s", 1), f"tcr_net_{unit}_sums")
         return self.grads
 
-    def _slot(self, name: str) -> torch.Tensor:
-        if name not in self.slots:
-            self.slots[name] = torch.zeros_like(self.params)
-        return self.slots[name]
 
-    def slot_arena(self, name: str) -> torch.Tensor:
-        """Arena-shaped optimiser slot under its TF name, created with TF's initial value: `RMSProp` (the rms accumulator)
-        starts at one, `ExponentialMovingAverage` as a copy of the variables, every other slot at zero."""
-        if name not in self.slots:
-            if name == "RMSProp":
-                self.slots[name] = torch.ones_like(self.params)
-            elif name == "ExponentialMovingAverage":
-                self.slots[name] = self.params.clone()
-            else:
-                self.slots[name] = torch.zeros_like(self.params)
-        return self.slots[name]
-
-    def ema_init(self):
-        self.slots["ExponentialMovingAverage"] = self.params.clone()
-
-    def sgd_momentum_step(self, lr: float, momentum: float = 0.9, weight_decay: float = 0.0, grad_scale: float = 1.0):
-        m = self._slot("Momentum")
-        self.lib.check(self.lib.tcr_sgd_momentum_step(self.params.data_ptr(), self.grads.data_ptr(), m.data_ptr(), self.n_param,
-                                                      self.n_decay, float(lr), float(momentum), float(weight_decay),
-                                                      float(grad_scale), self._stream()), "tcr_sgd_momentum_step")
-        self._kver += 1
-
-    def adam_step(self, lr: float, step: int, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
-                  weight_decay: float = 0.0, grad_scale: float = 1.0):
-        m, v = self._slot("Adam"), self._slot("Adam_1")
-        self.lib.check(self.lib.tcr_adam_step(self.params.data_ptr(), self.grads.data_ptr(), m.data_ptr(), v.data_ptr(),
-                                              self.n_param, self.n_decay, float(lr), float(beta1), float(beta2), float(eps),
-                                              int(step), float(weight_decay), float(grad_scale), self._stream()), "tcr_adam_step")
-        self._kver += 1
-
-    def rmsprop_step(self, lr: float, decay: float = 0.9, momentum: float = 0.0, eps: float = 1e-10, weight_decay: float = 0.0,
-                     grad_scale: float = 1.0):
-        """tf.train.RMSPropOptimizer; slot names as in TF (`RMSProp` = rms, initialised to one; `RMSProp_1` = momentum)."""
-        ms, mom = self.slot_arena("RMSProp"), self.slot_arena("RMSProp_1")
-        self.lib.check(self.lib.tcr_rmsprop_step(self.params.data_ptr(), self.grads.data_ptr(), ms.data_ptr(), mom.data_ptr(),
-                                                 self.n_param, self.n_decay, float(lr), float(decay), float(momentum), float(eps),
-                                                 float(weight_decay), float(grad_scale), self._stream()), "tcr_rmsprop_step")
-        self._kver += 1
-
-    def ema_step(self, decay: float):
-        """tf.train.ExponentialMovingAverage(decay).apply(trainables): the shadow arena starts as a copy of the variables'
-        initial values (`ema_init()`, called when the train op is built)."""
-        sh = self.slot_arena("ExponentialMovingAverage")
-        self.lib.check(self.lib.tcr_ema_step(sh.data_ptr(), self.params.data_ptr(), self.n_param, float(decay), self._stream()),
-                       "tcr_ema_step")
-
-    def l2_loss(self, weight_decay: float) -> torch.Tensor:
-        out = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.lib.check(self.lib.tcr_l2_loss(self.params.data_ptr(), self.n_decay, float(weight_decay), out.data_ptr(),
-                                            self._stream()), "tcr_l2_loss")
-        return out[0]
-
-
-class DSCNN(_Base):
+class DSCNN(_Network):
     """DS-CNN S / M / L: eval forward, train forward / backward, Adam (audio_nets/ds_cnn.py:19-118 of the reference)."""
 
+    PREFIX, FAMILY = "tcr_dscnn", _lib.FAMILY_DSCNN
     NET_DEFS = {            # depth, separable blocks, conv_1 stride, conv_ds_1 stride  (ds_cnn.py:19-43)
         "S": (64, 4, (2, 2), (1, 1)),
         "M": (172, 4, (2, 1), (2, 2)),
@@ -588,23 +613,12 @@ class DSCNN(_Base):
                        float(bn_decay), float(bn_eps))
         handle = C.c_void_p()
         self.lib.check(self.lib.tcr_dscnn_create(C.byref(cfg), C.byref(handle)), "tcr_dscnn_create")
-        self.cfg, self._h, self.size = cfg, handle, size
+        self._adopt(handle)
+        self.cfg, self.size = cfg, size
         self.num_classes, self.h_in, self.w_in = int(num_classes), int(h_in), int(w_in)
-        self.n_param = self.lib.tcr_dscnn_param_floats(handle)
+        self._bind_arenas()
         self.n_decay = self.n_param     # the reference's name filter excludes only "BatchNorm"; these scopes are "batch_norm"
-        self.n_stat = self.lib.tcr_dscnn_stat_floats(handle)
-        self.tensors: Dict[str, TensorInfo] = {}
-        for i in range(self.lib.tcr_dscnn_num_tensors(handle)):
-            ti = TensorInfo()
-            self.lib.check(self.lib.tcr_dscnn_tensor_info(handle, i, C.byref(ti)), "tcr_dscnn_tensor_info")
-            self.tensors[ti.name.decode()] = ti
-        self.params = torch.zeros(self.n_param, dtype=torch.float32, device=self.device)
-        self.stats = torch.zeros(self.n_stat, dtype=torch.float32, device=self.device)
-        self._grads_buf = torch.zeros(self.n_param + DP_TAIL, dtype=torch.float32, device=self.device)     # arena + the data-parallel tail (parallel.py)
-        self.grads = self._grads_buf[:self.n_param]
-        self.slots: Dict[str, torch.Tensor] = {}
-        self._ws: Dict[int, torch.Tensor] = {}
-        self._train_ws: Dict[int, torch.Tensor] = {}
+        self._train_ws: Dict[int, torch.Tensor] = {}        # (`_ws`: the eval workspaces, by batch)
         for n, ti in self.tensors.items():
             if ti.kind == 4:
                 self._view(n).fill_(1.0)
@@ -614,36 +628,12 @@ class DSCNN(_Base):
         """A DS-CNN given by its definition instead of a size name."""
         return cls(None, h_in, w_in, num_classes, net_def=(depth, n_separable, tuple(conv1_stride), tuple(ds1_stride), conv1_kh), **kw)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self.lib.tcr_dscnn_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    _view = TCResNet._view
-    grad_view = TCResNet.grad_view
-    trainable_names = TCResNet.trainable_names
-    state_dict = TCResNet.state_dict
-    load_state_dict = TCResNet.load_state_dict
-    _slot = TCResNet._slot
-    adam_step = TCResNet.adam_step
-    sgd_momentum_step = TCResNet.sgd_momentum_step
-    rmsprop_step = TCResNet.rmsprop_step
-    ema_step = TCResNet.ema_step
-    slot_arena = TCResNet.slot_arena
-    ema_init = TCResNet.ema_init
-
-    def total_params(self) -> int:
-        return sum(int(ti.size) for ti in self.tensors.values() if ti.arena == 0)
-
     def init_xavier(self, seed: int = 0):
         gen = torch.Generator().manual_seed(int(seed))
         for n, ti in self.tensors.items():
             if ti.kind != 0:
                 continue
-            shape = tuple(ti.shape[i] for i in range(ti.rank))
+            shape = _shape(ti)
             if ti.rank == 4:
                 kh, kw, cin, cout = shape
                 fan_in, fan_out = kh * kw * cin, kh * kw * cout
@@ -659,15 +649,13 @@ class DSCNN(_Base):
             raise TcrError(f"features must be planar [B, {want[0]}, {want[1]}], got {tuple(feat.shape)}")
 
     def train_workspace(self, batch: int) -> torch.Tensor:
-        ws = self._train_ws.get(batch)
-        if ws is None:
-            nbytes = self.lib.tcr_dscnn_train_workspace_bytes(self._h, batch)
-            if nbytes == 0:         # a configuration the training kernels cannot run (tcr_dscnn_cfg's limits): eval only
+        def nbytes():
+            n = self.lib.tcr_dscnn_train_workspace_bytes(self._h, batch)
+            if n == 0:         # a configuration the training kernels cannot run (tcr_dscnn_cfg's limits): eval only
                 msg = self.lib.tcr_last_error()
                 raise TcrError(f"tcr_dscnn_train_workspace_bytes: {msg.decode() if msg else 'bad argument'}")
-            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
-            self._train_ws[batch] = ws
-        return ws
+            return n
+        return self._cached_ws(self._train_ws, batch, nbytes)
 
     def forward_train(self, feat: torch.Tensor, labels: torch.Tensor, global_batch: Optional[int] = None,
                       label_smoothing: float = 0.0, **_unused):
@@ -679,19 +667,12 @@ class DSCNN(_Base):
         b = feat.shape[0]
         gb = int(global_batch or b)
         ws = self.train_workspace(b)
-        logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=self.device)
-        probs = torch.empty_like(logits)
-        loss = torch.empty(2, dtype=torch.float32, device=self.device)      # ([0]: written by the library; no fill kernel in front of the step)
+        logits, probs, loss = self._train_outputs(b)
         common = (self._h, self.params.data_ptr(), self.stats.data_ptr(), feat.data_ptr(), labels.data_ptr(), b, gb, float(label_smoothing),
                   ws.data_ptr(), ws.numel() * 4, logits.data_ptr(), probs.data_ptr(), loss.data_ptr())
-        if sync_hook is None:
-            self.lib.check(self.lib.tcr_dscnn_forward_train(*common, self._stream()), "tcr_dscnn_forward_train")
-        else:               # cross-replica BN: the host all-reduces each unit's float64 sums between stages
-            ns = self.lib.tcr_dscnn_num_stages(self._h)
-            for st in range(ns):
-                self.lib.check(self.lib.tcr_dscnn_forward_train_stage(*common, st, self._stream()), "tcr_dscnn_forward_train_stage")
-                if st < ns - 1:
-                    sync_hook(self._stage_sums(0, st, ws, b))
+        # (cross-replica BN: the host all-reduces each unit's float64 sums between stages)
+        self._run_staged(sync_hook, 0, ws, b, ("tcr_dscnn_forward_train", *common), ("tcr_dscnn_forward_train_stage", *common),
+                         ("tcr_dscnn_num_stages",), "tcr_dscnn_stage_sums")
         self._last = (feat, b, gb, sync_hook)
         return logits, probs, loss[0]
 
@@ -706,79 +687,47 @@ class DSCNN(_Base):
                        "tcr_dscnn_materialize_unit")
         return ws[off.value: off.value + batch * c.value * pad.value].view(batch, c.value, pad.value)[:, :, HALO:HALO + pos.value]
 
-    def _stage_sums(self, backward: int, stage: int, ws: torch.Tensor, batch: int) -> torch.Tensor:
-        ptr, n = C.c_void_p(), C.c_int64()
-        self.lib.check(self.lib.tcr_dscnn_stage_sums(self._h, backward, stage, ws.data_ptr(), batch, C.byref(ptr), C.byref(n)),
-                       "tcr_dscnn_stage_sums")
-        off = (ptr.value - ws.data_ptr()) // 4
-        return ws[off:off + 2 * n.value].view(torch.float64)
-
     def backward(self) -> torch.Tensor:
         """Gradient of the mean cross-entropy wrt every trainable, into self.grads."""
         feat, b, gb, sync_hook = self._last
         ws = self.train_workspace(b)
-        if sync_hook is None:
-            self.lib.check(self.lib.tcr_dscnn_backward(self._h, self.params.data_ptr(), feat.data_ptr(), b, ws.data_ptr(),
-                                                       ws.numel() * 4, self.grads.data_ptr(), self._stream()), "tcr_dscnn_backward")
-        else:
-            ns = self.lib.tcr_dscnn_num_stages(self._h)
-            for st in range(ns):
-                self.lib.check(self.lib.tcr_dscnn_backward_stage(self._h, self.params.data_ptr(), feat.data_ptr(), b, gb, ws.data_ptr(),
-                                                                 ws.numel() * 4, self.grads.data_ptr(), st, self._stream()),
-                               "tcr_dscnn_backward_stage")
-                if st < ns - 1:
-                    sync_hook(self._stage_sums(1, st, ws, b))
+        head, tail = (self._h, self.params.data_ptr(), feat.data_ptr(), b), (ws.data_ptr(), ws.numel() * 4, self.grads.data_ptr())
+        self._run_staged(sync_hook, 1, ws, b, ("tcr_dscnn_backward", *head, *tail), ("tcr_dscnn_backward_stage", *head, gb, *tail),
+                         ("tcr_dscnn_num_stages",), "tcr_dscnn_stage_sums")
         return self.grads
 
     def forward_infer(self, feat: torch.Tensor):
         self._check_feat(feat)
         b = feat.shape[0]
-        ws = self._ws.get(b)
-        if ws is None:
-            ws = torch.empty(self.lib.tcr_dscnn_workspace_bytes(self._h, b) // 4, dtype=torch.float32, device=self.device)
-            self._ws[b] = ws
-        logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=self.device)
-        probs = torch.empty_like(logits)
+        ws = self._cached_ws(self._ws, b, lambda: self.lib.tcr_dscnn_workspace_bytes(self._h, b))
+        logits, probs = self._outputs(b)
         self.lib.check(self.lib.tcr_dscnn_forward_infer(self._h, self.params.data_ptr(), self.stats.data_ptr(), feat.data_ptr(), b,
                                                         ws.data_ptr(), ws.numel() * 4, logits.data_ptr(), probs.data_ptr(),
                                                         self._stream()), "tcr_dscnn_forward_infer")
         return logits, probs
 
-    def l2_loss(self, weight_decay: float) -> torch.Tensor:
-        out = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.lib.check(self.lib.tcr_l2_loss(self.params.data_ptr(), self.n_decay, float(weight_decay), out.data_ptr(),
-                                            self._stream()), "tcr_l2_loss")
-        return out[0]
 
-
-class Graph2D(_Base):
+class Graph2D(_Network):
     """Generic 2-D layer graph on the HIP kernels (C ABI tcr_g2d_*): the remaining model families of the reference's factory
     -- ResNet2D8(/Pool), Res8/15(/Narrow), KWSModel (audio_nets/tc_resnet.py:73-99, res.py:6-123, kws.py:15-63).  The topology
     is described node by node by the builders in tcresnet_amd/audio_nets, the way the reference's Python builds its TF graph;
     variables are created under the TF names given there.  Input: the [T x F] single-channel feature plane ([N, T, F, 1])."""
 
+    PREFIX, FAMILY = "tcr_g2d", _lib.FAMILY_G2D
+
     def __init__(self, scope: str, h: int, w: int, c: int = 1, lib: Optional[_lib.Library] = None, device=None):
         self.lib, self.device = _resolve(lib, device)
         handle = C.c_void_p()
         self.lib.check(self.lib.tcr_g2d_create(scope.encode(), int(h), int(w), int(c), C.byref(handle)), "tcr_g2d_create")
-        self._h, self.scope = handle, scope
+        self._adopt(handle)
+        self.scope = scope
         self.h_in, self.w_in, self.c_in = int(h), int(w), int(c)
         self.initializers: Dict[str, object] = {}           # variable name -> "xavier" | ("truncated_normal", stddev) | "zeros"
         self.relu_nodes: List[int] = []                      # nodes whose output went through a ReLU, in build order
         self.dropout_nodes: List[int] = []                  # node ids of the dropout layers (each mask is keyed by its node id)
         self.constants: Dict[str, np.ndarray] = {}          # non-trainable variables of the reference graph that stay constant (checkpoint completeness)
         self.tf_shapes: Dict[str, Tuple[int, ...]] = {}      # variables whose TF shape differs from the kernel's [kh, kw, cin, cout] (matmul weights: [K, N])
-        self.finalized = False
-        self._ws: Dict[Tuple[int, int], torch.Tensor] = {}
-        self.slots: Dict[str, torch.Tensor] = {}
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self.lib.tcr_g2d_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        self.finalized = False          # (the arenas and the tensor table exist from `finalize` on)
 
     # ---- topology ---------------------------------------------------------------------------------------------------
     def _node(self, rc: int, what: str) -> int:
@@ -854,58 +803,27 @@ class Graph2D(_Base):
         self.lib.check(self.lib.tcr_g2d_finalize(self._h, logits), "tcr_g2d_finalize")
         self.finalized = True
         self.num_classes = self.lib.tcr_g2d_num_classes(self._h)
-        self.n_param = self.lib.tcr_g2d_param_floats(self._h)
+        self._bind_arenas()
         self.n_decay = self.lib.tcr_g2d_decay_floats(self._h)
-        self.n_stat = self.lib.tcr_g2d_stat_floats(self._h)
-        self.tensors: Dict[str, TensorInfo] = {}
-        for i in range(self.lib.tcr_g2d_num_tensors(self._h)):
-            ti = TensorInfo()
-            self.lib.check(self.lib.tcr_g2d_tensor_info(self._h, i, C.byref(ti)), "tcr_g2d_tensor_info")
-            self.tensors[ti.name.decode()] = ti
-        self.params = torch.zeros(self.n_param, dtype=torch.float32, device=self.device)
-        self.stats = torch.zeros(self.n_stat, dtype=torch.float32, device=self.device)
-        self._grads_buf = torch.zeros(self.n_param + DP_TAIL, dtype=torch.float32, device=self.device)     # arena + the data-parallel tail (parallel.py)
-        self.grads = self._grads_buf[:self.n_param]
         self.init_variables(0)
 
     # ---- variables ---------------------------------------------------------------------------------------------------
-    _view = TCResNet._view
-    grad_view = TCResNet.grad_view
-    trainable_names = TCResNet.trainable_names
-    total_params = TCResNet.total_params
-    _slot = TCResNet._slot
-    slot_arena = TCResNet.slot_arena
-    ema_init = TCResNet.ema_init
-    ema_step = TCResNet.ema_step
-    adam_step = TCResNet.adam_step
-    sgd_momentum_step = TCResNet.sgd_momentum_step
-    rmsprop_step = TCResNet.rmsprop_step
-    l2_loss = TCResNet.l2_loss
-
     def state_dict(self) -> Dict[str, np.ndarray]:
         """TF variable name -> array in the shape the reference's graph declares (matmul weights [K, N], not [h, w, c, N])."""
-        sd = {n: self._view(n).detach().cpu().numpy().copy().reshape(self.tf_shape(n)) for n in self.tensors}
+        sd = {n: v.reshape(self.tf_shape(n)) for n, v in super().state_dict().items()}
         sd.update({n: v.copy() for n, v in getattr(self, "constants", {}).items()})     # non-trainable graph variables that never change here
         return sd
 
-    def load_state_dict(self, sd: Dict[str, np.ndarray], strict: bool = True):
-        for n, ti in self.tensors.items():
-            if n not in sd:
-                if strict:
-                    raise KeyError(n)
-                continue
-            v = torch.as_tensor(np.asarray(sd[n], dtype=np.float32))
-            shape = tuple(ti.shape[i] for i in range(ti.rank))
-            if v.numel() != int(ti.size):
-                raise TcrError(f"{n}: shape {tuple(v.shape)} != {shape}")
-            self._view(n).copy_(v.reshape(shape).to(self.device))       # (a [K, N] matmul weight IS the [h, w, c, N] conv weight)
+    def _fit(self, v: torch.Tensor, ti: TensorInfo) -> torch.Tensor:
+        """Any array of the variable's element count is accepted (a [K, N] matmul weight IS the [h, w, c, N] conv weight)."""
+        return v.reshape(_shape(ti)) if v.numel() == int(ti.size) else v
 
     def init_variables(self, seed: int = 0):
         """Weights by the initializer the reference gives each variable (xavier uniform under the slim arg scopes,
         truncated normal in kws.py), biases / beta / moving_mean 0, gamma / moving_variance 1."""
         gen = torch.Generator().manual_seed(int(seed))
         for n, ti in self.tensors.items():
-            shape = tuple(ti.shape[i] for i in range(ti.rank))
+            shape = _shape(ti)
             if ti.kind == 0:
                 init = self.initializers.get(n, "xavier")
                 if init == "xavier":
@@ -928,12 +846,7 @@ class Graph2D(_Base):
 
     # ---- compute ------------------------------------------------------------------------------------------------------
     def workspace(self, batch: int, train: bool) -> torch.Tensor:
-        key = (int(batch), int(train))
-        ws = self._ws.get(key)
-        if ws is None:
-            ws = torch.empty(self.lib.tcr_g2d_workspace_bytes(self._h, batch, int(train)) // 4, dtype=torch.float32, device=self.device)
-            self._ws[key] = ws
-        return ws
+        return self._cached_ws(self._ws, (int(batch), int(train)), lambda: self.lib.tcr_g2d_workspace_bytes(self._h, batch, int(train)))
 
     def input_from_features(self, feat: torch.Tensor) -> torch.Tensor:
         """Front-end planar features [B, F, T + 2*HALO] -> the network's input plane [B, 1, T*F + 2*HALO] ([N, T, F, 1])."""
@@ -950,8 +863,7 @@ class Graph2D(_Base):
         x = self.input_from_features(feat)
         b = x.shape[0]
         ws = self.workspace(b, False)
-        logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=self.device)
-        probs = torch.empty_like(logits)
+        logits, probs = self._outputs(b)
         self.lib.check(self.lib.tcr_g2d_forward_infer(self._h, self.params.data_ptr(), self.stats.data_ptr(), x.data_ptr(), b, ws.data_ptr(),
                                                       ws.numel() * 4, logits.data_ptr(), probs.data_ptr(), self._stream()), "tcr_g2d_forward_infer")
         return logits, probs
@@ -965,39 +877,19 @@ class Graph2D(_Base):
         b = x.shape[0]
         gb = int(global_batch or b)
         ws = self.workspace(b, True)
-        logits = torch.empty((b, self.num_classes), dtype=torch.float32, device=self.device)
-        probs = torch.empty_like(logits)
-        loss = torch.empty(2, dtype=torch.float32, device=self.device)      # ([0]: written by the library; no fill kernel in front of the step)
+        logits, probs, loss = self._train_outputs(b)
         common = (self._h, self.params.data_ptr(), self.stats.data_ptr(), x.data_ptr(), labels.data_ptr(), b, gb, int(seed), int(sample_offset),
                   float(label_smoothing), ws.data_ptr(), ws.numel() * 4, logits.data_ptr(), probs.data_ptr(), loss.data_ptr())
-        if sync_hook is None:
-            self.lib.check(self.lib.tcr_g2d_forward_train(*common, self._stream()), "tcr_g2d_forward_train")
-        else:           # cross-replica BN: the forward stops behind every BN node's statistics (tcr_g2d_*_stage)
-            ns = self.lib.tcr_g2d_num_stages(self._h)
-            for st in range(ns):
-                self.lib.check(self.lib.tcr_g2d_forward_train_stage(*common, st, self._stream()), "tcr_g2d_forward_train_stage")
-                if st < ns - 1:
-                    sync_hook(self._stage_sums(0, st, ws, b))
+        # (cross-replica BN: the forward stops behind every BN node's statistics, tcr_g2d_*_stage)
+        self._run_staged(sync_hook, 0, ws, b, ("tcr_g2d_forward_train", *common), ("tcr_g2d_forward_train_stage", *common),
+                         ("tcr_g2d_num_stages",), "tcr_g2d_stage_sums")
         self._last = (x, b, int(seed), int(sample_offset), gb, sync_hook)
         return logits, probs, loss[0]
-
-    def _stage_sums(self, backward: int, stage: int, ws: torch.Tensor, batch: int) -> torch.Tensor:
-        ptr, n = C.c_void_p(), C.c_int64()
-        self.lib.check(self.lib.tcr_g2d_stage_sums(self._h, backward, stage, ws.data_ptr(), batch, C.byref(ptr), C.byref(n)), "tcr_g2d_stage_sums")
-        off = (ptr.value - ws.data_ptr()) // 4
-        return ws[off:off + 2 * n.value].view(torch.float64)
 
     def backward(self) -> torch.Tensor:
         x, b, seed, off, gb, sync_hook = self._last
         ws = self.workspace(b, True)
-        if sync_hook is None:
-            self.lib.check(self.lib.tcr_g2d_backward(self._h, self.params.data_ptr(), x.data_ptr(), b, seed, off, ws.data_ptr(), ws.numel() * 4,
-                                                     self.grads.data_ptr(), self._stream()), "tcr_g2d_backward")
-        else:
-            ns = self.lib.tcr_g2d_num_stages(self._h)
-            for st in range(ns):
-                self.lib.check(self.lib.tcr_g2d_backward_stage(self._h, self.params.data_ptr(), x.data_ptr(), b, gb, seed, off, ws.data_ptr(),
-                                                               ws.numel() * 4, self.grads.data_ptr(), st, self._stream()), "tcr_g2d_backward_stage")
-                if st < ns - 1:
-                    sync_hook(self._stage_sums(1, st, ws, b))
+        head, tail = (self._h, self.params.data_ptr(), x.data_ptr(), b), (seed, off, ws.data_ptr(), ws.numel() * 4, self.grads.data_ptr())
+        self._run_staged(sync_hook, 1, ws, b, ("tcr_g2d_backward", *head, *tail), ("tcr_g2d_backward_stage", *head, gb, *tail),
+                         ("tcr_g2d_num_stages",), "tcr_g2d_stage_sums")
         return self.grads

@@ -18,7 +18,7 @@ from typing import NamedTuple, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from ._lib import FAMILY_DSCNN, FAMILY_G2D, FAMILY_TCRESNET, ModelRef, TcrError, padded_len
+from ._lib import FAMILY_G2D, FAMILY_TCRESNET, ModelRef, TcrError, padded_len
 from .capturing import CapturedClips, CapturedHost, StreamingRecorder  # noqa: F401
 from .detection import (DEFAULT_MAX_WINDOWS, DetectionStage, PendingResets, _new_tensors, _ragged_scan_output,  # noqa: F401
                         _ragged_signals, _scan_output, check_on, ms_to_steps, reset_mask)
@@ -45,16 +45,10 @@ class _Detection:
 
     def _setup(self, what: str, noun: str, net: Network, frontend: Frontend, frames_per_step: int, average_window_ms: float,
                min_count: int, detection_threshold: float, suppression_ms: float) -> None:
-        if isinstance(net, TCResNet):
-            self._family = FAMILY_TCRESNET
-        elif isinstance(net, DSCNN):
-            self._family = FAMILY_DSCNN
-        elif isinstance(net, Graph2D):
-            if not net.finalized:
-                raise TcrError(f"{what}: the 2-D graph is not finalized")
-            self._family = FAMILY_G2D
-        else:
+        if not isinstance(net, (TCResNet, DSCNN, Graph2D)):
             raise TcrError(f"{what} runs TC-ResNet, DS-CNN and 2-D graph models, got {type(net).__name__}")
+        if net.FAMILY == FAMILY_G2D and not net.finalized:
+            raise TcrError(f"{what}: the 2-D graph is not finalized")
         if net.lib is not frontend.lib or net.device != frontend.device:
             raise TcrError("the network and the front-end must use the same library and device")
         self.net, self.frontend, self.lib, self.device = net, frontend, net.lib, net.device
@@ -71,7 +65,7 @@ class _Detection:
     def _bind_frozen(self, frozen_ss: Optional[torch.Tensor]) -> None:
         net = self.net
         if frozen_ss is not None:
-            if self._family != FAMILY_TCRESNET:
+            if net.FAMILY != FAMILY_TCRESNET:
                 raise TcrError(f"{self._what}: frozen_ss is a TC-ResNet folded BN table; {type(net).__name__} folds its BN from params / "
                                "stats in every call")
             net._check_tensor(frozen_ss, "frozen table")
@@ -81,21 +75,18 @@ class _Detection:
     def _ref(self, aux: Optional[torch.Tensor] = None) -> ModelRef:
         """The tcr_model_ref of a call: TC-ResNet with `aux` = its BN table (None for the size queries and init), DS-CNN / 2-D graph
         with the arenas the net holds now."""
-        net = self.net
-        if self._family == FAMILY_TCRESNET:
-            return ModelRef(self._family, net._h.value, net.params.data_ptr(), aux.data_ptr() if aux is not None else None)
-        return ModelRef(self._family, net._h.value, net.params.data_ptr(), net.stats.data_ptr())
+        return self.net.model_ref(aux)
 
     def _call_ref(self) -> ModelRef:
         """The reference of a push / scan, after the weight rules: TC-ResNet refolds (or checks the frozen table's arena)."""
-        if self._family != FAMILY_TCRESNET:
+        if self.net.FAMILY != FAMILY_TCRESNET:
             return self._ref()
         if self._frozen is not None:
             self._check_frozen_arena()
         return self._ref(self._table())
 
     def _after_call(self) -> None:
-        if self._family == FAMILY_TCRESNET:
+        if self.net.FAMILY == FAMILY_TCRESNET:
             self.net._note_fold_reader()
 
     def _ragged_workspace(self, what: str, n: int) -> torch.Tensor:
@@ -358,7 +349,7 @@ class StreamingDetector(_Detection, PendingResets):
         `stats` were rebound to other tensors.  Prepare it again then.  Resets requested with `reset` are applied by the next call."""
         self._check_samples(samples_buffer)
         net = self.net
-        if self._family != FAMILY_TCRESNET:
+        if net.FAMILY != FAMILY_TCRESNET:
             ref = self._ref()
             keep = (samples_buffer, net.params, net.stats, ref)
             bound_ptrs = (net.params.data_ptr(), net.stats.data_ptr())
