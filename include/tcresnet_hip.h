@@ -1201,7 +1201,7 @@ const char* tcr_kernel_name(int index);
 enum { TCR_TUNE_CONV_PATH = 0,   /* 0 auto: implicit-GEMM MFMA conv where the shape fits, 1: scalar-fed VALU conv, 2: as 0 */
        TCR_TUNE_FRONTEND = 1,    /* 0 / 5: packed-FP32 kernel (default); 1..4: scalar-FP32 kernel, variant (v-1): bit0 wave-local phase ordering, bit1 sample prefetch */
        TCR_TUNE_CONV_B = 2,      /* MFMA conv activations: 0 straight from global/L1 (default), 1 via an LDS image; 3: wide 1x1 convs on the register-fed kernel instead of the LDS-tiled one, DS-CNN conv_1 not fused with the first depthwise layer */
-       TCR_TUNE_NET_FUSED = 3,   /* eval forward: 0 one fused LDS-resident kernel for the whole net (default; layers of the flagship shapes run compile-time-specialised), 1 per-layer kernels, 2 fused with the features copied to LDS, 3 fused, generic layer walk only, 4 the round-2 static-shape layer, 5 the static kernel with four 16-position tiles per job in block 0's layers instead of two (round 5 experiment: bitwise, no faster), 7 fused without the bank-aligned utterance strides (A/B arm); the static kernels' nine-tap layers (round 6): 0 work dealt in 16-position units, as even over the waves as units allow, + a whole tap of weight lookahead in the layers of <= 32 input channels (TCResNet14-1.5: <= 48) (default), 8 jobs of two tiles dealt round-robin (rounds 3-5), 9 units without the lookahead; TCResNet8-1.0's kernel, conv0_1 (block 0's nine-tap layer of 24 input channels): 0 a row tile's whole weight set resident in registers across a wave's run of units, requested in front of the phase's barrier (default at 49 frames), 10 the round-6 walk (default at 98 frames, where the resident form measured no faster), 11 the resident walk at either frame count (all bitwise) */
+       TCR_TUNE_NET_FUSED = 3,   /* eval forward: 0 one fused LDS-resident kernel for the whole net (default; layers of the flagship shapes run compile-time-specialised), 1 per-layer kernels, 2 fused with the features copied to LDS, 3 fused, generic layer walk only, 4 the round-2 static-shape layer, 5 the static kernel with four 16-position tiles per job in block 0's layers instead of two (round 5 experiment: bitwise, no faster), 7 fused without the bank-aligned utterance strides (A/B arm); the static kernels' nine-tap layers (round 6): 0 work dealt in 16-position units, as even over the waves as units allow, + a whole tap of weight lookahead in the layers of <= 32 input channels (TCResNet14-1.5: <= 48) (default), 8 jobs of two tiles dealt round-robin (rounds 3-5), 9 units without the lookahead; TCResNet8-1.0's kernel, conv0_1 (block 0's nine-tap layer of 24 input channels): 0 a row tile's whole weight set resident in registers across a wave's run of units, requested in front of the phase's barrier (default at 49 frames), 10 the round-6 walk (default at 98 frames, where the resident form measured no faster), 11 the resident walk at either frame count (all bitwise); groups of 8 utterances at 49 frames (12 classes, 8 waves): 0 the TIME-MAJOR plan (default) -- positions ordered 8 * frame + utterance, LDS rows [channel][frame + 4 + 4 halo frames][8 utterances] with a channel pitch of 16 (mod 32) floats where a stride-1 layer reads them and 8 (mod 32) where a stride-2 layer does (rows no convolution reads: no halo, no pad), so a 16-position tile is two frames of every utterance and the taps that would multiply only SAME-padding zeros for both frames are not issued (conv0_1's resident walk stays whole), jobs dealt by live-tap count; bitwise unless a weight is not finite (Inf * 0 no longer enters the edge outputs) --, 12 the utterance-major walk on those groups too (A/B arm; what every other group size, the 98-frame kernel and TCResNet14-1.5 run) */
        TCR_TUNE_FUSED_GROUP = 4, /* utterances per workgroup group of the fused kernel (0: largest that fits 64 KB of LDS) */
        TCR_TUNE_FUSED_WAVES = 5, /* fused kernel: waves per workgroup (4, 8, 16) + 100 * weight-ring depth (4, 8, 16); 0: default */
        TCR_TUNE_CONV_KSPLIT = 6, /* train-mode conv / data-gradient: waves sharing one 32-position group's reduction (0 auto, 1, 2, 4) */
@@ -1240,6 +1240,20 @@ int tcr_tune(int knob, int value);
  * layer of `nrt` row tiles (16 output channels) x `nt16` column tiles (16 positions).  out3 = {row tile, first column, end column}: the
  * wave's units are (row tile, c) for first <= c < end, all in ONE row tile.  0, or -1 on bad arguments (nw not a multiple of nrt). */
 int tcr_fused_deal_run(int nrt, int nt16, int nw, int wave, int* out3);
+
+/* Host-side view of the fused eval kernel's TIME-MAJOR plan (TCR_TUNE_NET_FUSED, arm 0 / 12), no launch.
+ * tcr_fused_tm_taps: the taps of a (k, stride, SAME padding pad_lo) layer over `tin` frames that read a real input frame for output
+ *   tile `tile` (frames 2 * tile, 2 * tile + 1): out2 = {first, last}; the other taps are skipped for that tile.  0, or -1.
+ * tcr_fused_tm_deal: the jobs of wave `wave` of `nw` in such a layer of `cin` -> `cout` channels, written to jobs[0 .. return value)
+ *   (cap >= 8) as  row tile | first column tile << 4 | two tiles << 10 | first tap << 11 | last tap << 15;  *mfma (may be NULL): matrix
+ *   instructions the layer issues per group of 8 utterances.  -1 on bad arguments or a layer the table does not hold.
+ * tcr_net_fused_plan: what tcr_net_forward_infer would launch for `batch` utterances under the current knobs: out = {time-major,
+ *   utterances per group, waves per workgroup, LDS bytes per workgroup, workgroups per CU, layers L, then per layer: floats per
+ *   utterance (time-major: per channel) of its output / input / shortcut rows, stride of the layer that reads its output (0: none)}.
+ *   Returns the ints written (6 + 4 L <= cap), 0 when the fused kernel does not take this net, -1 on bad arguments. */
+int tcr_fused_tm_taps(int k, int stride, int tin, int pad_lo, int tile, int* out2);
+int tcr_fused_tm_deal(int k, int stride, int cin, int cout, int tin, int pad_lo, int nw, int wave, unsigned* jobs, int cap, int* mfma);
+int tcr_net_fused_plan(const tcr_net* net, int batch, int* out, int cap);
 
 /* The library's internal streams (hipStream_t), one set per device and process.  HIP multiplexes streams onto a few hardware queues
  * and streams that share a queue serialise; the set is chosen on first use -- candidates are probed -- so that streams 0, 1, 2 and

@@ -97,6 +97,9 @@ _PROTOTYPES = {
     "tcr_kernel_name": (C.c_char_p, [C.c_int]),
     "tcr_tune": (C.c_int, [C.c_int, C.c_int]),
     "tcr_fused_deal_run": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "tcr_fused_tm_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "tcr_fused_tm_deal": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_uint), C.c_int, C.POINTER(C.c_int)]),
+    "tcr_net_fused_plan": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "tcr_internal_stream": (_P, [C.c_int, _P]),
     "tcr_frontend_resolve": (C.c_int, [C.POINTER(FrontendCfg)]),
     "tcr_frontend_plan_bytes": (C.c_size_t, [C.POINTER(FrontendCfg)]),

@@ -252,26 +252,43 @@ __device__ __forceinline__ void fused_layer_t(const FusedArgs& a, const FusedLay
 // AHEAD: 0 the rolled tap loop with two half-tap weight sets; 1 a whole tap of weight lookahead.  (Measured and removed, round 6: a ring
 // of three full-tap sets running on ACROSS the jobs of a wave -- two taps of lookahead, the next job's first two taps requested behind
 // this job's last two: 98.9 us against 95.3 for the one-tap form, 128 registers + 124 B of scratch.)
-template <int K, int S, int CIN, int COUT, int TIN, bool HAS_RES, int NTJ, bool WLDS, int AHEAD = 0>
+// TM (time-major plan, kernels.h): cc[nt] is the wave-uniform TILE index (frames 2 c, 2 c + 1 x the 8 utterance slots), `npos` the group's
+// utterance count, [jlo, jhi] the job's live taps (fused_tm_taps); OCS: who reads the output rows (0: no convolution -- rows without
+// halo; 1 / 2: a stride-1 / stride-2 layer).  A lane's offset inside a tile (its slot and frame half, q * pitch) is the same for every
+// tile: the position -> (utterance, frame) division is gone; lanes of an absent frame or utterance read a clamped address and store
+// into the pad.
+template <int K, int S, int CIN, int COUT, int TIN, bool HAS_RES, int NTJ, bool WLDS, int AHEAD = 0, bool TM = false, int OCS = 0>
 __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer& L, const float* __restrict__ xin, const int in_sz,
                                             float* yout, const float* res, const float* w, const int npos, const int m, const int (&cc)[NTJ],
-                                            const int r, const int q) {
+                                            const int r, const int q, const int jlo = 0, const int jhi = K - 1) {
     constexpr int TOUT = (TIN + S - 1) / S;
     constexpr int PADT = ((TOUT - 1) * S + K - TIN) > 0 ? ((TOUT - 1) * S + K - TIN) : 0;
     constexpr int PADLO = PADT / 2;
-    constexpr int TPI = TIN + 2 * kHalo, TPO = TOUT + 2 * kHalo;
+    // channel pitch of the input / output / shortcut rows and floats per tap: time-major rows are [frame + halo][8]
+    constexpr int TPI = TM ? fused_tm_pitch(TIN, true, S) : TIN + 2 * kHalo;
+    constexpr int TPO = TM ? fused_tm_pitch(TOUT, OCS != 0, OCS) : TOUT + 2 * kHalo;
+    constexpr int TPR = TM ? fused_tm_pitch(TOUT, false, 0) : TPO;
+    constexpr int JS = TM ? kTmGroup : 1;
     constexpr int C4 = CIN / 4;
     constexpr int WSTEP = 4 * COUT, XSTEP = 4 * TPI;
     const int out_sz = L.out_sz;
     const int res_sz = L.res_sz;
+    const int ja = TM ? jlo : 0, jb = TM ? jhi : K - 1;         // (the other walks: constants)
     int gg[NTJ], tt[NTJ];
     const float* xp[NTJ];
 #pragma unroll
     for (int nt = 0; nt < NTJ; ++nt) {
+        if constexpr (TM) {
+            const int half = (TOUT % 2 == 1 && cc[nt] == TOUT / 2) ? 0 : (r >> 3);
+            gg[nt] = half * 8 + min(r & 7, npos - 1);           // this lane's (clamped) place in the tile
+            tt[nt] = cc[nt] * 16;
+            xp[nt] = xin + q * TPI + (S == 1 ? gg[nt] : 2 * gg[nt] - (gg[nt] & 7)) + tt[nt] * S + kTmGroup * (kHalo - PADLO);
+        } else {
         const int p = min(cc[nt], npos - 1);
         gg[nt] = p / TOUT;
         tt[nt] = p - gg[nt] * TOUT;
         xp[nt] = xin + gg[nt] * in_sz + q * TPI + tt[nt] * S + kHalo - PADLO;
+        }
     }
     const float* wp = w + q * COUT + min(m * 16 + r, COUT - 1);
     // This lane's four output channels cob .. cob + 3: COUT % 4 == 0, so they are inside Cout or beyond it TOGETHER; a quad beyond it is
@@ -304,7 +321,7 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
         const unsigned wo = (unsigned)L.w_off * 4u;
         float w0[C4], w1[C4];
 #pragma unroll
-        for (int c4 = 0; c4 < C4; ++c4) w0[c4] = buf_load_f32(wr, wl, wo + (unsigned)(c4 * WSTEP) * 4u);
+        for (int c4 = 0; c4 < C4; ++c4) w0[c4] = buf_load_f32(wr, wl, wo + (unsigned)((ja * C4 + c4) * WSTEP) * 4u);
         auto tap = [&](const int j, const float (&wu)[C4], float (&wf)[C4], const bool fill) {
             TCR_WHATIF_PRIO(32768, 2);
             if (fill && !TCR_WHATIF(4096)) {
@@ -321,7 +338,7 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
 #pragma unroll
             for (int c4 = 0; c4 < C4; ++c4)
 #pragma unroll
-                for (int nt = 0; nt < NTJ; ++nt) b[nt][c4] = xp[nt][c4 * XSTEP + j];
+                for (int nt = 0; nt < NTJ; ++nt) b[nt][c4] = xp[nt][c4 * XSTEP + JS * j];
             }
             __builtin_amdgcn_sched_barrier(0);                  // (the requests stay in front of the tap's MFMAs)
             TCR_WHATIF_PRIO(16384, 2);
@@ -332,6 +349,21 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
                 for (int nt = 0; nt < NTJ; ++nt) acc[nt] = TCR_MFMA(wu[c4], b[nt][c4], acc[nt]);
             TCR_WHATIF_PRIO(16384, 0);
         };
+        if constexpr (TM) {
+            // the live taps only: 5 - 9 of them, an odd or an even count
+            int j = ja;
+#pragma unroll 1
+            for (; j + 2 <= jb; j += 2) {
+                tap(j, w0, w1, true);
+                tap(j + 1, w1, w0, true);
+            }
+            if (j == jb) {
+                tap(j, w0, w1, false);
+            } else {
+                tap(j, w0, w1, true);
+                tap(j + 1, w1, w0, false);
+            }
+        } else {
 #pragma unroll 1
         for (int j = 0; j + 2 < K; j += 2) {
             tap(j, w0, w1, true);
@@ -342,6 +374,7 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
         } else {
             tap(K - 2, w0, w1, true);
             tap(K - 1, w1, w0, false);
+        }
         }
     } else {
     // rolled taps, two half-tap weight sets refilled for the next tap (the round-2 loop).  Weights in global memory (`w` is
@@ -357,16 +390,16 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
     };
     float wa[H0 > 0 ? H0 : 1], wb[H1];
 #pragma unroll
-    for (int c4 = 0; c4 < H0; ++c4) wa[c4] = wld(c4);
+    for (int c4 = 0; c4 < H0; ++c4) wa[c4] = wld(ja * C4 + c4);
 #pragma unroll
-    for (int c4 = 0; c4 < H1; ++c4) wb[c4] = wld(H0 + c4);
+    for (int c4 = 0; c4 < H1; ++c4) wb[c4] = wld(ja * C4 + H0 + c4);
     // (throughput kernels: rolled taps -- 128-register budget; small-batch kernel: unrolled, the LDS operand and weight reads of the
     //  following taps move ahead of the MFMAs)
     constexpr int kTapUnroll = WLDS ? K : 1;
 #pragma unroll kTapUnroll
-    for (int j = 0; j < K; ++j) {
-        const int jn = TCR_WHATIF(2) ? 0 : min(j + 1, K - 1);
-        const int jx = TCR_WHATIF(4) ? 0 : j;
+    for (int j = ja; j <= jb; ++j) {
+        const int jn = TCR_WHATIF(2) ? 0 : min(j + 1, jb);
+        const int jx = TCR_WHATIF(4) ? 0 : JS * j;
         {
             float b[NTJ][H0 > 0 ? H0 : 1];
 #pragma unroll
@@ -405,16 +438,16 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
     if (HAS_RES) {
 #pragma unroll
         for (int nt = 0; nt < NTJ; ++nt) {
-            const int rb = gg[nt] * res_sz + cob * TPO + kHalo + tt[nt];       // (clamped position, clamped quad: inside the rows)
+            const int rb = TM ? cob * TPR + tt[nt] + gg[nt] : gg[nt] * res_sz + cob * TPO + kHalo + tt[nt];       // (clamped position, clamped quad: inside the rows)
 #pragma unroll
-            for (int reg = 0; reg < 4; ++reg) rv[nt][reg] = res[rb + reg * TPO];
+            for (int reg = 0; reg < 4; ++reg) rv[nt][reg] = res[rb + reg * TPR];
         }
     }
 #pragma unroll
     for (int nt = 0; nt < NTJ; ++nt) {
-        const bool ok = cc[nt] < npos && cv && !TCR_WHATIF(32);
+        const bool ok = (TM ? 2 * cc[nt] + (r >> 3) < TOUT && (r & 7) < npos : cc[nt] < npos) && cv && !TCR_WHATIF(32);
         const f32x4 ac = acc[nt];
-        float* po = yout + (ok ? gg[nt] * out_sz + kHalo + tt[nt] + cob * TPO : dump);
+        float* po = yout + (ok ? (TM ? tt[nt] + r + (OCS != 0 ? kTmGroup * kHalo : 0) : gg[nt] * out_sz + kHalo + tt[nt]) + cob * TPO : dump);
         const int pitch = ok ? TPO : 0;
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
@@ -462,6 +495,49 @@ __device__ __forceinline__ void fused_layer_s(const FusedArgs& a, const FusedLay
 #pragma unroll
         for (int nt = 0; nt < NTJ; ++nt) cc[nt] = (IL && NTJ > 1) ? cp * JP + 32 * (nt >> 1) + 2 * r + (nt & 1) : cp * JP + 16 * nt + r;
         fused_job_s<K, S, CIN, COUT, TIN, HAS_RES, NTJ, WLDS>(a, L, xin, in_sz, yout, res, w, npos, m, cc, r, q);
+    }
+}
+
+// Zero halos of time-major rows [COUT][(TOUT + 8) x 8 | pad to PITCH]: two contiguous runs of 32 floats per channel, 16 bytes per thread.
+template <int NT, int COUT, int TOUT, int PITCH>
+__device__ __forceinline__ void fused_zero_halo_tm(float* yout, const int tid_in) {
+    if (TCR_WHATIF(1024)) return;
+    const int tid = tid_in + opaque_zero();
+    for (int i = tid; i < COUT * 16; i += NT) {
+        float4* p = reinterpret_cast<float4*>(yout + (i >> 4) * PITCH + ((i & 8) ? kTmGroup * (kHalo + TOUT) : 0) + 4 * (i & 7));
+        *p = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// A layer of the time-major plan (kernels.h: fused_tm_pitch / fused_tm_taps / fused_tm_deal): groups of 8 utterances, positions ordered
+// p = 8 * frame + utterance, so a 16-position tile is two frames of every utterance and a tap whose input frame lies in the SAME-padding
+// halo for both frames is dead for the whole tile -- wave-uniformly, and known at compile time.  Such taps multiplied finite weights
+// with zeros into accumulators that start at +0; here their MFMAs, operand reads and weight fetches are not issued (fused_job_s walks the
+// job's live taps [lo, hi] in the same order: bitwise).  The waves' jobs come from the compile-time deal, read with scalar loads.
+template <int NW, int K, int S, int CIN, int COUT, int TIN, bool HAS_RES, int OCS, int AHEAD>
+__device__ __forceinline__ void fused_layer_tm(const FusedArgs& a, const FusedLayer& L, float* lds, const int ng, const int wave, const int r_in, const int q_in) {
+    constexpr int TOUT = (TIN + S - 1) / S;
+    constexpr int PADT = ((TOUT - 1) * S + K - TIN) > 0 ? ((TOUT - 1) * S + K - TIN) : 0;
+    static constexpr FusedTmDeal deal = fused_tm_deal(K, S, CIN, COUT, TIN, PADT / 2, NW);
+    static_assert(fused_tm_deal_fits(deal, NW), "a wave's jobs exceed the deal's table (kTmMaxJobs)");
+    float* yout = lds + a.buf_off[L.out_buf];
+    if constexpr (OCS != 0) fused_zero_halo_tm<NW * 64, COUT, TOUT, fused_tm_pitch(TOUT, true, OCS)>(yout, (int)threadIdx.x);
+    const int oz = opaque_zero();
+    const int r = r_in + oz, q = q_in + oz;
+    const float* xin = lds + a.buf_off[L.in_buf];
+    const float* res = L.res_buf >= 0 ? lds + a.buf_off[L.res_buf] : nullptr;
+    const float* w = a.params + L.w_off;
+    const int n = deal.n[wave];
+    for (int i = 0; i < n; ++i) {
+        const unsigned jw = deal.job[wave][i];
+        const int m = (int)(jw & 15u), c = (int)(jw >> 4 & 63u), lo = (int)(jw >> 11 & 15u), hi = (int)(jw >> 15 & 15u);
+        if (jw >> 10 & 1u) {
+            const int cc[2] = {c, c + 1};
+            fused_job_s<K, S, CIN, COUT, TIN, HAS_RES, 2, false, AHEAD, true, OCS>(a, L, xin, 0, yout, res, w, ng, m, cc, r, q, lo, hi);
+        } else {
+            const int cc[1] = {c};
+            fused_job_s<K, S, CIN, COUT, TIN, HAS_RES, 1, false, AHEAD, true, OCS>(a, L, xin, 0, yout, res, w, ng, m, cc, r, q, lo, hi);
+        }
     }
 }
 
@@ -534,7 +610,7 @@ __device__ __forceinline__ void fused_resident_request(const FusedArgs& a, const
     for (int i = 0; i < K * C4; ++i) ws[i] = buf_load_f32(wr, wl, (unsigned)(i * WSTEP) * 4u);      // i = tap * C4 + channel quad
 }
 
-template <int NW, int K, int S, int CIN, int COUT, int TIN, bool HAS_RES>
+template <int NW, int K, int S, int CIN, int COUT, int TIN, bool HAS_RES, bool TM = false, int OCS = 0>
 __device__ __forceinline__ void fused_layer_r(const FusedArgs& a, const FusedLayer& L, const float* __restrict__ xin, const int in_sz,
                                               float* lds, const int ng, const int wave, const int r_in, const int q_in,
                                               const float (&ws)[K * (CIN / 4)]) {
@@ -545,15 +621,19 @@ __device__ __forceinline__ void fused_layer_r(const FusedArgs& a, const FusedLay
     constexpr bool IL = S == 1;
     constexpr int PADT = ((TOUT - 1) * S + K - TIN) > 0 ? ((TOUT - 1) * S + K - TIN) : 0;
     constexpr int PADLO = PADT / 2;
-    constexpr int TPI = TIN + 2 * kHalo, TPO = TOUT + 2 * kHalo;
+    // (time-major plan: pitches per channel, 8 floats per tap, tiles of two frames -- as fused_job_s; the walk stays whole: see OPTLOG)
+    constexpr int TPI = TM ? fused_tm_pitch(TIN, true, S) : TIN + 2 * kHalo;
+    constexpr int TPO = TM ? fused_tm_pitch(TOUT, OCS != 0, OCS) : TOUT + 2 * kHalo;
+    constexpr int TPR = TM ? fused_tm_pitch(TOUT, false, 0) : TPO;
+    constexpr int JS = TM ? kTmGroup : 1;
     constexpr int C4 = CIN / 4, XSTEP = 4 * TPI;
     float* yout = lds + a.buf_off[L.out_buf];
     const float* res = L.res_buf >= 0 ? lds + a.buf_off[L.res_buf] : nullptr;
     const int out_sz = L.out_sz;
     const int res_sz = L.res_sz;
-    const int npos = ng * TOUT;
+    const int npos = TM ? kTmGroup * TOUT : ng * TOUT;
     const int full = npos >> 5, rem = npos & 31;
-    const int nt16 = IL ? 2 * full + (rem == 0 ? 0 : (rem <= 16 ? 1 : 2)) : (npos + 15) >> 4;          // (tiles and columns: as fused_layer_u)
+    const int nt16 = TM ? (TOUT + 1) / 2 : IL ? 2 * full + (rem == 0 ? 0 : (rem <= 16 ? 1 : 2)) : (npos + 15) >> 4;          // (tiles and columns: as fused_layer_u)
     const int il_end = (IL && rem > 0 && rem <= 16) ? 2 * full : nt16;
     const FusedRun run = fused_deal_run(NRT, nt16, NW, wave);
     const int m = run.m;
@@ -569,6 +649,11 @@ __device__ __forceinline__ void fused_layer_r(const FusedArgs& a, const FusedLay
     // this lane's position in column tile c -> (utterance of the group, frame); computed twice per unit, in front of the taps for the operand
     // address and again behind them for the stores, so that nothing but the address is live across the 9 x C4 MFMAs (the 128-register budget)
     auto place = [&](const int c, const int rr, int& g, int& t) {
+        if constexpr (TM) {         // g: this lane's (clamped) place in the tile, t: the tile's first float
+            g = ((TOUT % 2 == 1 && c == TOUT / 2) ? 0 : (rr >> 3)) * 8 + min(rr & 7, ng - 1);
+            t = 16 * c;
+            return 2 * c + (rr >> 3) < TOUT && (rr & 7) < ng;
+        }
         const int cc = (IL && c < il_end) ? (c >> 1) * 32 + 2 * rr + (c & 1) : (IL ? full * 32 + rr : c * 16 + rr);
         const int p = min(cc, npos - 1);
         g = p / TOUT;
@@ -578,9 +663,12 @@ __device__ __forceinline__ void fused_layer_r(const FusedArgs& a, const FusedLay
     for (int c = run.c0; c < run.c1; ++c) {
         int g, t;
         place(c, r, g, t);
-        const float* xp = xin + g * in_sz + q * TPI + t * S + kHalo - PADLO;
+        const float* xp = TM ? xin + q * TPI + (S == 1 ? g : 2 * g - (g & 7)) + t * S + kTmGroup * (kHalo - PADLO)
+                             : xin + g * in_sz + q * TPI + t * S + kHalo - PADLO;
         f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
         // LDS operands: one register per channel quad, refilled for the next tap as soon as its MFMA has issued (a tap = C4 MFMAs of lookahead)
+        // (time-major, measured and removed: the tile's dead taps skipped behind a wave-uniform test per tap of this unrolled walk --
+        //  74.5 - 75.3 us against 74.6 - 74.7 with the walk whole: the four edge tiles of 13 save 120 of 1404 MFMAs and pay nine scalar branches per unit)
         float b[C4];
 #pragma unroll
         for (int c4 = 0; c4 < C4; ++c4) b[c4] = xp[c4 * XSTEP];
@@ -589,7 +677,7 @@ __device__ __forceinline__ void fused_layer_r(const FusedArgs& a, const FusedLay
 #pragma unroll
             for (int c4 = 0; c4 < C4; ++c4) {
                 acc = TCR_MFMA(ws[j * C4 + c4], b[c4], acc);
-                if (j + 1 < K) b[c4] = xp[c4 * XSTEP + (TCR_WHATIF(4) ? 0 : j + 1)];
+                if (j + 1 < K) b[c4] = xp[c4 * XSTEP + (TCR_WHATIF(4) ? 0 : JS * (j + 1))];
             }
         }
         // ---- epilogue: folded BN (+ shortcut) (+ ReLU) -> LDS rows (as fused_job_s) ----
@@ -601,12 +689,12 @@ __device__ __forceinline__ void fused_layer_r(const FusedArgs& a, const FusedLay
         const int cob = min(m * 16 + qe * 4, COUT - 4);
         float rv[4];
         if (HAS_RES) {
-            const int rb = g * res_sz + cob * TPO + kHalo + t;
+            const int rb = TM ? cob * TPR + t + g : g * res_sz + cob * TPO + kHalo + t;
 #pragma unroll
-            for (int reg = 0; reg < 4; ++reg) rv[reg] = res[rb + reg * TPO];
+            for (int reg = 0; reg < 4; ++reg) rv[reg] = res[rb + reg * TPR];
         }
         const bool ok = pv && (COUT % 16 == 0 || m * 16 + qe * 4 < COUT) && !TCR_WHATIF(32);
-        float* po = yout + (ok ? g * out_sz + kHalo + t + cob * TPO : dump);
+        float* po = yout + (ok ? (TM ? t + re + (OCS != 0 ? kTmGroup * kHalo : 0) : g * out_sz + kHalo + t) + cob * TPO : dump);
         const int pitch = ok ? TPO : 0;
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
@@ -628,26 +716,33 @@ __device__ __forceinline__ void fused_layer_r(const FusedArgs& a, const FusedLay
 // ahead -- 90 operand registers, 128 + 200 B of scratch: 103.7 us against 95.4 -- and half a job ahead in two sets of 15 -- less scratch
 // than this form, 96.4 against 95.3: the phase reads the whole feature tensor, 37 MB at batch 4096, with every wave of the chip asking at
 // the same moment; it is not a per-job latency.)
-template <int NW, int T0, bool WLDS = false>
+// TM (time-major plan): the rows it writes are [channel][frame + halo][8].  1: the jobs stay 16 consecutive frames of an utterance -- a lane
+// row's global reads stay one 64-byte run per channel and tap, its LDS stores are 8 floats apart (4-way bank conflicts on four stores per
+// job); 2: a job is two frames of every utterance -- conflict-free stores, the reads of a lane row split over 8 utterances (see OPTLOG
+// for the measurement that chose).
+#ifndef TCR_TM_CONV0
+#define TCR_TM_CONV0 1
+#endif
+template <int NW, int T0, bool WLDS = false, int TM = 0>
 __device__ __forceinline__ void fused_conv0_s(const FusedArgs& a, const FusedLayer& L, const float* __restrict__ xin, const int in_sz,
                                               float* lds, const int ng, const int wave, const int r_in, const int q_in,
                                               const int w_lds = 0) {
     const int oz = opaque_zero();
     const int r = r_in + oz, q = q_in + oz;
     constexpr int K = 3, CIN = 40, COUT = 16, C4 = CIN / 4;
-    constexpr int TPI = T0 + 2 * kHalo, TPO = TPI, TOUT = T0, PADLO = 1;
+    constexpr int TPI = T0 + 2 * kHalo, TPO = TM ? fused_tm_pitch(T0, true, 2) : TPI, TOUT = T0, PADLO = 1;
     constexpr int WSTEP = 4 * COUT, XSTEP = 4 * TPI;
     float* yout = lds + a.buf_off[L.out_buf];
     const int out_sz = L.out_sz;
     const int npos = ng * TOUT;
-    const int nct = (npos + 15) / 16;
+    const int nct = TM == 2 ? (TOUT + 1) / 2 : (npos + 15) / 16;
     const float* w = WLDS ? lds + w_lds : a.params + L.w_off;
     const float* scale = a.ss + L.ss_off;
     const float* shift = scale + L.c_pad;
     for (int job = wave; job < nct; job += NW) {            // job = 16 positions x 16 channels (30 + 30 operand registers)
         const int p0 = min(job * 16 + r, npos - 1);
-        const int g0 = p0 / TOUT;
-        const int t0 = p0 - g0 * TOUT;
+        const int g0 = TM == 2 ? min(r & 7, ng - 1) : p0 / TOUT;
+        const int t0 = TM == 2 ? min(2 * job + (r >> 3), TOUT - 1) : p0 - g0 * TOUT;
         const float* wp = w + q * COUT + r;
         const float* x0 = xin + g0 * in_sz + q * TPI + t0 + kHalo - PADLO;
         float b0[C4][K], wf[K][C4];
@@ -674,8 +769,8 @@ __device__ __forceinline__ void fused_conv0_s(const FusedArgs& a, const FusedLay
         TCR_WHATIF_PRIO(16384, 0);
         const int dump = a.buf_off[2] + a.group * a.buf_sz[2] + (q * 16 + r) - a.buf_off[L.out_buf];
         const float lo = L.relu ? 0.f : -3.4e38f;
-        const bool pv = job * 16 + r < npos;
-        const int base = g0 * out_sz + kHalo + t0;
+        const bool pv = TM == 2 ? 2 * job + (r >> 3) < TOUT && (r & 7) < ng : job * 16 + r < npos;
+        const int base = TM ? (kHalo + t0) * kTmGroup + g0 : g0 * out_sz + kHalo + t0;
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const float v = fmaxf(fmaf(acc0[reg], sc[reg], sh[reg]), lo);
@@ -688,10 +783,12 @@ __device__ __forceinline__ void fused_conv0_s(const FusedArgs& a, const FusedLay
 // arrangement of head.hip: bitwise the fmaf chain of `fused_head`), the softmax in registers with the class sum carried through the
 // three 16-lane rows in class order (bitwise the sequential sum of `fused_head`), and the stores.  `fused_head` -- runtime shapes,
 // 48 dependent global weight loads per dot product in batches of 8, twelve expf per thread -- cost 20 us of the kernel's 125.
-template <int NT, int FC, int FT, int NCLS>
+// TM (time-major plan): the block output's rows are [channel][frame][8], no halo -- a frame's 8 utterances are neighbours, pooled with stride 8.
+template <int NT, int FC, int FT, int NCLS, bool TM = false>
 __device__ __forceinline__ void fused_head_s(const FusedArgs& a, float* lds, const int n0, const int ng, const int tid) {
     static_assert(FC % 4 == 0 && NCLS + 2 <= 16, "one 16-row MFMA tile holds the logits and the two range outputs");
-    constexpr int TP = FT + 2 * kHalo;
+    constexpr int TP = TM ? fused_tm_pitch(FT, false, 0) : FT + 2 * kHalo;
+    constexpr int TS = TM ? kTmGroup : 1;
     const float* fb = lds + a.buf_off[a.feat_buf];
     const int fsz = a.feat_sz;
     float* pooled = lds + a.buf_off[(a.feat_buf + 1) % 3];
@@ -711,12 +808,15 @@ __device__ __forceinline__ void fused_head_s(const FusedArgs& a, float* lds, con
             af[s] = rz < NCLS + 2 ? v : 0.f;
         }
     }
-    for (int i = tid; i < ng * FC; i += NT) {
-        const int g = i / FC, c = i - g * FC;
-        const float* row = fb + g * fsz + c * TP + kHalo;
+    for (int i0 = tid; i0 < (TM ? kTmGroup : ng) * FC; i0 += NT) {
+        // (time-major: a thread per (channel, slot), slots fastest -- 32 lanes read 4 channels x 8 neighbouring floats: no bank conflict)
+        const int g = TM ? (i0 & 7) : i0 / FC, c = TM ? (i0 >> 3) : i0 - g * FC;
+        if (TM && g >= ng) continue;
+        const int i = g * FC + c;
+        const float* row = TM ? fb + c * TP + g : fb + g * fsz + c * TP + kHalo;
         float v[FT];
 #pragma unroll
-        for (int t = 0; t < FT; ++t) v[t] = row[t];
+        for (int t = 0; t < FT; ++t) v[t] = row[TS * t];
         float s = 0.f;
 #pragma unroll
         for (int t = 0; t < FT; ++t) s += v[t];
@@ -862,7 +962,9 @@ __device__ __forceinline__ void fused_layer_sel(const FusedArgs& a, const FusedL
     }
 }
 
-template <int NW, int T0, int WD, int NTJ0 = 2>
+// TM: the time-major plan (fused_layer_tm; the host lays the buffers out by the same fused_tm_pitch): groups of 8 at 49 frames, the default
+// there; TCR_TUNE_NET_FUSED = 12 keeps the utterance-major walk.
+template <int NW, int T0, int WD, int NTJ0 = 2, bool TM = false>
 __global__ __launch_bounds__(NW * 64) TCR_WAVES_PER_SIMD_4 void net_fused_tc8_kernel(const FusedArgs a) {
     constexpr int NT = NW * 64;
     constexpr int T1 = (T0 + 1) / 2, T2 = (T1 + 1) / 2;
@@ -889,12 +991,16 @@ __global__ __launch_bounds__(NW * 64) TCR_WAVES_PER_SIMD_4 void net_fused_tc8_ke
     // (NTJ0 = 6: conv0_1 -- block 0's nine-tap layer of 24 input channels -- in its resident-weight form, fused_layer_r; every other layer as NTJ0 = 3)
     constexpr bool RES = WD >= 0 && NTJ0 == 6;
     constexpr int NTJU = RES ? 3 : NTJ0;
+    // (who reads layer LI's output rows: nobody convolves a shortcut conv's or the last layer's; a block's first conv feeds its stride-1 second, which feeds the next block's stride-2 layers)
+#define TCR_TC8_OCS(LI, K_, S_) ((K_ == 1 || LI == 9) ? 0 : (S_ == 2 ? 1 : 2))
 #define TCR_TC8(LI, K_, S_, CI_, CO_, T_) do { const FusedLayer& L_ = TCR_LAYER_ROW(WD >= 0, LI); \
-        fused_layer_sel<NW, K_, S_, CI_, CO_, T_, WD, (LI == 3 || LI == 6 || LI == 9), (K_ != 1 && LI != 9), ((LI >= 1 && LI <= 3 && NTJU == 4) ? 4 : (((NTJU == 0 || NTJU == 3) && K_ == 9) ? NTJU : 2))>(a, L_, lds + a.buf_off[L_.in_buf], L_.in_sz, lds, ng, wave, r, q); } while (0)
+        if constexpr (TM) fused_layer_tm<NW, K_, S_, CI_, CO_, T_, (LI == 3 || LI == 6 || LI == 9), TCR_TC8_OCS(LI, K_, S_), ((K_ == 9 && CI_ <= 32) ? 1 : 0)>(a, L_, lds, ng, wave, r, q); \
+        else fused_layer_sel<NW, K_, S_, CI_, CO_, T_, WD, (LI == 3 || LI == 6 || LI == 9), (K_ != 1 && LI != 9), ((LI >= 1 && LI <= 3 && NTJU == 4) ? 4 : (((NTJU == 0 || NTJU == 3) && K_ == 9) ? NTJU : 2))>(a, L_, lds + a.buf_off[L_.in_buf], L_.in_sz, lds, ng, wave, r, q); } while (0)
     // (resident form of layer LI: halo zeros of its output rows, then the walk out of the set WS_ requested in front of the barrier)
 #define TCR_TC8_R(LI, S_, CI_, T_, WS_) do { const FusedLayer& L_ = TCR_LAYER_ROW(true, LI); \
-        fused_zero_halo<NT, 24, (T_ + S_ - 1) / S_>(lds + a.buf_off[L_.out_buf], L_.out_sz, ng, tid); \
-        fused_layer_r<NW, 9, S_, CI_, 24, T_, (LI == 3)>(a, L_, lds + a.buf_off[L_.in_buf], L_.in_sz, lds, ng, wave, r, q, WS_); } while (0)
+        if constexpr (TM) fused_zero_halo_tm<NT, 24, (T_ + S_ - 1) / S_, fused_tm_pitch((T_ + S_ - 1) / S_, true, TCR_TC8_OCS(LI, 9, S_))>(lds + a.buf_off[L_.out_buf], tid); \
+        else fused_zero_halo<NT, 24, (T_ + S_ - 1) / S_>(lds + a.buf_off[L_.out_buf], L_.out_sz, ng, tid); \
+        fused_layer_r<NW, 9, S_, CI_, 24, T_, (LI == 3), TM, TCR_TC8_OCS(LI, 9, S_)>(a, L_, lds + a.buf_off[L_.in_buf], L_.in_sz, lds, ng, wave, r, q, WS_); } while (0)
     for (int grp = blockIdx.x; grp < (TCR_WHATIF(512) ? 0 : a.n_groups); grp += gridDim.x) {
         const int n0 = grp * a.group;
         const int ng = min(a.group, a.batch - n0);
@@ -905,8 +1011,13 @@ __global__ __launch_bounds__(NW * 64) TCR_WAVES_PER_SIMD_4 void net_fused_tc8_ke
         if constexpr (WD < 0) fused_layer_sel<NW, 3, 1, 40, 16, T0, WD, false>(a, a.layer[0], a.feat + (size_t)n0 * row, row, lds, ng, wave, r, q);
         else if (!TCR_WHATIF(64)) {
             const FusedLayer& L0 = TCR_LAYER_ROW(true, 0);
+            if constexpr (TM) {
+                fused_zero_halo_tm<NT, 16, T0, fused_tm_pitch(T0, true, 2)>(lds + a.buf_off[L0.out_buf], tid);
+                fused_conv0_s<NW, T0, false, TCR_TM_CONV0>(a, L0, a.feat + (size_t)n0 * row, row, lds, ng, wave, r, q);
+            } else {
             fused_zero_halo<NT, 16, T0>(lds + a.buf_off[L0.out_buf], L0.out_sz, ng, tid);
             fused_conv0_s<NW, T0>(a, L0, a.feat + (size_t)n0 * row, row, lds, ng, wave, r, q);
+            }
         }
         if constexpr (RES) {
             float ws3[9 * 6];
@@ -937,7 +1048,7 @@ __global__ __launch_bounds__(NW * 64) TCR_WAVES_PER_SIMD_4 void net_fused_tc8_ke
         TCR_TC8_BARRIER;
         if constexpr (WD < 0) fused_head<NT>(a, lds, n0, ng, tid);
         else if (!TCR_WHATIF(16)) {
-            if (a.nc == 12) fused_head_s<NT, 48, (T2 + 1) / 2, 12>(a, lds, n0, ng, tid);
+            if (a.nc == 12 || TM) fused_head_s<NT, 48, (T2 + 1) / 2, 12, TM>(a, lds, n0, ng, tid);      // (time-major: launched for 12 classes only)
             else fused_head<NT>(a, lds, n0, ng, tid);
         }
 #if TCR_FUSED_WHATIF & 2048
@@ -948,6 +1059,7 @@ __global__ __launch_bounds__(NW * 64) TCR_WAVES_PER_SIMD_4 void net_fused_tc8_ke
 #endif
     }
 #undef TCR_TC8
+#undef TCR_TC8_OCS
 #undef TCR_TC8_R
 #undef TCR_TC8_BARRIER
 }
@@ -1120,6 +1232,24 @@ static int fused_tc14w_frames(const FusedArgs& a) {
         if (i == 2 || i == 7 || i == 12) t = (t + 1) / 2;
     }
     return t0;
+}
+
+static int fused_tc8_frames(const FusedArgs& a);
+// The time-major plan has ONE kernel instance: TCResNet8-1.0 at 49 frames and 12 classes, groups of 8, 8 waves, the default arm.
+bool fused_tmajor_applies(const FusedArgs& a, const int waves) {
+    return tune_get(TCR_TUNE_NET_FUSED) == 0 && a.group == kTmGroup && waves == 8 && a.nc == 12 && fused_tc8_frames(a) == 49;
+}
+// the kernel derives every pitch at compile time from the layer shapes; the host derived them from the plan's actual readers
+static bool fused_tmajor_pitches_agree(const FusedArgs& a) {
+    for (int i = 0; i < a.n_layers; ++i) {
+        const FusedLayer& L = a.layer[i];
+        const int ocs = (L.k == 1 || i == a.n_layers - 1) ? 0 : (L.stride == 2 ? 1 : 2);
+        if (L.out_sz != fused_tm_pitch(L.tout, ocs != 0, ocs)) return false;
+        if (i > 0 && L.in_sz != fused_tm_pitch(L.tin, true, L.stride)) return false;
+        if (L.res_buf >= 0 && L.res_sz != fused_tm_pitch(L.tout, false, 0)) return false;
+        if (L.pad_lo != (L.k == 9 ? 4 : L.k == 3 ? 1 : 0)) return false;
+    }
+    return a.feat_sz == fused_tm_pitch(a.feat_t, false, 0);
 }
 
 // 49 / 98 when the plan is exactly TCResNet8-1.0 on 40 coefficients read from global memory, else 0
@@ -1372,6 +1502,11 @@ int launch_net_fused(const FusedArgs& a, size_t lds_bytes, int grid, int waves, 
 #define TCR_FS(NW_, T_) if (tc8 == T_ && waves == NW_) kern = r2 ? net_fused_tc8_kernel<NW_, T_, -1> : (j4 ? net_fused_tc8_kernel<NW_, T_, 0, 4> : (ju ? net_fused_tc8_kernel<NW_, T_, 0, 0> : (j2 ? net_fused_tc8_kernel<NW_, T_, 0, 2> : ((jr || (T_ == 49 && !jl)) ? net_fused_tc8_kernel<NW_, T_, 0, 6> : net_fused_tc8_kernel<NW_, T_, 0, 3>))));
     TCR_FS(4, 49) TCR_FS(8, 49) TCR_FS(16, 49) TCR_FS(4, 98) TCR_FS(8, 98) TCR_FS(16, 98)
 #undef TCR_FS
+    if (a.tmajor) {
+        // the host laid the buffers out time-major (fused_tmajor_applies held): the one instance built for it, or an error -- never the other walk on these rows
+        if (!fused_tmajor_applies(a, waves) || !fused_tmajor_pitches_agree(a)) { set_error("fused kernel: time-major plan without its kernel instance"); return TCR_ERR_ARG; }
+        kern = net_fused_tc8_kernel<8, 49, 0, 6, true>;
+    }
     const int tc14 = (kern || tune_get(TCR_TUNE_NET_FUSED) == 3 || tune_get(TCR_TUNE_NET_FUSED) == 4) ? 0 : fused_tc14w_frames(a);
 #define TCR_F14(NW_, T_) if (tc14 == T_ && waves == NW_) kern = ju ? net_fused_tc14w_kernel<NW_, T_, 0> : (j2 ? net_fused_tc14w_kernel<NW_, T_, 2> : net_fused_tc14w_kernel<NW_, T_, 13>);
     TCR_F14(8, 49) TCR_F14(16, 49) TCR_F14(8, 98) TCR_F14(16, 98)
@@ -1392,6 +1527,30 @@ int launch_net_fused(const FusedArgs& a, size_t lds_bytes, int grid, int waves, 
 }
 
 }  // namespace tcr
+
+extern "C" int tcr_fused_tm_taps(int k, int stride, int tin, int pad_lo, int tile, int* out2) {
+    if (!out2 || k < 1 || stride < 1 || tin < 1 || pad_lo < 0 || tile < 0 || 2 * tile >= (tin + stride - 1) / stride) {
+        tcr::set_error("tcr_fused_tm_taps: bad arguments (k %d, stride %d, %d frames, tile %d)", k, stride, tin, tile);
+        return TCR_ERR_ARG;
+    }
+    const tcr::FusedTaps t = tcr::fused_tm_taps(k, stride, tin, pad_lo, tile);
+    out2[0] = t.lo; out2[1] = t.hi;
+    return TCR_OK;
+}
+
+extern "C" int tcr_fused_tm_deal(int k, int stride, int cin, int cout, int tin, int pad_lo, int nw, int wave, unsigned* jobs, int cap, int* mfma) {
+    if (!jobs || k < 1 || stride < 1 || cin < 4 || cout < 1 || cout > 256 || tin < 1 || tin > 126 || (nw != 4 && nw != 8 && nw != 16) || wave < 0 || wave >= nw || cap < tcr::kTmMaxJobs) {
+        tcr::set_error("tcr_fused_tm_deal: bad arguments");
+        return TCR_ERR_ARG;
+    }
+    const int tout = (tin + stride - 1) / stride;
+    if (((cout + 15) / 16) * ((tout + 1) / 2) > nw * tcr::kTmMaxJobs) { tcr::set_error("tcr_fused_tm_deal: more jobs than the table holds"); return TCR_ERR_ARG; }
+    const tcr::FusedTmDeal d = tcr::fused_tm_deal(k, stride, cin, cout, tin, pad_lo, nw);
+    if (d.n[wave] > tcr::kTmMaxJobs) { tcr::set_error("tcr_fused_tm_deal: more jobs than the table holds"); return TCR_ERR_ARG; }
+    for (int i = 0; i < d.n[wave]; ++i) jobs[i] = d.job[wave][i];
+    if (mfma) *mfma = d.mfma;
+    return d.n[wave];
+}
 
 extern "C" int tcr_fused_deal_run(int nrt, int nt16, int nw, int wave, int* out3) {
     if (!out3 || nrt < 1 || nt16 < 0 || nw < nrt || nw % nrt != 0 || wave < 0 || wave >= nw) {

@@ -179,6 +179,7 @@ struct FusedLayer {
     int no_barrier;                     // the next layer reads the same input and writes another buffer: no s_barrier in between
     // floats per utterance of this layer's input / output / shortcut rows (<= buf_sz of the buffer): the host pads the stride of a
     // layer's output so that the 32 lanes of one LDS read of its consumer fall into 32 distinct banks (net.cpp: fused_strides)
+    // (time-major plan, FusedArgs::tmajor: floats per CHANNEL of those rows -- fused_tm_pitch)
     int in_sz, out_sz, res_sz;
 };
 
@@ -198,8 +199,84 @@ struct FusedArgs {
     int feat_sz;                // floats per utterance of the last block output
     int fc_off, fc2_off;
     int in_global;              // the first layer reads the feature rows straight from global memory (no LDS copy)
+    int tmajor;                 // time-major plan (groups of 8, TCResNet8-1.0 at 49 frames): rows are [channel][frame (+ halo)][8 utterances]
     FusedLayer layer[kFusedMaxLayers];
 };
+
+// ---- time-major plan of the static TCResNet8 kernel (fused.hip: fused_layer_tm), shared by the host's layout and the kernel ----
+// Positions of a group of 8 are ordered p = 8 * frame + utterance, so a 16-position tile is 2 frames x 8 utterances and a row of a
+// buffer is [frame + halo][8].  Floats per channel of a row of `t` frames: one ds_read_b32 of a consumer serves lanes (q, q + 1) x 16
+// positions against 32 banks -- a stride-1 consumer (cs = 1) reads 16 consecutive floats per channel, so the next channel starts
+// 16 banks on; a stride-2 consumer (cs = 2) reads banks {0-7, 16-23}, so the next channel starts 8 banks on; cs = 0: rows that no
+// convolution reads (shortcut outputs, the pooled block output) carry neither halo nor pad.
+constexpr int kTmGroup = 8;
+__host__ __device__ constexpr int fused_tm_pitch(const int t, const bool halo, const int cs) {
+    int n = (t + (halo ? 2 * TCR_HALO : 0)) * kTmGroup;
+    if (cs == 1) while (n % 32 != 16) n += 8;
+    if (cs == 2) while (n % 32 != 8) n += 8;
+    return n;
+}
+// Taps of a (k, stride, SAME padding pad_lo) layer over `tin` frames that read at least one real input frame for output tile `tile`
+// (frames 2 * tile and 2 * tile + 1; the absent second frame of an odd last tile counts for nothing): [lo, hi].  Every other tap
+// multiplies halo zeros for the whole tile and is skipped.
+struct FusedTaps { int lo, hi; };
+__host__ __device__ constexpr FusedTaps fused_tm_taps(const int k, const int stride, const int tin, const int pad_lo, const int tile) {
+    const int tout = (tin + stride - 1) / stride;
+    const int a = 2 * tile, b = a + 1 < tout ? a + 1 : tout - 1;
+    const int lo = pad_lo - b * stride, hi = tin - 1 + pad_lo - a * stride;
+    return FusedTaps{lo > 0 ? lo : 0, hi < k - 1 ? hi : k - 1};
+}
+// Deal of a time-major layer's work over the waves.  Jobs: per row tile (16 output channels), neighbouring column tiles with the SAME
+// live taps go in pairs (one weight fragment feeds both), the rest -- the edge tiles, whose tap ranges all differ -- alone, so that
+// every dead tap is skipped.  A wave's time per tap is nearly the same for one tile as for two (the tap waits for its weight
+// fragments, requested one tap ahead, and a lone accumulator is a dependent MFMA chain), so a job costs kTmTapCost per tap of a pair,
+// kTmLoneCost per tap alone, + kTmJobCost for its prologue and stores; jobs go longest first to the SIMD with the least work so far
+// (a SIMD hosts waves w, w + 4, ...) and there to its wave with the least.  word = m | c << 4 | pair << 10 | lo << 11 | hi << 15.
+// (Measured and removed: pairs of unlike tiles walking the UNION of their live taps -- fewer, longer jobs, 520 instead of 784 MFMAs
+//  dropped per group: 75.9 - 76.0 us against 74.9 - 75.0 in one process, OPTLOG "time-major".)
+constexpr int kTmMaxJobs = 8, kTmTapCost = 8, kTmLoneCost = 7, kTmJobCost = 8;
+struct FusedTmDeal {
+    int n[16];
+    unsigned job[16][kTmMaxJobs];
+    int mfma;           // MFMAs of the layer per group (what SQ_INSTS_MFMA counts)
+};
+__host__ __device__ constexpr FusedTmDeal fused_tm_deal(const int k, const int stride, const int cin, const int cout, const int tin, const int pad_lo, const int nw) {
+    FusedTmDeal d{};
+    const int tout = (tin + stride - 1) / stride, nt16 = (tout + 1) / 2, nrt = (cout + 15) / 16;
+    unsigned words[256] = {};
+    int cost[256] = {};
+    int nj = 0;
+    for (int m = 0; m < nrt; ++m)
+        for (int c = 0; c < nt16;) {
+            const FusedTaps t = fused_tm_taps(k, stride, tin, pad_lo, c);
+            bool pair = false;
+            if (c + 1 < nt16) {
+                const FusedTaps u = fused_tm_taps(k, stride, tin, pad_lo, c + 1);
+                pair = u.lo == t.lo && u.hi == t.hi;
+            }
+            words[nj] = (unsigned)m | (unsigned)c << 4 | (pair ? 1u : 0u) << 10 | (unsigned)t.lo << 11 | (unsigned)t.hi << 15;
+            cost[nj] = (t.hi - t.lo + 1) * (pair ? kTmTapCost : kTmLoneCost) + kTmJobCost;
+            d.mfma += (t.hi - t.lo + 1) * (pair ? 2 : 1) * (cin / 4);
+            ++nj;
+            c += pair ? 2 : 1;
+        }
+    int wload[16] = {}, sload[4] = {};
+    bool used[256] = {};
+    for (int it = 0; it < nj; ++it) {
+        int best = -1;
+        for (int i = 0; i < nj; ++i) if (!used[i] && (best < 0 || cost[i] > cost[best])) best = i;
+        used[best] = true;
+        int s = 0;
+        for (int i = 1; i < 4 && i < nw; ++i) if (sload[i] < sload[s]) s = i;
+        int w = s;
+        for (int i = s + 4; i < nw; i += 4) if (wload[i] < wload[w]) w = i;
+        if (d.n[w] < kTmMaxJobs) d.job[w][d.n[w]] = words[best];
+        ++d.n[w];                               // (> kTmMaxJobs: the table is too small -- fused_layer_tm asserts, tcr_fused_tm_deal refuses)
+        wload[w] += cost[best];
+        sload[s] += cost[best];
+    }
+    return d;
+}
 
 // Deal of a layer's units (16 output channels x 16 positions; row tile m, column c, u = m * nt16 + c) for the resident-weight walk
 // (fused_layer_r): a wave keeps ONE row tile's weight fragments in registers, so its run [c0, c1) lies inside one row tile m.  The nw
@@ -215,9 +292,16 @@ __host__ __device__ inline FusedRun fused_deal_run(const int nrt, const int nt16
     return FusedRun{m, c0, c0 + per + (rank < extra ? 1 : 0)};
 }
 
+__host__ __device__ constexpr bool fused_tm_deal_fits(const FusedTmDeal& d, const int nw) {
+    for (int w = 0; w < nw; ++w) if (d.n[w] > kTmMaxJobs) return false;
+    return true;
+}
+
 constexpr int kSmallBatchMax = 64;      // batches up to this many utterances take the small-batch (latency) kernel where it exists
 // returns 1 when the launch could not be configured (caller falls back to the per-layer kernels)
 int launch_net_fused(const FusedArgs& a, size_t lds_bytes, int grid, int waves, int ring, hipStream_t s);
+// the plan (layers, group, classes; before any layout) has a time-major kernel instance at `waves` waves and the knobs select it
+bool fused_tmajor_applies(const FusedArgs& a, int waves);
 
 // ---- train_fused.hip : group-resident phases of the train-mode forward ---------------------------
 constexpr int kPhaseMaxRows = 1024;     // partial rows (= workgroups) a phase may write per BN layer

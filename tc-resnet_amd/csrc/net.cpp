@@ -371,8 +371,9 @@ static int conv_forward_with_down(const ConvLayer& la, const ConvLayer& ld, cons
 
 // Whole-network fused launch (fused.hip): three rotating LDS buffers per utterance,
 //   R0: features, later the `down` outputs;  R1: conv0 / block outputs;  R2: conv_a outputs.
+// plan != nullptr: nothing is launched; the plan is described there (tcr_net_fused_plan) and *plan_n set to the ints written.
 static int forward_infer_fused(const tcr_net& net, const float* params, const float* ss, const float* feat, int batch,
-                               float* logits, float* probs, float* ranges, hipStream_t s) {
+                               float* logits, float* probs, float* ranges, hipStream_t s, int* plan = nullptr, int plan_cap = 0, int* plan_n = nullptr) {
     FusedArgs a;
     std::memset(&a, 0, sizeof(a));
     if ((int)net.units.size() > kFusedMaxLayers) return 1;
@@ -443,7 +444,44 @@ static int forward_infer_fused(const tcr_net& net, const float* params, const fl
     if (group > 16) group = 16;
     if (group > batch) group = batch;
     if (group < 1) group = 1;
-    const size_t lds = lds_of(group);
+    a.in_c = net.cfg.in_channels; a.in_tp = tcr_padded_len(net.cfg.t_in);
+    a.in_global = in_global ? 1 : 0;
+    a.feat_buf = 1; a.feat_c = net.feat_c; a.feat_t = net.feat_t; a.nc = net.cfg.num_classes;
+    a.fc_off = (int)net.layers[net.fc].w_off; a.fc2_off = (int)net.layers[net.fc2].w_off;
+    // Time-major plan (fused.hip: fused_layer_tm) where its kernel instance exists -- groups of 8, TCResNet8-1.0 at 49 frames: every row is
+    // [channel][frame (+ 4 + 4 halo frames)][8 utterance slots], its channel pitch chosen by who reads it (kernels.h: fused_tm_pitch; rows
+    // that no convolution reads -- shortcut outputs, the pooled block output -- carry neither halo nor pad, which is what lets two
+    // workgroups share a CU).  A forced group of 8 stays 8 slots wide below 8 utterances (the empty slots are dummy lanes).
+    const int knob_w = tune_get(TCR_TUNE_FUSED_WAVES);
+    a.group = kTmGroup;
+    if ((group == kTmGroup || tune_get(TCR_TUNE_FUSED_GROUP) == kTmGroup) && (knob_w % 100 == 0 || knob_w % 100 == 8) && fused_tmajor_applies(a, 8)) {
+        int tsz[3] = {0, 0, 0};
+        FusedArgs t = a;
+        for (int i = 0; i < t.n_layers; ++i) {
+            FusedLayer& P = t.layer[i];
+            int cs = 0;
+            for (int j = i + 1; j < t.n_layers; ++j) {
+                if (t.layer[j].in_buf == P.out_buf && cs == 0) cs = t.layer[j].stride;
+                if (t.layer[j].out_buf == P.out_buf) break;
+            }
+            P.out_sz = fused_tm_pitch(P.tout, cs != 0, cs);
+            if (P.cout * P.out_sz > tsz[P.out_buf]) tsz[P.out_buf] = P.cout * P.out_sz;
+        }
+        for (int i = 0; i < t.n_layers; ++i) {
+            FusedLayer& C = t.layer[i];
+            for (int j = i - 1; j >= 0; --j) if (t.layer[j].out_buf == C.in_buf) { C.in_sz = t.layer[j].out_sz; break; }
+            if (C.res_buf >= 0) for (int j = i - 1; j >= 0; --j) if (t.layer[j].out_buf == C.res_buf) { C.res_sz = t.layer[j].out_sz; break; }
+        }
+        t.feat_sz = t.layer[t.n_layers - 1].out_sz;
+        const size_t tlds = ((size_t)tsz[0] + tsz[1] + tsz[2] + 64) * sizeof(float);
+        if (2 * tlds <= 160 * 1024 && kTmGroup * (net.feat_c + net.cfg.num_classes + 2) <= tsz[2]) {
+            a = t;
+            a.tmajor = 1;
+            group = kTmGroup;
+            for (int b = 0; b < 3; ++b) sz[b] = tsz[b] / kTmGroup;      // (pitches are multiples of 8)
+        }
+    }
+    const size_t lds = a.tmajor ? ((size_t)group * (sz[0] + sz[1] + sz[2]) + 64) * sizeof(float) : lds_of(group);
     if (lds > 160 * 1024) return 1;
     // the head scratch (pooled + logits) lives in a buffer other than the feature buffer
     if ((int64_t)group * (net.feat_c + net.cfg.num_classes + 2) > (int64_t)group * sz[2] && (int64_t)group * (net.feat_c + net.cfg.num_classes + 2) > (int64_t)group * sz[0]) return 1;
@@ -451,10 +489,6 @@ static int forward_infer_fused(const tcr_net& net, const float* params, const fl
     a.batch = batch; a.group = group; a.n_groups = ceil_div(batch, group);
     a.buf_off[0] = 0; a.buf_off[1] = group * sz[0]; a.buf_off[2] = group * (sz[0] + sz[1]);
     a.buf_sz[0] = sz[0]; a.buf_sz[1] = sz[1]; a.buf_sz[2] = sz[2];
-    a.in_c = net.cfg.in_channels; a.in_tp = tcr_padded_len(net.cfg.t_in);
-    a.in_global = in_global ? 1 : 0;
-    a.feat_buf = 1; a.feat_c = net.feat_c; a.feat_t = net.feat_t; a.nc = net.cfg.num_classes;
-    a.fc_off = (int)net.layers[net.fc].w_off; a.fc2_off = (int)net.layers[net.fc2].w_off;
     int per_cu = (int)((160 * 1024) / lds);
     if (per_cu > 4) per_cu = 4;
     if (per_cu < 1) per_cu = 1;
@@ -462,8 +496,23 @@ static int forward_infer_fused(const tcr_net& net, const float* params, const fl
     if (grid > a.n_groups) grid = a.n_groups;
     if (tune_get(TCR_TUNE_FUSED_GRID) > 0 && grid > tune_get(TCR_TUNE_FUSED_GRID)) grid = tune_get(TCR_TUNE_FUSED_GRID);
     // knob: waves + 100 * ring (0: default)
-    const int knob = tune_get(TCR_TUNE_FUSED_WAVES);
+    const int knob = knob_w;
     const int waves = knob % 100 ? knob % 100 : (per_cu >= 4 ? 4 : (per_cu >= 2 ? 8 : 16)), ring = knob / 100 ? knob / 100 : 4;
+    if (plan) {
+        const int need = 6 + 4 * a.n_layers;
+        if (plan_cap < need) { set_error("tcr_net_fused_plan: room for %d ints, %d needed", plan_cap, need); return TCR_ERR_ARG; }
+        plan[0] = a.tmajor; plan[1] = a.group; plan[2] = waves; plan[3] = (int)lds; plan[4] = per_cu; plan[5] = a.n_layers;
+        for (int i = 0; i < a.n_layers; ++i) {
+            int reader = 0;         // stride of the first layer that reads this layer's output rows as its input
+            for (int j = i + 1; j < a.n_layers; ++j) {
+                if (a.layer[j].in_buf == a.layer[i].out_buf && reader == 0) reader = a.layer[j].stride;
+                if (a.layer[j].out_buf == a.layer[i].out_buf) break;
+            }
+            plan[6 + 4 * i] = a.layer[i].out_sz; plan[7 + 4 * i] = a.layer[i].in_sz; plan[8 + 4 * i] = a.layer[i].res_sz; plan[9 + 4 * i] = reader;
+        }
+        *plan_n = need;
+        return TCR_OK;
+    }
     return launch_net_fused(a, lds, grid, waves, ring, s);
 }
 
@@ -499,6 +548,13 @@ extern "C" int tcr_net_forward_infer(const tcr_net* net, const float* params, co
                                      float* logits, float* probs, float* ranges, void* stream) {
     TCR_REQUIRE(stats, "tcr_net_forward_infer: null argument");
     return forward_infer_impl(net, params, stats, nullptr, feat, batch, workspace, workspace_bytes, logits, probs, ranges, stream);
+}
+
+extern "C" int tcr_net_fused_plan(const tcr_net* net, int batch, int* out, int cap) {
+    TCR_REQUIRE(net && out && batch > 0, "tcr_net_fused_plan: bad arguments");
+    int n = 0;
+    const int rc = tcr::forward_infer_fused(*net, nullptr, nullptr, nullptr, batch, nullptr, nullptr, nullptr, nullptr, out, cap, &n);
+    return rc == 1 ? 0 : (rc == TCR_OK ? n : rc);
 }
 
 extern "C" int64_t tcr_net_frozen_floats(const tcr_net* net) { return net ? ss_floats(*net) : 0; }
