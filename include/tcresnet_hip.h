@@ -153,9 +153,24 @@ int tcr_net_forward_infer(const tcr_net* net, const float* params, const float* 
  *   tcr_net_frozen_floats   size of the constant table;
  *   tcr_net_fold_bn         params + moving stats -> the table (what a frozen export stores next to the conv weights);
  *   tcr_net_forward_frozen  eval forward from (conv weights in `params`, table): no variable is read, the BN entries of
- *                           `params` and the moving statistics are not needed.  Bitwise tcr_net_forward_infer. */
+ *                           `params` and the moving statistics are not needed.  Bitwise tcr_net_forward_infer.
+ * Layout of the table (tcr_net_frozen_floats floats, every caller sizes it by that call): per BN unit scale[c_pad], shift[c_pad]
+ * (offsets and contents as ever); rounded up to 4 floats; a header of 4 words {flag, image floats, 0, 0}; the WEIGHT IMAGE: every
+ * conv layer's weights in the order a lane of the fused eval kernel reads its matrix fragments,
+ *   [layer, forward order][row tile m][tap j][c4 / 4][lane 0..63][width],
+ * c4 the channel quad, width = 4 (the last group of a tap: C4 % 4 when that is not 0, C4 = Cin / 4), lane = 16 q + r holding
+ * W[j][4 c4 + q][min(16 m + r, Cout - 1)] -- one 16-byte load per lane for four channel quads of a tap where the kernel took four
+ * 4-byte loads at scattered rows.  (Networks with a layer of Cin % 4 != 0 have no image: the table ends behind the header.)
+ *   tcr_net_fold_bn         writes scale / shift and CLEARS the flag: with the flag clear every call that takes the table reads the conv
+ *                           weights from `params`, exactly as before the image existed;
+ *   tcr_net_fold_weights    writes the image from `params` and SETS the flag (table on a 16-byte boundary).  With the flag set, the
+ *                           kernels that know the image (TCResNet8-1.0 at 49 frames in groups of 8, the benchmark's shape) take their CONV
+ *                           WEIGHTS FROM THE TABLE, not from `params`: after changing a conv weight the caller must fold again (or
+ *                           clear the flag with tcr_net_fold_bn).  fc / fc2 and every other kernel keep reading `params`.
+ * A call whose plan sizes the image differently from the kernel it selects is refused (TCR_ERR_ARG). */
 int64_t tcr_net_frozen_floats(const tcr_net* net);
 int tcr_net_fold_bn(const tcr_net* net, const float* params, const float* stats, float* frozen_ss, void* stream);
+int tcr_net_fold_weights(const tcr_net* net, const float* params, float* frozen_ss, void* stream);
 int tcr_net_forward_frozen(const tcr_net* net, const float* params, const float* frozen_ss, const float* feat,
                            int batch, void* workspace, size_t workspace_bytes,
                            float* logits, float* probs, float* ranges, void* stream);
@@ -166,7 +181,8 @@ int tcr_net_forward_frozen(const tcr_net* net, const float* params, const float*
  * tcr_frontend_fwd + tcr_net_fold_bn + tcr_net_forward_frozen; it exists for small batches, where three host calls cost more than
  * the kernels (B <= 64: ~70 us -> the kernels' own time).
  * feat: caller-owned scratch for the features, [batch][n_coef][n_frames + 2 * TCR_HALO] floats; frozen_ss: the folded table
- * (tcr_net_frozen_floats), rewritten when `refold` is non-zero (stats may be NULL otherwise). */
+ * (tcr_net_frozen_floats), its scale / shift rewritten and its weight-image flag cleared when `refold` is non-zero (stats may be NULL
+ * otherwise). */
 int tcr_forward_waveform(const tcr_frontend_cfg* cfg, const void* plan_dev, const tcr_net* net, const float* params,
                          const float* stats, float* frozen_ss, int refold, const float* wav, int batch, float* feat,
                          void* workspace, size_t workspace_bytes, float* logits, float* probs, float* ranges, void* stream);
@@ -1201,7 +1217,7 @@ const char* tcr_kernel_name(int index);
 enum { TCR_TUNE_CONV_PATH = 0,   /* 0 auto: implicit-GEMM MFMA conv where the shape fits, 1: scalar-fed VALU conv, 2: as 0 */
        TCR_TUNE_FRONTEND = 1,    /* 0 / 5: packed-FP32 kernel (default); 1..4: scalar-FP32 kernel, variant (v-1): bit0 wave-local phase ordering, bit1 sample prefetch */
        TCR_TUNE_CONV_B = 2,      /* MFMA conv activations: 0 straight from global/L1 (default), 1 via an LDS image; 3: wide 1x1 convs on the register-fed kernel instead of the LDS-tiled one, DS-CNN conv_1 not fused with the first depthwise layer */
-       TCR_TUNE_NET_FUSED = 3,   /* eval forward: 0 one fused LDS-resident kernel for the whole net (default; layers of the flagship shapes run compile-time-specialised), 1 per-layer kernels, 2 fused with the features copied to LDS, 3 fused, generic layer walk only, 4 the round-2 static-shape layer, 5 the static kernel with four 16-position tiles per job in block 0's layers instead of two (round 5 experiment: bitwise, no faster), 7 fused without the bank-aligned utterance strides (A/B arm); the static kernels' nine-tap layers (round 6): 0 work dealt in 16-position units, as even over the waves as units allow, + a whole tap of weight lookahead in the layers of <= 32 input channels (TCResNet14-1.5: <= 48) (default), 8 jobs of two tiles dealt round-robin (rounds 3-5), 9 units without the lookahead; TCResNet8-1.0's kernel, conv0_1 (block 0's nine-tap layer of 24 input channels): 0 a row tile's whole weight set resident in registers across a wave's run of units, requested in front of the phase's barrier (default at 49 frames), 10 the round-6 walk (default at 98 frames, where the resident form measured no faster), 11 the resident walk at either frame count (all bitwise); groups of 8 utterances at 49 frames (12 classes, 8 waves): 0 the TIME-MAJOR plan (default) -- positions ordered 8 * frame + utterance, LDS rows [channel][frame + 4 + 4 halo frames][8 utterances] with a channel pitch of 16 (mod 32) floats where a stride-1 layer reads them and 8 (mod 32) where a stride-2 layer does (rows no convolution reads: no halo, no pad), so a 16-position tile is two frames of every utterance and the taps that would multiply only SAME-padding zeros for both frames are not issued (conv0_1's resident walk stays whole), jobs dealt by live-tap count; bitwise unless a weight is not finite (Inf * 0 no longer enters the edge outputs) --, 12 the utterance-major walk on those groups too (A/B arm; what every other group size, the 98-frame kernel and TCResNet14-1.5 run) */
+       TCR_TUNE_NET_FUSED = 3,   /* eval forward: 0 one fused LDS-resident kernel for the whole net (default; layers of the flagship shapes run compile-time-specialised), 1 per-layer kernels, 2 fused with the features copied to LDS, 3 fused, generic layer walk only, 4 the round-2 static-shape layer, 5 the static kernel with four 16-position tiles per job in block 0's layers instead of two (round 5 experiment: bitwise, no faster), 7 fused without the bank-aligned utterance strides (A/B arm); the static kernels' nine-tap layers (round 6): 0 work dealt in 16-position units, as even over the waves as units allow, + a whole tap of weight lookahead in the layers of <= 32 input channels (TCResNet14-1.5: <= 48) (default), 8 jobs of two tiles dealt round-robin (rounds 3-5), 9 units without the lookahead; TCResNet8-1.0's kernel, conv0_1 (block 0's nine-tap layer of 24 input channels): 0 a row tile's whole weight set resident in registers across a wave's run of units, requested in front of the phase's barrier (default at 49 frames), 10 the round-6 walk (default at 98 frames, where the resident form measured no faster), 11 the resident walk at either frame count (all bitwise); groups of 8 utterances at 49 frames (12 classes, 8 waves): 0 the TIME-MAJOR plan (default) -- positions ordered 8 * frame + utterance, LDS rows [channel][frame + 4 + 4 halo frames][8 utterances] with a channel pitch of 16 (mod 32) floats where a stride-1 layer reads them and 8 (mod 32) where a stride-2 layer does (rows no convolution reads: no halo, no pad), so a 16-position tile is two frames of every utterance and the taps that would multiply only SAME-padding zeros for both frames are not issued (conv0_1's resident walk stays whole), jobs dealt by live-tap count, weight fragments by 16-byte loads out of the frozen table's weight image where the table carries one (13: the time-major plan with the 4-byte loads from `params` whatever the table carries, A/B arm, bitwise); bitwise unless a weight is not finite (Inf * 0 no longer enters the edge outputs) --, 12 the utterance-major walk on those groups too (A/B arm; what every other group size, the 98-frame kernel and TCResNet14-1.5 run) */
        TCR_TUNE_FUSED_GROUP = 4, /* utterances per workgroup group of the fused kernel (0: largest that fits 64 KB of LDS) */
        TCR_TUNE_FUSED_WAVES = 5, /* fused kernel: waves per workgroup (4, 8, 16) + 100 * weight-ring depth (4, 8, 16); 0: default */
        TCR_TUNE_CONV_KSPLIT = 6, /* train-mode conv / data-gradient: waves sharing one 32-position group's reduction (0 auto, 1, 2, 4) */

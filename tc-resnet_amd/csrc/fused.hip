@@ -17,11 +17,62 @@
 namespace tcr {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// 16 / 8 bytes per lane through a buffer descriptor (buffer_load_dwordx4 / dwordx2: gfx950_isa.h, buf_load_f32); a compiler without
+// the wide builtins takes the same bytes dword by dword.
+__device__ __forceinline__ f32x4 buf_load_f32x4(buf_rsrc rs, unsigned lane_off_bytes, unsigned uniform_off_bytes) {
+#if __has_builtin(__builtin_amdgcn_raw_buffer_load_b128)
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lane_off_bytes, (int)uniform_off_bytes, 0));
+#else
+    return (f32x4){buf_load_f32(rs, lane_off_bytes, uniform_off_bytes), buf_load_f32(rs, lane_off_bytes, uniform_off_bytes + 4u),
+                   buf_load_f32(rs, lane_off_bytes, uniform_off_bytes + 8u), buf_load_f32(rs, lane_off_bytes, uniform_off_bytes + 12u)};
+#endif
+}
+__device__ __forceinline__ f32x2 buf_load_f32x2(buf_rsrc rs, unsigned lane_off_bytes, unsigned uniform_off_bytes) {
+#if __has_builtin(__builtin_amdgcn_raw_buffer_load_b64)
+    return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)lane_off_bytes, (int)uniform_off_bytes, 0));
+#else
+    return (f32x2){buf_load_f32(rs, lane_off_bytes, uniform_off_bytes), buf_load_f32(rs, lane_off_bytes, uniform_off_bytes + 4u)};
+#endif
+}
+
+// Fragments of channel quads [C0, C0 + N) of one tap out of the frozen table's weight image (kernels.h "weight image"): `uni` is the
+// byte offset of the tap's first fragment -- layer, row tile, tap: wave-uniform --, `lane` the lane index; a group of four quads is
+// [lane][4], so an aligned run of 4 / 2 quads is one 16 / 8-byte load at lane * 16 (+ 8), the 2-wide last group of C4 = 6, 10 one
+// 8-byte load at lane * 8.
+template <int C4, int C0, int N>
+__device__ __forceinline__ void wimg_load(const buf_rsrc wr, const unsigned lane, const unsigned uni, float* dst) {
+    if constexpr (N > 0) {
+        constexpr int G = C0 / 4, I = C0 - 4 * G, WD = C4 - 4 * G < 4 ? C4 - 4 * G : 4;
+        constexpr unsigned GO = (unsigned)(4 * G * 64 + I) * 4u;
+        const unsigned lo = lane * (unsigned)(4 * WD);
+        if constexpr (I == 0 && WD == 4 && N >= 4) {
+            const f32x4 v = buf_load_f32x4(wr, lo, uni + GO);
+            dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
+            wimg_load<C4, C0 + 4, N - 4>(wr, lane, uni, dst + 4);
+        } else if constexpr (I % 2 == 0 && WD % 2 == 0 && I + 2 <= WD && N >= 2) {
+            const f32x2 v = buf_load_f32x2(wr, lo, uni + GO);
+            dst[0] = v[0]; dst[1] = v[1];
+            wimg_load<C4, C0 + 2, N - 2>(wr, lane, uni, dst + 2);
+        } else {
+            dst[0] = buf_load_f32(wr, lo, uni + GO);
+            wimg_load<C4, C0 + 1, N - 1>(wr, lane, uni, dst + 1);
+        }
+    }
+}
+// the image is there: the flag word and the size its writer recorded agree with the plan (wave-uniform: scalar loads)
+__device__ __forceinline__ bool wimg_present(const FusedArgs& a) {
+    if (!a.wimg) return false;
+    const unsigned* h = reinterpret_cast<const unsigned*>(a.wimg);
+    return h[0] == kWimgMagic && h[1] == (unsigned)a.wimg_floats;
+}
 
 // Timing what-ifs of the static-shape kernel (scripts/build_whatif.py compiles this file with -DTCR_FUSED_WHATIF=<mask> into
 // side libraries; WRONG results, never part of the product build): 1 no MFMAs, 2 weights of tap 0 only, 4 LDS operands of tap 0
 // only, 8 no barriers, 16 no head, 32 no epilogue stores, 64 no first conv, 512 empty kernel, 1024 no halo-zero passes, 2048 phase stamps
 // (scripts/fused_ts.py), 4096 / 8192 the lookahead layers without their weight refills / without LDS operand reads after tap 0,
+// 65536 restricts 4096 to conv1_0 (the stride-2 layer 24 -> 32),
 // 16384 / 32768 (right results) s_setprio 2 around a tap's MFMA burst / around its operand requests: 110 / 101 us against 98 -- slower, not built in.
 #ifndef TCR_FUSED_WHATIF
 #define TCR_FUSED_WHATIF 0
@@ -257,10 +308,11 @@ __device__ __forceinline__ void fused_layer_t(const FusedArgs& a, const FusedLay
 // halo; 1 / 2: a stride-1 / stride-2 layer).  A lane's offset inside a tile (its slot and frame half, q * pitch) is the same for every
 // tile: the position -> (utterance, frame) division is gone; lanes of an absent frame or utterance read a clamped address and store
 // into the pad.
-template <int K, int S, int CIN, int COUT, int TIN, bool HAS_RES, int NTJ, bool WLDS, int AHEAD = 0, bool TM = false, int OCS = 0>
+// IMG: weight fragments, scale and shift by 16 / 8-byte loads out of the frozen table's weight image (wimg_load) -- same values, same order.
+template <int K, int S, int CIN, int COUT, int TIN, bool HAS_RES, int NTJ, bool WLDS, int AHEAD = 0, bool TM = false, int OCS = 0, bool IMG = false>
 __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer& L, const float* __restrict__ xin, const int in_sz,
                                             float* yout, const float* res, const float* w, const int npos, const int m, const int (&cc)[NTJ],
-                                            const int r, const int q, const int jlo = 0, const int jhi = K - 1) {
+                                            const int r, const int q, const int jlo = 0, const int jhi = K - 1, const int wio = 0) {     // wio (IMG): float offset of the layer's fragments in the image
     constexpr int TOUT = (TIN + S - 1) / S;
     constexpr int PADT = ((TOUT - 1) * S + K - TIN) > 0 ? ((TOUT - 1) * S + K - TIN) : 0;
     constexpr int PADLO = PADT / 2;
@@ -299,11 +351,22 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
     const buf_rsrc sr = make_rsrc(a.ss);
     const unsigned sl = (unsigned)cob * 4u;
     float sc[4], sh[4];
+    if constexpr (IMG) {
+        const f32x4 vs = buf_load_f32x4(sr, sl, (unsigned)L.ss_off * 4u), vh = buf_load_f32x4(sr, sl, (unsigned)(L.ss_off + L.c_pad) * 4u);
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) { sc[reg] = vs[reg]; sh[reg] = vh[reg]; }
+    } else {
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
         sc[reg] = buf_load_f32(sr, sl, (unsigned)(L.ss_off + reg) * 4u);
         sh[reg] = buf_load_f32(sr, sl, (unsigned)(L.ss_off + L.c_pad + reg) * 4u);
     }
+    }
+    // (IMG) the image's descriptor, this lane's index and the byte offset of row tile m's first tap; a tap is C4 * 64 floats
+    const buf_rsrc ir = make_rsrc(IMG ? a.wimg : a.params);
+    const unsigned il = (unsigned)(q * 16 + r);
+    const unsigned io = (unsigned)(kWimgHeader + wio + m * (K * C4 * 64)) * 4u;
+    constexpr unsigned kTapBytes = (unsigned)(C4 * 64) * 4u;
     f32x4 acc[NTJ];
 #pragma unroll
     for (int nt = 0; nt < NTJ; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -320,13 +383,19 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
         const unsigned wl = (unsigned)(q * COUT + min(m * 16 + r, COUT - 1)) * 4u;
         const unsigned wo = (unsigned)L.w_off * 4u;
         float w0[C4], w1[C4];
+        if constexpr (IMG) wimg_load<C4, 0, C4>(ir, il, io + (unsigned)ja * kTapBytes, w0);
+        else {
 #pragma unroll
         for (int c4 = 0; c4 < C4; ++c4) w0[c4] = buf_load_f32(wr, wl, wo + (unsigned)((ja * C4 + c4) * WSTEP) * 4u);
+        }
         auto tap = [&](const int j, const float (&wu)[C4], float (&wf)[C4], const bool fill) {
             TCR_WHATIF_PRIO(32768, 2);
-            if (fill && !TCR_WHATIF(4096)) {
+            if (fill && !(TCR_WHATIF(4096) && (!TCR_WHATIF(65536) || (S == 2 && CIN == 24 && COUT == 32)))) {
+                if constexpr (IMG) wimg_load<C4, 0, C4>(ir, il, io + (unsigned)(j + 1) * kTapBytes, wf);
+                else {
 #pragma unroll
                 for (int c4 = 0; c4 < C4; ++c4) wf[c4] = buf_load_f32(wr, wl, wo + (unsigned)(((j + 1) * C4 + c4) * WSTEP) * 4u);
+                }
             }
             float b[NTJ][C4];
             if (TCR_WHATIF(8192) && j > 0) {
@@ -389,10 +458,23 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
         else return buf_load_f32(wr, wl, wo + (unsigned)(step * WSTEP) * 4u);
     };
     float wa[H0 > 0 ? H0 : 1], wb[H1];
+    // a half-tap set of tap j (IMG: its aligned runs of 4 / 2 channel quads, one load each)
+    auto wfill_a = [&](const int j) {
+        if constexpr (IMG) wimg_load<C4, 0, H0>(ir, il, io + (unsigned)j * kTapBytes, wa);
+        else {
 #pragma unroll
-    for (int c4 = 0; c4 < H0; ++c4) wa[c4] = wld(ja * C4 + c4);
+            for (int c4 = 0; c4 < H0; ++c4) wa[c4] = wld(j * C4 + c4);
+        }
+    };
+    auto wfill_b = [&](const int j) {
+        if constexpr (IMG) wimg_load<C4, H0, H1>(ir, il, io + (unsigned)j * kTapBytes, wb);
+        else {
 #pragma unroll
-    for (int c4 = 0; c4 < H1; ++c4) wb[c4] = wld(ja * C4 + H0 + c4);
+            for (int c4 = 0; c4 < H1; ++c4) wb[c4] = wld(j * C4 + H0 + c4);
+        }
+    };
+    wfill_a(ja);
+    wfill_b(ja);
     // (throughput kernels: rolled taps -- 128-register budget; small-batch kernel: unrolled, the LDS operand and weight reads of the
     //  following taps move ahead of the MFMAs)
     constexpr int kTapUnroll = WLDS ? K : 1;
@@ -410,8 +492,7 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
             for (int c4 = 0; c4 < H0; ++c4)
 #pragma unroll
                 for (int nt = 0; nt < NTJ; ++nt) acc[nt] = TCR_MFMA(wa[c4], b[nt][c4], acc[nt]);
-#pragma unroll
-            for (int c4 = 0; c4 < H0; ++c4) wa[c4] = wld(jn * C4 + c4);
+            wfill_a(jn);
         }
         {
             float b[NTJ][H1];
@@ -423,8 +504,7 @@ __device__ __forceinline__ void fused_job_s(const FusedArgs& a, const FusedLayer
             for (int c4 = 0; c4 < H1; ++c4)
 #pragma unroll
                 for (int nt = 0; nt < NTJ; ++nt) acc[nt] = TCR_MFMA(wb[c4], b[nt][c4], acc[nt]);
-#pragma unroll
-            for (int c4 = 0; c4 < H1; ++c4) wb[c4] = wld(jn * C4 + H0 + c4);
+            wfill_b(jn);
         }
     }
     }
@@ -514,8 +594,8 @@ __device__ __forceinline__ void fused_zero_halo_tm(float* yout, const int tid_in
 // halo for both frames is dead for the whole tile -- wave-uniformly, and known at compile time.  Such taps multiplied finite weights
 // with zeros into accumulators that start at +0; here their MFMAs, operand reads and weight fetches are not issued (fused_job_s walks the
 // job's live taps [lo, hi] in the same order: bitwise).  The waves' jobs come from the compile-time deal, read with scalar loads.
-template <int NW, int K, int S, int CIN, int COUT, int TIN, bool HAS_RES, int OCS, int AHEAD>
-__device__ __forceinline__ void fused_layer_tm(const FusedArgs& a, const FusedLayer& L, float* lds, const int ng, const int wave, const int r_in, const int q_in) {
+template <int NW, int K, int S, int CIN, int COUT, int TIN, bool HAS_RES, int OCS, int AHEAD, bool IMG = false>
+__device__ __forceinline__ void fused_layer_tm(const FusedArgs& a, const FusedLayer& L, float* lds, const int ng, const int wave, const int r_in, const int q_in, const int wio = 0) {
     constexpr int TOUT = (TIN + S - 1) / S;
     constexpr int PADT = ((TOUT - 1) * S + K - TIN) > 0 ? ((TOUT - 1) * S + K - TIN) : 0;
     static constexpr FusedTmDeal deal = fused_tm_deal(K, S, CIN, COUT, TIN, PADT / 2, NW);
@@ -533,10 +613,10 @@ __device__ __forceinline__ void fused_layer_tm(const FusedArgs& a, const FusedLa
         const int m = (int)(jw & 15u), c = (int)(jw >> 4 & 63u), lo = (int)(jw >> 11 & 15u), hi = (int)(jw >> 15 & 15u);
         if (jw >> 10 & 1u) {
             const int cc[2] = {c, c + 1};
-            fused_job_s<K, S, CIN, COUT, TIN, HAS_RES, 2, false, AHEAD, true, OCS>(a, L, xin, 0, yout, res, w, ng, m, cc, r, q, lo, hi);
+            fused_job_s<K, S, CIN, COUT, TIN, HAS_RES, 2, false, AHEAD, true, OCS, IMG>(a, L, xin, 0, yout, res, w, ng, m, cc, r, q, lo, hi, wio);
         } else {
             const int cc[1] = {c};
-            fused_job_s<K, S, CIN, COUT, TIN, HAS_RES, 1, false, AHEAD, true, OCS>(a, L, xin, 0, yout, res, w, ng, m, cc, r, q, lo, hi);
+            fused_job_s<K, S, CIN, COUT, TIN, HAS_RES, 1, false, AHEAD, true, OCS, IMG>(a, L, xin, 0, yout, res, w, ng, m, cc, r, q, lo, hi, wio);
         }
     }
 }
@@ -596,21 +676,28 @@ __device__ __forceinline__ void fused_layer_u(const FusedArgs& a, const FusedLay
 // trip per phase, shared with the wait for the slowest wave.  Phase stamps (OPTLOG "Resident weights"): conv0_1 35.6 -> 29.6 k cycles per
 // group, what the phase takes with its weight refills removed (28.2 k); requested BEHIND the barrier the gain is gone (35.3 k).  conv0_0
 // (16 -> 24) in this form gains nothing (as its no-refill what-if said) and its request lengthens the first conv's phase: not used there.
-template <int NW, int K, int CIN, int COUT>
+template <int NW, int K, int CIN, int COUT, bool IMG = false>
 __device__ __forceinline__ void fused_resident_request(const FusedArgs& a, const FusedLayer& L, const int wave, const int r_in, const int q_in,
-                                                       float (&ws)[K * (CIN / 4)]) {
+                                                       float (&ws)[K * (CIN / 4)], const int wio = 0) {
     constexpr int NRT = (COUT + 15) / 16, C4 = CIN / 4, WSTEP = 4 * COUT;
     static_assert(NW % NRT == 0, "the waves split evenly over the row tiles");
     const int oz = opaque_zero();          // (keeps the request inside the group loop: hoisted, the set would live through every layer)
     const int r = r_in + oz, q = q_in + oz;
     const int m = wave / (NW / NRT);       // this wave's row tile (fused_deal_run); requested whether or not its run is empty
+    if constexpr (IMG) {            // (the image's row tile m: K taps of C4 * 64 floats, wimg_load)
+        const buf_rsrc ir = make_rsrc(a.wimg);
+        const unsigned io = (unsigned)(kWimgHeader + wio + m * (K * C4 * 64)) * 4u;
+#pragma unroll
+        for (int j = 0; j < K; ++j) wimg_load<C4, 0, C4>(ir, (unsigned)(q * 16 + r), io + (unsigned)(j * C4 * 64) * 4u, ws + j * C4);
+    } else {
     const buf_rsrc wr = make_rsrc(a.params + L.w_off);
     const unsigned wl = (unsigned)(q * COUT + min(m * 16 + r, COUT - 1)) * 4u;
 #pragma unroll
     for (int i = 0; i < K * C4; ++i) ws[i] = buf_load_f32(wr, wl, (unsigned)(i * WSTEP) * 4u);      // i = tap * C4 + channel quad
+    }
 }
 
-template <int NW, int K, int S, int CIN, int COUT, int TIN, bool HAS_RES, bool TM = false, int OCS = 0>
+template <int NW, int K, int S, int CIN, int COUT, int TIN, bool HAS_RES, bool TM = false, int OCS = 0, bool IMG = false>
 __device__ __forceinline__ void fused_layer_r(const FusedArgs& a, const FusedLayer& L, const float* __restrict__ xin, const int in_sz,
                                               float* lds, const int ng, const int wave, const int r_in, const int q_in,
                                               const float (&ws)[K * (CIN / 4)]) {
@@ -641,10 +728,16 @@ __device__ __forceinline__ void fused_layer_r(const FusedArgs& a, const FusedLay
     const buf_rsrc sr = make_rsrc(a.ss);                        // (scale / shift of the lane's channel quad: as fused_job_s)
     const unsigned sl = (unsigned)min(m * 16 + q * 4, COUT - 4) * 4u;
     float sc[4], sh[4];
+    if constexpr (IMG) {
+        const f32x4 vs = buf_load_f32x4(sr, sl, (unsigned)L.ss_off * 4u), vh = buf_load_f32x4(sr, sl, (unsigned)(L.ss_off + L.c_pad) * 4u);
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) { sc[reg] = vs[reg]; sh[reg] = vh[reg]; }
+    } else {
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
         sc[reg] = buf_load_f32(sr, sl, (unsigned)(L.ss_off + reg) * 4u);
         sh[reg] = buf_load_f32(sr, sl, (unsigned)(L.ss_off + L.c_pad + reg) * 4u);
+    }
     }
     // this lane's position in column tile c -> (utterance of the group, frame); computed twice per unit, in front of the taps for the operand
     // address and again behind them for the stores, so that nothing but the address is live across the 9 x C4 MFMAs (the 128-register budget)
@@ -723,10 +816,10 @@ __device__ __forceinline__ void fused_layer_r(const FusedArgs& a, const FusedLay
 #ifndef TCR_TM_CONV0
 #define TCR_TM_CONV0 1
 #endif
-template <int NW, int T0, bool WLDS = false, int TM = 0>
+template <int NW, int T0, bool WLDS = false, int TM = 0, bool IMG = false>
 __device__ __forceinline__ void fused_conv0_s(const FusedArgs& a, const FusedLayer& L, const float* __restrict__ xin, const int in_sz,
                                               float* lds, const int ng, const int wave, const int r_in, const int q_in,
-                                              const int w_lds = 0) {
+                                              const int w_lds = 0, const int wio = 0) {
     const int oz = opaque_zero();
     const int r = r_in + oz, q = q_in + oz;
     constexpr int K = 3, CIN = 40, COUT = 16, C4 = CIN / 4;
@@ -750,15 +843,24 @@ __device__ __forceinline__ void fused_conv0_s(const FusedArgs& a, const FusedLay
         for (int c4 = 0; c4 < C4; ++c4)
 #pragma unroll
             for (int j = 0; j < K; ++j) b0[c4][j] = x0[c4 * XSTEP + j];
+        float sc[4], sh[4];
+        if constexpr (IMG && !WLDS) {       // (one row tile: the image's taps follow one another, wimg_load; scale / shift of the lane's channel quad)
+            const buf_rsrc ir = make_rsrc(a.wimg), sr = make_rsrc(a.ss);
+#pragma unroll
+            for (int j = 0; j < K; ++j) wimg_load<C4, 0, C4>(ir, (unsigned)(q * 16 + r), (unsigned)(kWimgHeader + wio + j * C4 * 64) * 4u, wf[j]);
+            const f32x4 vs = buf_load_f32x4(sr, (unsigned)q * 16u, (unsigned)L.ss_off * 4u), vh = buf_load_f32x4(sr, (unsigned)q * 16u, (unsigned)(L.ss_off + L.c_pad) * 4u);
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) { sc[reg] = vs[reg]; sh[reg] = vh[reg]; }
+        } else {
 #pragma unroll
         for (int j = 0; j < K; ++j)
 #pragma unroll
             for (int c4 = 0; c4 < C4; ++c4) wf[j][c4] = wp[(j * C4 + c4) * WSTEP];
-        float sc[4], sh[4];
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             sc[reg] = scale[q * 4 + reg];
             sh[reg] = shift[q * 4 + reg];
+        }
         }
         f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f};
         TCR_WHATIF_PRIO(16384, 2);
@@ -964,104 +1066,41 @@ __device__ __forceinline__ void fused_layer_sel(const FusedArgs& a, const FusedL
 
 // TM: the time-major plan (fused_layer_tm; the host lays the buffers out by the same fused_tm_pitch): groups of 8 at 49 frames, the default
 // there; TCR_TUNE_NET_FUSED = 12 keeps the utterance-major walk.
+// ONE table of the ten layers, in the order the walk runs them: fused_tc8_frames admits only a plan whose layers are these rows in this order, the
+// image's layer order is the plan's (net.cpp), and the kernel's image offsets come from the same rows (fused_tc8_walk.inc calls layer LI with row LI's shape).
+struct Tc8Shape { int k, stride, cin, cout; };
+__host__ __device__ constexpr Tc8Shape tc8_shape(const int li) {
+    constexpr Tc8Shape shape[10] = {{3, 1, 40, 16}, {1, 2, 16, 24}, {9, 2, 16, 24}, {9, 1, 24, 24}, {1, 2, 24, 32},
+                                    {9, 2, 24, 32}, {9, 1, 32, 32}, {1, 2, 32, 48}, {9, 2, 32, 48}, {9, 1, 48, 48}};
+    return shape[li];
+}
+// float offset of layer li's fragments in TCResNet8-1.0's weight image (li = 10: the image's size)
+__host__ __device__ constexpr int tc8_wimg_off(const int li) {
+    int n = 0;
+    for (int i = 0; i < li && i < 10; ++i) n += wimg_layer_floats(tc8_shape(i).k, tc8_shape(i).cin, tc8_shape(i).cout);
+    return n;
+}
+
+// The kernel's walk is ONE text, fused_tc8_walk.inc, compiled as the kernel itself (weights from `params`: every instance but the one below)
+// and as a function with IMG as a parameter for the instance that chooses per launch.  (All of them calling the function cost the
+// utterance-major instances 8 B of scratch: a function's code is simplified before it is inlined, without the kernel's workgroup size.)
 template <int NW, int T0, int WD, int NTJ0 = 2, bool TM = false>
 __global__ __launch_bounds__(NW * 64) TCR_WAVES_PER_SIMD_4 void net_fused_tc8_kernel(const FusedArgs a) {
-    constexpr int NT = NW * 64;
-    constexpr int T1 = (T0 + 1) / 2, T2 = (T1 + 1) / 2;
-    float* lds = reinterpret_cast<float*>(dyn_lds());
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 15, q = lane >> 4;
-    const int row = a.in_c * a.in_tp;
-#if TCR_FUSED_WHATIF & 2048
-    // phase timing (diagnostic side build, WRONG outputs): cycles between the barriers, written over the group's first probabilities
-    long long ts[14];
-    int nts = 0;
-#define TCR_TC8_BARRIER do { __syncthreads(); ts[nts++] = (long long)__builtin_readcyclecounter(); } while (0)
-#elif TCR_FUSED_WHATIF & 8
-#define TCR_TC8_BARRIER ((void)0)
-#else
-#define TCR_TC8_BARRIER __syncthreads()
-#endif
-    // (Measured and removed, round 6: the upper half of the waves running a block's first conv BEFORE its shortcut conv -- both read the same rows --
-    //  so that a SIMD's two waves are not in the shortcut's load / store-bound jobs together: 96.5 vs 95.6 us at 49 frames, 173.9 vs 176.1 at 98.)
-    // (tiles per job: two; NTJ0 = 4: four for block 0's layers -- 16 / 24 channels at T0 / 2 frames --, the TCR_TUNE_NET_FUSED = 5 arm)
-    // (NTJ0 = 0: the nine-tap layers' work dealt in 16-position units, fused_layer_u)
-    // (NTJ0 = 6: conv0_1 -- block 0's nine-tap layer of 24 input channels -- in its resident-weight form, fused_layer_r; every other layer as NTJ0 = 3)
-    constexpr bool RES = WD >= 0 && NTJ0 == 6;
-    constexpr int NTJU = RES ? 3 : NTJ0;
-    // (who reads layer LI's output rows: nobody convolves a shortcut conv's or the last layer's; a block's first conv feeds its stride-1 second, which feeds the next block's stride-2 layers)
-#define TCR_TC8_OCS(LI, K_, S_) ((K_ == 1 || LI == 9) ? 0 : (S_ == 2 ? 1 : 2))
-#define TCR_TC8(LI, K_, S_, CI_, CO_, T_) do { const FusedLayer& L_ = TCR_LAYER_ROW(WD >= 0, LI); \
-        if constexpr (TM) fused_layer_tm<NW, K_, S_, CI_, CO_, T_, (LI == 3 || LI == 6 || LI == 9), TCR_TC8_OCS(LI, K_, S_), ((K_ == 9 && CI_ <= 32) ? 1 : 0)>(a, L_, lds, ng, wave, r, q); \
-        else fused_layer_sel<NW, K_, S_, CI_, CO_, T_, WD, (LI == 3 || LI == 6 || LI == 9), (K_ != 1 && LI != 9), ((LI >= 1 && LI <= 3 && NTJU == 4) ? 4 : (((NTJU == 0 || NTJU == 3) && K_ == 9) ? NTJU : 2))>(a, L_, lds + a.buf_off[L_.in_buf], L_.in_sz, lds, ng, wave, r, q); } while (0)
-    // (resident form of layer LI: halo zeros of its output rows, then the walk out of the set WS_ requested in front of the barrier)
-#define TCR_TC8_R(LI, S_, CI_, T_, WS_) do { const FusedLayer& L_ = TCR_LAYER_ROW(true, LI); \
-        if constexpr (TM) fused_zero_halo_tm<NT, 24, (T_ + S_ - 1) / S_, fused_tm_pitch((T_ + S_ - 1) / S_, true, TCR_TC8_OCS(LI, 9, S_))>(lds + a.buf_off[L_.out_buf], tid); \
-        else fused_zero_halo<NT, 24, (T_ + S_ - 1) / S_>(lds + a.buf_off[L_.out_buf], L_.out_sz, ng, tid); \
-        fused_layer_r<NW, 9, S_, CI_, 24, T_, (LI == 3), TM, TCR_TC8_OCS(LI, 9, S_)>(a, L_, lds + a.buf_off[L_.in_buf], L_.in_sz, lds, ng, wave, r, q, WS_); } while (0)
-    for (int grp = blockIdx.x; grp < (TCR_WHATIF(512) ? 0 : a.n_groups); grp += gridDim.x) {
-        const int n0 = grp * a.group;
-        const int ng = min(a.group, a.batch - n0);
-#if TCR_FUSED_WHATIF & 2048
-        nts = 0;
-        ts[nts++] = (long long)__builtin_readcyclecounter();
-#endif
-        if constexpr (WD < 0) fused_layer_sel<NW, 3, 1, 40, 16, T0, WD, false>(a, a.layer[0], a.feat + (size_t)n0 * row, row, lds, ng, wave, r, q);
-        else if (!TCR_WHATIF(64)) {
-            const FusedLayer& L0 = TCR_LAYER_ROW(true, 0);
-            if constexpr (TM) {
-                fused_zero_halo_tm<NT, 16, T0, fused_tm_pitch(T0, true, 2)>(lds + a.buf_off[L0.out_buf], tid);
-                fused_conv0_s<NW, T0, false, TCR_TM_CONV0>(a, L0, a.feat + (size_t)n0 * row, row, lds, ng, wave, r, q);
-            } else {
-            fused_zero_halo<NT, 16, T0>(lds + a.buf_off[L0.out_buf], L0.out_sz, ng, tid);
-            fused_conv0_s<NW, T0>(a, L0, a.feat + (size_t)n0 * row, row, lds, ng, wave, r, q);
-            }
-        }
-        if constexpr (RES) {
-            float ws3[9 * 6];
-            TCR_TC8_BARRIER;
-            TCR_TC8(1, 1, 2, 16, 24, T0);
-            TCR_TC8(2, 9, 2, 16, 24, T0);
-            fused_resident_request<NW, 9, 24, 24>(a, TCR_LAYER_ROW(true, 3), wave, r, q, ws3);      // (no job state is live here: the set costs no register of the budget)
-            TCR_TC8_BARRIER;
-            TCR_TC8_R(3, 1, 24, T1, ws3);
-            TCR_TC8_BARRIER;
-        } else {
-        TCR_TC8_BARRIER;
-        TCR_TC8(1, 1, 2, 16, 24, T0);           // block0/down (reads the same rows as conv0_0: no barrier in between)
-        TCR_TC8(2, 9, 2, 16, 24, T0);
-        TCR_TC8_BARRIER;
-        TCR_TC8(3, 9, 1, 24, 24, T1);
-        TCR_TC8_BARRIER;
-        }
-        TCR_TC8(4, 1, 2, 24, 32, T1);
-        TCR_TC8(5, 9, 2, 24, 32, T1);
-        TCR_TC8_BARRIER;
-        TCR_TC8(6, 9, 1, 32, 32, T2);
-        TCR_TC8_BARRIER;
-        TCR_TC8(7, 1, 2, 32, 48, T2);
-        TCR_TC8(8, 9, 2, 32, 48, T2);
-        TCR_TC8_BARRIER;
-        TCR_TC8(9, 9, 1, 48, 48, (T2 + 1) / 2);
-        TCR_TC8_BARRIER;
-        if constexpr (WD < 0) fused_head<NT>(a, lds, n0, ng, tid);
-        else if (!TCR_WHATIF(16)) {
-            if (a.nc == 12 || TM) fused_head_s<NT, 48, (T2 + 1) / 2, 12, TM>(a, lds, n0, ng, tid);      // (time-major: launched for 12 classes only)
-            else fused_head<NT>(a, lds, n0, ng, tid);
-        }
-#if TCR_FUSED_WHATIF & 2048
-        __syncthreads();
-        ts[nts++] = (long long)__builtin_readcyclecounter();
-        if (tid == 0)
-            for (int i = 0; i + 1 < nts && i < 12; ++i) a.probs[(size_t)n0 * a.nc + i] = (float)(ts[i + 1] - ts[i]);
-#endif
-    }
-#undef TCR_TC8
-#undef TCR_TC8_OCS
-#undef TCR_TC8_R
-#undef TCR_TC8_BARRIER
+    constexpr bool IMG = false;
+#include "fused_tc8_walk.inc"
+}
+// IMG: the weight fragments, scale and shift come out of the frozen table's fragment-ordered image.
+template <int NW, int T0, int WD, int NTJ0, bool TM, bool IMG>
+__device__ __forceinline__ void net_fused_tc8_walk(const FusedArgs& a) {
+#include "fused_tc8_walk.inc"
+}
+// The time-major instance reads the table's weight image where a launch finds it valid (both walks are compiled in; the test is
+// wave-uniform, once per launch), `params` otherwise.  (An overload of the kernel template: six arguments, the last one WIMG = true.)
+template <int NW, int T0, int WD, int NTJ0, bool TM, bool WIMG>
+__global__ __launch_bounds__(NW * 64) TCR_WAVES_PER_SIMD_4 void net_fused_tc8_kernel(const FusedArgs a) {
+    static_assert(TM && WIMG, "the instance with a weight image is the time-major one");
+    if (wimg_present(a)) net_fused_tc8_walk<NW, T0, WD, NTJ0, TM, true>(a);
+    else net_fused_tc8_walk<NW, T0, WD, NTJ0, TM, false>(a);
 }
 
 // Small-batch (latency) form of the same network, TCResNet8-1.0 at 49 frames: ONE utterance per 8-wave workgroup, every phase's weights
@@ -1237,7 +1276,7 @@ static int fused_tc14w_frames(const FusedArgs& a) {
 static int fused_tc8_frames(const FusedArgs& a);
 // The time-major plan has ONE kernel instance: TCResNet8-1.0 at 49 frames and 12 classes, groups of 8, 8 waves, the default arm.
 bool fused_tmajor_applies(const FusedArgs& a, const int waves) {
-    return tune_get(TCR_TUNE_NET_FUSED) == 0 && a.group == kTmGroup && waves == 8 && a.nc == 12 && fused_tc8_frames(a) == 49;
+    return (tune_get(TCR_TUNE_NET_FUSED) == 0 || tune_get(TCR_TUNE_NET_FUSED) == 13) && a.group == kTmGroup && waves == 8 && a.nc == 12 && fused_tc8_frames(a) == 49;
 }
 // the kernel derives every pitch at compile time from the layer shapes; the host derived them from the plan's actual readers
 static bool fused_tmajor_pitches_agree(const FusedArgs& a) {
@@ -1254,15 +1293,14 @@ static bool fused_tmajor_pitches_agree(const FusedArgs& a) {
 
 // 49 / 98 when the plan is exactly TCResNet8-1.0 on 40 coefficients read from global memory, else 0
 static int fused_tc8_frames(const FusedArgs& a) {
-    static const int shape[10][4] = {{3, 1, 40, 16}, {1, 2, 16, 24}, {9, 2, 16, 24}, {9, 1, 24, 24}, {1, 2, 24, 32},
-                                     {9, 2, 24, 32}, {9, 1, 32, 32}, {1, 2, 32, 48}, {9, 2, 32, 48}, {9, 1, 48, 48}};
     if (a.n_layers != 10 || !a.in_global || a.in_c != 40) return 0;
     const int t0 = a.layer[0].tin;
     if (t0 != 49 && t0 != 98) return 0;
     int t = t0;
     for (int i = 0; i < 10; ++i) {
         const FusedLayer& L = a.layer[i];
-        if (L.k != shape[i][0] || L.stride != shape[i][1] || L.cin != shape[i][2] || L.cout != shape[i][3] || L.tin != t) return 0;
+        const Tc8Shape sh = tc8_shape(i);
+        if (L.k != sh.k || L.stride != sh.stride || L.cin != sh.cin || L.cout != sh.cout || L.tin != t) return 0;
         if (i == 2 || i == 5 || i == 8) t = (t + 1) / 2;
     }
     return t0;
@@ -1505,7 +1543,13 @@ int launch_net_fused(const FusedArgs& a, size_t lds_bytes, int grid, int waves, 
     if (a.tmajor) {
         // the host laid the buffers out time-major (fused_tmajor_applies held): the one instance built for it, or an error -- never the other walk on these rows
         if (!fused_tmajor_applies(a, waves) || !fused_tmajor_pitches_agree(a)) { set_error("fused kernel: time-major plan without its kernel instance"); return TCR_ERR_ARG; }
-        kern = net_fused_tc8_kernel<8, 49, 0, 6, true>;
+        // The instance that takes its weight fragments out of the frozen table's image where the table carries a valid one (the kernel tests the
+        // header); TCR_TUNE_NET_FUSED = 13: the dword loads from `params` whatever the table carries (A/B arm, bitwise).  The image's layout is fixed
+        // by the layer shapes, compiled into the kernel: a plan that sizes it differently is refused.
+        constexpr int kImg = tc8_wimg_off(10);
+        if (a.wimg_floats != kImg) { set_error("fused kernel: the plan's weight image has %d floats, the kernel's %d", a.wimg_floats, kImg); return TCR_ERR_ARG; }
+        if (a.wimg && reinterpret_cast<uintptr_t>(a.wimg) % 16 != 0) { set_error("fused kernel: the frozen table's weight image is not on a 16-byte boundary"); return TCR_ERR_ARG; }
+        kern = tune_get(TCR_TUNE_NET_FUSED) == 13 ? net_fused_tc8_kernel<8, 49, 0, 6, true> : net_fused_tc8_kernel<8, 49, 0, 6, true, true>;
     }
     const int tc14 = (kern || tune_get(TCR_TUNE_NET_FUSED) == 3 || tune_get(TCR_TUNE_NET_FUSED) == 4) ? 0 : fused_tc14w_frames(a);
 #define TCR_F14(NW_, T_) if (tc14 == T_ && waves == NW_) kern = ju ? net_fused_tc14w_kernel<NW_, T_, 0> : (j2 ? net_fused_tc14w_kernel<NW_, T_, 2> : net_fused_tc14w_kernel<NW_, T_, 13>);
@@ -1524,6 +1568,35 @@ int launch_net_fused(const FusedArgs& a, size_t lds_bytes, int grid, int waves, 
     }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(waves * 64), lds_bytes, s, a);
     return check_launch("net_fused_kernel");
+}
+
+// Frozen table's weight image (kernels.h "weight image"): one thread per float of the image gathers its weight; thread 0 then writes the header.
+__global__ __launch_bounds__(256) void wimg_fold_kernel(const WimgFoldArgs a) {
+    float* img = a.header + kWimgHeader;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < a.total; e += gridDim.x * 256) {
+        int li = 0;
+        while (li + 1 < a.n && e >= a.img_off[li + 1]) ++li;
+        const int k = a.k[li], cin = a.cin[li], cout = a.cout[li], C4 = cin >> 2;
+        const int x0 = e - a.img_off[li];
+        const int per = k * C4 * 64;
+        const int m = x0 / per, x1 = x0 - m * per;
+        const int j = x1 / (C4 * 64), x2 = x1 - j * (C4 * 64);
+        const int g = x2 >> 8, wd = min(4, C4 - 4 * g), y = x2 - (g << 8);
+        const int lane = y / wd, c4 = 4 * g + (y - lane * wd);
+        const int q = lane >> 4, r = lane & 15;
+        img[e] = a.params[(size_t)a.w_off[li] + (size_t)((j * C4 + c4) * 4 + q) * cout + min(16 * m + r, cout - 1)];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        unsigned* h = reinterpret_cast<unsigned*>(a.header);
+        h[0] = kWimgMagic; h[1] = (unsigned)a.total; h[2] = 0u; h[3] = 0u;
+    }
+}
+
+int launch_wimg_fold(const WimgFoldArgs& a, hipStream_t s) {
+    if (a.n < 1 || a.total < 1) { set_error("weight image: nothing to fold"); return TCR_ERR_ARG; }
+    const int grid = min((a.total + 255) / 256, 1024);
+    hipLaunchKernelGGL(wimg_fold_kernel, dim3(grid), dim3(256), 0, s, a);
+    return check_launch("wimg_fold_kernel");
 }
 
 }  // namespace tcr

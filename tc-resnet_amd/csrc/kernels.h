@@ -201,6 +201,9 @@ struct FusedArgs {
     int in_global;              // the first layer reads the feature rows straight from global memory (no LDS copy)
     int tmajor;                 // time-major plan (groups of 8, TCResNet8-1.0 at 49 frames): rows are [channel][frame (+ halo)][8 utterances]
     FusedLayer layer[kFusedMaxLayers];
+    // (behind the layer table: the kernels that do not read the image see the arguments where they always were)
+    const float* wimg;          // header of the frozen table's weight image ("weight image" below), nullptr: the table is scale / shift only
+    int wimg_floats;            // floats of the image the plan expects behind the header (the layers' images follow one another in plan order)
 };
 
 // ---- time-major plan of the static TCResNet8 kernel (fused.hip: fused_layer_tm), shared by the host's layout and the kernel ----
@@ -296,6 +299,28 @@ __host__ __device__ constexpr bool fused_tm_deal_fits(const FusedTmDeal& d, cons
     for (int w = 0; w < nw; ++w) if (d.n[w] > kTmMaxJobs) return false;
     return true;
 }
+
+// ---- fragment-ordered weight image of the frozen table (tcr_net_fold_weights) ----
+// Behind the scale / shift block (rounded up to 4 floats) the table carries a header of kWimgHeader words -- {kWimgMagic when the image is
+// valid, its size in floats, 0, 0} -- and behind that every conv layer's weights in the order a lane of the fused kernel reads them:
+// [layer][row tile m][tap j][channel-quad group c4 / 4][lane 0..63][width], width = 4 channel quads (the last group of a tap: C4 % 4 when
+// that is not 0), lane = 16 q + r holding W[j][4 c4 + q][min(16 m + r, Cout - 1)].  A lane's fragments for four consecutive channel
+// quads of a tap are one 16-byte load at a constant lane offset, a wave's request 1 KB contiguous.
+constexpr unsigned kWimgMagic = 0x474d4957u;
+constexpr int kWimgHeader = 4;
+__host__ __device__ constexpr int wimg_layer_floats(const int k, const int cin, const int cout) { return ((cout + 15) / 16) * k * (cin / 4) * 64; }
+// float offset inside a layer's image of (row tile m, tap j, channel quad c4, lane)
+__host__ __device__ constexpr int wimg_index(const int k, const int cin, const int m, const int j, const int c4, const int lane) {
+    const int C4 = cin / 4, g = c4 / 4, wd = C4 - 4 * g < 4 ? C4 - 4 * g : 4;
+    return ((m * k + j) * C4 + 4 * g) * 64 + lane * wd + (c4 - 4 * g);
+}
+struct WimgFoldArgs {
+    const float* params;
+    float* header;              // kWimgHeader words, the image behind them
+    int n, total;               // conv layers, floats of the whole image
+    int k[kFusedMaxLayers], cin[kFusedMaxLayers], cout[kFusedMaxLayers], w_off[kFusedMaxLayers], img_off[kFusedMaxLayers];
+};
+int launch_wimg_fold(const WimgFoldArgs& a, hipStream_t s);
 
 constexpr int kSmallBatchMax = 64;      // batches up to this many utterances take the small-batch (latency) kernel where it exists
 // returns 1 when the launch could not be configured (caller falls back to the per-layer kernels)

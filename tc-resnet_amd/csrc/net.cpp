@@ -369,10 +369,30 @@ static int conv_forward_with_down(const ConvLayer& la, const ConvLayer& ld, cons
     return launch_conv_mfma_with_down(a, params + ld.w_off, yd, scd, shd, la.pad_lo, epi, s);
 }
 
+// The frozen table: scale / shift of every BN unit, then (kernels.h "weight image") a header and the conv weights in fragment order.
+static int64_t ss_floats(const tcr_net& net) {
+    int64_t n = 0;
+    for (const ConvLayer& l : net.layers) if (l.bn) n += 2 * l.c_pad;
+    return n;
+}
+static int64_t wimg_header_off(const tcr_net& net) { return align_up(ss_floats(net), 4); }
+// floats of the image; 0: this network has none (a layer whose input channels are no multiple of 4, or an arena beyond 32-bit offsets)
+static int64_t wimg_floats_of(const tcr_net& net) {
+    int64_t n = 0;
+    if (net.param_floats >= (int64_t)1 << 31 || (int)net.units.size() > kFusedMaxLayers) return 0;
+    for (int li : net.units) {
+        const ConvLayer& l = net.layers[li];
+        if (l.cin % 4 != 0) return 0;
+        n += wimg_layer_floats(l.k, l.cin, l.cout);
+    }
+    return n < ((int64_t)1 << 29) ? n : 0;
+}
+
 // Whole-network fused launch (fused.hip): three rotating LDS buffers per utterance,
 //   R0: features, later the `down` outputs;  R1: conv0 / block outputs;  R2: conv_a outputs.
 // plan != nullptr: nothing is launched; the plan is described there (tcr_net_fused_plan) and *plan_n set to the ints written.
-static int forward_infer_fused(const tcr_net& net, const float* params, const float* ss, const float* feat, int batch,
+// wimg: header of the weight image behind a frozen table's scale / shift block (nullptr: `ss` is no such table)
+static int forward_infer_fused(const tcr_net& net, const float* params, const float* ss, const float* wimg, const float* feat, int batch,
                                float* logits, float* probs, float* ranges, hipStream_t s, int* plan = nullptr, int plan_cap = 0, int* plan_n = nullptr) {
     FusedArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -385,6 +405,7 @@ static int forward_infer_fused(const tcr_net& net, const float* params, const fl
         L.k = l.k; L.stride = l.stride; L.cin = l.cin; L.cout = l.cout; L.tin = l.tin; L.tout = l.tout; L.pad_lo = l.pad_lo;
         L.relu = l.relu; L.in_buf = in_buf; L.out_buf = out_buf; L.res_buf = res_buf;
         L.w_off = (int)l.w_off; L.ss_off = (int)l.ss_off; L.c_pad = l.c_pad;
+        a.wimg_floats += wimg_layer_floats(l.k, l.cin, l.cout);       // (units in forward order: the image's layer order, wimg_floats_of)
         grow(out_buf, l.cout, l.tout);
         return l.cin % 4 == 0;
     };
@@ -485,7 +506,8 @@ static int forward_infer_fused(const tcr_net& net, const float* params, const fl
     if (lds > 160 * 1024) return 1;
     // the head scratch (pooled + logits) lives in a buffer other than the feature buffer
     if ((int64_t)group * (net.feat_c + net.cfg.num_classes + 2) > (int64_t)group * sz[2] && (int64_t)group * (net.feat_c + net.cfg.num_classes + 2) > (int64_t)group * sz[0]) return 1;
-    a.params = params; a.ss = ss; a.feat = feat; a.logits = logits; a.probs = probs; a.ranges = ranges;
+    a.params = params; a.ss = ss; a.feat = feat;
+    a.wimg = a.wimg_floats == wimg_floats_of(net) ? wimg : nullptr; a.logits = logits; a.probs = probs; a.ranges = ranges;
     a.batch = batch; a.group = group; a.n_groups = ceil_div(batch, group);
     a.buf_off[0] = 0; a.buf_off[1] = group * sz[0]; a.buf_off[2] = group * (sz[0] + sz[1]);
     a.buf_sz[0] = sz[0]; a.buf_sz[1] = sz[1]; a.buf_sz[2] = sz[2];
@@ -533,10 +555,27 @@ static int fold_bn(const tcr_net& net, const float* params, const float* stats, 
     }
     return launch_bn_fold(f, s);
 }
-static int64_t ss_floats(const tcr_net& net) {
-    int64_t n = 0;
-    for (const ConvLayer& l : net.layers) if (l.bn) n += 2 * l.c_pad;
-    return n;
+// conv weights of every unit -> the table's image; then the header that makes it valid
+static int fold_weights(const tcr_net& net, const float* params, float* frozen, hipStream_t s) {
+    WimgFoldArgs f;
+    std::memset(&f, 0, sizeof(f));
+    f.params = params; f.header = frozen + wimg_header_off(net);
+    for (int li : net.units) {
+        const ConvLayer& l = net.layers[li];
+        f.k[f.n] = l.k; f.cin[f.n] = l.cin; f.cout[f.n] = l.cout; f.w_off[f.n] = (int)l.w_off; f.img_off[f.n] = f.total;
+        f.total += wimg_layer_floats(l.k, l.cin, l.cout);
+        ++f.n;
+    }
+    return launch_wimg_fold(f, s);
+}
+// the header's flag word cleared: the table is scale / shift only and every forward reads the conv weights from `params`
+static int clear_wimg_flag(const tcr_net& net, float* frozen, hipStream_t s) {
+    if (hipMemsetAsync(frozen + wimg_header_off(net), 0, kWimgHeader * sizeof(float), s) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("frozen table: cannot clear the weight image's header");
+        return TCR_ERR_HIP;
+    }
+    return TCR_OK;
 }
 }  // namespace tcr
 
@@ -553,15 +592,23 @@ extern "C" int tcr_net_forward_infer(const tcr_net* net, const float* params, co
 extern "C" int tcr_net_fused_plan(const tcr_net* net, int batch, int* out, int cap) {
     TCR_REQUIRE(net && out && batch > 0, "tcr_net_fused_plan: bad arguments");
     int n = 0;
-    const int rc = tcr::forward_infer_fused(*net, nullptr, nullptr, nullptr, batch, nullptr, nullptr, nullptr, nullptr, out, cap, &n);
+    const int rc = tcr::forward_infer_fused(*net, nullptr, nullptr, nullptr, nullptr, batch, nullptr, nullptr, nullptr, nullptr, out, cap, &n);
     return rc == 1 ? 0 : (rc == TCR_OK ? n : rc);
 }
 
-extern "C" int64_t tcr_net_frozen_floats(const tcr_net* net) { return net ? ss_floats(*net) : 0; }
+extern "C" int64_t tcr_net_frozen_floats(const tcr_net* net) { return net ? wimg_header_off(*net) + kWimgHeader + wimg_floats_of(*net) : 0; }
 
 extern "C" int tcr_net_fold_bn(const tcr_net* net, const float* params, const float* stats, float* frozen_ss, void* stream) {
     TCR_REQUIRE(net && params && stats && frozen_ss, "tcr_net_fold_bn: null argument");
+    TCR_TRY(clear_wimg_flag(*net, frozen_ss, static_cast<hipStream_t>(stream)));
     return fold_bn(*net, params, stats, frozen_ss, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int tcr_net_fold_weights(const tcr_net* net, const float* params, float* frozen_ss, void* stream) {
+    TCR_REQUIRE(net && params && frozen_ss, "tcr_net_fold_weights: null argument");
+    TCR_REQUIRE(reinterpret_cast<uintptr_t>(frozen_ss) % 16 == 0, "tcr_net_fold_weights: the table must start on a 16-byte boundary");
+    if (wimg_floats_of(*net) == 0) return clear_wimg_flag(*net, frozen_ss, static_cast<hipStream_t>(stream));     // no image for this network: params stay the source
+    return fold_weights(*net, params, frozen_ss, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int tcr_net_forward_frozen(const tcr_net* net, const float* params, const float* frozen_ss, const float* feat,
@@ -581,6 +628,7 @@ extern "C" int tcr_forward_waveform(const tcr_frontend_cfg* cfg, const void* pla
     TCR_TRY(tcr_frontend_fwd(cfg, plan_dev, wav, batch, feat, stream));
     if (refold) {
         TCR_REQUIRE(params && stats, "tcr_forward_waveform: refold needs params and stats");
+        TCR_TRY(clear_wimg_flag(*net, frozen_ss, static_cast<hipStream_t>(stream)));
         TCR_TRY(fold_bn(*net, params, stats, frozen_ss, static_cast<hipStream_t>(stream)));
     }
     return forward_infer_impl(net, params, nullptr, frozen_ss, feat, batch, workspace, workspace_bytes, logits, probs, ranges, stream);
@@ -604,7 +652,7 @@ static int forward_infer_impl(const tcr_net* net, const float* params, const flo
     }
 
     if (tune_get(TCR_TUNE_NET_FUSED) != 1) {
-        const int rc = forward_infer_fused(*net, params, ss, feat, batch, logits, probs, ranges, s);
+        const int rc = forward_infer_fused(*net, params, ss, frozen_ss ? frozen_ss + wimg_header_off(*net) : nullptr, feat, batch, logits, probs, ranges, s);
         if (rc != 1) return rc;         // launched (or failed); 1 == does not fit -> per-layer kernels below
     }
 

@@ -49,7 +49,14 @@ class FrozenModel:
             self.engine = TCResNet(meta["scope"], meta["channels"], meta["width"], meta["height"], meta["num_classes"],
                                    bn_decay=meta["bn_decay"], bn_eps=meta["bn_eps"], lib=lib, device=device)
             self.engine.load_state_dict({k: v for k, v in constants.items() if k.endswith("/weights")}, strict=False)
-            self.frozen_ss = torch.from_numpy(np.ascontiguousarray(constants["__folded_batch_norm__"])).to(self.engine.device)
+            ss = np.ascontiguousarray(constants["__folded_batch_norm__"], dtype=np.float32).reshape(-1)
+            full = int(self.engine.lib.tcr_net_frozen_floats(self.engine._h))
+            if ss.size < full:      # the artifact stores scale / shift only: room for the weight image behind them
+                ss = np.concatenate([ss, np.zeros(full - ss.size, np.float32)])
+            self.frozen_ss = torch.from_numpy(ss).to(self.engine.device)
+            # the conv weights are in `params` now and an artifact's never change: their fragment-ordered image, once (the table's flag set)
+            self.engine.lib.check(self.engine.lib.tcr_net_fold_weights(self.engine._h, self.engine.params.data_ptr(), self.frozen_ss.data_ptr(),
+                                                                       self.engine._stream()), "tcr_net_fold_weights")
         elif fam == "dscnn":
             self.engine = DSCNN(meta["size"], meta["height"], meta["width"], meta["num_classes"], lib=lib, device=device)
             self.engine.load_state_dict(constants)
@@ -155,7 +162,7 @@ def export_frozen(model, include_preprocess: bool, inputs: List[TensorSpec], out
         meta.update(family="tcresnet", scope=eng.scope, channels=[int(c) for c in eng.channels], bn_decay=float(eng.cfg.bn_decay),
                     bn_eps=float(eng.cfg.bn_eps))
         consts = {k: v for k, v in sd.items() if k.endswith("/weights")}
-        consts["__folded_batch_norm__"] = eng.fold_bn().cpu().numpy()
+        consts["__folded_batch_norm__"] = eng.fold_bn()[:eng.n_stat].cpu().numpy()        # scale / shift only (2 x c_pad per BN unit, as the moving statistics): the loader rebuilds the weight image
     elif isinstance(eng, DSCNN):
         meta.update(family="dscnn", size=eng.size)
         consts = dict(sd)

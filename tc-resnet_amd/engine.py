@@ -404,7 +404,14 @@ class TCResNet(_Network):
     def model_ref(self, aux: Optional[torch.Tensor] = None) -> _lib.ModelRef:
         """The tcr_model_ref of a detection call: (family, handle, params, `aux`), `aux` the folded BN table the call reads (`fold_bn`'s
         layout); None for the size queries and init, which read no weights."""
+        self._check_table(aux)
         return _lib.ModelRef(self.FAMILY, self._h.value, self.params.data_ptr(), _ptr(aux))
+
+    def _check_table(self, table: Optional[torch.Tensor]):
+        """A frozen table is read up to `tcr_net_frozen_floats` (the weight image's header lies behind scale / shift): a shorter one is an error."""
+        if table is not None and table.numel() < self.lib.tcr_net_frozen_floats(self._h):
+            raise TcrError(f"frozen table of {table.numel()} floats, this network's has {self.lib.tcr_net_frozen_floats(self._h)} "
+                           "(tcr_net_frozen_floats): allocate it by `fold_bn()` or load the artifact through deploy.FrozenModel")
 
     def _folded_table(self) -> torch.Tensor:
         """Eval-mode BN folded to (scale, shift) ONCE per weight version (the fold used to be a launch in front of every eval
@@ -421,6 +428,9 @@ class TCResNet(_Network):
                         cur.wait_stream(st)
             self.lib.check(self.lib.tcr_net_fold_bn(self._h, self.params.data_ptr(), self.stats.data_ptr(), self._fold_ss.data_ptr(),
                                                     self._stream()), "tcr_net_fold_bn")
+            # (the conv weights in the fused kernel's fragment order, behind scale / shift: same version key, same event)
+            self.lib.check(self.lib.tcr_net_fold_weights(self._h, self.params.data_ptr(), self._fold_ss.data_ptr(), self._stream()),
+                           "tcr_net_fold_weights")
             self._fold_key = key
             self._fold_readers = {}
             self._fold_waited = set()
@@ -490,6 +500,8 @@ class TCResNet(_Network):
                                                      ws.data_ptr(), ws.numel() * 4, logits.data_ptr(), probs.data_ptr(), _ptr(ranges),
                                                      self._stream()), "tcr_forward_waveform")
         if refold:          # the call refolded in line (on the fold stream, no other readers): other streams order themselves behind THIS fold
+            # (the in-line fold wrote scale / shift and cleared the weight image's flag: the image of this weight version, in front of the event)
+            self.lib.check(self.lib.tcr_net_fold_weights(self._h, self.params.data_ptr(), ss.data_ptr(), self._stream()), "tcr_net_fold_weights")
             self._fold_key = ver
             self._fold_readers = {}
             self._fold_waited = set()
@@ -543,6 +555,7 @@ class TCResNet(_Network):
         """Eval forward from constants only (conv / fc weights of the arena + the folded table); bitwise forward_infer."""
         self._check_feat(feat)
         self._check_tensor(frozen_ss, "frozen table")
+        self._check_table(frozen_ss)
         b = feat.shape[0]
         ws = self.workspace(b, False)
         logits, probs = self._outputs(b)
