@@ -904,6 +904,43 @@ int tcr_compose(int n_signals, const int64_t* sample_offsets /* DEVICE [N + 1] *
                 const int64_t* bg_len, const int64_t* bg_phase, const float* bg_vol /* [N] or NULL */, float* out /* or NULL */,
                 int16_t* out_pcm /* or NULL */, void* stream);
 
+/* Reverberation: every clip of a table convolved with a room impulse response out of a bank, so that a corpus can vary the room
+ * as tcr_compose varies the noise.  Every pointer is device memory; everything is enqueued on `stream` -- no copy, no wait.
+ *
+ * tcr_reverb: n_clips inputs; clip j is the n = in_len[j] (int64) samples from in[in_off[j]] (int64) on -- in_format 1: int16,
+ * decoded as (float)v * (1 / 32768.f), exact; in_format 0: float32, finite (precondition).  The bank: response r is the
+ * L = ir_len[r] (int32) float32 taps h[0 .. L - 1] from ir[ir_off[r]] (int64) on, finite, 1 <= L <= TCR_REVERB_TAPS_MAX; clip j
+ * uses r = clip_ir[j] (int32).  Clip j writes the m = out_off[j + 1] - out_off[j] outputs out_off[j] .. of the packed output
+ * (out_off int64 [n_clips + 1], from 0, non-decreasing); any m >= 0 is allowed, outputs at or beyond n + L - 1 are 0.  Output i:
+ *     y[i] = the fmaf chain from 0.f over the input index jj ascending, jj = max(0, i - L + 1) .. min(i, n - 1):
+ *            acc = fmaf(h[i - jj], x[jj], acc)
+ * one chain per output, one rounding per product: the k-ordered chain of v_mfma_f32_16x16x4_f32.  A zero-padded term
+ * fmaf(0, finite, acc) leaves acc's bits alone, so a sample's bits do not depend on the tile, the launch, the clip's neighbours or
+ * where the clip and the response lie in their buffers.
+ * out (float32, packed, or NULL): y.  out_pcm (int16, packed, or NULL): tcr_mine_gather's rounding of y,
+ * clamp(rint(y * 32768), -32768, 32767) with ties to even -- the response [1.0f] reproduces an int16 clip byte for byte.
+ * tile_off (int64 [n_clips + 1]): the prefix sums of ceil(m_j / TCR_REVERB_TILE) from 0, total_tiles == tile_off[n_clips], which
+ * the host knows (a precondition, like tcr_compose's total_samples).  in_samples and ir_floats are the element counts of `in` and
+ * `ir`: no load touches anything outside them, whatever the tables hold.
+ * Preconditions (the Python layer checks them): 0 <= clip_ir[j] < the bank's size, 1 <= ir_len[r] <= TCR_REVERB_TAPS_MAX, clips
+ * inside in[0 .. in_samples) and responses inside ir[0 .. ir_floats), out / out_pcm of out_off[n_clips] elements.
+ * How: one launch, one workgroup per tile of TCR_REVERB_TILE outputs, which finds its clip by a binary search of tile_off through
+ * scalar loads, so the work is proportional to the tiles and one-second clips and a ten-minute recording go in the same call.  The
+ * convolution is a product with a banded Toeplitz matrix on the exact-f32 matrix core, the k loop over the input index ascending in
+ * stages of TCR_REVERB_STAGE input samples staged through LDS; stages and 16-sample groups that hold only padding are skipped, so
+ * the cost is about outputs x min(L, n + TCR_REVERB_TILE) multiply-adds.  Stores at a clip's ends are element-wise.
+ * n_clips == 0 or total_tiles == 0: a successful no-op.
+ * Refused (TCR_ERR_ARG, tcr_last_error; nothing is launched, nothing written): out and out_pcm both NULL, n_clips < 0, a null in /
+ * in_off / in_len / ir / ir_off / ir_len / clip_ir / out_off / tile_off, an in_format other than 0 and 1, an out or ir that is not
+ * 4-byte aligned (out_pcm: 2-byte; in: its element), a negative total_tiles / in_samples / ir_floats, 2^31 tiles or clips or more. */
+#define TCR_REVERB_TILE 4096
+#define TCR_REVERB_STAGE 1024
+#define TCR_REVERB_TAPS_MAX 16384
+int tcr_reverb(int64_t n_clips, const void* in, int in_format, int64_t in_samples, const int64_t* in_off, const int64_t* in_len,
+               const float* ir, int64_t ir_floats, const int64_t* ir_off, const int32_t* ir_len, const int32_t* clip_ir,
+               const int64_t* out_off /* [n_clips + 1] */, const int64_t* tile_off /* [n_clips + 1] */, int64_t total_tiles,
+               float* out /* or NULL */, int16_t* out_pcm /* or NULL */, void* stream);
+
 /* Phrase detection: multi-word phrases ("go left", "stop ... no") scored from a scan's word posteriors, as a transform of posteriors --
  * values [steps][num_classes] in, out [steps][P + 1] phrase posteriors out, the last column a background class -- so that
  * tcr_detect_redetect, tcr_detect_sweep(_ragged), tcr_detect_grid and tcr_mine_* apply to phrases unchanged with num_classes = P + 1.

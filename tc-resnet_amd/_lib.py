@@ -17,6 +17,9 @@ GRID_TILE = 256            # == TCR_GRID_TILE: steps per tile of tcr_detect_grid
 MINE_TILE = 256            # == TCR_MINE_TILE: steps per tile of tcr_mine_peaks
 MINE_RADIUS_MAX = 2560     # == TCR_MINE_RADIUS_MAX: the largest radius tcr_mine_peaks takes
 COMPOSE_TILE = 2048        # == TCR_COMPOSE_TILE: packed samples per workgroup of tcr_compose
+REVERB_TILE = 4096         # == TCR_REVERB_TILE: outputs per workgroup of tcr_reverb
+REVERB_STAGE = 1024        # == TCR_REVERB_STAGE: input samples of one LDS stage of tcr_reverb's k loop
+REVERB_TAPS_MAX = 16384    # == TCR_REVERB_TAPS_MAX: the longest impulse response tcr_reverb takes
 PHRASE_TILE = 256          # == TCR_PHRASE_TILE: steps per tile of tcr_phrase_scores
 PHRASE_MAX = 64            # == TCR_PHRASE_MAX: phrases per call
 PHRASE_MAX_WORDS = 8       # == TCR_PHRASE_MAX_WORDS
@@ -253,6 +256,7 @@ _PROTOTYPES = {
     "tcr_mine_gather": (C.c_int, [C.c_int, _P, _P, C.c_int64, _P, _P, C.c_int, _P, _P, _P]),
     "tcr_pcm_energy": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P]),
     "tcr_compose": (C.c_int, [C.c_int, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "tcr_reverb": (C.c_int, [C.c_int64, _P, C.c_int, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P]),
     "tcr_phrase_window_max": (C.c_int, [C.c_int]),
     "tcr_phrase_scores": (C.c_int, [C.c_int, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.POINTER(PhraseCfg), _P, _P]),
     "tcr_phrase_scores_ragged": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int, _P, _P, C.POINTER(PhraseCfg), _P, _P]),

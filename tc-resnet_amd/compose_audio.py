@@ -5,6 +5,7 @@ the device (`composing.Composer`, tcr_compose), written as WAV files with the ev
                             [--frames_per_step k] [--window_stride_ms MS] [--sample_rate HZ] | [--step_samples M]
                             [--min_gap_ms MS] [--max_gap_ms MS] [--keywords l0,l1,...] [--foreground_gain G] [--background_volume V]
                             [--snr_db X | LO:HI] [--seed SEED] [--prefix NAME]
+                            [--rir_dir DIR | --rir_rt60 X | LO:HI [--rir_count N]] [--rir_probability P] [--rir_tail_ms MS] [--rir_seed S]
 
 D/<split>/<label>/*.wav and D/<split>/_background_noise_/*.wav are read as training reads them (`SingleLabelAudioDataWrapper`: every
 clip decoded once into an int16 pool on the device).  Every recording is --seconds long, rounded down to whole steps of
@@ -12,6 +13,12 @@ clip decoded once into an int16 pool on the device).  Every recording is --secon
 `Composer.plan`'s, from one generator seeded with --seed: per recording a background recording and its phase, then clip, gap, clip,
 gap .. with gaps of --min_gap_ms .. --max_gap_ms, clips from the --keywords (default: every label), each at --foreground_gain or at
 --snr_db over the background (a number, or LO:HI drawn per clip).  --min_gap_ms has to exceed the --tolerance_ms of the sweep.
+
+Reverberation (`Composer.reverberated`, tcr_reverb): with --rir_dir (every *.wav of DIR is a room impulse response, sorted by name,
+resampled to --sample_rate where needed) or --rir_rt60 (--rir_count synthetic responses, default 16, RT60 in seconds: a number, or
+LO:HI drawn per response) every clip is convolved on the device with a response drawn from the bank, or left dry at probability
+1 - --rir_probability; --rir_tail_ms caps the tail a wet clip -- and with it its event -- is lengthened by (default: the whole
+response); --rir_seed seeds the bank and the draws.  --snr_db then counts the wet clips' power.
 
 Files: OUT/<prefix>_<n>.wav (16-bit mono) and OUT/events.csv (file,start_ms,end_ms,label with label names), directly usable as
     python sweep_audio.py --frozen M --wav OUT/*.wav --events OUT/events.csv --ragged --labels <the dataset's label names>
@@ -28,9 +35,11 @@ from typing import List, Optional
 if __package__ in (None, ""):           # run as a script: import the package through the repository's shim
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from tcresnet_amd.composing import Composer
+    from tcresnet_amd.reverberation import ImpulseResponses
     from tcresnet_amd.datasets.audio_data_wrapper import SingleLabelAudioDataWrapper
 else:
     from .composing import Composer
+    from .reverberation import ImpulseResponses
     from .datasets.audio_data_wrapper import SingleLabelAudioDataWrapper
 
 
@@ -53,6 +62,12 @@ def parse_arguments(arguments: Optional[List[str]] = None):
     p.add_argument("--snr_db", default=None, help="X or LO:HI: the clips' gain from their power over the background's")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--prefix", default="rec", help="the files are <prefix>_<n>.wav")
+    p.add_argument("--rir_dir", default=None, help="a directory of room impulse responses (*.wav): the clips are reverberated")
+    p.add_argument("--rir_rt60", default=None, help="X or LO:HI seconds: synthetic impulse responses instead of --rir_dir")
+    p.add_argument("--rir_count", type=int, default=None, help="the number of synthetic responses (default 16; with --rir_rt60)")
+    p.add_argument("--rir_probability", type=float, default=None, help="the share of clips that get a response (default 1)")
+    p.add_argument("--rir_tail_ms", type=float, default=None, help="the longest tail a clip is lengthened by (default: the response's)")
+    p.add_argument("--rir_seed", type=int, default=None, help="seeds the synthetic bank and the draws per clip (default 0)")
     return p.parse_args(arguments)
 
 
@@ -76,7 +91,44 @@ def check_arguments(args):
         if len(parts) not in (1, 2) or (len(parts) == 2 and parts[1] < parts[0]):
             raise SystemExit(f"--snr_db {args.snr_db}: expected X or LO:HI with HI >= LO")
         args.snr_db = parts[0] if len(parts) == 1 else (parts[0], parts[1])
+    if args.rir_dir is not None and args.rir_rt60 is not None:
+        raise SystemExit("--rir_dir and --rir_rt60 exclude each other: measured responses or synthetic ones")
+    if args.rir_dir is None and args.rir_rt60 is None:
+        for flag in ("rir_count", "rir_probability", "rir_tail_ms", "rir_seed"):
+            if getattr(args, flag) is not None:
+                raise SystemExit(f"--{flag} needs --rir_dir or --rir_rt60: there is nothing to reverberate with")
+    if args.rir_count is not None and args.rir_rt60 is None:
+        raise SystemExit("--rir_count counts synthetic responses: it needs --rir_rt60 (--rir_dir takes every file)")
+    if args.rir_count is not None and args.rir_count < 1:
+        raise SystemExit(f"--rir_count must be >= 1 (got {args.rir_count})")
+    if args.rir_probability is not None and not 0.0 <= args.rir_probability <= 1.0:
+        raise SystemExit(f"--rir_probability must be in [0, 1] (got {args.rir_probability})")
+    if args.rir_tail_ms is not None and not args.rir_tail_ms >= 0:
+        raise SystemExit(f"--rir_tail_ms must be >= 0 (got {args.rir_tail_ms})")
+    if args.rir_rt60 is not None:
+        try:
+            parts = [float(x) for x in str(args.rir_rt60).split(":")]
+        except ValueError:
+            parts = []
+        if len(parts) not in (1, 2) or not parts[0] > 0 or (len(parts) == 2 and parts[1] < parts[0]):
+            raise SystemExit(f"--rir_rt60 {args.rir_rt60}: expected X or LO:HI seconds with 0 < LO <= HI")
+        args.rir_rt60 = parts[0] if len(parts) == 1 else (parts[0], parts[1])
     return args
+
+
+def open_responses(args, device):
+    """The bank --rir_dir or --rir_rt60 asks for on `device`, or None."""
+    if args.rir_dir is None and args.rir_rt60 is None:
+        return None
+    seed = args.rir_seed or 0
+    if args.rir_dir is not None:
+        if not os.path.isdir(args.rir_dir):
+            raise SystemExit(f"--rir_dir {args.rir_dir}: no such directory")
+        paths = sorted(os.path.join(args.rir_dir, f) for f in os.listdir(args.rir_dir) if f.lower().endswith(".wav"))
+        if not paths:
+            raise SystemExit(f"--rir_dir {args.rir_dir}: no *.wav files")
+        return ImpulseResponses.from_files(paths, args.sample_rate, device=device)
+    return ImpulseResponses.synthetic(args.rir_count or 16, args.rir_rt60, args.sample_rate, seed=seed, device=device)
 
 
 def open_dataset(args) -> SingleLabelAudioDataWrapper:
@@ -94,6 +146,9 @@ def open_dataset(args) -> SingleLabelAudioDataWrapper:
 def main(args) -> int:
     args = check_arguments(args)
     composer = Composer.from_dataset(open_dataset(args))
+    irs = open_responses(args, composer.device)
+    if irs is not None:
+        composer = composer.reverberated(irs, 1.0 if args.rir_probability is None else args.rir_probability, args.rir_tail_ms, args.rir_seed or 0)
     names = composer.label_names
     classes = None
     if args.keywords:
@@ -114,8 +169,10 @@ def main(args) -> int:
     for evs in rec.events:
         for _, _, label in evs:
             counts[names[label]] = counts.get(names[label], 0) + 1
-    print(json.dumps({"recordings": len(paths), "seconds": float(plan.total_samples) / plan.sample_rate, "events": counts,
-                      "output_dir": args.output_dir}), file=sys.stderr)
+    info = {"recordings": len(paths), "seconds": float(plan.total_samples) / plan.sample_rate, "events": counts, "output_dir": args.output_dir}
+    if irs is not None:
+        info.update(responses=len(irs), wet_clips=int((composer.ir_index >= 0).sum()))
+    print(json.dumps(info), file=sys.stderr)
     return 0
 
 

@@ -190,6 +190,20 @@ class Composer:
         """Everything from a `SingleLabelAudioDataWrapper`: its clip pool, labels, label names and background pool."""
         return cls(wrapper.pool, wrapper.labels, wrapper.label_names, wrapper.background, int(wrapper.args.sample_rate))
 
+    def reverberated(self, irs, probability: float = 1.0, tail_ms: Optional[float] = None, seed: int = 0) -> "Composer":
+        """A composer over the wet pool (`reverberation.reverberate`, on the device): the same labels, label names and background;
+        every clip convolved with a response drawn uniformly from `irs` (an `ImpulseResponses`), or left dry at probability
+        1 - probability, the draws from np.random.default_rng(seed) (`wet.ir_index`: the response per clip, -1 dry).  A wet clip is
+        min(L - 1, tail_ms) samples longer than the dry one, and a plan's events cover that whole extent, tail included: a small
+        tail_ms tightens the events to the audible part of the decay (None keeps the whole response).  `energies()` and snr_db act
+        on the wet clips."""
+        from .reverberation import draw_responses, reverberate
+        idx = draw_responses(len(self.pool), len(irs), probability, seed)
+        wet = Composer(reverberate(self.pool, irs, idx, tail_ms, self.sample_rate), self.labels, self.label_names, self.background,
+                       self.sample_rate)
+        wet.ir_index = idx
+        return wet
+
     def energies(self) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """(per clip, per background recording or None) the int64 sums of squared samples (tcr_pcm_energy), computed once."""
         if self._energies is None:

@@ -597,3 +597,4 @@ int launch_frontend_pk3_stream(int nc, const FrontendArgs& a, int n_items, hipSt
 #include "resample.hip"
 #include "stream_cascade.hip"
 #include "dtw.hip"
+#include "reverb.hip"
