@@ -331,6 +331,21 @@ void tcr_g2d_destroy(tcr_g2d* g);
  * A fully connected layer over a flattened [h][w][c] activation is the VALID conv with kh = h, kw = w. */
 int tcr_g2d_conv(tcr_g2d* g, int in, int kh, int kw, int cout, int sh, int sw, int dh, int dw, int valid_padding, int relu,
                  const char* weights_name, const char* biases_name);
+/* tf.nn.depthwise_conv2d with channel multiplier 1 -- slim.separable_conv2d(num_outputs=None, depth_multiplier=1) -- (+ bias, + ReLU):
+ * one kh x kw filter per channel, output channels = input channels C; no other multiplier is offered.  Window, padding and output
+ * size are exactly tcr_g2d_conv's (SAME pads with the extra element on the high side; dilation needs stride 1).  Weights
+ * [kh][kw][C][1] under `weights_name`, bias [C] under `biases_name` (NULL / "": none); both sit in the decayed arena by the name rule
+ * of every other variable.  With in(o, t) = o * stride + t * rate - pad_lo per dimension and positions outside the plane reading 0:
+ *   forward            y[n][c][oy][ox]  = act(bias[c] + sum_{i,j} x[n][c][in(oy, i)][in(ox, j)] * W[i][j][c])
+ *   data gradient      dx[n][c][iy][ix] += sum_{i,j} dy[n][c][(iy + pt - i*dh) / sh][(ix + pl - j*dw) / sw] * W[i][j][c]   (exact divisions only)
+ *   filter gradient    dW[i][j][c]      = sum_{n,oy,ox} x[n][c][in(oy, i)][in(ox, j)] * dy[n][c][oy][ox]
+ * Each forward output is one fused-multiply-add chain over the taps in (i, then j) order, so its bits do not depend on how the plane
+ * is tiled; the filter gradient is summed per utterance chunk and the chunks in a fixed order (no atomics): repeated runs give the
+ * same bits.  Operand pointers need 4-byte alignment only.  Refused at construction (message in tcr_last_error): kh * kw > 1024 taps;
+ * min((kh - 1) * dh + 1, h) * w > 4096 floats (the rows one output row reads must fit one staged tile -- the plane's HEIGHT is not
+ * limited); a kernel that does not fit the input under VALID padding; dilation together with a stride. */
+int tcr_g2d_depthwise_conv(tcr_g2d* g, int in, int kh, int kw, int sh, int sw, int dh, int dw, int valid_padding, int relu,
+                           const char* weights_name, const char* biases_name);
 /* slim.batch_norm(fused): optional beta (center) / gamma (scale), optional ReLU; variables `<prefix>/gamma|beta|moving_*`. */
 int tcr_g2d_batch_norm(tcr_g2d* g, int in, int center, int scale, int relu, float decay, float eps, const char* prefix);
 /* slim.avg_pool2d / tf.nn.max_pool; kh <= 0: the window is the whole plane (global pool). */

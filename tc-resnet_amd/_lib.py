@@ -166,6 +166,8 @@ _PROTOTYPES = {
     "tcr_g2d_destroy": (None, [_P]),
     "tcr_g2d_conv": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p,
                                C.c_char_p]),
+    "tcr_g2d_depthwise_conv": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p,
+                                         C.c_char_p]),
     "tcr_g2d_batch_norm": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_char_p]),
     "tcr_g2d_pool": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "tcr_g2d_add": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),

@@ -21,7 +21,7 @@ OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIBDIR, "libtcresnet_hip.so")
 SOURCES = ["tcr_common.cpp", "frontend_plan.cpp", "frontend.hip", "frontend_pk.hip", "frontend_pk3.hip", "conv.hip", "mfma.hip", "bn.hip", "head.hip",
            "optim.hip", "net.cpp", "dscnn.hip", "dscnn_bwd.hip", "fused.hip", "train_fused.hip", "train_fused_bwd.hip", "bwd_lazy.hip", "augment.hip", "net2d_kernels.hip", "net2d.cpp"]
-HEADERS = ["stream.hip", "scan.hip", "sweep.hip", "detect_grid.hip", "scan_select.hip", "mine.hip", "compose.hip", "phrase.hip", "capture.hip", "resample.hip", "stream_cascade.hip", "dtw.hip", "reverb.hip", "detect_model.h", "tcr_common.h", "gfx950_isa.h", "fused_tc8_walk.inc", "frontend_plan.h", "frontend_args.h", "kernels.h", "net2d.h", os.path.join("..", "..", "include", "tcresnet_hip.h")]
+HEADERS = ["stream.hip", "scan.hip", "sweep.hip", "detect_grid.hip", "scan_select.hip", "mine.hip", "compose.hip", "phrase.hip", "capture.hip", "resample.hip", "stream_cascade.hip", "dtw.hip", "reverb.hip", "net2d_dw.hip", "detect_model.h", "tcr_common.h", "gfx950_isa.h", "fused_tc8_walk.inc", "frontend_plan.h", "frontend_args.h", "kernels.h", "net2d.h", os.path.join("..", "..", "include", "tcresnet_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-I", CSRC, "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-Wno-pass-failed"] + os.environ.get("TCR_BUILD_EXTRA", "").split()      # (diagnostic builds: extra -D flags)

@@ -13,7 +13,7 @@
 #include "net2d.h"
 
 namespace tcr {
-enum { G2D_CONV = 0, G2D_BN = 1, G2D_POOL = 2, G2D_ADD = 3, G2D_DROPOUT = 4, G2D_TFILT = 5, G2D_GSUM = 6 };
+enum { G2D_CONV = 0, G2D_BN = 1, G2D_POOL = 2, G2D_ADD = 3, G2D_DROPOUT = 4, G2D_TFILT = 5, G2D_GSUM = 6, G2D_DWCONV = 7 };
 
 struct G2dNode {
     int kind = 0, in0 = -1, in1 = -1;       // inputs: node ids, -1 = the network input
@@ -99,6 +99,10 @@ static G2dWorkspace carve2d(const tcr_g2d& g, int batch, bool train) {
             const int64_t wg = (int64_t)conv2d_wgrad_partial_floats(n.kh, n.kw, n.cin, n.c, batch);
             wgmax = wg > wgmax ? wg : wgmax;
         }
+        if (train && n.kind == G2D_DWCONV) {
+            const int64_t wg = (int64_t)dw2d_wgrad_partial_floats(n.kh, n.kw, n.c, batch);
+            wgmax = wg > wgmax ? wg : wgmax;
+        }
     }
     if (train) {
         w.grad_begin = o;
@@ -141,6 +145,17 @@ static Conv2dArgs conv_args(const tcr_g2d& g, const G2dNode& n, int batch) {
     return a;
 }
 
+static DwConv2dArgs dw_args(const tcr_g2d& g, const G2dNode& n, int batch) {
+    DwConv2dArgs a;
+    std::memset(&a, 0, sizeof(a));
+    int c, h, wd;
+    shape_of(g, n.in0, &c, &h, &wd);
+    a.batch = batch; a.c = n.c; a.h = h; a.w = wd; a.oh = n.h; a.ow = n.w;
+    a.kh = n.kh; a.kw = n.kw; a.sh = n.sh; a.sw = n.sw; a.dh = n.dh; a.dw = n.dw; a.pt = n.pt; a.pl = n.pl;
+    a.ppi = pp_of(h, wd); a.ppo = pp_of(n.h, n.w); a.relu = n.relu ? 1 : 0;
+    return a;
+}
+
 }  // namespace tcr
 
 // ---- construction -----------------------------------------------------------------------------------------------------------
@@ -169,6 +184,29 @@ extern "C" int tcr_g2d_conv(tcr_g2d* g, int in, int kh, int kw, int cout, int sh
     out_dim(h, (kh - 1) * dh + 1, sh, valid_padding != 0, &n.h, &n.pt);
     out_dim(w, (kw - 1) * dw + 1, sw, valid_padding != 0, &n.w, &n.pl);
     TCR_REQUIRE(n.h > 0 && n.w > 0, "tcr_g2d_conv: %dx%d kernel does not fit the %dx%d input", kh, kw, h, w);
+    n.relu = relu != 0; n.w_name = weights_name;
+    if (biases_name && biases_name[0]) { n.bias = true; n.b_name = biases_name; }
+    g->nodes.push_back(n);
+    return (int)g->nodes.size() - 1;
+}
+
+// tf.nn.depthwise_conv2d, channel multiplier 1 (slim.separable_conv2d(num_outputs=None, depth_multiplier=1)): net2d_dw.hip
+extern "C" int tcr_g2d_depthwise_conv(tcr_g2d* g, int in, int kh, int kw, int sh, int sw, int dh, int dw, int valid_padding, int relu,
+                                      const char* weights_name, const char* biases_name) {
+    G2D_CHECK_IN(g, in, "tcr_g2d_depthwise_conv");
+    TCR_REQUIRE(kh > 0 && kw > 0 && sh > 0 && sw > 0 && dh > 0 && dw > 0 && weights_name && weights_name[0], "tcr_g2d_depthwise_conv: bad argument");
+    TCR_REQUIRE((dh == 1 && dw == 1) || (sh == 1 && sw == 1), "tcr_g2d_depthwise_conv: dilation needs stride 1");
+    TCR_REQUIRE((int64_t)kh * kw <= dw2d_max_taps(), "tcr_g2d_depthwise_conv: %dx%d kernel has more than %d taps", kh, kw, dw2d_max_taps());
+    G2dNode n;
+    n.kind = G2D_DWCONV; n.in0 = in;
+    int c, h, w;
+    shape_of(*g, in, &c, &h, &w);
+    n.cin = c; n.c = c; n.kh = kh; n.kw = kw; n.sh = sh; n.sw = sw; n.dh = dh; n.dw = dw;
+    out_dim(h, (kh - 1) * dh + 1, sh, valid_padding != 0, &n.h, &n.pt);
+    out_dim(w, (kw - 1) * dw + 1, sw, valid_padding != 0, &n.w, &n.pl);
+    TCR_REQUIRE(n.h > 0 && n.w > 0, "tcr_g2d_depthwise_conv: %dx%d kernel does not fit the %dx%d input", kh, kw, h, w);
+    TCR_REQUIRE(dw2d_fits((kh - 1) * dh + 1, h, w), "tcr_g2d_depthwise_conv: a window of %d rows on a plane %d wide needs more than the %d floats a tile stages",
+                std::min((kh - 1) * dh + 1, h), w, dw2d_lds_floats());
     n.relu = relu != 0; n.w_name = weights_name;
     if (biases_name && biases_name[0]) { n.bias = true; n.b_name = biases_name; }
     g->nodes.push_back(n);
@@ -289,6 +327,16 @@ extern "C" int tcr_g2d_finalize(tcr_g2d* g, int logits_node) {
                     info(n.b_name, TCR_BETA, 0, o, n.c, {n.c});
                     o = al64(o + n.c + 64);
                 }
+            } else if (n.kind == G2D_DWCONV && pass == 0) {
+                const int64_t sz = (int64_t)n.kh * n.kw * n.c;
+                n.w_off = o;
+                info(n.w_name, TCR_WEIGHT, 0, o, sz, {n.kh, n.kw, n.c, 1});
+                o = al64(o + sz + 64);
+                if (n.bias) {
+                    n.b_off = o;
+                    info(n.b_name, TCR_BETA, 0, o, n.c, {n.c});
+                    o = al64(o + n.c + 64);
+                }
             } else if (n.kind == G2D_TFILT && pass == 0) {
                 const int64_t sz = (int64_t)n.c * n.cin;
                 n.w_off = o;
@@ -394,6 +442,12 @@ static int g2d_forward(const tcr_g2d* g, const float* params, float* stats, cons
                 Conv2dArgs a = conv_args(*g, n, batch);
                 a.x = in0; a.wgt = params + n.w_off; a.y = out; a.bias = n.bias ? params + n.b_off : nullptr;
                 TCR_TRY(launch_conv2d_fwd(a, s));
+                break;
+            }
+            case G2D_DWCONV: {
+                DwConv2dArgs a = dw_args(*g, n, batch);
+                a.x = in0; a.wgt = params + n.w_off; a.y = out; a.bias = n.bias ? params + n.b_off : nullptr;
+                TCR_TRY(launch_dw2d_fwd(a, s));
                 break;
             }
             case G2D_BN: {
@@ -577,6 +631,19 @@ static int g2d_backward(const tcr_g2d* g, const float* params, const float* x, i
                 if (gin0) {
                     a.x = G; a.y = gin0;
                     TCR_TRY(launch_conv2d_dgrad(a, s));
+                }
+                break;
+            }
+            case G2D_DWCONV: {
+                if (n.relu) TCR_TRY(relu_mask());
+                DwConv2dArgs a = dw_args(*g, n, batch);
+                a.wgt = params + n.w_off;
+                if (n.bias) TCR_TRY(launch_chan_sum2d(G, grads + n.b_off, batch, n.c, n.h * n.w, pp, s));
+                a.x = in0; a.dy = G;
+                TCR_TRY(launch_dw2d_wgrad(a, grads + n.w_off, base + w.wgrad, s));
+                if (gin0) {
+                    a.x = G; a.y = gin0;
+                    TCR_TRY(launch_dw2d_dgrad(a, s));
                 }
                 break;
             }

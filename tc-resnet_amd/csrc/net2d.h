@@ -17,6 +17,20 @@ struct Conv2dArgs {
     int relu;
 };
 
+// depthwise convolution, channel multiplier 1 (net2d_dw.hip)
+struct DwConv2dArgs {
+    const float* x;         // gathered operand: forward / wgrad: input [B][C][ppi]; dgrad: dy [B][C][ppo]
+    const float* wgt;       // [kh][kw][C][1]
+    float* y;               // forward: output [B][C][ppo] (assigned); dgrad: dx [B][C][ppi] (accumulated)
+    const float* bias;      // forward: [C] or nullptr
+    const float* dy;        // wgrad: [B][C][ppo]
+    int batch, c;
+    int h, w, oh, ow;       // input / output planes
+    int kh, kw, sh, sw, dh, dw, pt, pl;
+    int ppi, ppo;
+    int relu;
+};
+
 struct Pool2dArgs {
     const float* x;         // [planes][ppi]
     float* y;               // [planes][ppo]
@@ -44,6 +58,13 @@ int launch_conv2d_dgrad(const Conv2dArgs& a, hipStream_t s);
 int conv2d_wgrad_chunks(int batch);
 size_t conv2d_wgrad_partial_floats(int kh, int kw, int cin, int cout, int batch);
 int launch_conv2d_wgrad(const Conv2dArgs& a, float* dw, float* scratch, hipStream_t s);
+int dw2d_max_taps();                             // taps (kh * kw) a depthwise node may have
+int dw2d_lds_floats();                           // floats one tile stages
+bool dw2d_fits(int k_eff_h, int h, int w);       // one output row's window rows x the plane's width can be staged
+int launch_dw2d_fwd(const DwConv2dArgs& a, hipStream_t s);
+int launch_dw2d_dgrad(const DwConv2dArgs& a, hipStream_t s);
+size_t dw2d_wgrad_partial_floats(int kh, int kw, int c, int batch);
+int launch_dw2d_wgrad(const DwConv2dArgs& a, float* dw, float* scratch, hipStream_t s);
 int launch_chan_sum2d(const float* g, float* out, int batch, int c, int plane, int pp, hipStream_t s);
 int launch_pool2d_fwd(const Pool2dArgs& a, hipStream_t s);
 int launch_pool2d_bwd(const Pool2dArgs& a, hipStream_t s);

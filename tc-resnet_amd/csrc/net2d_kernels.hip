@@ -485,3 +485,6 @@ int launch_features_to_plane(const float* feat, float* out, int batch, int t, in
 }
 
 }  // namespace tcr
+
+// depthwise convolution (its own text: forward / data gradient / filter gradient of the G2D_DWCONV node)
+#include "net2d_dw.hip"

@@ -172,6 +172,7 @@ extern "C" const char* tcr_kernel_name(int index) {
         "stream_stage_kernel", "stream_init_kernel", "stream_detect_kernel",
         "scan_stage_kernel", "scan_gather_kernel", "scan_carry_kernel", "scan_scatter_kernel", "scan_smooth_kernel", "scan_suppress_kernel",
         "sweep_kernel",
+        "dw2d_kernel", "dw2d_wgrad_kernel",
     };
     const int n = (int)(sizeof(names) / sizeof(names[0]));
     return (index >= 0 && index < n) ? names[index] : nullptr;

@@ -763,6 +763,29 @@ class Graph2D(_Network):
         return self._relu(relu, self._node(self.lib.tcr_g2d_conv(self._h, inp, kh, kw, int(cout), sh, sw, dh, dw, int(padding == "VALID"),
                                                                  int(relu), weights_name.encode(), (biases_name or "").encode()), "tcr_g2d_conv"))
 
+    def __getattr__(self, name: str):
+        # `graph.depthwise_conv(...)` resolves here (Python calls this for names the instance and the class do not have).  Nothing is
+        # stored on the instance, so a graph holds no reference to itself and its handle goes with the last reference to it.
+        if name == "depthwise_conv":
+            return self._depthwise_conv
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
+    def _depthwise_conv(self, inp: int, kernel, weights_name: str, stride=(1, 1), rate=(1, 1), padding: str = "SAME", relu: bool = False,
+                        biases_name: Optional[str] = None, init="xavier") -> int:
+        """`graph.depthwise_conv(...)`: tf.nn.depthwise_conv2d with channel multiplier 1 (slim.separable_conv2d(num_outputs=None,
+        depth_multiplier=1)): one kh x kw filter per channel, variable [kh, kw, C, 1].  Window, padding and output size as `conv`."""
+        kh, kw = (kernel, kernel) if isinstance(kernel, int) else kernel
+        sh, sw = (stride, stride) if isinstance(stride, int) else stride
+        dh, dw = (rate, rate) if isinstance(rate, int) else rate
+        if padding not in ("SAME", "VALID"):
+            raise ValueError(padding)
+        node = self._node(self.lib.tcr_g2d_depthwise_conv(self._h, inp, kh, kw, sh, sw, dh, dw, int(padding == "VALID"), int(relu),
+                                                          weights_name.encode(), (biases_name or "").encode()), "tcr_g2d_depthwise_conv")
+        self.initializers[weights_name] = init
+        if biases_name:
+            self.initializers[biases_name] = "zeros"
+        return self._relu(relu, node)
+
     def batch_norm(self, inp: int, prefix: str, center: bool = True, scale: bool = True, relu: bool = False, decay: float = 0.997,
                    eps: float = 0.001) -> int:
         return self._relu(relu, self._node(self.lib.tcr_g2d_batch_norm(self._h, inp, int(center), int(scale), int(relu), float(decay),

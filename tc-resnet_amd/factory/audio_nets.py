@@ -15,7 +15,7 @@ from typing import Dict, Tuple
 import torch
 
 from .. import runtime
-from ..audio_nets import kws, res, tc_resnet
+from ..audio_nets import ds_cnn, kws, res, tc_resnet
 from ..datasets import preprocessor_factory
 from ..common import tf_utils
 from ..parallel import DataParallel
@@ -25,6 +25,8 @@ _available_nets = [
     "KWSModel", "Res8Model", "Res8NarrowModel", "Res15Model", "Res15NarrowModel", "DSCNNSModel", "DSCNNMModel",
     "DSCNNLModel", "TCResNet8Model", "TCResNet14Model", "ResNet2D8Model", "ResNet2D8PoolModel",
 ]
+# model classes beyond the reference's twelve (the command lines offer both lists)
+_extension_nets = ["DSCNNModel"]
 
 
 class AudioNetModel(TFModel):
@@ -402,6 +404,28 @@ class Res15Model(_ResModel):
 
 class Res15NarrowModel(_ResModel):
     variant = "Res15Narrow"
+
+
+class DSCNNModel(_GraphModel):
+    """A DS-CNN of any definition on the 2-D graph engine (audio_nets/ds_cnn.py): what DSCNNSModel / MModel / LModel's dedicated engine
+    refuses -- other depths, block counts, kernels, strides, a dilation, training at 98 x 40.  Sizes are "HxW" strings: a frozen
+    artifact keeps scalar arguments only, and deploy.FrozenModel rebuilds the engine from them."""
+
+    @staticmethod
+    def add_arguments(parser):
+        parser.add_argument("--depth", default=64, type=int)
+        parser.add_argument("--num_separable", default=4, type=int)
+        parser.add_argument("--conv1_kernel", default="10x4", type=str)
+        parser.add_argument("--conv1_stride", default="2x2", type=str)
+        parser.add_argument("--ds_kernel", default="3x3", type=str)
+        parser.add_argument("--ds1_stride", default="1x1", type=str)
+        parser.add_argument("--ds_rate", default="1x1", type=str)
+        parser.add_argument("--weight_decay", default=0.0, type=float)
+
+    def _engine_for(self, inputs):
+        a = self.args
+        return ds_cnn.get_engine(a.depth, a.num_separable, a.conv1_kernel, a.conv1_stride, a.ds_kernel, a.ds1_stride, a.ds_rate,
+                                 int(inputs.shape[1]), int(inputs.shape[2]), a.num_classes)
 
 
 class _ResNet2D8Model(_GraphModel):

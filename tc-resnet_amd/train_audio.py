@@ -56,7 +56,7 @@ def add_metric_arguments(parser):
 
 def add_model_subparsers(parser):
     subparsers = parser.add_subparsers(title="Model", description="")
-    for class_name in audio_nets._available_nets:
+    for class_name in audio_nets._available_nets + audio_nets._extension_nets:
         sub = subparsers.add_parser(class_name)
         sub.add_argument("--model", default=class_name, type=str, help="DO NOT FIX ME")
         getattr(audio_nets, class_name).add_arguments(sub)
